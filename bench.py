@@ -14,6 +14,11 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): every rank aligns i
 own replica of the reference (weak scaling, no data-path collective — coarse tracking of independent frames
 does not shard); timing is barrier + synchronize bracketed and MAX-reduced.
 
+A plain run sets up, warms up, times the K steps and reports the headline.  --full adds everything else the
+benchmark measures: the k_track_lm roofline and its HBM traffic, the CPU baselines, the PCIe legs, the batch
+sweep, the BA / trace / overlap / live / VIO / drop-in legs.  --dump-outputs DIR writes the results of the last
+timed step (what trackNewestCoarse hands its caller, rank 0) as DIR/<name>.npy in float64.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -63,6 +68,9 @@ def parse():
     ap.add_argument("--no-concurrent", action="store_true", help="skip ba.concurrent_windows (several windows in flight on one GPU)")
     ap.add_argument("--ba-points", type=int, default=2000)
     ap.add_argument("--ba-iters", type=int, default=300, help="timed GN iterations of the BA leg")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else (roofline, HBM traffic, CPU baselines, PCIe, sweep, BA, trace, overlap, "
+                                                        "live, VIO, drop-in; each can still be skipped with its --no-* option); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the results of the last timed step (rank 0) as DIR/<name>.npy, float64")
     return ap.parse_args()
 
 
@@ -102,6 +110,11 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
+    if not args.full:
+        # the headline only: every secondary leg is skipped as its --no-* option would skip it (the roofline is gated on args.full below)
+        args.no_traffic = args.no_cpu = args.no_pcie = args.no_sweep = args.no_ba = True
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1 and not args.traffic_child:
             self_launch(args)
@@ -284,7 +297,9 @@ def main():
     step_ms = 1e3 * np.diff(np.array([t0] + step_marks))
     if not res_pipe["good"].all():
         raise SystemExit("bench: a pipelined step lost tracking")
-    trk.fetch()                                         # drain the last launch (outside the timed region: K launches, K unpacks inside)
+    last = trk.fetch()                                  # drain the last launch (outside the timed region: K launches, K unpacks inside)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, ctx.levels)
     # the other pipeline variant, after the timed region (the same K steps, the same work per step): reported beside the headline, not in it
     other_ms = None
     if overlap_build:
@@ -326,47 +341,49 @@ def main():
 
     # ---------------- kernel-level roofline of the dominant kernel (k_track_lm), HIP events on ITS stream
     ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
-    reps = max(3, min(args.steps, 10))
-    trk.stage(slots, poses0, affs0)
-    torch.cuda.synchronize(dev)
-    kms = []
-    for _ in range(reps):
-        ev0.record(stream); trk.launch(); ev1.record(stream)
-        ev1.synchronize()
-        kms.append(ev0.elapsed_time(ev1))
-    trk.fetch()
-    n_evals, n_point_evals = trk.last_work()
-    tk_step, tk_eval = trk.last_ticks()
-    k_ms = float(np.mean(kms))
-    alg_bytes = BYTES_PER_POINT_EVAL * n_point_evals
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-    roofline = dict(bound="hbm", kernel="k_track_lm", achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBS, 5), traffic=None,
-                    kernel_ms=round(k_ms, 4), algorithmic_bytes_per_launch=int(alg_bytes),
-                    point_evals_per_launch=int(n_point_evals), evals_per_launch=int(n_evals),
-                    in_kernel_us_per_problem=dict(lm_control=round(tk_step / 100.0 / B, 2), evaluation=round(tk_eval / 100.0 / B, 2)))
-    # HBM traffic of k_track_lm: measured now, by a rocprofv3 --kernel-trace --pmc FETCH_SIZE child run of this very workload (rank 0, N = 1), calibrated on
-    # k_build_pyramids of the same run, whose read volume is known exactly (MI355X_MICROARCH.md: gfx950 tallies wide reads at half their size)
+    roofline = None
     tr = None
-    if rank == 0 and world == 1 and not args.no_traffic and not args.traffic_child:
-        tr = measure_traffic(args, B, w, h)
-        if tr is not None:
-            roofline["traffic"] = tr["traffic"]
-            roofline["traffic_source"] = tr["source"]
-            roofline["frac_hbm_counter"] = round(tr["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-    pm = None
-    if not args.no_pyramid:
-        pms = []
+    if args.full:
+        reps = max(3, min(args.steps, 10))
+        trk.stage(slots, poses0, affs0)
+        torch.cuda.synchronize(dev)
+        kms = []
         for _ in range(reps):
-            ev0.record(stream); ctx.frames_attach_device_batch(slots, raw_ptr, frame_bytes); ev1.record(stream)
-            ev1.synchronize(); pms.append(ev0.elapsed_time(ev1))
-        pm = float(np.mean(pms))
-        pyr_bytes = B * (4 * w * h + sum(4 * (w >> l) * (h >> l) for l in range(1, ctx.levels)))  # read the resident image + write the coarser levels (level 0 is the image itself)
-        roofline["pyramid_kernel_ms"] = round(pm, 4)
-        roofline["pyramid_GBps"] = round(pyr_bytes / (pm * 1e-3) / 1e9, 1)
-        # the whole step against the same peak: algorithmic bytes of tracking + the build's traffic over the step time of the timed region
-        roofline["step"] = dict(bytes=int(alg_bytes + pyr_bytes), ms=round(ms_per_step, 4), achieved=round((alg_bytes + pyr_bytes) / (ms_per_step * 1e-3) / 1e9, 1),
-                                frac=round((alg_bytes + pyr_bytes) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5))
+            ev0.record(stream); trk.launch(); ev1.record(stream)
+            ev1.synchronize()
+            kms.append(ev0.elapsed_time(ev1))
+        trk.fetch()
+        n_evals, n_point_evals = trk.last_work()
+        tk_step, tk_eval = trk.last_ticks()
+        k_ms = float(np.mean(kms))
+        alg_bytes = BYTES_PER_POINT_EVAL * n_point_evals
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+        roofline = dict(bound="hbm", kernel="k_track_lm", achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(achieved / HBM_PEAK_GBS, 5), traffic=None,
+                        kernel_ms=round(k_ms, 4), algorithmic_bytes_per_launch=int(alg_bytes),
+                        point_evals_per_launch=int(n_point_evals), evals_per_launch=int(n_evals),
+                        in_kernel_us_per_problem=dict(lm_control=round(tk_step / 100.0 / B, 2), evaluation=round(tk_eval / 100.0 / B, 2)))
+        # HBM traffic of k_track_lm: measured now, by a rocprofv3 --kernel-trace --pmc FETCH_SIZE child run of this very workload (rank 0, N = 1), calibrated on
+        # k_build_pyramids of the same run, whose read volume is known exactly (gfx950's FETCH_SIZE tallies wide reads at half their size)
+        if rank == 0 and world == 1 and not args.no_traffic and not args.traffic_child:
+            tr = measure_traffic(args, B, w, h)
+            if tr is not None:
+                roofline["traffic"] = tr["traffic"]
+                roofline["traffic_source"] = tr["source"]
+                roofline["frac_hbm_counter"] = round(tr["traffic"] / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+        pm = None
+        if not args.no_pyramid:
+            pms = []
+            for _ in range(reps):
+                ev0.record(stream); ctx.frames_attach_device_batch(slots, raw_ptr, frame_bytes); ev1.record(stream)
+                ev1.synchronize(); pms.append(ev0.elapsed_time(ev1))
+            pm = float(np.mean(pms))
+            pyr_bytes = B * (4 * w * h + sum(4 * (w >> l) * (h >> l) for l in range(1, ctx.levels)))  # read the resident image + write the coarser levels (level 0 is the image itself)
+            roofline["pyramid_kernel_ms"] = round(pm, 4)
+            roofline["pyramid_GBps"] = round(pyr_bytes / (pm * 1e-3) / 1e9, 1)
+            # the whole step against the same peak: algorithmic bytes of tracking + the build's traffic over the step time of the timed region
+            roofline["step"] = dict(bytes=int(alg_bytes + pyr_bytes), ms=round(ms_per_step, 4), achieved=round((alg_bytes + pyr_bytes) / (ms_per_step * 1e-3) / 1e9, 1),
+                                    frac=round((alg_bytes + pyr_bytes) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5))
 
     # ---------------- CPU baseline: the oracle (port of the reference's SSE path), 1 thread, bounded sample
     cpu = None
@@ -673,6 +690,27 @@ def main():
         dist.destroy_process_group()
 
 
+def dump_outputs(d, res, levels, max_bytes=64 * 10 ** 6):
+    """The arrays one trackNewestCoarse batch hands its caller (pose7, aff, lastResiduals, flow, H, b, good, iterations), one DIR/<name>.npy each, as float64
+    (the integer flags and counts are exact in it): two builds run with the same arguments can be compared output for output.  lastResiduals has a slot per
+    possible pyramid level (five, the reference's Vec5); only the slots of the `levels` levels tracked are written, the others stay NaN and hold no result.
+    Every value written is finite: a non-finite one is an error, not an output.  A batch whose arrays would exceed max_bytes is cut to a fixed, seeded
+    sample of its frames, listed in frame_index.npy."""
+    res = dict(res, lastResiduals=np.asarray(res["lastResiduals"])[:, :levels])
+    for name, a in res.items():
+        if not np.isfinite(np.asarray(a, dtype=np.float64)).all():
+            raise SystemExit("bench: the last timed step returned non-finite values in %s" % name)
+    os.makedirs(d, exist_ok=True)
+    B = len(res["good"])
+    per_frame = sum(np.asarray(a[0]).size * 8 for a in res.values()) + 8
+    keep = np.arange(B)
+    if B * per_frame > max_bytes:
+        keep = np.sort(np.random.RandomState(0).choice(B, max_bytes // per_frame, replace=False))
+    for name, a in res.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64)[keep])
+    np.save(os.path.join(d, "frame_index.npy"), keep.astype(np.float64))
+
+
 def measure_traffic(args, B, w, h):
     """HBM bytes per k_track_lm launch from a `rocprofv3 --kernel-trace --pmc FETCH_SIZE` child run of this workload (counters only, no other tracing)."""
     import glob
@@ -686,7 +724,7 @@ def measure_traffic(args, B, w, h):
     d = tempfile.mkdtemp(prefix="dmvio_pmc_", dir="/tmp")
     try:
         env = dict(os.environ); env["TMPDIR"] = "/tmp"
-        cmd = [exe, "--kernel-trace", "--pmc", "FETCH_SIZE", "-d", d, "-o", "c", "--", sys.executable, os.path.abspath(__file__), "--traffic-child", "--no-cpu"] + \
+        cmd = [exe, "--kernel-trace", "--pmc", "FETCH_SIZE", "-d", d, "-o", "c", "--", sys.executable, os.path.abspath(__file__), "--traffic-child", "--full", "--no-cpu"] + \
               (["--no-ba"] if args.no_ba else ["--ba-iters", "60", "--ba-points", str(args.ba_points)]) + ["--no-sweep", "--no-pcie", "--no-traffic", "--no-concurrent", "--steps", "3", "--warmup", "1", "--batch", str(B), "--points", str(args.points), "--size", str(args.size),
                "--distinct", str(args.distinct)]
         r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=300)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract(gpu_required):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "256", "--no-sweep", "--no-traffic",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "256", "--full", "--no-sweep", "--no-traffic",
            "--cpu-seconds", "2", "--ba-iters", "50", "--dropin-frames", "60"]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -71,6 +72,28 @@ def test_bench_line_contract(gpu_required):
     assert d["max_pose_err_m"] < 5e-3
 
 
+def test_plain_run_reports_the_headline_and_dumps_the_last_step(gpu_required, tmp_path):
+    """Without --full the line carries the headline only (every secondary leg null, nothing measured beyond the timed steps); --dump-outputs writes what the last
+    timed step hands its caller, float64, one file per array."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "256", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"] and d["max_pose_err_m"] < 5e-3
+    for k in ("roofline", "cpu_baseline", "ba", "trace", "drop_in", "overlap", "live", "vio_handoff", "pcie", "batch_sweep"):
+        assert d[k] is None, k
+    # lastResiduals: one column per pyramid level tracked (4 at 512x512; the reference's fifth, NaN slot holds no result)
+    shapes = dict(pose7=(256, 7), aff=(256, 2), lastResiduals=(256, 4), flow=(256, 3), H=(256, 8, 8), b=(256, 8), good=(256,), iterations=(256,), frame_index=(256,))
+    assert sorted(f.name for f in tmp_path.iterdir()) == sorted(n + ".npy" for n in shapes)
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == shape and np.isfinite(a).all(), (name, a.dtype, a.shape)
+    assert (np.load(tmp_path / "good.npy") != 0).all() and (np.load(tmp_path / "iterations.npy") > 0).all()
+
+
 @pytest.mark.parametrize("launcher", ["torch.distributed.run", "plain"])
 def test_bench_two_ranks_share_the_device(gpu_required, launcher):
     """The N > 1 code path of bench.py in BOTH forms the driver uses — under torch.distributed.run (one process per rank) and as plain `python bench.py --gpus 2`, which starts
@@ -81,7 +104,7 @@ def test_bench_two_ranks_share_the_device(gpu_required, launcher):
     env = dict(os.environ, DMVIO_BENCH_BACKEND="gloo", DMVIO_BENCH_SHARE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    bench = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "256", "--ba-iters", "50"]
+    bench = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "256", "--full", "--ba-iters", "50"]
     if launcher == "plain":
         cmd = [sys.executable] + bench
     else:

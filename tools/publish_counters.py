@@ -35,7 +35,7 @@ if cf:
     cyc = C["GRBM_GUI_ACTIVE"] / 8.0
     valu_busy = 4 * C["SQ_ACTIVE_INST_VALU"] / (1024 * cyc)
     out = ["# %s — hardware counters of the headline step (`tools/profile_counters.sh %s`: one `rocprofv3 --kernel-trace --pmc <group>` run per group of" % (R, R),
-           "`python bench.py --no-cpu --no-ba --steps 3 --warmup 1`, batch 4096, 1x MI355X; per-dispatch values summed over the device)", "",
+           "`python bench.py --full --no-cpu --no-ba --steps 3 --warmup 1`, batch 4096, 1x MI355X; per-dispatch values summed over the device)", "",
            "## What they say about `k_track_lm<256,4>` (%d alignment problems, %.1f M point-evaluations, %.2f ms per launch by HIP events)" % (d["config"]["frames_per_step_per_gpu"], pe / 1e6, rf["kernel_ms"]), "",
            "* `GRBM_GUI_ACTIVE` %.1f M = 8 XCDs x %.2f M cycles; `SQ_BUSY_CU_CYCLES` %.0f M = 256 CUs x %.2f M: every CU is busy for the whole launch."
            % (C["GRBM_GUI_ACTIVE"] / 1e6, cyc / 1e6, C["SQ_BUSY_CU_CYCLES"] / 1e6, C["SQ_BUSY_CU_CYCLES"] / 256e6),
