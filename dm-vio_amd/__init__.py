@@ -18,6 +18,7 @@ INCLUDE_PATH = os.path.join(os.path.dirname(_HERE), "include", "dmvio_hip.h")
 c_f = C.POINTER(C.c_float)
 c_d = C.POINTER(C.c_double)
 c_i = C.POINTER(C.c_int)
+c_u8 = C.POINTER(C.c_ubyte)
 
 _lib = None
 
@@ -59,6 +60,11 @@ class BACallbacks(C.Structure):
 class BAVioOptions(C.Structure):
     _fields_ = [("coarseTrackingWasGood", C.c_int), ("updateDynamicWeightDuringOptimization", C.c_int), ("minOptIterations", C.c_int), ("resInA_at_entry", C.c_int),
                 ("HMForGTSAM", c_d), ("bMForGTSAM", c_d)]
+
+
+class PixelSelectorSettings(C.Structure):
+    """dmvio_hip_pixel_selector_settings (settings.cpp:167-170)"""
+    _fields_ = [("minGradHistCut", C.c_float), ("minGradHistAdd", C.c_float), ("gradDownweightPerLevel", C.c_float), ("selectDirectionDistribution", C.c_int)]
 
 
 def _sig(L):
@@ -168,6 +174,21 @@ def _sig(L):
     L.dmvio_hip_comm_unique_id.argtypes = [c_u8]
     L.dmvio_hip_comm_init_rank.argtypes = [vp, c_u8, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.dmvio_hip_comm_destroy.argtypes = [vp]
+    L.dmvio_hip_pixel_selector_default_settings.argtypes = [C.POINTER(PixelSelectorSettings)]
+    L.dmvio_hip_pixel_selector_default_settings.restype = None
+    L.dmvio_hip_pixel_selector_create.restype = vp
+    L.dmvio_hip_pixel_selector_create.argtypes = [vp, c_u8]
+    L.dmvio_hip_pixel_selector_destroy.argtypes = [vp]
+    L.dmvio_hip_pixel_selector_destroy.restype = None
+    L.dmvio_hip_pixel_selector_set_settings.argtypes = [vp, C.POINTER(PixelSelectorSettings)]
+    L.dmvio_hip_pixel_selector_get_potential.argtypes = [vp]
+    L.dmvio_hip_pixel_selector_set_potential.argtypes = [vp, C.c_int]
+    L.dmvio_hip_pixel_selector_make_maps.argtypes = [vp, C.c_int, c_f, C.c_float, C.c_int, C.c_float, c_i, c_i, c_f]
+    L.dmvio_hip_pixel_selector_get_selection.argtypes = [vp, c_i, c_i, c_i]
+    L.dmvio_hip_pixel_selector_get_thresholds.argtypes = [vp, c_f, c_f]
+    L.dmvio_hip_pixel_selector_get_passes.argtypes = [vp, C.c_int, c_i, c_i]
+    L.dmvio_hip_pixel_selector_get_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.dmvio_hip_immature_add_selected.argtypes = [vp, C.c_int, C.c_int, vp]
 
 
 def load_library():
@@ -701,6 +722,13 @@ class ImmaturePointsHip:
             raise HipLibraryError("immature_add_points: %s" % _err(self.L))
         return r
 
+    def add_selected(self, host_tag, host_slot, selector):
+        """The loop of FullSystem::makeNewTraces over the selector's last selection; the coordinates stay on the device.  Returns the index of the first new point."""
+        r = self.L.dmvio_hip_immature_add_selected(self.p, host_tag, host_slot, selector.p)
+        if r < 0:
+            raise HipLibraryError("immature_add_selected: %s" % _err(self.L))
+        return r
+
     def get_static(self):
         n = self.n
         o = dict(u=np.zeros(n, np.float32), v=np.zeros(n, np.float32), host=np.zeros(n, np.int32), color=np.zeros((n, 8), np.float32),
@@ -750,6 +778,77 @@ class ImmaturePointsHip:
                                                         new_exposure, H, _d(host_c2w7), _d(ha), _f(he), _d(np.ascontiguousarray(fxfycxcy, dtype=np.float64)), _i(counts)),
              "trace_new_coarse")
         return dict(zip(("good", "oob", "outlier", "skipped", "badcondition", "uninitialized"), counts.tolist()))
+
+
+class PixelSelectorHip:
+    """Mirror of PixelSelector (PixelSelector2.cpp): makeMaps on a resident frame.  random_pattern = the reference's randomPattern table (w*h bytes: rand() & 0xFF after
+    srand(3141592) in the reference's constructor); the library never touches the process's rand() state, so the caller supplies it."""
+
+    def __init__(self, ctx, random_pattern):
+        self.ctx, self.L = ctx, ctx.L
+        pat = np.ascontiguousarray(random_pattern, dtype=np.uint8).reshape(-1)
+        if pat.size < ctx.w * ctx.h:
+            raise HipLibraryError("PixelSelectorHip: random_pattern needs w*h = %d bytes, got %d" % (ctx.w * ctx.h, pat.size))
+        p = self.L.dmvio_hip_pixel_selector_create(ctx.p, pat.ctypes.data_as(c_u8))
+        if not p:
+            raise HipLibraryError("dmvio_hip_pixel_selector_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.w, self.h = ctx.w, ctx.h
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_pixel_selector_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def currentPotential(self):
+        return _chk(self.L, self.L.dmvio_hip_pixel_selector_get_potential(self.p), "pixel_selector_get_potential")
+
+    @currentPotential.setter
+    def currentPotential(self, pot):
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_set_potential(self.p, int(pot)), "pixel_selector_set_potential")
+
+    def set_settings(self, minGradHistCut=0.5, minGradHistAdd=7.0, gradDownweightPerLevel=0.75, selectDirectionDistribution=1):
+        st = PixelSelectorSettings(minGradHistCut, minGradHistAdd, gradDownweightPerLevel, int(selectDirectionDistribution))
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_set_settings(self.p, C.byref(st)), "pixel_selector_set_settings")
+
+    def makeMaps(self, slot, density, recursionsLeft=1, thFactor=1.0, B=None, want_map=True):
+        """-> (return value of makeMaps, status map uint8 [h, w] or None); self.counts = (n2, n3, n4) of the last select"""
+        n = np.zeros(1, np.int32); cnt = np.zeros(3, np.int32)
+        m = np.zeros(self.w * self.h, np.float32) if want_map else None
+        Bf = None if B is None else _f(np.ascontiguousarray(B, dtype=np.float32))
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_make_maps(self.p, slot, Bf, density, recursionsLeft, thFactor, _i(n), _i(cnt), None if m is None else _f(m)),
+             "pixel_selector_make_maps")
+        self.counts = tuple(int(x) for x in cnt)
+        return int(n[0]), (None if m is None else m.astype(np.uint8).reshape(self.h, self.w))
+
+    def get_selection(self):
+        st = self.stats()
+        u = np.zeros(st["n_selected"], np.int32); v = np.zeros_like(u); t = np.zeros_like(u)
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_get_selection(self.p, _i(u), _i(v), _i(t)), "pixel_selector_get_selection")
+        return u, v, t
+
+    def get_thresholds(self):
+        nb = (self.w // 16) * (self.h // 16)
+        a = np.zeros(nb, np.float32); b = np.zeros(nb, np.float32)
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_get_thresholds(self.p, _f(a), _f(b)), "pixel_selector_get_thresholds")
+        return a, b
+
+    def get_passes(self):
+        """[(potential, (n2, n3, n4))] of the select passes of the last makeMaps"""
+        pot = np.zeros(16, np.int32); cnt = np.zeros(48, np.int32)
+        n = _chk(self.L, self.L.dmvio_hip_pixel_selector_get_passes(self.p, 16, _i(pot), _i(cnt)), "pixel_selector_get_passes")
+        return [(int(pot[i]), tuple(int(x) for x in cnt[3 * i:3 * i + 3])) for i in range(min(n, 16))]
+
+    def stats(self):
+        s = (C.c_longlong * 4)()
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_get_stats(self.p, s), "pixel_selector_get_stats")
+        return dict(exact_path_runs=int(s[0]), passes=int(s[1]), n_selected=int(s[2]), n_window=int(s[3]))
 
 
 class BundleAdjusterBatch:

@@ -107,6 +107,32 @@ int dmvio_hip_immature_add_points(dmvio_hip_immature* m, int host_tag, int host_
   return first;
 }
 
+// the loop of FullSystem::makeNewTraces (FullSystem.cpp:1653-1663) over the selector's device-resident list: the coordinates never visit the host, only their count does
+int dmvio_hip_immature_add_selected(dmvio_hip_immature* m, int host_tag, int host_slot, dmvio_hip_pixel_selector* sel) {
+  IMM_READY(m);
+  dmvio_hip_ctx* c = m->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  dmvio_hip_ctx* sc = nullptr;
+  const float *d_u = nullptr, *d_v = nullptr;
+  const int n = dmv_selector_window_list(sel, &sc, &d_u, &d_v);
+  if (n < 0) return n;
+  if (sc != c) return failmsg("immature_add_selected: the selector belongs to another context");
+  if (m->n + n > m->capacity) return failmsg("immature_add_selected: capacity exceeded");
+  if (host_slot < 0 || host_slot >= c->n_slots || host_tag < 0 || host_tag >= IMM_MAX_HOSTS) return failmsg("immature_add_selected: slot / tag out of range");
+  if (int r = dmv_ensure_row_major_locked(c, host_slot)) return r;
+  if (n == 0) return m->n;
+  const int first = m->n;
+  // the window (3 <= x < w-4, 3 <= y < h-4) lies inside the margin the constructor needs (dmvio_hip_immature_add_points)
+  HIPCHK(hipMemcpyAsync(m->P.u + first, d_u, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(m->P.v + first, d_v, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  m->P.n = first + n;
+  hipLaunchKernelGGL(k_immature_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->levelPtr(host_slot, 0), c->w, first, n, m->P, host_tag, m->S);
+  HIPCHK(hipGetLastError());
+  m->n = first + n;
+  m->max_tag = std::max(m->max_tag, host_tag);
+  return first;
+}
+
 int dmvio_hip_immature_get_static(dmvio_hip_immature* m, float* u, float* v, int* host_tag, float* color8, float* weights8, float* gradH4, float* energyTH) {
   IMM_READY(m);
   hipStream_t s = m->ctx->stream;

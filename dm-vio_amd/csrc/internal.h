@@ -157,6 +157,11 @@ struct dmvio_hip_graph {
                                                      // flat order (dmvio_hip_graph_set_idepths) are only accepted while the two agree
 };
 
+// the device-resident list of the selector's last selection restricted to the window FullSystem::makeNewTraces walks (capi_select.hip; read by
+// dmvio_hip_immature_add_selected in capi_immature.hip): pixel positions as floats, raster order.  Returns the number of entries or <0.
+struct dmvio_hip_pixel_selector;
+int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, const float** d_u, const float** d_v);
+
 // hypothesis-parallel trackNewCoarse: the element-wise fp64 sum over all ranks of a small HOST buffer, in place (set by dmvio_hip_tracker_set_comm /
 // _set_comm_callbacks in capi_ba.hip, which owns the RCCL calls; used by dmvio_hip_tracker_track_new_coarse in capi.hip)
 struct dmvio_hip_tracker;

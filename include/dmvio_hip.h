@@ -638,6 +638,56 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* ini, int lvl, i
                                           float couplingWeight, double priorY, double priorX, float* H_out64, float* b_out8, float* H_sc64, float* b_sc8,
                                           float res3[3], float* energy_new2, unsigned char* isGood_new, float* maxstep, float* lastHessian_new, float* JbBuffer_new10);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Pixel selection: the candidates of a new keyframe, chosen on the device from the resident pyramid.
+ *   PixelSelector::PixelSelector   src/dso/FullSystem/PixelSelector2.cpp:43-72    -> dmvio_hip_pixel_selector_create
+ *   PixelSelector::makeMaps        src/dso/FullSystem/PixelSelector2.cpp:158-307  -> dmvio_hip_pixel_selector_make_maps
+ *     (with makeHists :94-157 and select :311-454; the `plot` branch :276-304 and the commented-out FAST branch :168-189 are not built)
+ *   FullSystem::makeNewTraces      src/dso/FullSystem/FullSystem.cpp:1640-1666    -> dmvio_hip_pixel_selector_make_maps + dmvio_hip_immature_add_selected
+ * One handle per context, like the reference's one PixelSelector per FullSystem.  Results (status map, counts, return value, currentPotential) are integers and equal
+ * the reference's bit for bit; rows 0 and h-1 of absSquaredGrad, which the reference never writes, are zero (dmvio_hip_frame_abs_squared_grad). */
+typedef struct dmvio_hip_pixel_selector dmvio_hip_pixel_selector;
+typedef struct dmvio_hip_pixel_selector_settings {
+  float minGradHistCut;            /* setting_minGradHistCut               0.5   src/dso/util/settings.cpp:167 */
+  float minGradHistAdd;            /* setting_minGradHistAdd               7     src/dso/util/settings.cpp:168 */
+  float gradDownweightPerLevel;    /* setting_gradDownweightPerLevel       0.75  src/dso/util/settings.cpp:169 */
+  int selectDirectionDistribution; /* setting_selectDirectionDistribution  1     src/dso/util/settings.cpp:170 */
+} dmvio_hip_pixel_selector_settings;
+void dmvio_hip_pixel_selector_default_settings(dmvio_hip_pixel_selector_settings* s);
+/* random_pattern_wh: w*h bytes, PixelSelector::randomPattern.  The reference fills it from rand() after srand(3141592) (PixelSelector2.cpp:45-47); the library does
+ * not touch the process's rand() state, so the caller passes the table.  NULL is an error.  Image sizes not divisible by 16 are refused (PixelSelector2.cpp:53-61).
+ * All device scratch is allocated here, sized for potential 1. */
+dmvio_hip_pixel_selector* dmvio_hip_pixel_selector_create(dmvio_hip_ctx* ctx, const unsigned char* random_pattern_wh);
+void dmvio_hip_pixel_selector_destroy(dmvio_hip_pixel_selector* sel);
+int dmvio_hip_pixel_selector_set_settings(dmvio_hip_pixel_selector* sel, const dmvio_hip_pixel_selector_settings* s);
+/* PixelSelector::currentPotential (3 at creation, PixelSelector2.cpp:49): state that survives from keyframe to keyframe */
+int dmvio_hip_pixel_selector_get_potential(dmvio_hip_pixel_selector* sel);
+int dmvio_hip_pixel_selector_set_potential(dmvio_hip_pixel_selector* sel, int potential);
+/* makeMaps on the resident frame in `slot`: makeHists (recomputed on every call; the reference caches it per FrameHessian pointer, :200), select, the re-selection
+ * with another potential (:205-245: the loop runs inside the call, one 16-byte read per pass), the random sub-selection (:247-265), the update of currentPotential
+ * (:273).  B_lut256: as in dmvio_hip_frame_abs_squared_grad (setting_gammaWeightsPixelSelect == 1), or NULL.  density = numWant, recursions_left / th_factor as the
+ * reference's arguments (defaults 1 / 1; CoarseInitializer::setFirst passes th_factor 2).  *n_selected = makeMaps' return value; counts3 (may be NULL) = (n2, n3, n4)
+ * of the last select; map_out_host (may be NULL) = the w*h status map, 0 / 1 / 2 / 4 (PixelSelectorStatus as float, as the reference's map_out). */
+int dmvio_hip_pixel_selector_make_maps(dmvio_hip_pixel_selector* sel, int slot, const float* B_lut256, float density, int recursions_left, float th_factor,
+                                       int* n_selected, int counts3[3], float* map_out_host);
+/* the selected pixels of the last call in raster order (the order FullSystem::makeNewTraces walks the map, FullSystem.cpp:1653-1657), compacted on the device;
+ * arrays of *n_selected entries, each may be NULL; type = the map value.  Returns the number of entries or <0. */
+int dmvio_hip_pixel_selector_get_selection(dmvio_hip_pixel_selector* sel, int* u, int* v, int* type);
+/* PixelSelector::ths / thsSmoothed of the last call (nbW*nbH = (w/16)*(h/16) floats each, may be NULL): tells a wrong histogram from a wrong selection */
+int dmvio_hip_pixel_selector_get_thresholds(dmvio_hip_pixel_selector* sel, float* ths, float* thsSmoothed);
+/* the select passes of the last call (the first one and each re-selection): potential[i] and counts3[3*i .. 3*i+2] = (n2, n3, n4) of pass i, at most max_passes
+ * entries written; returns the number of passes */
+int dmvio_hip_pixel_selector_get_passes(dmvio_hip_pixel_selector* sel, int max_passes, int* potential, int* counts3);
+/* diagnostics: [0] select passes since creation whose n2 had to be found by the sequential recurrence (a cell whose selection depends on the direction
+ * randomPattern[n2] draws, PixelSelector2.cpp:376,397-401), [1] select passes of the last call, [2] its return value, [3] how many of those lie in the window
+ * FullSystem::makeNewTraces walks */
+int dmvio_hip_pixel_selector_get_stats(dmvio_hip_pixel_selector* sel, long long stats4[4]);
+/* the loop of FullSystem::makeNewTraces (FullSystem.cpp:1653-1663) for the selector's last selection: constructs an ImmaturePoint for every selected pixel with
+ * patternPadding+1 <= x < w-patternPadding-2, same for y (patternPadding = 2, src/dso/util/settings.h:229) — select admits rows up to h-4 (PixelSelector2.cpp:385)
+ * that this loop skips.  The coordinates stay on the device; points are treated as by dmvio_hip_immature_add_points.  Returns the index of the first new point or <0;
+ * dmvio_hip_immature_count then tells how many were added. */
+int dmvio_hip_immature_add_selected(dmvio_hip_immature* imm, int host_tag, int host_slot, dmvio_hip_pixel_selector* sel);
+
 #ifdef __cplusplus
 }
 #endif

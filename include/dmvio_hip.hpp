@@ -362,5 +362,40 @@ class WindowBatch {
   dmvio_hip_ba_batch* b_;
 };
 
+/* PixelSelector (FullSystem/PixelSelector2.h) on a resident frame: the reference's surface over dmvio_hip_pixel_selector_*.  randomPattern = the w*h table the
+ * reference's constructor fills from rand() after srand(3141592) (PixelSelector2.cpp:45-47); the library does not touch the process's rand() state. */
+class PixelSelector {
+ public:
+  PixelSelector(dmvio_hip_ctx* ctx, const unsigned char* randomPattern) : s_(dmvio_hip_pixel_selector_create(ctx, randomPattern)) {}
+  ~PixelSelector() { if (s_) dmvio_hip_pixel_selector_destroy(s_); }
+  PixelSelector(const PixelSelector&) = delete;
+  PixelSelector& operator=(const PixelSelector&) = delete;
+  bool valid() const { return s_ != nullptr; }
+  /* makeMaps (PixelSelector2.cpp:158-307) of the frame in `slot`; map_out (w*h floats, 0 / 1 / 2 / 4) may be NULL when only the device-resident list is wanted.
+   * B = CalibHessian::B for setting_gammaWeightsPixelSelect == 1, or NULL.  Returns numHaveSub, or <0 on an error (lastError()). */
+  int makeMaps(int slot, float* map_out, float density, int recursionsLeft = 1, float thFactor = 1, const float* B = nullptr) {
+    int n = 0;
+    if (!s_) return -1;
+    const int r = dmvio_hip_pixel_selector_make_maps(s_, slot, B, density, recursionsLeft, thFactor, &n, nullptr, map_out);
+    return r < 0 ? r : n;
+  }
+  int currentPotential() const { return s_ ? dmvio_hip_pixel_selector_get_potential(s_) : -1; }
+  bool setCurrentPotential(int pot) { return s_ && dmvio_hip_pixel_selector_set_potential(s_, pot) == 0; }
+  bool setSettings(const dmvio_hip_pixel_selector_settings& st) { return s_ && dmvio_hip_pixel_selector_set_settings(s_, &st) == 0; }
+  /* the selected pixels of the last makeMaps in the order FullSystem::makeNewTraces walks the map */
+  bool selection(std::vector<int>& u, std::vector<int>& v, std::vector<int>& type) {
+    long long st[4];
+    if (!s_ || dmvio_hip_pixel_selector_get_stats(s_, st) != 0) return false;
+    u.assign((size_t)st[2], 0); v.assign((size_t)st[2], 0); type.assign((size_t)st[2], 0);
+    return dmvio_hip_pixel_selector_get_selection(s_, u.data(), v.data(), type.data()) >= 0;
+  }
+  /* the point-construction loop of FullSystem::makeNewTraces (FullSystem.cpp:1653-1663) for the last makeMaps: index of the first new point of `points`, or <0 */
+  int makeNewTraces(dmvio_hip_immature* points, int host_tag, int host_slot) { return s_ ? dmvio_hip_immature_add_selected(points, host_tag, host_slot, s_) : -1; }
+  dmvio_hip_pixel_selector* handle() const { return s_; }
+
+ private:
+  dmvio_hip_pixel_selector* s_;
+};
+
 }  // namespace dmvio_hip
 #endif

@@ -1,0 +1,84 @@
+#!/usr/bin/env python
+"""Device time of the pixel selector per keyframe (dmvio_hip_pixel_selector_make_maps, and make_maps + dmvio_hip_immature_add_selected) on synthetic frames.
+
+    python tools/bench_pixel_select.py [--size 512 512] [--density 1500] [--calls 200] [--warmup 20] [--image ref|edges]      -> one JSON line
+    rocprofv3 --kernel-trace --stats -d <dir> -o sel -- python tools/bench_pixel_select.py --loop-only --calls 50            (per-kernel times; summarise with
+    tools/rocprof_summary.py <dir>/.../sel_results.db)
+
+Times are HIP events on the context's stream around each call (the device-side span of the call, the idle gaps in which the host reads the pass counts included) and the
+host's wall clock around the same call; the median over --calls after --warmup calls, by which the potential has settled.  The figure to set them against is the
+reference's own makeMaps + ImmaturePoint constructors on a CPU, recorded in tests/golden/pixel_select.npz (timing_us / timing_label / cpu)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as g  # noqa: E402
+import pixel_select_ref as PS  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, nargs=2, default=[512, 512])
+    ap.add_argument("--density", type=float, default=1500)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--image", default="ref")
+    ap.add_argument("--loop-only", action="store_true", help="no events, no JSON: just the calls (for a profiler)")
+    a = ap.parse_args()
+    import torch
+    P = g.load_package()
+    import dmvio_amd.synth as synth
+    w, h = a.size
+    dev = torch.device("cuda", 0)
+    ctx = P.Context(w, h, n_slots=2)
+    stream = torch.cuda.Stream(device=dev)
+    ctx.set_stream(stream.cuda_stream)
+    ctx.frame_upload(0, PS.case_image(synth, a.image, w, h))
+    golden = np.load(os.path.join(ROOT, "tests", "golden", "pixel_select.npz"))
+    pat = golden["pattern"]
+    pat = pat[:w * h] if pat.size >= w * h else PS.glibc_rand_pattern(w * h)
+    sel = P.PixelSelectorHip(ctx, pat)
+    imm = P.ImmaturePointsHip(ctx, capacity=w * h)
+    for _ in range(a.warmup):
+        sel.makeMaps(0, a.density, want_map=False)
+        imm.clear(); imm.add_selected(0, 0, sel)
+    ctx.synchronize()
+    pot = sel.currentPotential
+    if a.loop_only:
+        for _ in range(a.calls):
+            sel.makeMaps(0, a.density, want_map=False)
+            imm.clear(); imm.add_selected(0, 0, sel)
+        ctx.synchronize()
+        return
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True); e2 = torch.cuda.Event(enable_timing=True)
+    dm, dt, hm, ht = [], [], [], []
+    exact0 = sel.stats()["exact_path_runs"]
+    for _ in range(a.calls):
+        imm.clear()
+        t0 = time.perf_counter()
+        e0.record(stream)
+        ret, _ = sel.makeMaps(0, a.density, want_map=False)
+        e1.record(stream)
+        t1 = time.perf_counter()
+        imm.add_selected(0, 0, sel)
+        e2.record(stream)
+        e2.synchronize()
+        t2 = time.perf_counter()
+        dm.append(e0.elapsed_time(e1)); dt.append(e0.elapsed_time(e2)); hm.append(1e3 * (t1 - t0)); ht.append(1e3 * (t2 - t0))
+    st = sel.stats()
+    med = lambda x: float(np.median(x))
+    print(json.dumps(dict(tool="bench_pixel_select", w=w, h=h, image=a.image, density=a.density, calls=a.calls, potential_settled=pot, potential_after=sel.currentPotential,
+                          passes_last_call=st["passes"], n_selected=ret, n_points=imm.n, exact_path_runs=st["exact_path_runs"] - exact0,
+                          make_maps_event_ms=med(dm), make_maps_add_selected_event_ms=med(dt), make_maps_host_ms=med(hm), make_maps_add_selected_host_ms=med(ht),
+                          make_maps_event_ms_p90=float(np.percentile(dm, 90)),
+                          reference_cpu=dict(cpu=str(golden["cpu"][0]), us=[float(x) for x in golden["timing_us"]], what=[str(s) for s in golden["timing_label"]]))))
+
+
+if __name__ == "__main__":
+    main()
