@@ -573,11 +573,15 @@ __device__ __forceinline__ void baLinearizeBody(const BAWindow& W, const BAPoint
   if (D.mode < 0) return;
   // the last workgroup to arrive takes the decisions (energy sum, threshold of the newest keyframe, accept / reject)
   // What the deciding workgroup reads (energy partials, per-residual energies) was stored with agent-scope atomic stores, i.e. written
-  // through to the device's coherence point; waiting for those stores (workgroup-scope release = s_waitcnt) before a RELAXED arrive is enough.
-  // An agent-scope release / acquire here would write back and invalidate the whole L2 of the XCD — once per workgroup, with megabytes of
-  // freshly written records in it (measured: +40 us per launch).
+  // through to the device's coherence point; every wave WAITS for its own stores (s_waitcnt vmcnt(0)) before the workgroup's RELAXED arrive.
+  // The workgroup-scope release alone does not make it wait: the waves of a workgroup share a compute unit, so that scope needs no wait for
+  // global stores, the barrier does not wait for them either, and the arrive is issued by another wave than the one that stored the partial —
+  // seen as an energy sum that held a partial of the previous linearisation (about one batched call in 300, in the trace's E_A alone where
+  // the accept test's margin was large).  An agent-scope release / acquire here would write back and invalidate the whole L2 of the XCD —
+  // once per workgroup, with megabytes of freshly written records in it (measured: +40 us per launch).
   __shared__ int s_last;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   __syncthreads();
   if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(&D.ctl->cnt_lin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(nblocks - 1) ? 1 : 0;
   __syncthreads();
@@ -827,6 +831,7 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
   if (D.mode < 0) return;
   __shared__ int s_last1;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every wave's write-through stores are acknowledged before the arrive (see baLinearizeBody)
   __syncthreads();
   if (threadIdx.x == 0) s_last1 = __hip_atomic_fetch_add(&D.ctl->cnt_lin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(nblocks - 1) ? 1 : 0;
   __syncthreads();

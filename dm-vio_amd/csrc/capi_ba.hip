@@ -2108,10 +2108,10 @@ struct BAWorkers {
     }
     cv.notify_all();
   }
-  int waitAsync() {
+  int waitAsync(const bool report = true) {   // report = false: on the caller's own error path — wait only, its error message stays
     std::unique_lock<std::mutex> lk(mu);
     cv_done.wait(lk, [&] { return pending == 0; });
-    if (rc) { dmv_err() = err; dmv_err_epoch()++; }
+    if (rc && report) { dmv_err() = err; dmv_err_epoch()++; }
     return rc;
   }
   ~BAWorkers() {
@@ -2291,7 +2291,16 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
   hipStream_t s = B->stream;
   const auto t_call = std::chrono::steady_clock::now();
   auto stamp = [&](const int k) { B->host_us[k] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count(); };
-  struct StreamSwap {   // the handles' own entry points (table uploads, the reset kernel) enqueue on the batch's stream for the duration of the call
+  // the stream groups of the call (why and how they run: at the launches below)
+  const int maxG = B->streams > 0 ? B->streams : 3;   // measured (tools/ba_batch_streams.py): three groups are best at W = 16 and 64; a fourth stream shares a hardware queue
+                                                        // with another one (GPU_MAX_HW_QUEUES = 4, one of them busy with the handles' own streams) and loses
+  const int G = (Wn >= 4 && !B->profile) ? std::max(1, std::min(maxG, Wn / 2)) : 1;
+  struct Grp { hipStream_t st; int w0, cnt; };
+  Grp grp[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
+  for (int g = 0; g < G; g++) { grp[g].st = B->gstream[g]; grp[g].w0 = (int)(((long long)Wn * g) / G); grp[g].cnt = (int)(((long long)Wn * (g + 1)) / G) - grp[g].w0; }
+  auto groupOf = [&](const int w) { int g = 0; while (g + 1 < G && w >= grp[g + 1].w0) g++; return g; };
+  struct StreamSwap {   // the handles' own entry points (prepare()'s table uploads) enqueue on the stream of the window's GROUP for the duration of the call: what a group's
+                        // kernels read is then in front of them in stream order, whichever thread prepares the window and however late it does so
     std::vector<std::pair<dmvio_hip_ba*, hipStream_t>> saved;
     ~StreamSwap() { for (auto& kv : saved) kv.first->stream = kv.second; }
   } swap;
@@ -2299,7 +2308,8 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
   const int n_gather = (tot + 256) / 256, n_stitch = F + F2;
   for (int w = 0; w < Wn; w++) {
     dmvio_hip_ba* b = hs[w];
-    if (b->stream != s) { HIPCHK(hipStreamSynchronize(b->stream)); swap.saved.emplace_back(b, b->stream); b->stream = s; }
+    const hipStream_t gs = grp[groupOf(w)].st;
+    if (b->stream != gs) { HIPCHK(hipStreamSynchronize(b->stream)); swap.saved.emplace_back(b, b->stream); b->stream = gs; }
     const int nacc = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
     gx_lin = std::max(gx_lin, b->n_lin_blocks); gx_pt8 = std::max(gx_pt8, b->n_pt8_blocks); gx_acc = std::max(gx_acc, nacc); gx_res = std::max(gx_res, (b->H.R + 255) / 256); gx_pts = std::max(gx_pts, b->H.N);
   }
@@ -2310,7 +2320,7 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
     b->pending_reject = false; b->pending_trace = -1; b->sums_fresh = false; b->sys_ready = false;
     b->fullJ_applied = false;   // the batched linearisations relinearise and apply every residual without writing d_fullJ: what the buffer holds is no longer the applied state's
     if (int r = resolveTh(b)) return r;
-    if (b->adj_dirty) { if (int r = uploadAdjoints(b)) return r; }
+    if (b->adj_dirty) { if (int r = uploadAdjoints(b)) return r; }   // on the group's stream (StreamSwap): in front of the group's first k_ba_stitch_b
     // (the precalc table, the thresholds and the activation of all residuals travel with the batch: one upload, one launch for all windows)
     H.getNullspaces();
     H.prepareOrthogonalize();
@@ -2392,12 +2402,6 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
   // call (dmvio_hip_ba_batch_set_profile) runs as ONE group: its timed linearisation then covers all windows of the call, alone on the device.
   // The host's per-window work is pipelined along the groups too: group g's tables are prepared, uploaded and its first chain enqueued while the device already works on the
   // groups before it; behind the loop group g's states are written back (and its final linearisation enqueued) while the later groups still run.
-  const int maxG = B->streams > 0 ? B->streams : 3;   // measured (tools/ba_batch_streams.py): three groups are best at W = 16 and 64; a fourth stream shares a hardware queue
-                                                        // with another one (GPU_MAX_HW_QUEUES = 4, one of them busy with the handles' own streams) and loses
-  const int G = (Wn >= 4 && !B->profile) ? std::max(1, std::min(maxG, Wn / 2)) : 1;
-  struct Grp { hipStream_t st; int w0, cnt; };
-  Grp grp[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
-  for (int g = 0; g < G; g++) { grp[g].st = B->gstream[g]; grp[g].w0 = (int)(((long long)Wn * g) / G); grp[g].cnt = (int)(((long long)Wn * (g + 1)) / G) - grp[g].w0; }
   // the eight-lane kernel hides latency (few windows); the one-lane kernel does an eighth of the lane work (a grid that fills the device)
   const bool lin1 = B->lin_lanes == 1 && Wn >= 4;
   const int gx_lin1 = (gx_res * 256 + LIN_THREADS - 1) / LIN_THREADS;
@@ -2439,17 +2443,27 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
   std::atomic<int> prepared[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
   for (int g = 0; g < G; g++) prepared[g].store(0, std::memory_order_relaxed);
   const bool async_prepare = !B->workers.th.empty() && Wn >= 8 && G > 1;
-  auto groupOf = [&](const int w) { int g = 0; while (g + 1 < G && w >= grp[g + 1].w0) g++; return g; };
-  if (async_prepare) B->workers.startAsync(Wn, [&](const int w) -> int { const int r = prepare(w); prepared[groupOf(w)].fetch_add(1, std::memory_order_release); return r; });
+  std::atomic<int> prepare_failed{0};   // set BEFORE the window is counted: whoever sees a group complete (acquire) sees the failure of any of its windows
+  if (async_prepare)
+    B->workers.startAsync(Wn, [&](const int w) -> int {
+      const int r = prepare(w);
+      if (r) prepare_failed.store(1, std::memory_order_relaxed);
+      prepared[groupOf(w)].fetch_add(1, std::memory_order_release);
+      return r;
+    });
   else if (int r = B->workers.parallelFor(Wn, prepare)) return r;
+  struct AsyncGuard {   // the workers run a lambda over this frame's locals: no way out of the launch loop (HIPCHK returns) without waiting for them
+    BAWorkers& wk; bool armed;
+    ~AsyncGuard() { if (armed) wk.waitAsync(false); }
+  } asyncGuard{B->workers, async_prepare};
   int rc_launch = 0;
   for (int g = 0; g < G; g++) {
     const Grp& q = grp[g];
     const BAWinDev* dwq = B->d_wins + q.w0;
     if (async_prepare) while (prepared[g].load(std::memory_order_acquire) < q.cnt) __builtin_ia32_pause();
     if (g == 0) stamp(1);
-    if (async_prepare && B->workers.rc) { rc_launch = 1; break; }   // a window's preparation failed: nothing of it (or of the groups behind it) is launched
-    if (g == 0) { HIPCHK(hipEventRecord(B->ev[0], s)); for (int k = 1; k < G; k++) HIPCHK(hipStreamWaitEvent(grp[k].st, B->ev[0], 0)); }   // (the other streams: behind whatever the batch's stream still holds)
+    if (async_prepare && prepare_failed.load(std::memory_order_relaxed)) { rc_launch = 1; break; }   // a window's preparation failed: nothing of it (or of the groups behind it) is launched
+    if (g == 0) { HIPCHK(hipEventRecord(B->ev[0], s)); for (int k = 1; k < G; k++) HIPCHK(hipStreamWaitEvent(grp[k].st, B->ev[0], 0)); }   // (the other streams: behind whatever the batch's stream still holds; prepare()'s own uploads need no event: they are on the group's stream)
     HIPCHK(hipMemcpyAsync(B->d_wins + q.w0, B->h_wins + q.w0, sizeof(BAWinDev) * q.cnt, hipMemcpyHostToDevice, q.st));
     HIPCHK(hipMemcpyAsync(B->d_tab + B->tab_stride * (size_t)q.w0, B->h_tab + B->tab_stride * (size_t)q.w0, B->tab_stride * (size_t)(q.cnt - 1) + used_tab, hipMemcpyHostToDevice, q.st));
     if (g > 0) HIPCHK(hipStreamWaitEvent(q.st, B->gev[g - 1][0], 0));   // the stagger
@@ -2461,6 +2475,7 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
     chain(q, g, 1, 0, BA_GATE_ALWAYS, false);
   }
   if (async_prepare) {
+    asyncGuard.armed = false;
     const int r = B->workers.waitAsync();
     if (r || rc_launch) { for (int g = 0; g < G; g++) hipStreamSynchronize(grp[g].st); return r ? r : -1; }
   }
@@ -2576,7 +2591,9 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
     if (iterations) iterations[w] = b->iterations_done;
     if (trace) memcpy(trace + (size_t)256 * w, b->trace, sizeof(b->trace));
     b->sums_fresh = false; b->sys_ready = false;
-    if (b->bounce.used || !b->bounce.outs.empty()) HIPCHK(b->bounce.finish(s));   // the staging area of this call's uploads is free again
+    // the staging area of this call's uploads is free again: they went out on the group's stream in front of the group's last kernel, which `s` has waited for (gev[g][2])
+    // before the host waited for `s` above — so waiting for `s` covers them (and costs nothing more: a first host wait on each group's stream measured ~2 % of a W = 16 call)
+    if (b->bounce.used || !b->bounce.outs.empty()) HIPCHK(b->bounce.finish(s));
   }
   stamp(7);
   return 0;

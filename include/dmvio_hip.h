@@ -544,7 +544,12 @@ int dmvio_hip_ba_optimize_vio(dmvio_hip_ba* ba, int mnumOptIts, const dmvio_hip_
  * host round trip per iteration, two waits per call.  windows[W]: distinct handles of the batch's context, each with its window set; windows with different keyframe
  * counts run as separate groups.  rmse / finalEnergy / iterations: W entries (may be NULL); trace: W x 64 x 4 or NULL.  A window's result does not depend on the
  * other windows of the call (bit-identical to a batch of one).  Against dmvio_hip_ba_optimize's host-driven loop the device loop differs in the elementary functions of the
- * frame step (device sin / cos / exp within 1 ulp of the C library's) and, unless dmvio_hip_ba_batch_set_exact_backsub(1), in the association of the back substitution. */
+ * frame step (device sin / cos / exp within 1 ulp of the C library's) and, unless dmvio_hip_ba_batch_set_exact_backsub(1), in the association of the back substitution.
+ * The call may be REPEATED on the same handles without a new graph in between (any subset of them, in any order, through any batch object of the context, and mixed with
+ * the handles' own entry points): like FullSystem::optimize it leaves every window with its optimised states, the newest keyframe re-anchored (its evaluation point moved
+ * to the optimised pose, state and state_zero reset to the affine parameters alone; adjoints and pair tables recomputed) and the residuals that the final
+ * linearizeAll(true) found inactive removed.  The next call starts from that state and gives each window what a batch of that window alone gives after the same
+ * sequence of calls, bit for bit (tests/test_ba_batch_scale_gpu.py). */
 typedef struct dmvio_hip_ba_batch dmvio_hip_ba_batch;
 dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows);
 void dmvio_hip_ba_batch_destroy(dmvio_hip_ba_batch* batch);

@@ -307,6 +307,7 @@ struct OWindow {
   std::unique_ptr<WorkerPool> pool;
   // statistics
   double lastEnergyTrace[64][4];
+  double acceptMargin[64];   // per iteration of the last optimize(): (E_tried - E_before) / E_before, E = E_A + E_L + E_M — how far the accept test was from a tie (record only)
   int nIterationsDone = 0;
 
   void calibSetValue(const double v[4]) {
@@ -1288,6 +1289,7 @@ struct OWindow {
       double newEnergyL = calcLEnergy();
       double newEnergyM = calcMEnergy();
       const bool accept = S.forceAcceptStep || (newEnergy + newEnergyL + newEnergyM < lastEnergy + lastEnergyL + lastEnergyM);
+      if (iteration < 64) acceptMargin[iteration] = ((newEnergy + newEnergyL + newEnergyM) - (lastEnergy + lastEnergyL + lastEnergyM)) / (lastEnergy + lastEnergyL + lastEnergyM);
       if (accept) {
         for (int ri : activeResiduals) applyRes(res[ri]);
         lastEnergy = newEnergy; lastEnergyL = newEnergyL; lastEnergyM = newEnergyM;
@@ -1539,6 +1541,8 @@ float orc_ba_optimize(void* p, int mnumOptIts, double* finalEnergy, int* iterati
   if (trace) memcpy(trace, W->lastEnergyTrace, sizeof(W->lastEnergyTrace));
   return rmse;
 }
+// the accept test's relative margin of every iteration of the last orc_ba_optimize (accepted and rejected steps): out[64], the first `iterations` entries are valid
+void orc_ba_accept_margins(void* p, double* out) { memcpy(out, ((OWindow*)p)->acceptMargin, sizeof(double) * 64); }
 // one GN iteration body (FullSystemOptimize.cpp:485-586) for timing; returns 1 when the step was accepted
 int orc_ba_gn_iteration(void* p, int iteration, double* lambda_io, double lastE[3]) {
   OWindow* W = (OWindow*)p;

@@ -390,6 +390,7 @@ def _ba_sig(L):
     L.orc_ba_calc_menergy.restype = C.c_double; L.orc_ba_calc_menergy.argtypes = [vp]
     L.orc_ba_optimize.restype = C.c_float; L.orc_ba_optimize.argtypes = [vp, C.c_int, c_d, ci, c_d]
     L.orc_ba_gn_iteration.argtypes = [vp, C.c_int, c_d, c_d]
+    L.orc_ba_accept_margins.restype = None; L.orc_ba_accept_margins.argtypes = [vp, c_d]
     _BA_SIG = True
 
 
@@ -555,7 +556,9 @@ class BAWindow:
     def optimize(self, its=6):
         fe = C.c_double(0); it = C.c_int(0); tr = np.zeros((64, 4))
         rmse = self.L.orc_ba_optimize(self.p, its, C.byref(fe), C.byref(it), _d(tr))
-        return dict(rmse=rmse, finalEnergy=fe.value, iterations=it.value, trace=tr[:it.value + 1])
+        mg = np.zeros(64); self.L.orc_ba_accept_margins(self.p, _d(mg))
+        # margins[k]: (E_tried - E_before) / E_before of iteration k's accept test, E = E_A + E_L + E_M (negative: accepted); trace[k + 1] is that iteration's row
+        return dict(rmse=rmse, finalEnergy=fe.value, iterations=it.value, trace=tr[:it.value + 1], margins=mg[:it.value])
 
     def gn_iteration(self, iteration, lam, lastE):
         l = C.c_double(lam); e = np.array(lastE, dtype=np.float64)

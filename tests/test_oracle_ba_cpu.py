@@ -275,3 +275,52 @@ def test_marginalize_frame_is_schur_complement(oracle, synth):
         assert ev.min() > -1e-6 * max(ev.max(), 1e-12)
         assert (ev > 1e-9 * max(ev.max(), 1e-30)).sum() <= 8
         assert Hn.shape == (n - 8, n - 8) and np.allclose(Hn, Hn.T)
+
+
+def test_preconditions_of_the_batched_ba_gpu_tests(oracle):
+    """tests/test_ba_batch_scale_gpu.py compares the batched loop with the oracle only where the oracle's own accept test is not marginal (tests/ba_batch_cases.py: margin
+    >= 1e-3, ten times the 1e-4 energy bar), under caps that keep the rule from hiding a failure, and relies on the adjoint tables moving between calls.  With the oracle
+    alone, on the very inputs of those tests (calls of 3 iterations):
+    * the margin record agrees with the trace: margin < 0 exactly where the step was accepted (forceAcceptStep off), for every iteration of every call;
+    * the caps hold: at least 3/4 of the windows decidable over the whole first call, at least 2/3 over the whole second one (tests 1, 2; test 4's ten-keyframe windows: first call);
+    * the single windows that tests 5 and 6 compare with the oracle are decidable throughout their first call;
+    * the adjoint tables of every window move by more than 1e-3 in their largest entry over the first call (what the second call would read if its upload came late)."""
+    import math
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import ba_batch_cases as bc
+
+    def check(name, specs, calls, caps):
+        whole = [0] * calls
+        moved = []
+        smallest = np.inf
+        for sp in specs:
+            runs = bc.oracle_run(oracle, sp, calls)
+            for c, run in enumerate(runs):
+                m, tr = run["r"]["margins"], run["r"]["trace"]
+                assert len(m) == run["r"]["iterations"] == bc.ORACLE_ITS and len(tr) == len(m) + 1
+                assert np.array_equal(m < 0, tr[1:, 3] == 1), (name, sp, c, m, tr[:, 3])
+                smallest = min(smallest, np.abs(m).min())
+            for c, (_, _, w) in enumerate(bc.comparable(runs)):
+                whole[c] += int(w)
+            moved.append(runs[0]["adj_moved"])
+        print("%s: %d windows, decidable over the whole call: %s; smallest margin %.2e; adjoint tables move by %.2e .. %.2e over the first call"
+              % (name, len(specs), whole, smallest, min(moved), max(moved)))
+        for c, cap in enumerate(caps):
+            assert whole[c] >= math.ceil(cap * len(specs) - 1e-9), (name, c, whole, len(specs))
+        assert min(moved) > bc.ADJOINT_MOVE_MIN, (name, min(moved))
+        return whole
+
+    t1 = bc.repeated_calls_windows()
+    assert len(set(t1)) == 16
+    check("repeated calls (16 windows of 6 keyframes)", t1, 2, (bc.CAP_CALL1, bc.CAP_CALL2))
+    t2 = bc.benchmark_width_windows(64)
+    assert len(set(t2)) == 64
+    check("benchmark width (64 windows of 8 keyframes)", t2, 2, (bc.CAP_CALL1, bc.CAP_CALL2))
+    t4 = [s for s in bc.mixed_windows() if bc.case(s[0])["n_frames"] == 10]
+    assert len(t4) >= 8
+    check("mixed keyframe counts (windows of 10 keyframes)", t4, 1, (bc.CAP_CALL1,))
+    t6 = bc.kept_linearised_windows()
+    assert t6[4][2] == "lin" and t6[0][2] == "plain"
+    check("single windows of tests 5 and 6", [bc.uneven_windows()[0], t6[4], t6[0]], 1, (1.0,))
