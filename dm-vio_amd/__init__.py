@@ -189,6 +189,30 @@ def _sig(L):
     L.dmvio_hip_pixel_selector_get_passes.argtypes = [vp, C.c_int, c_i, c_i]
     L.dmvio_hip_pixel_selector_get_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.dmvio_hip_immature_add_selected.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.dmvio_hip_distance_map_create.restype = vp
+    L.dmvio_hip_distance_map_create.argtypes = [vp]
+    L.dmvio_hip_distance_map_destroy.argtypes = [vp]
+    L.dmvio_hip_distance_map_destroy.restype = None
+    L.dmvio_hip_distance_map_size.argtypes = [vp, c_i, c_i]
+    L.dmvio_hip_distance_map_tables_from_poses.argtypes = [c_d, C.c_int, c_d, c_d, c_f, c_f]
+    L.dmvio_hip_distance_map_make.argtypes = [vp, C.c_int, c_f, c_f, C.c_int, c_i, c_f, c_f, c_f]
+    L.dmvio_hip_distance_map_add.argtypes = [vp, C.c_int, C.c_int]
+    L.dmvio_hip_distance_map_get.argtypes = [vp, c_f]
+    L.dmvio_hip_immature_set_types.argtypes = [vp, c_f]
+    L.dmvio_hip_immature_get_types.argtypes = [vp, c_f]
+    L.dmvio_hip_immature_select_for_activation.argtypes = [vp, vp, C.c_int, c_f, c_f, c_u8, C.c_int, C.c_float, C.c_float, c_i, c_i]
+    L.dmvio_hip_immature_get_activation_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.dmvio_hip_immature_get_activation.argtypes = [vp, c_i, c_i]
+    L.dmvio_hip_immature_get_marks.argtypes = [vp, c_u8]
+    L.dmvio_hip_immature_set_activation_walk.argtypes = [vp, C.c_int]
+    L.dmvio_hip_immature_optimize_selected.argtypes = [vp, C.c_int, c_i, c_d, c_d, c_f, c_d, C.c_int, c_i, c_f, c_i]
+    L.dmvio_hip_immature_get_activated.argtypes = [vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i]
+    L.dmvio_hip_immature_remove_marked.argtypes = [vp]
+    L.dmvio_hip_immature_set_last_trace.argtypes = [vp, c_f, c_f]
+    L.dmvio_hip_immature_mark_optimized.argtypes = [vp, c_i]
+    L.dmvio_hip_immature_remove_host.argtypes = [vp, C.c_int]
+    L.dmvio_hip_min_act_dist_update.argtypes = [C.c_float, C.c_int, C.c_float]
+    L.dmvio_hip_min_act_dist_update.restype = C.c_float
 
 
 def load_library():
@@ -778,6 +802,169 @@ class ImmaturePointsHip:
                                                         new_exposure, H, _d(host_c2w7), _d(ha), _f(he), _d(np.ascontiguousarray(fxfycxcy, dtype=np.float64)), _i(counts)),
              "trace_new_coarse")
         return dict(zip(("good", "oob", "outlier", "skipped", "badcondition", "uninitialized"), counts.tolist()))
+
+
+    # ---- point activation (FullSystem::activatePointsMT) ----
+    def get_types(self):
+        t = np.zeros(self.n, np.float32)
+        _chk(self.L, self.L.dmvio_hip_immature_get_types(self.p, _f(t)), "immature_get_types")
+        return t
+
+    def set_types(self, my_type):
+        t = np.ascontiguousarray(my_type, dtype=np.float32)
+        if t.size != self.n:
+            raise HipLibraryError("immature_set_types: need %d values, got %d" % (self.n, t.size))
+        _chk(self.L, self.L.dmvio_hip_immature_set_types(self.p, _f(t)), "immature_set_types")
+
+    def set_last_trace(self, lastTraceUV=None, lastTracePixelInterval=None):
+        a = None if lastTraceUV is None else np.ascontiguousarray(lastTraceUV, dtype=np.float32)
+        b = None if lastTracePixelInterval is None else np.ascontiguousarray(lastTracePixelInterval, dtype=np.float32)
+        _chk(self.L, self.L.dmvio_hip_immature_set_last_trace(self.p, None if a is None else _f(a), None if b is None else _f(b)), "immature_set_last_trace")
+
+    def mark_optimized(self, result):
+        """The marks of FullSystem.cpp:732-756 from results computed elsewhere: result[k] of toOptimize[k]."""
+        r = np.ascontiguousarray(result, dtype=np.int32)
+        _chk(self.L, self.L.dmvio_hip_immature_mark_optimized(self.p, _i(r)), "immature_mark_optimized")
+
+    def set_activation_walk(self, global_memory):
+        """False: the ordered walk keeps the map in LDS when it fits (default); True: always in global memory.  Same results."""
+        _chk(self.L, self.L.dmvio_hip_immature_set_activation_walk(self.p, int(bool(global_memory))), "immature_set_activation_walk")
+
+    def select_for_activation(self, dmap, KRKi, Kt, host_flagged, newest_tag, minActDist, minTraceQuality=3.0):
+        """The candidate loop of FullSystem::activatePointsMT against dmap (made for the same keyframe).  -> (n_selected, n_deleted)"""
+        KRKi = np.ascontiguousarray(KRKi, dtype=np.float32).reshape(-1, 9); Kt = np.ascontiguousarray(Kt, dtype=np.float32).reshape(-1, 3)
+        fl = np.ascontiguousarray(host_flagged, dtype=np.uint8)
+        if len(fl) != len(KRKi) or len(Kt) != len(KRKi):
+            raise HipLibraryError("immature_select_for_activation: KRKi, Kt and host_flagged need one row per host")
+        ns = np.zeros(1, np.int32); nd = np.zeros(1, np.int32)
+        _chk(self.L, self.L.dmvio_hip_immature_select_for_activation(self.p, dmap.p, len(KRKi), _f(KRKi), _f(Kt), fl.ctypes.data_as(c_u8), int(newest_tag), float(minActDist),
+                                                                      float(minTraceQuality), _i(ns), _i(nd)), "immature_select_for_activation")
+        return int(ns[0]), int(nd[0])
+
+    def activation_stats(self):
+        s = (C.c_longlong * 4)()
+        _chk(self.L, self.L.dmvio_hip_immature_get_activation_stats(self.p, s), "immature_get_activation_stats")
+        return dict(classified=int(s[0]), walk_length=int(s[1]), accepted=int(s[2]), deleted=int(s[3]))
+
+    def get_activation(self):
+        """-> (decision per point: 0 stays / 1 selected / 2 deleted, order: handle index of toOptimize[k])"""
+        n = self.n
+        dec = np.zeros(n, np.int32); order = np.zeros(n, np.int32)
+        k = _chk(self.L, self.L.dmvio_hip_immature_get_activation(self.p, _i(dec), _i(order)), "immature_get_activation")
+        return dec, order[:k].copy()
+
+    def get_marks(self):
+        m = np.zeros(max(self.n, 1), np.uint8)
+        _chk(self.L, self.L.dmvio_hip_immature_get_marks(self.p, m.ctypes.data_as(c_u8)), "immature_get_marks")
+        return m[:self.n].astype(bool)
+
+    def optimize_selected(self, frame_slots, w2c7, fxfycxcy, aff=None, exposure=None, min_obs=1):
+        """optimize() for the device-resident selection; -> (result, idepth, res_state[n_selected, F]) in toOptimize order.  Marks the points that leave the handle."""
+        slots = np.ascontiguousarray(frame_slots, dtype=np.int32); F = len(slots)
+        w2c7 = np.ascontiguousarray(w2c7, dtype=np.float64).reshape(F, 7)
+        a = np.zeros((F, 2)) if aff is None else np.ascontiguousarray(aff, dtype=np.float64)
+        e = np.ones(F, np.float32) if exposure is None else np.ascontiguousarray(exposure, dtype=np.float32)
+        ns = _chk(self.L, self.L.dmvio_hip_immature_get_activation(self.p, None, None), "immature_get_activation")
+        result = np.zeros(max(ns, 1), np.int32); idepth = np.zeros(max(ns, 1), np.float32); res_state = np.zeros((max(ns, 1), F), np.int32)
+        self.n_activated = _chk(self.L, self.L.dmvio_hip_immature_optimize_selected(self.p, F, _i(slots), _d(w2c7), _d(a), _f(e),
+                                                                                   _d(np.ascontiguousarray(fxfycxcy, dtype=np.float64)), min_obs, _i(result), _f(idepth),
+                                                                                   _i(res_state)), "immature_optimize_selected")
+        self._last_F = F
+        return result[:ns], idepth[:ns], res_state[:ns]
+
+    def get_activated(self):
+        """The activated points of the last optimize_selected in toOptimize order: what the PointHessian constructor copies, the optimised idepth, the residual states."""
+        k = max(int(getattr(self, "n_activated", 0)), 1); F = int(getattr(self, "_last_F", 8))
+        o = dict(host=np.zeros(k, np.int32), u=np.zeros(k, np.float32), v=np.zeros(k, np.float32), my_type=np.zeros(k, np.float32), idepth_min=np.zeros(k, np.float32),
+                 idepth_max=np.zeros(k, np.float32), color=np.zeros((k, 8), np.float32), weights=np.zeros((k, 8), np.float32), energyTH=np.zeros(k, np.float32),
+                 idepth=np.zeros(k, np.float32), res_state=np.zeros((k, F), np.int32))
+        n = _chk(self.L, self.L.dmvio_hip_immature_get_activated(self.p, _i(o["host"]), _f(o["u"]), _f(o["v"]), _f(o["my_type"]), _f(o["idepth_min"]), _f(o["idepth_max"]),
+                                                                  _f(o["color"]), _f(o["weights"]), _f(o["energyTH"]), _f(o["idepth"]), _i(o["res_state"])),
+                 "immature_get_activated")
+        return {key: val[:n] for key, val in o.items()}
+
+    def remove_marked(self):
+        """FullSystem.cpp:759-770 on the device; -> new number of points"""
+        return _chk(self.L, self.L.dmvio_hip_immature_remove_marked(self.p), "immature_remove_marked")
+
+    def remove_host(self, tag):
+        return _chk(self.L, self.L.dmvio_hip_immature_remove_host(self.p, int(tag)), "immature_remove_host")
+
+
+class DistanceMapHip:
+    """Mirror of CoarseDistanceMap (CoarseTracker.cpp:903-1115) at pyramid level 1: makeDistanceMap, addIntoDistFinal, fwdWarpedIDDistFinal."""
+
+    def __init__(self, ctx):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_distance_map_create(ctx.p)
+        if not p:
+            raise HipLibraryError("dmvio_hip_distance_map_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.w1, self.h1 = ctx.w >> 1, ctx.h >> 1
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_distance_map_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def make(self, KRKi, Kt, host_tag, u, v, idepth_scaled):
+        KRKi = np.ascontiguousarray(KRKi, dtype=np.float32).reshape(-1, 9); Kt = np.ascontiguousarray(Kt, dtype=np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(host_tag, dtype=np.int32)
+        a = [np.ascontiguousarray(x, dtype=np.float32) for x in (u, v, idepth_scaled)]
+        _chk(self.L, self.L.dmvio_hip_distance_map_make(self.p, len(KRKi), _f(KRKi), _f(Kt), len(t), _i(t), _f(a[0]), _f(a[1]), _f(a[2])), "distance_map_make")
+
+    def add(self, u, v):
+        _chk(self.L, self.L.dmvio_hip_distance_map_add(self.p, int(u), int(v)), "distance_map_add")
+
+    def get(self):
+        m = np.zeros(self.w1 * self.h1, np.float32)
+        _chk(self.L, self.L.dmvio_hip_distance_map_get(self.p, _f(m)), "distance_map_get")
+        return m.reshape(self.h1, self.w1)
+
+
+def distance_map_tables(new_w2c7, host_c2w7, fxfycxcy):
+    """KRKi = K[1] * R * Ki[0], Kt = K[1] * t of every host against the newest keyframe (CoarseTracker.cpp:949-951); host only"""
+    L = load_library()
+    host_c2w7 = np.ascontiguousarray(host_c2w7, dtype=np.float64).reshape(-1, 7)
+    H = len(host_c2w7)
+    KRKi = np.zeros((H, 9), np.float32); Kt = np.zeros((H, 3), np.float32)
+    _chk(L, L.dmvio_hip_distance_map_tables_from_poses(_d(np.ascontiguousarray(new_w2c7, dtype=np.float64)), H, _d(host_c2w7),
+                                                        _d(np.ascontiguousarray(fxfycxcy, dtype=np.float64)), _f(KRKi), _f(Kt)), "distance_map_tables_from_poses")
+    return KRKi, Kt
+
+
+def min_act_dist_update(cur, n_points, desired_density=2000.0):
+    """currentMinActDist after the controller of FullSystem.cpp:608-627"""
+    return float(load_library().dmvio_hip_min_act_dist_update(float(cur), int(n_points), float(desired_density)))
+
+
+def activate_points(imm, dmap, frame_slots, w2c7, fxfycxcy, active, host_flagged=None, minActDist=2.0, minTraceQuality=3.0, aff=None, exposure=None, min_obs=1):
+    """FullSystem::activatePointsMT after its controller: tables -> makeDistanceMap -> candidate loop -> optimizeImmaturePoint -> compaction, the candidates never leaving
+    the device.  The newest keyframe is the last of frame_slots; host_tag of a point = its keyframe's index.  active: dict(host, u, v, idepth) of the window's
+    active points.  -> dict(activated=records of get_activated(), result, idepth, res_state, order, decision, n_deleted, n_points)"""
+    F = len(frame_slots)
+    w2c7 = np.ascontiguousarray(w2c7, dtype=np.float64).reshape(F, 7)
+    c2w = np.zeros((F, 7))
+    for k in range(F):
+        q = w2c7[k, 3:7]; t = w2c7[k, :3]
+        x, y, z, w = q
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        c2w[k, :3] = -R.T @ t; c2w[k, 3:6] = -q[:3]; c2w[k, 6] = q[3]
+    KRKi, Kt = distance_map_tables(w2c7[F - 1], c2w, fxfycxcy)
+    dmap.make(KRKi, Kt, active["host"], active["u"], active["v"], active["idepth"])
+    fl = np.zeros(F, np.uint8) if host_flagged is None else host_flagged
+    n_sel, n_del = imm.select_for_activation(dmap, KRKi, Kt, fl, F - 1, minActDist, minTraceQuality)
+    decision, order = imm.get_activation()
+    result, idepth, res_state = imm.optimize_selected(frame_slots, w2c7, fxfycxcy, aff=aff, exposure=exposure, min_obs=min_obs)
+    rec = imm.get_activated()
+    n = imm.remove_marked()
+    return dict(activated=rec, result=result, idepth=idepth, res_state=res_state, order=order, decision=decision, n_deleted=n_del, n_points=n)
 
 
 class PixelSelectorHip:

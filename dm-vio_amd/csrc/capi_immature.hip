@@ -6,40 +6,9 @@
 #include "internal.h"
 #include "lie_dev.h"
 #include "immature_kernels.hpp"
+#include "immature_handle.h"
 
 using namespace dmv;
-
-struct dmvio_hip_immature {
-  dmvio_hip_ctx* ctx = nullptr;
-  int capacity = 0, n = 0, max_tag = -1;   // max_tag: largest host_tag among the points (validated against the tables of a call)
-  ImmaturePts P{};
-  ImmatureSettings S;
-  float* d_tables = nullptr;   // [KRKi 9H | Kt 3H | aff 2H], H <= 64
-  float* h_tables = nullptr;   // pinned
-  int* h_counts = nullptr;     // pinned: status histogram of the last traceNewCoarse, written by k_status_hist
-  int* d_uv_stage = nullptr;   // 2 x capacity ints
-  float* d_opt_tables = nullptr;   // [R 9 F*F | t 3 F*F | aff 2 F*F], F <= 8
-  float* h_opt_tables = nullptr;
-  int *d_result = nullptr, *d_res_state = nullptr;
-  float* d_idepth = nullptr;
-  unsigned char* d_select = nullptr;
-  DmvBounce bounce;            // caller-owned arrays cross PCIe through the library's pinned memory (internal.h)
-  std::vector<void*> allocs;
-};
-
-#define IMM_READY(m) do { if (!(m)) return failmsg("null immature handle"); HIPCHK(hipSetDevice((m)->ctx->device)); } while (0)
-enum { IMM_MAX_HOSTS = 64 };
-
-template <class T>
-static int ialloc(dmvio_hip_immature* m, T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, sizeof(T) * std::max<size_t>(n, 1)));
-  HIPCHK(hipMemset(*p, 0, sizeof(T) * std::max<size_t>(n, 1)));
-  // hipMemset clears on the NULL stream without blocking the host, and the handle's stream is non-blocking: without this wait an upload enqueued next could
-  // land before the clear does (seen with two processes sharing a GPU)
-  HIPCHK(hipStreamSynchronize(nullptr));
-  m->allocs.push_back(*p);
-  return 0;
-}
 
 extern "C" {
 
@@ -48,14 +17,16 @@ dmvio_hip_immature* dmvio_hip_immature_create(dmvio_hip_ctx* ctx, int capacity) 
   if (hipSetDevice(ctx->device) != hipSuccess) { failmsg("immature_create: hipSetDevice failed"); return nullptr; }
   dmvio_hip_immature* m = new dmvio_hip_immature();
   m->ctx = ctx; m->capacity = capacity;
-  ImmaturePts& P = m->P;
   const size_t c = capacity;
-  if (ialloc(m, &P.u, c) || ialloc(m, &P.v, c) || ialloc(m, &P.host, c) || ialloc(m, &P.color, 8 * c) || ialloc(m, &P.weights, 8 * c) || ialloc(m, &P.gradH, 4 * c) ||
-      ialloc(m, &P.energyTH, c) || ialloc(m, &P.idepth_min, c) || ialloc(m, &P.idepth_max, c) || ialloc(m, &P.quality, c) || ialloc(m, &P.lastTraceUV, 2 * c) ||
-      ialloc(m, &P.lastTracePixelInterval, c) || ialloc(m, &P.lastTraceStatus, c) || ialloc(m, &m->d_tables, 14 * IMM_MAX_HOSTS) || ialloc(m, &m->d_uv_stage, 2 * c) || ialloc(m, &m->d_opt_tables, 14 * 64) || ialloc(m, &m->d_result, c) || ialloc(m, &m->d_res_state, 8 * c) ||
-      ialloc(m, &m->d_idepth, c) || ialloc(m, &m->d_select, c) || hipHostMalloc((void**)&m->h_opt_tables, sizeof(float) * 14 * 64, hipHostMallocDefault) != hipSuccess ||
+  // two sets of per-point arrays: dmvio_hip_immature_remove_marked compacts from one into the other
+  if (dmv_immature_alloc_pts(m, m->P) || dmv_immature_alloc_pts(m, m->P2) || ialloc(m, &m->d_tables, 14 * IMM_MAX_HOSTS) || ialloc(m, &m->d_uv_stage, 2 * c) ||
+      ialloc(m, &m->d_opt_tables, 14 * 64) || ialloc(m, &m->d_result, c) || ialloc(m, &m->d_res_state, 8 * c) || ialloc(m, &m->d_idepth, c) || ialloc(m, &m->d_select, c) ||
+      ialloc(m, &m->d_decision, c) || ialloc(m, &m->d_mark, c) || ialloc(m, &m->d_act_select, c) || ialloc(m, &m->d_order, c) || ialloc(m, &m->d_surv, c) || ialloc(m, &m->d_pidx, c) || ialloc(m, &m->d_frac, c) ||
+      ialloc(m, &m->d_thr, c) || ialloc(m, &m->d_newidx, c) || ialloc(m, &m->d_holes, c) || ialloc(m, &m->d_act_counts, 8 + IMM_MAX_HOSTS) ||
+      ialloc(m, &m->d_gather_i, (size_t)(2 + 8) * c) || ialloc(m, &m->d_gather_f, (size_t)(7 + 16) * c) ||
+      hipHostMalloc((void**)&m->h_opt_tables, sizeof(float) * 14 * 64, hipHostMallocDefault) != hipSuccess ||
       hipHostMalloc((void**)&m->h_tables, sizeof(float) * 14 * IMM_MAX_HOSTS, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&m->h_counts, sizeof(int) * 8, hipHostMallocDefault) != hipSuccess) {
+      hipHostMalloc((void**)&m->h_counts, sizeof(int) * (16 + IMM_MAX_HOSTS), hipHostMallocDefault) != hipSuccess) {
     for (void* p : m->allocs) hipFree(p);
     delete m;
     return nullptr;
@@ -73,7 +44,7 @@ void dmvio_hip_immature_destroy(dmvio_hip_immature* m) {
   m->bounce.release();
   delete m;
 }
-int dmvio_hip_immature_clear(dmvio_hip_immature* m) { IMM_READY(m); m->n = 0; m->max_tag = -1; return 0; }
+int dmvio_hip_immature_clear(dmvio_hip_immature* m) { IMM_READY(m); m->n = 0; m->max_tag = -1; m->have_selection = false; m->n_selected = m->n_activated = 0; return 0; }
 int dmvio_hip_immature_count(dmvio_hip_immature* m) { return m ? m->n : -1; }
 
 int dmvio_hip_immature_add_points(dmvio_hip_immature* m, int host_tag, int host_slot, int n, const int* u, const int* v) {
@@ -127,6 +98,7 @@ int dmvio_hip_immature_add_selected(dmvio_hip_immature* m, int host_tag, int hos
   HIPCHK(hipMemcpyAsync(m->P.v + first, d_v, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   m->P.n = first + n;
   hipLaunchKernelGGL(k_immature_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->levelPtr(host_slot, 0), c->w, first, n, m->P, host_tag, m->S);
+  hipLaunchKernelGGL(k_immature_types_from_map, dim3((n + 255) / 256), dim3(256), 0, c->stream, dmv_selector_map(sel), c->w, first, n, m->P);
   HIPCHK(hipGetLastError());
   m->n = first + n;
   m->max_tag = std::max(m->max_tag, host_tag);
@@ -213,25 +185,9 @@ int dmvio_hip_trace_new_coarse(dmvio_hip_immature* m, int new_slot, const double
   IMM_READY(m);
   if (!new_w2c7 || !new_aff || !host_c2w7 || !host_aff2 || !host_exposure || !fxfycxcy || n_hosts < 1 || n_hosts > IMM_MAX_HOSTS) return failmsg("trace_new_coarse: bad argument");
   std::vector<float> KRKi(9 * (size_t)n_hosts), Kt(3 * (size_t)n_hosts), aff(2 * (size_t)n_hosts);
-  const float fx = (float)fxfycxcy[0], fy = (float)fxfycxcy[1], cx = (float)fxfycxcy[2], cy = (float)fxfycxcy[3];
-  const float K[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1};
-  // K.inverse(): Eigen's 3x3 cofactor inverse
-  const float a = K[0], e = K[4], cc = K[2], ff = K[5];
-  const float det = a * (e * 1.0f - ff * 0.0f), invdet = 1.0f / det;
-  const float Ki[9] = {(e * 1.0f - ff * 0.0f) * invdet, (cc * 0.0f - 0.0f * 1.0f) * invdet, (0.0f * ff - cc * e) * invdet,
-                       (ff * 0.0f - 0.0f * 1.0f) * invdet, (a * 1.0f - cc * 0.0f) * invdet, (cc * 0.0f - a * ff) * invdet,
-                       (0.0f * 0.0f - e * 0.0f) * invdet, (0.0f * 0.0f - a * 0.0f) * invdet, (a * e - 0.0f * 0.0f) * invdet};
-  const Pose Tn = poseFrom7(new_w2c7);
+  const float K[9] = {(float)fxfycxcy[0], 0, (float)fxfycxcy[2], 0, (float)fxfycxcy[1], (float)fxfycxcy[3], 0, 0, 1};
+  dmv_host_tables(K, fxfycxcy, new_w2c7, n_hosts, host_c2w7, KRKi.data(), Kt.data());
   for (int hI = 0; hI < n_hosts; hI++) {
-    const Pose T = poseMul(Tn, poseFrom7(host_c2w7 + 7 * hI));
-    double Rd[9];
-    quatToR(T.q, Rd);
-    float R[9], t[3], KR[9];
-    for (int i = 0; i < 9; i++) R[i] = (float)Rd[i];
-    for (int i = 0; i < 3; i++) t[i] = (float)T.t[i];
-    for (int r = 0; r < 3; r++) for (int q = 0; q < 3; q++) KR[r * 3 + q] = K[r * 3 + 0] * R[q] + K[r * 3 + 1] * R[3 + q] + K[r * 3 + 2] * R[6 + q];
-    for (int r = 0; r < 3; r++) for (int q = 0; q < 3; q++) KRKi[9 * hI + r * 3 + q] = KR[r * 3 + 0] * Ki[q] + KR[r * 3 + 1] * Ki[3 + q] + KR[r * 3 + 2] * Ki[6 + q];
-    for (int r = 0; r < 3; r++) Kt[3 * hI + r] = K[r * 3 + 0] * t[0] + K[r * 3 + 1] * t[1] + K[r * 3 + 2] * t[2];
     double ab[2];
     affFromTo(host_exposure[hI], new_exposure, host_aff2[2 * hI], host_aff2[2 * hI + 1], new_aff[0], new_aff[1], ab);
     aff[2 * hI] = (float)ab[0]; aff[2 * hI + 1] = (float)ab[1];
@@ -258,7 +214,23 @@ int dmvio_hip_immature_optimize(dmvio_hip_immature* m, int F, const int* frame_s
   IMM_READY(m);
   dmvio_hip_ctx* c = m->ctx;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (F < 2 || F > 8 || !frame_slots || !w2c7 || !aff2 || !exposure || !fxfycxcy || !result || !idepth) return failmsg("immature_optimize: bad argument");
+  if (!result || !idepth) return failmsg("immature_optimize: bad argument");
+  if (m->n == 0) return 0;
+  if (select) HIPCHK(m->bounce.h2d(m->d_select, select, m->n, c->stream));
+  if (int r = dmv_immature_optimize_launch_locked(m, F, frame_slots, w2c7, aff2, exposure, fxfycxcy, select ? m->d_select : nullptr, minObs)) return r;
+  HIPCHK(m->bounce.d2h(result, m->d_result, sizeof(int) * m->n, c->stream));
+  HIPCHK(m->bounce.d2h(idepth, m->d_idepth, sizeof(float) * m->n, c->stream));
+  if (res_state) HIPCHK(m->bounce.d2h(res_state, m->d_res_state, sizeof(int) * (size_t)m->n * F, c->stream));
+  HIPCHK(m->bounce.finish(c->stream));
+  return 0;
+}
+
+}  // extern "C"
+
+int dmv_immature_optimize_launch_locked(dmvio_hip_immature* m, int F, const int* frame_slots, const double* w2c7, const double* aff2, const float* exposure,
+                                        const double fxfycxcy[4], const unsigned char* d_mask, int minObs) {
+  dmvio_hip_ctx* c = m->ctx;
+  if (F < 2 || F > 8 || !frame_slots || !w2c7 || !aff2 || !exposure || !fxfycxcy) return failmsg("immature_optimize: bad argument");
   if (m->n == 0) return 0;
   if (m->max_tag >= F) return failmsg("immature_optimize: a point's host_tag is not a keyframe index of this window (host_tag >= F)");
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -290,16 +262,31 @@ int dmvio_hip_immature_optimize(dmvio_hip_immature* m, int F, const int* frame_s
   T.R = m->d_opt_tables; T.t = m->d_opt_tables + 9 * 64; T.aff = m->d_opt_tables + 12 * 64;
   T.fxl = (float)fxfycxcy[0]; T.fyl = (float)fxfycxcy[1]; T.cxl = (float)fxfycxcy[2]; T.cyl = (float)fxfycxcy[3];
   T.fxli = 1.0f / T.fxl; T.fyli = 1.0f / T.fyl;   // CalibHessian::setValueScaled (HessianBlocks.h:373-387)
-  if (select) HIPCHK(m->bounce.h2d(m->d_select, select, m->n, c->stream));
   m->P.n = m->n;
-  hipLaunchKernelGGL(k_immature_optimize, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->fs, c->w, c->h, m->P, T, select ? m->d_select : nullptr, minObs,
+  hipLaunchKernelGGL(k_immature_optimize, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->fs, c->w, c->h, m->P, T, d_mask, minObs,
                      100.0f /* setting_minIdepthH_act */, 3 /* setting_GNItsOnPointActivation */, m->S.huberTH, m->d_result, m->d_idepth, m->d_res_state);
   HIPCHK(hipGetLastError());
-  HIPCHK(m->bounce.d2h(result, m->d_result, sizeof(int) * m->n, c->stream));
-  HIPCHK(m->bounce.d2h(idepth, m->d_idepth, sizeof(float) * m->n, c->stream));
-  if (res_state) HIPCHK(m->bounce.d2h(res_state, m->d_res_state, sizeof(int) * (size_t)m->n * F, c->stream));
-  HIPCHK(m->bounce.finish(c->stream));
   return 0;
 }
 
-}  // extern "C"
+void dmv_host_tables(const float K[9], const double fxfycxcy[4], const double new_w2c7[7], int n_hosts, const double* host_c2w7, float* KRKi, float* Kt) {
+  const float fx = (float)fxfycxcy[0], fy = (float)fxfycxcy[1], cx = (float)fxfycxcy[2], cy = (float)fxfycxcy[3];
+  // K0.inverse(): Eigen's 3x3 cofactor inverse
+  const float a = fx, e = fy, cc = cx, ff = cy;
+  const float det = a * (e * 1.0f - ff * 0.0f), invdet = 1.0f / det;
+  const float Ki[9] = {(e * 1.0f - ff * 0.0f) * invdet, (cc * 0.0f - 0.0f * 1.0f) * invdet, (0.0f * ff - cc * e) * invdet,
+                       (ff * 0.0f - 0.0f * 1.0f) * invdet, (a * 1.0f - cc * 0.0f) * invdet, (cc * 0.0f - a * ff) * invdet,
+                       (0.0f * 0.0f - e * 0.0f) * invdet, (0.0f * 0.0f - a * 0.0f) * invdet, (a * e - 0.0f * 0.0f) * invdet};
+  const Pose Tn = poseFrom7(new_w2c7);
+  for (int hI = 0; hI < n_hosts; hI++) {
+    const Pose T = poseMul(Tn, poseFrom7(host_c2w7 + 7 * hI));
+    double Rd[9];
+    quatToR(T.q, Rd);
+    float R[9], t[3], KR[9];
+    for (int i = 0; i < 9; i++) R[i] = (float)Rd[i];
+    for (int i = 0; i < 3; i++) t[i] = (float)T.t[i];
+    for (int r = 0; r < 3; r++) for (int q = 0; q < 3; q++) KR[r * 3 + q] = K[r * 3 + 0] * R[q] + K[r * 3 + 1] * R[3 + q] + K[r * 3 + 2] * R[6 + q];
+    for (int r = 0; r < 3; r++) for (int q = 0; q < 3; q++) KRKi[9 * hI + r * 3 + q] = KR[r * 3 + 0] * Ki[q] + KR[r * 3 + 1] * Ki[3 + q] + KR[r * 3 + 2] * Ki[6 + q];
+    for (int r = 0; r < 3; r++) Kt[3 * hI + r] = K[r * 3 + 0] * t[0] + K[r * 3 + 1] * t[1] + K[r * 3 + 2] * t[2];
+  }
+}

@@ -294,3 +294,4 @@ int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, c
   *ctx = s->ctx; *d_u = s->d_wu; *d_v = s->d_wv;
   return s->n_window;
 }
+const unsigned char* dmv_selector_map(dmvio_hip_pixel_selector* s) { return s->d_map; }

@@ -9,30 +9,9 @@
 #pragma once
 #include "common.h"
 #include "interp.hpp"
+#include "immature_types.hpp"
 
 namespace dmv {
-
-enum { IPS_GOOD = 0, IPS_OOB, IPS_OUTLIER, IPS_SKIPPED, IPS_BADCONDITION, IPS_UNINITIALIZED };
-
-struct ImmaturePts {
-  int n;
-  // static part (constructor)
-  float *u, *v;              // pixel position in the host (integers stored as float, ImmaturePoint.h:66)
-  int* host;                 // index into the per-host tables of a trace call
-  float *color, *weights;    // n x 8
-  float* gradH;              // n x 4 (00 01 10 11)
-  float* energyTH;
-  // mutable part
-  float *idepth_min, *idepth_max, *quality, *lastTraceUV /* n x 2 */, *lastTracePixelInterval;
-  int* lastTraceStatus;
-};
-
-struct ImmatureSettings {
-  float outlierTH = 12 * 12, outlierTHSumComponent = 50 * 50, overallEnergyTHWeight = 1;
-  float maxPixSearch = 0.027f, huberTH = 9;
-  int minTraceTestRadius = 2, GNIterations = 3;
-  float stepsize = 1.0f, GNThreshold = 0.1f, extraSlackOnTH = 1.2f, slackInterval = 1.5f, minImprovementFactor = 2;
-};
 
 // status histogram of FullSystem::traceNewCoarse's printout / bookkeeping (FullSystem.cpp:562-583): one workgroup, counts stored straight into
 // pinned host memory (out6)
@@ -119,6 +98,15 @@ __global__ void __launch_bounds__(256) k_immature_init(const float* __restrict__
   P.idepth_min[i] = 0.f; P.idepth_max[i] = NAN; P.quality[i] = 10000.f;
   P.lastTraceUV[2 * i] = 0.f; P.lastTraceUV[2 * i + 1] = 0.f; P.lastTracePixelInterval[i] = 0.f;
   P.lastTraceStatus[i] = IPS_UNINITIALIZED;
+  P.my_type[i] = 1.f;
+}
+
+// my_type of the points [first, first + n) from the selector's status map (FullSystem::makeNewTraces passes selectionMap[i], FullSystem.cpp:1660)
+__global__ void __launch_bounds__(256) k_immature_types_from_map(const unsigned char* __restrict__ map, const int w, const int first, const int n, const ImmaturePts P) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int i = first + k;
+  P.my_type[i] = (float)map[(int)P.u[i] + (int)P.v[i] * w];
 }
 
 // first-minimum argmin over the wave: (value, index) with the reference's strict '<' scan order (smallest index among equal minima)

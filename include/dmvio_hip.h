@@ -693,6 +693,72 @@ int dmvio_hip_pixel_selector_get_stats(dmvio_hip_pixel_selector* sel, long long 
  * dmvio_hip_immature_count then tells how many were added. */
 int dmvio_hip_immature_add_selected(dmvio_hip_immature* imm, int host_tag, int host_slot, dmvio_hip_pixel_selector* sel);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Point activation: which immature points become active points, chosen on the device.
+ *   CoarseDistanceMap::makeK            src/dso/FullSystem/CoarseTracker.cpp:1086-1115  -> dmvio_hip_distance_map_tables_from_poses
+ *   CoarseDistanceMap::makeDistanceMap  src/dso/FullSystem/CoarseTracker.cpp:931-967    -> dmvio_hip_distance_map_make
+ *   CoarseDistanceMap::growDistBFS      src/dso/FullSystem/CoarseTracker.cpp:979-1073   (inside make / add / select_for_activation)
+ *   CoarseDistanceMap::addIntoDistFinal src/dso/FullSystem/CoarseTracker.cpp:1076-1082  -> dmvio_hip_distance_map_add
+ *   FullSystem::activatePointsMT        src/dso/FullSystem/FullSystem.cpp:604-773       -> dmvio_hip_min_act_dist_update (:608-627), dmvio_hip_immature_select_for_activation
+ *     (:646-717), dmvio_hip_immature_optimize_selected (:723-756), dmvio_hip_immature_remove_marked (:759-770)
+ * The map has the size of pyramid level 1, (w>>1, h>>1); values are the reference's: 0..39, or 1000 where no point is within 39 steps.  Every result is an integer or
+ * a copied float and equals the reference's. */
+typedef struct dmvio_hip_distance_map dmvio_hip_distance_map;
+dmvio_hip_distance_map* dmvio_hip_distance_map_create(dmvio_hip_ctx* ctx);
+void dmvio_hip_distance_map_destroy(dmvio_hip_distance_map* dm);
+/* returns w1*h1 */
+int dmvio_hip_distance_map_size(dmvio_hip_distance_map* dm, int* w1, int* h1);
+/* the per-host rows KRKi = K[1] * R * Ki[0], Kt = K[1] * t of hostToNew = new_w2c * host_c2w (CoarseTracker.cpp:949-951, FullSystem.cpp:650-652), floats, with the level
+ * tables of makeK: fx[1] = fx[0]*0.5, cx[1] = (cx[0]+0.5)/2-0.5, Ki[0] the 3x3 cofactor inverse.  Host only. */
+int dmvio_hip_distance_map_tables_from_poses(const double new_w2c7[7], int n_hosts, const double* host_c2w7, const double fxfycxcy[4], float* KRKi9, float* Kt3);
+/* makeDistanceMap: the map is filled with 1000, every active point (host_tag = row of the tables, u, v, PointHessian::idepth_scaled) is projected into the newest
+ * keyframe's level 1 and seeds a 0; 39 growth steps follow */
+int dmvio_hip_distance_map_make(dmvio_hip_distance_map* dm, int n_hosts, const float* KRKi9, const float* Kt3, int n_points, const int* host_tag, const float* u,
+                                const float* v, const float* idepth_scaled);
+/* addIntoDistFinal(u, v) on the current map */
+int dmvio_hip_distance_map_add(dmvio_hip_distance_map* dm, int u, int v);
+/* fwdWarpedIDDistFinal: w1*h1 floats */
+int dmvio_hip_distance_map_get(dmvio_hip_distance_map* dm, float* map);
+
+/* ImmaturePoint::my_type (ImmaturePoint.h:73) per point: the selector's map value for points of dmvio_hip_immature_add_selected, 1 for dmvio_hip_immature_add_points */
+int dmvio_hip_immature_set_types(dmvio_hip_immature* imm, const float* my_type);
+int dmvio_hip_immature_get_types(dmvio_hip_immature* imm, float* my_type);
+/* ImmaturePoint::lastTraceUV (2 per point) / lastTracePixelInterval, for a caller that restores a traced state (dmvio_hip_immature_set_state sets the rest); either may be NULL */
+int dmvio_hip_immature_set_last_trace(dmvio_hip_immature* imm, const float* lastTraceUV2, const float* lastTracePixelInterval);
+/* The candidate loop of FullSystem::activatePointsMT (FullSystem.cpp:646-717) over the handle's points against the map `dm` holds (dmvio_hip_distance_map_make of the
+ * same keyframe).  Hosts are walked in ascending host_tag without newest_tag, the points of a host in ascending handle index.  host_flagged[t] =
+ * FrameHessian::flaggedForMarginalization of host t; minActDist = currentMinActDist; minTraceQuality = setting_minTraceQuality (3, settings.cpp:119).  Tables as from
+ * dmvio_hip_distance_map_tables_from_poses.  Afterwards the map is the reference's final map.  *n_selected = toOptimize.size(), *n_deleted = points deleted by the loop. */
+int dmvio_hip_immature_select_for_activation(dmvio_hip_immature* imm, dmvio_hip_distance_map* dm, int n_hosts, const float* KRKi9, const float* Kt3,
+                                             const unsigned char* host_flagged, int newest_tag, float minActDist, float minTraceQuality, int* n_selected, int* n_deleted);
+/* of the last selection: [0] candidates that reached the distance test, [1] those that pass it on the map as make left it (= length of the ordered walk), [2] accepted,
+ * [3] deleted */
+int dmvio_hip_immature_get_activation_stats(dmvio_hip_immature* imm, long long stats4[4]);
+/* decision[i] per point: 0 stays, 1 selected, 2 deleted; order[k] = handle index of toOptimize[k] (n_selected entries).  Either may be NULL.  Returns n_selected. */
+int dmvio_hip_immature_get_activation(dmvio_hip_immature* imm, int* decision, int* order);
+/* mark[i] != 0: the point leaves the handle at the next dmvio_hip_immature_remove_marked */
+int dmvio_hip_immature_get_marks(dmvio_hip_immature* imm, unsigned char* mark);
+/* where the ordered walk keeps the map: 0 = in LDS when it fits (default), 1 = always in global memory.  The results are the same. */
+int dmvio_hip_immature_set_activation_walk(dmvio_hip_immature* imm, int global_memory);
+/* dmvio_hip_immature_optimize for the selected points, the mask never leaving the device; result / idepth / res_state (n_selected, n_selected, n_selected*F entries, each
+ * may be NULL) come back in toOptimize order.  Marks for removal as FullSystem.cpp:732-756: result 1 (the point becomes active), result -1, result 0 with status OOB.
+ * Returns the number of activated points or <0. */
+int dmvio_hip_immature_optimize_selected(dmvio_hip_immature* imm, int F, const int* frame_slots, const double* w2c7, const double* aff2, const float* exposure,
+                                         const double fxfycxcy[4], int minObs, int* result, float* idepth, int* res_state);
+/* the marks of FullSystem.cpp:732-756 for a caller that optimised the selection itself: result[k] (1 / 0 / -1) of toOptimize[k] */
+int dmvio_hip_immature_mark_optimized(dmvio_hip_immature* imm, const int* result);
+/* what the PointHessian constructor copies (HessianBlocks.cpp:36-58) of every activated point, in toOptimize order, plus its optimised idepth and residual states;
+ * arrays of the count dmvio_hip_immature_optimize_selected returned, each may be NULL.  Returns that count. */
+int dmvio_hip_immature_get_activated(dmvio_hip_immature* imm, int* host_tag, float* u, float* v, float* my_type, float* idepth_min, float* idepth_max, float* color8,
+                                     float* weights8, float* energyTH, float* idepth, int* res_state);
+/* FullSystem.cpp:759-770: every host's list compacted the reference's way (list[i] = list.back(); pop_back()), hosts packed in ascending host_tag.  Returns the new
+ * number of points or <0; the selection is consumed. */
+int dmvio_hip_immature_remove_marked(dmvio_hip_immature* imm);
+/* a marginalised keyframe leaves the window: its points are dropped, larger host_tags move down by one.  Returns the new number of points or <0. */
+int dmvio_hip_immature_remove_host(dmvio_hip_immature* imm, int tag);
+/* currentMinActDist after the controller of FullSystem.cpp:608-627 (nPoints = ef->nPoints, desiredDensity = setting_desiredPointDensity).  Host only. */
+float dmvio_hip_min_act_dist_update(float cur, int nPoints, float desiredDensity);
+
 #ifdef __cplusplus
 }
 #endif

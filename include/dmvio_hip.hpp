@@ -14,6 +14,7 @@
  * Header-only; link with -ldmvio_hip.  Not thread-safe per object, like the reference's tracker (one tracker per thread). */
 #ifndef DMVIO_HIP_HPP
 #define DMVIO_HIP_HPP
+#include <algorithm>
 #include <cmath>
 #include <functional>
 #include <string>
@@ -395,6 +396,90 @@ class PixelSelector {
 
  private:
   dmvio_hip_pixel_selector* s_;
+};
+
+/* CoarseDistanceMap (FullSystem/CoarseTracker.h) at pyramid level 1 over dmvio_hip_distance_map_*: the map FullSystem::activatePointsMT tests its candidates against. */
+class DistanceMap {
+ public:
+  explicit DistanceMap(dmvio_hip_ctx* ctx) : d_(dmvio_hip_distance_map_create(ctx)) {}
+  ~DistanceMap() { if (d_) dmvio_hip_distance_map_destroy(d_); }
+  DistanceMap(const DistanceMap&) = delete;
+  DistanceMap& operator=(const DistanceMap&) = delete;
+  bool valid() const { return d_ != nullptr; }
+  /* the rows KRKi = K[1] * R * Ki[0], Kt = K[1] * t of every keyframe against the newest (CoarseTracker.cpp:949-951); pose7 = tx ty tz qx qy qz qw */
+  static bool tablesFromPoses(const double newWorldToCam7[7], int nHosts, const double* hostCamToWorld7, const double fxfycxcy[4], std::vector<float>& KRKi,
+                              std::vector<float>& Kt) {
+    KRKi.assign(9 * (size_t)nHosts, 0.f); Kt.assign(3 * (size_t)nHosts, 0.f);
+    return dmvio_hip_distance_map_tables_from_poses(newWorldToCam7, nHosts, hostCamToWorld7, fxfycxcy, KRKi.data(), Kt.data()) == 0;
+  }
+  /* makeDistanceMap (CoarseTracker.cpp:931-967) from the window's active points: host index, u, v, idepth_scaled */
+  bool makeDistanceMap(const std::vector<float>& KRKi, const std::vector<float>& Kt, const std::vector<int>& host, const std::vector<float>& u, const std::vector<float>& v,
+                       const std::vector<float>& idepthScaled) {
+    return d_ && dmvio_hip_distance_map_make(d_, (int)(Kt.size() / 3), KRKi.data(), Kt.data(), (int)host.size(), host.data(), u.data(), v.data(), idepthScaled.data()) == 0;
+  }
+  bool addIntoDistFinal(int u, int v) { return d_ && dmvio_hip_distance_map_add(d_, u, v) == 0; }
+  /* fwdWarpedIDDistFinal, (w>>1)*(h>>1) floats */
+  bool get(std::vector<float>& map) {
+    if (!d_) return false;
+    map.assign((size_t)dmvio_hip_distance_map_size(d_, nullptr, nullptr), 0.f);
+    return dmvio_hip_distance_map_get(d_, map.data()) == 0;
+  }
+  dmvio_hip_distance_map* handle() const { return d_; }
+
+ private:
+  dmvio_hip_distance_map* d_;
+};
+
+/* The window's immature points (dmvio_hip_immature_*) with the steps of FullSystem::activatePointsMT (FullSystem.cpp:604-773) that run on the device.  Does not own the
+ * handle when constructed from one. */
+class ImmaturePoints {
+ public:
+  ImmaturePoints(dmvio_hip_ctx* ctx, int capacity) : m_(dmvio_hip_immature_create(ctx, capacity)), own_(true) {}
+  explicit ImmaturePoints(dmvio_hip_immature* handle) : m_(handle), own_(false) {}
+  ~ImmaturePoints() { if (m_ && own_) dmvio_hip_immature_destroy(m_); }
+  ImmaturePoints(const ImmaturePoints&) = delete;
+  ImmaturePoints& operator=(const ImmaturePoints&) = delete;
+  bool valid() const { return m_ != nullptr; }
+  int size() const { return m_ ? dmvio_hip_immature_count(m_) : -1; }
+  static float updateMinActDist(float currentMinActDist, int nPoints, float desiredPointDensity) {
+    return dmvio_hip_min_act_dist_update(currentMinActDist, nPoints, desiredPointDensity);
+  }
+  /* the candidate loop (FullSystem.cpp:646-717): toOptimize.size(), or <0 */
+  int selectForActivation(DistanceMap& map, const std::vector<float>& KRKi, const std::vector<float>& Kt, const std::vector<unsigned char>& flaggedForMarginalization,
+                          int newestTag, float currentMinActDist, float minTraceQuality = 3.0f, int* nDeleted = nullptr) {
+    int n = 0;
+    if (!m_) return -1;
+    const int r = dmvio_hip_immature_select_for_activation(m_, map.handle(), (int)(Kt.size() / 3), KRKi.data(), Kt.data(), flaggedForMarginalization.data(), newestTag,
+                                                           currentMinActDist, minTraceQuality, &n, nDeleted);
+    return r < 0 ? r : n;
+  }
+  /* decision per point (0 stays, 1 selected, 2 deleted) and the handle indices of toOptimize */
+  bool activation(std::vector<int>& decision, std::vector<int>& order) {
+    if (!m_) return false;
+    const int n = dmvio_hip_immature_get_activation(m_, nullptr, nullptr);
+    if (n < 0) return false;
+    decision.assign((size_t)size(), 0); order.assign((size_t)n, 0);
+    return dmvio_hip_immature_get_activation(m_, decision.data(), order.data()) >= 0;
+  }
+  /* optimizeImmaturePoint of the selection (FullSystem.cpp:723-756), results in toOptimize order: number of activated points, or <0 */
+  int optimizeSelected(int F, const int* frameSlots, const double* worldToCam7, const double* aff2, const float* exposure, const double fxfycxcy[4], int minObs,
+                       std::vector<int>& result, std::vector<float>& idepth, std::vector<int>& resState) {
+    if (!m_) return -1;
+    const int n = dmvio_hip_immature_get_activation(m_, nullptr, nullptr);
+    if (n < 0) return n;
+    result.assign((size_t)n, 0); idepth.assign((size_t)n, 0.f); resState.assign((size_t)n * F, -1);
+    return dmvio_hip_immature_optimize_selected(m_, F, frameSlots, worldToCam7, aff2, exposure, fxfycxcy, minObs, result.data(), idepth.data(), resState.data());
+  }
+  /* the compaction (FullSystem.cpp:759-770): new number of points, or <0 */
+  int removeMarked() { return m_ ? dmvio_hip_immature_remove_marked(m_) : -1; }
+  /* a marginalised keyframe leaves: its points go, larger tags move down */
+  int removeHost(int tag) { return m_ ? dmvio_hip_immature_remove_host(m_, tag) : -1; }
+  bool types(std::vector<float>& myType) { myType.assign((size_t)std::max(size(), 0), 0.f); return m_ && dmvio_hip_immature_get_types(m_, myType.data()) == 0; }
+  dmvio_hip_immature* handle() const { return m_; }
+
+ private:
+  dmvio_hip_immature* m_;
+  bool own_;
 };
 
 }  // namespace dmvio_hip
