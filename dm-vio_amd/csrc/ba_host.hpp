@@ -190,6 +190,23 @@ struct BAHost {
       }
     for (int i = 0; i < 4; i++) { cPrior[i] = S.initialCalibHessian; cPriorF[i] = (float)cPrior[i]; }
   }
+  // the tail of FullSystem::optimize (FullSystemOptimize.cpp:596-603): the newest keyframe's optimised pose becomes its evaluation point, its state zero with the affine
+  // terms kept; the adjoints and the pair tables follow the new evaluation point
+  void reanchorNewest() {
+    BAFrameHost& last = fr[F - 1];
+    const double newStateZero[10] = {0, 0, 0, 0, 0, 0, last.state[6], last.state[7], 0, 0};
+    last.evalPT = last.w2c;
+    frameSetState(last, newStateZero);
+    frameSetStateZero(last, newStateZero);
+    setAdjointsF();
+    setPrecalcValues();
+  }
+  // the iteration count of FullSystem::optimize for small windows (FullSystemOptimize.cpp:420-421), both tests as the reference takes them
+  static int optIterations(const int F, int mnumOptIts) {
+    if (F < 3) mnumOptIts = 20;
+    if (F < 4) mnumOptIts = 15;
+    return mnumOptIts;
+  }
 
   int n() const { return 4 + 8 * F; }
   void getNullspaces() {

@@ -1,7 +1,5 @@
 // libdmvio_hip.so — C ABI of the bundle-adjustment path (include/dmvio_hip.h, "sliding-window BA" section).
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>   // types and prototypes only: the library itself is loaded on first use (below)
-#include <dlfcn.h>
 #include <memory>
 #include <cstdio>
 #include <cstdlib>
@@ -20,168 +18,9 @@
 
 using namespace dmv;
 
-// RCCL is bound at RUN time, on the first call that needs a communicator: libdmvio_hip.so itself has no link dependency on librccl.so, so hosts without RCCL (a single-GPU
-// workstation, a CPU-only build box) load the library and run everything but the multi-GPU entry points, which then fail with a message instead of a loader error.
-namespace {
-struct RcclApi {
-  decltype(&ncclAllReduce) allReduce = nullptr;
-  decltype(&ncclAllGather) allGather = nullptr;
-  decltype(&ncclCommCount) commCount = nullptr;
-  decltype(&ncclCommUserRank) commUserRank = nullptr;
-  decltype(&ncclGetUniqueId) getUniqueId = nullptr;
-  decltype(&ncclCommInitRank) commInitRank = nullptr;
-  decltype(&ncclCommDestroy) commDestroy = nullptr;
-  decltype(&ncclGetErrorString) getErrorString = nullptr;
-  bool ok = false;
-  std::string why;
-};
-RcclApi& rccl() {
-  static RcclApi api;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    void* h = nullptr;
-    for (const char* name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) { h = dlopen(name, RTLD_NOW | RTLD_GLOBAL); if (h) break; }
-    if (!h) { api.why = std::string("librccl.so cannot be loaded (") + (dlerror() ? dlerror() : "?") + ")"; return; }
-    bool all = true;
-    auto get = [&](const char* sym) { void* p = dlsym(h, sym); if (!p) { all = false; api.why = std::string("librccl.so lacks ") + sym; } return p; };
-    api.allReduce = (decltype(api.allReduce))get("ncclAllReduce"); api.allGather = (decltype(api.allGather))get("ncclAllGather");
-    api.commCount = (decltype(api.commCount))get("ncclCommCount"); api.commUserRank = (decltype(api.commUserRank))get("ncclCommUserRank");
-    api.getUniqueId = (decltype(api.getUniqueId))get("ncclGetUniqueId"); api.commInitRank = (decltype(api.commInitRank))get("ncclCommInitRank");
-    api.commDestroy = (decltype(api.commDestroy))get("ncclCommDestroy"); api.getErrorString = (decltype(api.getErrorString))get("ncclGetErrorString");
-    api.ok = all;
-  });
-  return api;
-}
-}  // namespace
-#define RCCL_READY() do { if (!rccl().ok) return failmsg("RCCL is not available: " + rccl().why); } while (0)
+#include "rccl_api.h"    // the sharded iteration's collectives (loader and communicator entry points: capi_comm.hip)
+#include "ba_handle.h"   // struct dmvio_hip_ba, its lock / ready checks and the transitions of the loops' caches
 
-#include <chrono>
-// optional host-side time split of the GN iteration (DMVIO_HIP_BA_TIMING=1 prints it when the handle is destroyed)
-struct BATimes { double t[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long n = 0; };
-static inline double nowUs() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-struct dmvio_hip_ba {
-  // The mapping side owns a HIP stream and a lock of its own: the tracking thread (context stream, context lock) and the mapping
-  // thread (this stream, this lock) overlap on the device like coarseTracker / mapping do in the reference (FullSystem.cpp:980-985).
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  std::recursive_mutex mu;   // every entry point that takes the handle holds it from its first line (entry points may call each other: recursive)
-  dmvio_hip_ctx* ctx = nullptr;
-  DmvBounce bounce;   // caller-owned arrays (and this file's short-lived host vectors) cross PCIe through the library's pinned memory (internal.h), on `stream`, under `mu`
-  BAHost H;
-  BAWindow W{};
-  BAPoints P{};
-  BARes Rs{};
-  // host copies of the graph
-  std::vector<int> h_host, h_point, h_target, h_res_begin;
-  std::vector<int> h_newest;   // residuals that target the newest keyframe (inputs of setNewFrameEnergyTH), ascending
-  std::vector<unsigned char> h_prior_flag;
-  // device storage.  The window is rebuilt for every keyframe (dmvio_hip_ba_set_graph): its ~75 device arrays are carved out of a few large chunks that stay with the
-  // handle and are cleared with one memset each — not allocated, cleared and freed one by one (that cost milliseconds per keyframe, more than optimize(6) itself)
-  std::vector<void*> allocs;
-  struct Arena { std::vector<std::pair<char*, size_t>> chunks; std::vector<size_t> used; size_t cur = 0, off = 0; bool on = false; } arena;   // used[k]: bytes of chunk k handed out since it was last cleared
-  size_t cap_spart = 0, cap_idepth_backup = 0;   // capacities of the grow-only pinned host buffers
-  BAPrecalc* d_pre = nullptr;        // the precalc table the kernels read: one of the two halves of d_pre2
-  BAPrecalc* d_pre2 = nullptr;       // [2][F*F]: the table of the backed-up state stays resident, a rejected step switches back to it
-  int pre_half = 0;
-  double *d_adHost = nullptr, *d_adTarget = nullptr;
-  int *d_top_begin = nullptr, *d_top_members = nullptr, *d_scd_begin = nullptr, *d_scd_members = nullptr;
-  float *d_accTop = nullptr, *d_accD = nullptr, *d_accE = nullptr, *d_accC = nullptr;
-  int *d_numTop = nullptr, *d_numD = nullptr;
-  StitchBufs SB{};
-  double *h_sys = nullptr;     // [H_A | b_A | H_sc | b_sc | resInA]: pinned host memory, written by k_ba_stitch_gather
-  float *d_spart = nullptr, *h_spart = nullptr;  // point-step partial sums
-  // pinned staging for the per-linearisation precalc upload (no pageable copy, no sync before the kernel that consumes it)
-  BAPrecalc* h_pre[2] = {nullptr, nullptr};
-  int pre_toggle = 0;
-  float* d_fullJ = nullptr;
-  // device-side decisions (ba_kernels.hpp, BACtl): control block, host-coherent result block, device copies of what the decisions read
-  BACtl* d_ctl = nullptr;
-  BAHostRes* h_res = nullptr;
-  bool th_pending = false;            // the newest keyframe's threshold of the last accept-test pass is stored a few microseconds behind its decision (BAHostRes::th_ticket)
-  unsigned int th_pending_ticket = 0;
-  float *d_frameTH = nullptr, *h_frameTH = nullptr;   // FrameHessian::frameEnergyTH of every keyframe (the newest one is updated on the device)
-  bool th_dirty = true;        // the host changed a threshold: upload before the next linearisation
-  double* d_epart = nullptr;
-  int* d_newestSlot = nullptr;   // per residual: its position among the residuals that target the newest keyframe, or -1
-  float* d_newestE = nullptr;    // their state_NewEnergyWithOutlier, contiguous
-  ResubArgs x_none{};            // placeholder argument of linearisations without the fused back-substitution
-  BAPreDyn dyn_cur;              // step-dependent precalc members of the CURRENT state (kernel argument of the GN loop's linearisations)
-  bool pre_static_valid = false; // the device table holds the evaluation-point members (R0, t0, b0) of the current window
-  float* d_newEnergyWO = nullptr;
-  unsigned int ticket = 0, acc_ticket = 0;
-  float th_cap = -1.0f;        // IMUIntegration::newFrameEnergyTH cap (<= 0: none)
-  // a rejected step whose relinearisation the host has not waited for (the loop inside dmvio_hip_ba_optimize): its energy / threshold are picked up at the next wait
-  bool pending_reject = false;
-  unsigned int pending_ticket = 0;
-  int pending_trace = -1;
-  bool sys_ready = false;      // h_sys holds the stitched system of the CURRENT state (left behind by the previous GN iteration's chain)
-  int n_lin_blocks = 0, n_pt_blocks = 0, n_pt8_blocks = 0, n_epart = 0;   // n_pt8: kernels with eight lanes per point
-  bool keep_fullJ = false;   // the 74-float RawResidualJacobian is only materialised on request (dmvio_hip_ba_keep_jacobians) and for marginalisation
-  // partial accumulators per bucket: 1 (default) replays the single-threaded reference order bit for bit; DMVIO_HIP_BA_SPLIT=k uses k
-  // partial accumulators per bucket: k > 1 = the structure of the reference's multi-threaded accumulation (per-worker fp32 accumulators summed
-  // in double, AccumulatedTopHessian.h:91-139) with a FIXED assignment of members to partials; 1 = the reference's single-threaded order, bit for bit
-  int nsTop = 4, nsD = 4, nsC = 16;
-  bool graph_ready = false;
-  // energies of the last optimize
-  double trace[64][4];
-  int iterations_done = 0;
-  double final_energy = 0;
-  BATimes tm;
-  bool timing = false;
-  double tm_graph[6] = {0, 0, 0, 0, 0, 0}; long tm_graph_n = 0;   // dmvio_hip_ba_set_graph: drain + arena memset, host lists, allocation, uploads, pinned buffers + slot table, adjoints + final wait
-  // true only between a REJECTED step of gnIteration and the next gnIteration: the state was restored to the one the per-point sums (and the
-  // point backup) were computed at, so k_ba_point_sums would reproduce what is already there.  Every other entry point clears it.
-  bool sums_fresh = false;
-  // point marginalisation scratch (dmvio_hip_ba_marginalize_points)
-  unsigned char *d_cand = nullptr, *d_decision = nullptr, *d_margActive = nullptr;
-  float *d_mHdiF = nullptr, *d_mbdSumF = nullptr, *d_mHcd = nullptr, *d_margRec = nullptr, *d_adHTdelta = nullptr;
-  long long* d_accTicks = nullptr;   // per-block stamps of k_ba_accumulate (timing mode only)
-  int accTicksBlocks = 0;
-  // flat arrays of dmvio_hip_ba_set_graph_from (kept between keyframes: no allocation in the steady state)
-  struct GraphScratch { std::vector<int> host, res_point, res_target; std::vector<float> u, v, idepth, color, weights, linJ, linRtz; std::vector<unsigned char> prior, lin; } gscratch;
-  // ---- points sharded over ranks (dmvio_hip_ba_set_comm): every rank holds all keyframes and ITS points; the stitched system is summed by
-  // an all-reduce in HBM on this handle's stream, the accept / threshold decisions are taken over the all-gathered per-rank records
-  int rank = 0, world = 0;           // world == 0: no communicator
-  ncclComm_t nccl = nullptr;         // RCCL communicator (not owned)
-  dmvio_hip_comm_callbacks comm_cb{};   // host-staged transport (MPI, gloo, ...) when nccl == NULL
-  double* d_sys = nullptr;           // [H_A | b_A | H_sc | b_sc | resInA] of this rank's points, all-reduced in place
-  float *d_xchg_local = nullptr, *d_xchg_all = nullptr;
-  int xchg_width = 0;                // floats per rank record: BA_XCHG_HEADER + the largest per-rank count of residuals that target the newest keyframe
-  std::vector<double> h_stage;       // callback transport only
-  // ---- the reference's DEFAULT solver branch (setting_useGTSAMIntegration, dmvio_hip_ba_optimize_vio): hooks of the running call, the dynamic weight,
-  // PointHessian::idepth_backup mirrored into host-coherent memory by the per-point sums (the |idepth_backup| sum of doStepFromBackup's canbreak test)
-  const dmvio_hip_ba_callbacks* vio = nullptr;
-  const dmvio_hip_ba_vio_options* vio_opt = nullptr;
-  double dynW = 1.0;
-  int resInA_solve = 0;              // ef->resInA as the reference holds it: set by the accumulation of the last solveSystemF
-  float* h_idepth_backup = nullptr;
-  std::vector<dmvio_hip_ba_frame_view> vio_frames;
-  hipEvent_t* prof = nullptr;        // dmvio_hip_ba_profile_chain: six events recorded between the launches of linearise -> per-point sums -> accumulate -> stitch -> gather
-  // dmvio_hip_ba_set_device_loop: dmvio_hip_ba_optimize runs the device-resident loop (a batch of one window) instead of the host-driven one
-  bool device_loop = false;
-  struct dmvio_hip_ba_batch* own_batch = nullptr;
-  // dmvio_hip_ba_comm_timing: HIP events around the collectives of the sharded iteration (RCCL transport), kind 0 = all-reduce of the packed system, 1 = all-gather of the
-  // decision records; up to COMM_EVS of each are kept and summed when asked for
-  enum { COMM_EVS = 64 };
-  bool comm_timing = false;
-  hipEvent_t comm_ev[2][COMM_EVS][2] = {};
-  int comm_n[2] = {0, 0};
-  long comm_total[2] = {0, 0};
-  // ---- residuals kept linearised outside a marginalisation (dmvio_hip_ba_fix_linearization; ba_kernels.hpp "residuals kept linearised"): flags, res_toZeroF, the record
-  // addPoint<1> consumes, the activity views of the three accumulation passes, the per-point LF sums; host copies of what calcLEnergyPt reads
-  int n_lin = 0;
-  long long n_lin_global = 0;   // sharded window: the ranks' n_lin summed (dmvio_hip_ba_fix_linearization is collective there) — every rank takes the three-pass accumulation or none
-  double* d_red1 = nullptr;     // one double for small all-reduces (the linearised energy of a sharded window)
-  unsigned char *d_lin = nullptr, *d_linMask = nullptr, *d_linActive = nullptr, *d_topActive = nullptr;
-  float *d_rtz = nullptr, *d_linRec = nullptr, *d_lHdd = nullptr, *d_lbd = nullptr, *d_lHcd = nullptr, *d_HcdAF = nullptr, *d_linE = nullptr;
-  std::vector<unsigned char> h_lin, h_linAct;
-  std::vector<float> h_linJ, h_rtz;
-  bool fullJ_applied = false;   // d_fullJ holds the Jacobians of the APPLIED linearisation (the last linearisation was followed by its applyRes)
-  bool adj_dirty = false;   // the host's adjoint tables (H.adHost / adTarget) are newer than the device copy: uploaded by the next consumer (accumulateViews, a batch call)
-};
-#define BA_LOCK(b) std::lock_guard<std::recursive_mutex> lk_(b->mu)
-#define BA_PROF(b, k) do { if ((b)->prof) hipEventRecord((b)->prof[k], (b)->stream); } while (0)
 // The kernels whose ARGUMENTS are sized by the window (ba_kernels.hpp: BAPreDynT / ResubArgsT, the stitch workgroup of 64 F threads): windows of up to BA_MAXF keyframes
 // take the compact instantiation (the host's wide structs cut down to their prefix), larger ones (up to BA_MAXF_CAP) the wide one.
 #define BA_LAUNCH_LINEARIZE(b, W_, fullJ_, mask_, D_, gate_, use_backup_, T_, use_dyn_, X_, do_resub_) do { \
@@ -191,7 +30,11 @@ struct dmvio_hip_ba {
     else hipLaunchKernelGGL((k_ba_linearize<BA_MAXF_CAP>), dim3((b)->n_lin_blocks), dim3(LIN_THREADS), 0, (b)->stream, W_, (b)->P, (b)->Rs, (const BAPrecalc*)(b)->d_pre, \
         (b)->ctx->fs, fullJ_, mask_, D_, (int)(gate_), (int)(use_backup_), T_, (int)(use_dyn_), X_, (int)(do_resub_)); \
   } while (0)
-#define NCCLCHK(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) return failmsg((std::string("RCCL: ") + rccl().getErrorString(r_) + " in " #x).c_str()); } while (0)
+// the other launch pairs of that kind: `...` (a launch that names M_ as its template argument) once with M_ = BA_MAXF, once with M_ = BA_MAXF_CAP, the window's F picks
+#define BA_BY_MAXF(F_, M_, ...) do { \
+    if ((F_) <= BA_MAXF) { constexpr int M_ = BA_MAXF; __VA_ARGS__; } \
+    else { constexpr int M_ = BA_MAXF_CAP; __VA_ARGS__; } \
+  } while (0)
 
 // one chunk holds the ~75 arrays of a window of 8 keyframes / 4000 points / 30k residuals; allocated (and the pinned host buffers with it) when the handle is created, so that
 // no keyframe of a live system pays for hipMalloc / hipHostMalloc (seen in tests/dropin: 1.2 ms per keyframe on average over the first ten, 0.4 ms in the steady state)
@@ -268,7 +111,7 @@ static void dynFromHost(const BAHost& H, BAPreDyn& T) {
 static int uploadWindowTables(dmvio_hip_ba* b, bool new_state = false, bool switch_back = false) {
   BAHost& H = b->H;
   BAWindow& W = b->W;
-  b->pre_static_valid = true;
+  b->evalPointUploaded();
   W.F = H.F; W.w = H.w; W.h = H.h; W.N = H.N; W.R = H.R;
   W.fx = H.c_f[0]; W.fy = H.c_f[1]; W.cx = H.c_f[2]; W.cy = H.c_f[3];
   W.fxi = H.c_i[0]; W.fyi = H.c_i[1]; W.cxi = H.c_i[2]; W.cyi = H.c_i[3];
@@ -762,7 +605,7 @@ int dmvio_hip_ba_keep_jacobians(dmvio_hip_ba* b, int on) {
 static int setComm(dmvio_hip_ba* b, ncclComm_t comm, const dmvio_hip_comm_callbacks* cb, int rank, int world) {
   if (!b) return failmsg("null ba");
   BA_LOCK(b);
-  if (world == 0 || (!comm && !cb)) { b->world = 0; b->rank = 0; b->nccl = nullptr; b->comm_cb = dmvio_hip_comm_callbacks{}; b->sys_ready = false; b->sums_fresh = false; return 0; }
+  if (world == 0 || (!comm && !cb)) { b->world = 0; b->rank = 0; b->nccl = nullptr; b->comm_cb = dmvio_hip_comm_callbacks{}; b->stateChanged(); return 0; }
   if (world < 1 || rank < 0 || rank >= world) return failmsg("ba_set_comm: 0 <= rank < world");
   if (b->n_lin > 0) return failmsg("ba_set_comm: the graph already carries residuals kept linearised — set the communicator first, dmvio_hip_ba_fix_linearization is collective on a sharded window");
   if (cb && (!cb->allreduce_sum_f64 || !cb->allgather)) return failmsg("ba_set_comm_callbacks: both callbacks are required");
@@ -776,7 +619,7 @@ static int setComm(dmvio_hip_ba* b, ncclComm_t comm, const dmvio_hip_comm_callba
   b->rank = rank; b->world = world; b->nccl = comm;
   b->comm_cb = cb ? *cb : dmvio_hip_comm_callbacks{};
   b->xchg_width = 0;            // agreed on at the next linearisation
-  b->sys_ready = false; b->sums_fresh = false;
+  b->stateChanged();
   return 0;
 }
 int dmvio_hip_ba_set_comm(dmvio_hip_ba* b, void* nccl_comm, int rank, int world) { return setComm(b, (ncclComm_t)nccl_comm, nullptr, rank, world); }
@@ -833,84 +676,6 @@ int dmvio_hip_ba_partition_points(const int* host, int N, int world, double max_
   return 0;
 }
 int dmvio_hip_ba_set_comm_callbacks(dmvio_hip_ba* b, const dmvio_hip_comm_callbacks* cb, int rank, int world) { return setComm(b, nullptr, cb, rank, world); }
-int dmvio_hip_comm_unique_id(unsigned char id128[128]) {
-  if (!id128) return failmsg("null argument");
-  static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-  RCCL_READY();
-  ncclUniqueId id;
-  NCCLCHK(rccl().getUniqueId(&id));
-  memcpy(id128, &id, 128);
-  return 0;
-}
-int dmvio_hip_comm_init_rank(dmvio_hip_ctx* ctx, const unsigned char id128[128], int rank, int world, void** out) {
-  if (!ctx || !id128 || !out) return failmsg("null argument");
-  HIPCHK(hipSetDevice(ctx->device));
-  RCCL_READY();
-  ncclUniqueId id;
-  memcpy(&id, id128, 128);
-  ncclComm_t comm = nullptr;
-  NCCLCHK(rccl().commInitRank(&comm, world, id, rank));
-  *out = (void*)comm;
-  return 0;
-}
-// ---- hypothesis-parallel FullSystem::trackNewCoarse (include/dmvio_hip.h): the per-try records of dmvio_hip_tracker_track_new_coarse summed over the ranks
-int dmvio_hip_tracker_set_comm(dmvio_hip_tracker* t, void* nccl_comm, int rank, int world) {
-  dmvio_hip_ctx* c = dmv_tracker_ctx(t);
-  if (!c) return failmsg("null tracker");
-  const bool force1 = world == 1 && nccl_comm && dmv_tracker_debug_split1(t);   // test hook (dmvio_hip_tracker_debug_split_single_rank), see dmv_tracker_set_exchange
-  if (!nccl_comm || (world <= 1 && !force1)) return dmv_tracker_set_exchange(t, nullptr, 0, 0);
-  ncclComm_t comm = (ncclComm_t)nccl_comm;
-  RCCL_READY();
-  int n = 0, r = -1;
-  NCCLCHK(rccl().commCount(comm, &n));
-  NCCLCHK(rccl().commUserRank(comm, &r));
-  if (n != world || r != rank) return failmsg("tracker_set_comm: rank / world do not match the communicator");
-  // 20 doubles per hypothesis: a few KB, staged through a device buffer that stays with the exchange (and through the context's pinned staging area) for RCCL on the context's stream
-  struct XchgBuf { double* d = nullptr; size_t cap = 0; int device = 0; ~XchgBuf() { if (d) { hipSetDevice(device); hipFree(d); } } };
-  std::shared_ptr<XchgBuf> st = std::make_shared<XchgBuf>();
-  st->device = c->device;
-  return dmv_tracker_set_exchange(t, [c, comm, st](double* buf, size_t count) -> int {
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    if (count > st->cap) {
-      if (st->d) { HIPCHK(hipFree(st->d)); st->d = nullptr; st->cap = 0; }
-      HIPCHK(hipMalloc((void**)&st->d, sizeof(double) * 2 * count));
-      st->cap = 2 * count;
-    }
-    HIPCHK(c->bounce.h2d(st->d, buf, sizeof(double) * count, c->stream));
-    const ncclResult_t nr = rccl().allReduce(st->d, st->d, count, ncclDouble, ncclSum, comm, c->stream);
-    if (nr != ncclSuccess) return failmsg(std::string("RCCL: ") + rccl().getErrorString(nr) + " in the hypothesis exchange");
-    HIPCHK(c->bounce.d2h(buf, st->d, sizeof(double) * count, c->stream));
-    HIPCHK(c->bounce.finish(c->stream));
-    return 0;
-  }, rank, world);
-}
-int dmvio_hip_tracker_set_comm_callbacks(dmvio_hip_tracker* t, const dmvio_hip_comm_callbacks* cb, int rank, int world) {
-  if (!dmv_tracker_ctx(t)) return failmsg("null tracker");
-  if (!cb || world <= 1) return dmv_tracker_set_exchange(t, nullptr, 0, 0);
-  if (!cb->allreduce_sum_f64) return failmsg("tracker_set_comm_callbacks: allreduce_sum_f64 is required");
-  const dmvio_hip_comm_callbacks k = *cb;
-  return dmv_tracker_set_exchange(t, [k](double* buf, size_t count) -> int {
-    return k.allreduce_sum_f64(k.user, buf, count) == 0 ? 0 : failmsg("comm callback allreduce_sum_f64 failed");
-  }, rank, world);
-}
-// ncclCommCount / ncclCommUserRank of a communicator: what RCCL itself says about the group (bench.py prints it in the N > 1 line)
-int dmvio_hip_comm_info(void* comm, int* n_ranks, int* rank) {
-  if (!comm) return failmsg("null communicator");
-  RCCL_READY();
-  int n = 0, r = -1;
-  NCCLCHK(rccl().commCount((ncclComm_t)comm, &n));
-  NCCLCHK(rccl().commUserRank((ncclComm_t)comm, &r));
-  if (n_ranks) *n_ranks = n;
-  if (rank) *rank = r;
-  return 0;
-}
-int dmvio_hip_comm_destroy(void* comm) {
-  if (!comm) return 0;
-  RCCL_READY();
-  NCCLCHK(rccl().commDestroy((ncclComm_t)comm));
-  return 0;
-}
 
 // The stream the mapping side enqueues on (default: a stream owned by the handle).  NULL restores an own stream.
 int dmvio_hip_ba_set_stream(dmvio_hip_ba* b, void* stream) {
@@ -929,7 +694,7 @@ int dmvio_hip_ba_set_window(dmvio_hip_ba* b, int F, const int* slots, const doub
                             const int* frameIDs, const double fxfycxcy[4]) {
   if (!b || !slots || !pose7_w2c || !fxfycxcy) return failmsg("ba_set_window: null argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   if (F < 1 || F > BA_MAXF_CAP) return failmsg("ba_set_window: 1 <= F <= " + std::to_string(BA_MAXF_CAP) + " keyframes (dmvio_hip_ba_max_frames)");
   // a threshold still on its way from the previous window's last accepted step (th_ticket follows the decision) belongs to THAT window: it must neither be waited for
   // after the host-coherent record is cleared (set_graph) nor land in the new window's newest keyframe
@@ -965,7 +730,7 @@ int dmvio_hip_ba_set_window(dmvio_hip_ba* b, int F, const int* slots, const doub
 int dmvio_hip_ba_set_marg_prior(dmvio_hip_ba* b, const double* HM, const double* bM) {
   if (!b || !HM || !bM) return failmsg("ba_set_marg_prior: null argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   const int n = b->H.n();
   b->H.HM.assign(HM, HM + (size_t)n * n); b->H.bM.assign(bM, bM + n);
   return 0;
@@ -975,7 +740,7 @@ int dmvio_hip_ba_set_marg_prior(dmvio_hip_ba* b, const double* HM, const double*
 int dmvio_hip_ba_marginalize_points(dmvio_hip_ba* b, const unsigned char* candidates, unsigned char* decision, double* Hadd, double* badd, int* resInM, int update_prior) {
   if (!b || !b->graph_ready) return failmsg("ba_marginalize_points: window / graph not set");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   if (!candidates || !decision) return failmsg("ba_marginalize_points: null argument");
   dmvio_hip_ctx* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
@@ -1039,7 +804,7 @@ static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u,
                         const float* weights8, const unsigned char* hasDepthPrior, int R, const int* res_point, const int* res_target, bool wait) {
   if (!b || !host || !u || !v || !idepth || !color8 || !weights8 || !res_point || !res_target) return failmsg("ba_set_graph: null argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   BAHost& H = b->H;
   if (H.F < 1) return failmsg("ba_set_graph: set_window first");
   if (N < 1 || R < 1) return failmsg("ba_set_graph: empty graph");
@@ -1182,7 +947,7 @@ static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u,
   if (!b->h_sys) HIPCHK(hipHostMalloc((void**)&b->h_sys, sizeof(double) * (2 * (NMAXF * NMAXF + NMAXF) + 1), hipHostMallocCoherent | hipHostMallocMapped));   // polled: host-coherent; sized for BA_MAXF_CAP keyframes once
   if (dalloc(b, &b->d_sys, (size_t)tot + 1)) return -1;
   b->xchg_width = 0; b->d_xchg_local = b->d_xchg_all = nullptr;
-  b->pending_reject = false; b->pending_trace = -1;
+  b->graphReplaced();
   if (!b->h_res) HIPCHK(hipHostMalloc((void**)&b->h_res, sizeof(BAHostRes), hipHostMallocCoherent | hipHostMallocMapped));
   memset(b->h_res, 0, sizeof(BAHostRes));
   if (!b->h_frameTH) HIPCHK(hipHostMalloc((void**)&b->h_frameTH, sizeof(float) * BA_MAXF_CAP, hipHostMallocDefault));
@@ -1199,8 +964,6 @@ static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u,
     if (R) HIPCHK(b->bounce.h2d(b->d_newestSlot, slot.data(), sizeof(int) * R, s));   // staged (the vector may go): asynchronous like the other uploads
     Rs.newestSlot = b->d_newestSlot; Rs.newestE = b->d_newestE;
   }
-  b->pre_static_valid = false;
-  b->th_dirty = true; b->sys_ready = false;
   for (int k = 0; k < 2; k++) if (!b->h_pre[k]) HIPCHK(hipHostMalloc((void**)&b->h_pre[k], sizeof(BAPrecalc) * BA_MAXF_CAP * BA_MAXF_CAP, hipHostMallocDefault));
   Rs.newEnergyWO = b->d_newEnergyWO;
   if ((size_t)2 * b->n_pt_blocks > b->cap_spart) {
@@ -1267,9 +1030,6 @@ int dmvio_hip_ba_set_graph_from(dmvio_hip_ba* b, dmvio_hip_graph* g) {
   return 0;
 }
 
-#define BA_READY_LOCKED(b) do { if (!(b)->graph_ready) return failmsg("ba: set_window + set_graph first"); (b)->sums_fresh = false; (b)->sys_ready = false; HIPCHK(hipSetDevice((b)->ctx->device)); } while (0)
-// first statement of an entry point: null check, the handle's lock for the whole call (declares a guard in the function's scope), then the state checks
-#define BA_READY(b) if (!(b)) return failmsg("ba: null handle"); BA_LOCK(b); BA_READY_LOCKED(b)
 
 // buffers of the residuals kept linearised (first use on a graph)
 static int linAlloc(dmvio_hip_ba* b) {
@@ -1330,7 +1090,7 @@ static int linImport(dmvio_hip_ba* b, const unsigned char* flags, const float* J
     hipLaunchKernelGGL(k_ba_lin_import, dim3((n + 255) / 256), dim3(256), 0, s, n, (const int*)d_idx, (const float*)d_packed, b->Rs, b->d_fullJ, b->d_rtz, b->d_linRec, b->d_lin);
     HIPCHK(hipGetLastError());
   }
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   return linFinish(b, n_linearized);
 }
 
@@ -1552,7 +1312,7 @@ int dmvio_hip_ba_get_marg_prior(dmvio_hip_ba* b, double* HM, double* bM) {
 int dmvio_hip_ba_set_frame_state(dmvio_hip_ba* b, int f, const double state10[10]) {
   if (!b || !state10 || f < 0 || f >= b->H.F) return failmsg("ba_set_frame_state: bad argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   BAHost::frameSetState(b->H.fr[f], state10);
   b->H.setPrecalcValues();
   return 0;
@@ -1562,9 +1322,9 @@ int dmvio_hip_ba_set_frame_state(dmvio_hip_ba* b, int f, const double state10[10
 int dmvio_hip_ba_set_frame_zero(dmvio_hip_ba* b, int f, const double state_zero10[10]) {
   if (!b || !state_zero10 || f < 0 || f >= b->H.F) return failmsg("ba_set_frame_zero: bad argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   BAHost::frameSetStateZero(b->H.fr[f], state_zero10);
-  b->pre_static_valid = false;
+  b->evalPointChanged();
   b->H.frameTakeData(b->H.fr[f]);
   b->H.setPrecalcValues();
   return 0;
@@ -1572,12 +1332,12 @@ int dmvio_hip_ba_set_frame_zero(dmvio_hip_ba* b, int f, const double state_zero1
 int dmvio_hip_ba_set_frame_states(dmvio_hip_ba* b, const double* state_zero10, const double* state10) {
   if (!b || b->H.F < 1) return failmsg("ba_set_frame_states: bad argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   for (int f = 0; f < b->H.F; f++) {
     if (state_zero10) { BAHost::frameSetStateZero(b->H.fr[f], state_zero10 + 10 * f); b->H.frameTakeData(b->H.fr[f]); }
     if (state10) BAHost::frameSetState(b->H.fr[f], state10 + 10 * f);
   }
-  if (state_zero10) b->pre_static_valid = false;
+  if (state_zero10) b->evalPointChanged();
   b->H.setPrecalcValues();
   return 0;
 }
@@ -1600,7 +1360,7 @@ int dmvio_hip_ba_set_frame_energy_th_cap(dmvio_hip_ba* b, float maxFrameEnergyTh
 int dmvio_hip_ba_set_calib_values(dmvio_hip_ba* b, const double value[4], const double value_zero[4]) {
   if (!b || !value || !value_zero) return failmsg("ba_set_calib_values: null argument");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   for (int i = 0; i < 4; i++) b->H.c_value_zero[i] = value_zero[i];
   b->H.calibSetValue(value);
   b->H.setPrecalcValues();
@@ -1852,9 +1612,7 @@ int dmvio_hip_ba_last_decide_ticks(dmvio_hip_ba* b, int ticks4[4]) {
 int dmvio_hip_ba_gn_iteration(dmvio_hip_ba* b, int iteration, double* lambda_io, double lastE[3], int* accepted) {
   if (!b) return failmsg("ba: null handle");
   BA_LOCK(b);
-  const bool sums_fresh = b->sums_fresh, sys_ready = b->sys_ready;
-  BA_READY_LOCKED(b);
-  b->sums_fresh = sums_fresh; b->sys_ready = sys_ready;
+  BA_CHECK_LOCKED(b);
   bool acc = false;
   double lam = *lambda_io;
   if (int r = gnIteration(b, iteration, lam, lastE, acc)) return r;
@@ -1916,7 +1674,7 @@ int dmvio_hip_ba_linearize_local(dmvio_hip_ba* b, int fix, double* energy, float
 int dmvio_hip_ba_set_new_frame_energy_th(dmvio_hip_ba* b, float th) {
   if (!b) return failmsg("null ba");
   BA_LOCK(b);
-  b->sums_fresh = false; b->sys_ready = false;
+  b->stateChanged();
   b->H.fr[b->H.F - 1].frameEnergyTH = th;
   b->th_dirty = true;
   return 0;
@@ -1935,8 +1693,7 @@ static int optimizeImpl(dmvio_hip_ba* b, int mnumOptIts, const dmvio_hip_ba_call
                         double* trace /* 64x4 or NULL */) {
   BAHost& H = b->H;
   if (H.F < 2) { if (rmse) *rmse = 0; return 0; }
-  if (H.F < 3) mnumOptIts = 20;
-  if (H.F < 4) mnumOptIts = 15;
+  mnumOptIts = BAHost::optIterations(H.F, mnumOptIts);
   struct VioScope {   // the hooks are those of this call only
     dmvio_hip_ba* b;
     ~VioScope() { b->vio = nullptr; b->vio_opt = nullptr; b->H.gtsam = false; b->dynW = 1.0; }
@@ -1974,14 +1731,8 @@ static int optimizeImpl(dmvio_hip_ba* b, int mnumOptIts, const dmvio_hip_ba_call
   if (int r = settleReject(b, lastE, true)) return r;
   if (vio) b->dynW = vioDynamicWeight(b, lastE[0], b->resInA_solve);   // "Update again!" (FullSystemOptimize.cpp:594)
   // fix the newest frame's linearisation point, re-linearise with applyRes (FullSystemOptimize.cpp:596-609)
-  BAFrameHost& last = H.fr[H.F - 1];
-  double newStateZero[10] = {0, 0, 0, 0, 0, 0, last.state[6], last.state[7], 0, 0};
-  last.evalPT = last.w2c;
-  BAHost::frameSetState(last, newStateZero);
-  BAHost::frameSetStateZero(last, newStateZero);
-  H.setAdjointsF();
-  if (int r = uploadAdjoints(b)) return r;
-  H.setPrecalcValues();
+  H.reanchorNewest();
+  if (int r = uploadAdjoints(b)) return r;   // (nothing is enqueued between the two: the upload stands in the stream where it stood inside the sequence)
   double fe = 0;
   if (int r = linearizeAll(b, true, &fe)) return r;
   b->final_energy = fe; b->iterations_done = done;
@@ -2035,622 +1786,9 @@ int dmvio_hip_ba_solve_ldlt(int n, const double* HPassed, const double* b_in, do
 
 }  // extern "C"
 
-// ================================================================================================= device-resident Gauss-Newton loop, W windows per launch (round 5)
-// FullSystem::optimize (FullSystemOptimize.cpp:417-647) for W windows at once, the reference's non-GTSAM solver branch: per Gauss-Newton iteration the host enqueues ONE
-// fixed sequence of kernels for all windows (ba_batch_kernels.hpp) and never waits — the 68x68 solve, the frame step, the pair tables, the energies and the accept test run
-// on the device (k_ba_solve + the decision pass of the linearisation), every kernel of the chain takes its window from blockIdx.y and is gated on that window's own decision.
-// Two waits per call: behind the loop (the frame states come back, the host re-anchors the newest keyframe, FullSystemOptimize.cpp:596-603) and behind the final
-// fix-linearisation.  Windows of one call must hold the same number of keyframes (the adjoint stitch's workgroup shape); the caller groups them.
-// the per-window host work of a batch call (tables, nullspace bases, staging copies before the launches; state write-back, adjoints and pair tables behind the loop:
-// 30-40 us per window each) is dealt out over a few persistent worker threads — at 64 windows it was 4.3 ms of a 12 ms call
-#include <thread>
-#include <condition_variable>
-struct BAWorkers {
-  std::vector<std::thread> th;
-  std::mutex mu;
-  std::condition_variable cv, cv_done;
-  std::function<int(int)> fn;
-  int next = 0, count = 0, pending = 0, rc = 0, device = 0;
-  unsigned long long gen = 0;
-  bool quit = false;
-  std::string err;
-  void start(int n, int dev) {
-    device = dev;
-    for (int i = 0; i < n; i++) th.emplace_back([this] { run(); });
-  }
-  void run() {
-    hipSetDevice(device);
-    unsigned long long seen = 0;
-    for (;;) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return quit || (gen != seen && next < count); });
-      if (quit) return;
-      while (next < count) {
-        const int i = next++;
-        lk.unlock();
-        const int r = fn(i);
-        std::string e = r ? dmv_err() : std::string();
-        lk.lock();
-        if (r && !rc) { rc = r; err = e; }
-        if (--pending == 0) cv_done.notify_all();
-      }
-      seen = gen;
-    }
-  }
-  // fn(i) for i in [0, n): on the workers and on the calling thread; returns the first non-zero result (its message becomes this thread's last error)
-  int parallelFor(int n, std::function<int(int)> f, const int serial_below = 8) {
-    if (th.empty() || n < serial_below) { for (int i = 0; i < n; i++) if (int r = f(i)) return r; return 0; }
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      fn = std::move(f); next = 0; count = n; pending = n; rc = 0; gen++;
-    }
-    cv.notify_all();
-    for (;;) {
-      std::unique_lock<std::mutex> lk(mu);
-      if (next >= count) { cv_done.wait(lk, [&] { return pending == 0; }); break; }
-      const int i = next++;
-      lk.unlock();
-      const int r = fn(i);
-      std::string e = r ? dmv_err() : std::string();
-      lk.lock();
-      if (r && !rc) { rc = r; err = e; }
-      if (--pending == 0) cv_done.notify_all();
-    }
-    if (rc) { dmv_err() = err; dmv_err_epoch()++; }
-    return rc;
-  }
-  // fn(i) for i in [0, n), handed out in index order, on the workers ALONE: the caller goes on (it enqueues one group's launches while the next group's tables are prepared)
-  // and collects the result with waitAsync().  Needs workers (th.empty(): use parallelFor).
-  void startAsync(int n, std::function<int(int)> f) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      fn = std::move(f); next = 0; count = n; pending = n; rc = 0; gen++;
-    }
-    cv.notify_all();
-  }
-  int waitAsync(const bool report = true) {   // report = false: on the caller's own error path — wait only, its error message stays
-    std::unique_lock<std::mutex> lk(mu);
-    cv_done.wait(lk, [&] { return pending == 0; });
-    if (rc && report) { dmv_err() = err; dmv_err_epoch()++; }
-    return rc;
-  }
-  ~BAWorkers() {
-    { std::lock_guard<std::mutex> lk(mu); quit = true; }
-    cv.notify_all();
-    for (auto& t : th) t.join();
-  }
-};
-struct dmvio_hip_ba_batch {
-  BAWorkers workers;
-  dmvio_hip_ctx* ctx = nullptr;
-  hipStream_t stream = nullptr;
-  int cap = 0;
-  std::mutex mu;
-  BAWinDev* d_wins = nullptr;
-  BAWinDev* h_wins = nullptr;      // pinned
-  char* d_tab = nullptr;           // per window: [HM | bM | basis | adHostF | adTargetF] (uploaded) — stride tab_stride
-  char* h_tab = nullptr;           // pinned
-  char* d_out = nullptr;           // per window: [sys | trace (64 x 4) | x_last] (device-only / downloaded) — stride out_stride
-  double* h_trace = nullptr;       // pinned: cap x (256 + NMAX) doubles
-  size_t tab_stride = 0, out_stride = 0;
-  int exact_backsub = 0;
-  double host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host clock of the last call's phases (dmvio_hip_ba_batch_last_host_us)
-  float last_ms[3] = {0, 0, 0};    // HIP-event times of the last call: the loop (init chain + iterations), the final fix-linearisation, [profile] one stepped linearisation
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // a batch of >= 4 windows is cut into groups (three by default, at most BA_BATCH_STREAMS), one stream each, their launches interleaved stage by stage (optimizeBatchGroup): while one group's
-  // k_ba_solve runs (one workgroup per window) the other groups' linearisations / accumulations fill the device
-  enum { BA_BATCH_STREAMS = 8 };
-  hipStream_t gstream[BA_BATCH_STREAMS] = {};   // [0] = stream
-  hipEvent_t gev[BA_BATCH_STREAMS][3] = {};                                        // per group: [0] its initial linearisation is enqueued (the next group's start), [1] its loop is done and its states are on the host, [2] its last kernel
-  int lin_lanes = 1;               // dmvio_hip_ba_batch_set_linearize_lanes: 1 = k_ba_linearize_b1 (one lane per residual) from 4 windows on, 8 = always the eight-lane kernel
-  int streams = 0;                 // dmvio_hip_ba_batch_set_streams: 0 = automatic, k >= 1 = at most k groups (1: the whole batch on one stream)
-  int profile = 0;                 // dmvio_hip_ba_batch_set_profile: events around the stepped linearisation of iteration 1 (k_ba_linearize_b of all windows)
-};
-static constexpr int BA_BATCH_NMAX = 4 + 8 * BA_MAXF_CAP;
-static size_t batchTabBytes() {
-  const size_t n = BA_BATCH_NMAX, F2 = (size_t)BA_MAXF_CAP * BA_MAXF_CAP;
-  return ((n * n + n + 7 * n) * sizeof(double) + 2 * F2 * 64 * sizeof(float) + F2 * sizeof(BAPrecalc) + 255) & ~(size_t)255;
-}
-static size_t batchOutBytes() {   // [sys | trace | x_last | H_L, b_L of the residuals kept linearised]
-  const size_t n = BA_BATCH_NMAX;
-  return ((2 * (n * n + n) + 1 + 256 + n + (n * n + n)) * sizeof(double) + 255) & ~(size_t)255;
-}
-extern "C" {
-dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
-  if (!ctx || max_windows < 1 || max_windows > 4096) { failmsg("ba_batch_create: bad argument"); return nullptr; }
-  if (hipSetDevice(ctx->device) != hipSuccess) { failmsg("ba_batch_create: hipSetDevice failed"); return nullptr; }
-  dmvio_hip_ba_batch* B = new dmvio_hip_ba_batch();
-  B->ctx = ctx; B->cap = max_windows;
-  B->tab_stride = batchTabBytes(); B->out_stride = batchOutBytes();
-  bool ok = hipStreamCreateWithFlags(&B->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc((void**)&B->d_wins, sizeof(BAWinDev) * max_windows) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&B->h_wins, sizeof(BAWinDev) * max_windows, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc((void**)&B->d_tab, B->tab_stride * max_windows) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&B->h_tab, B->tab_stride * max_windows, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc((void**)&B->d_out, B->out_stride * max_windows) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&B->h_trace, sizeof(double) * (257 + BA_BATCH_NMAX) * max_windows, hipHostMallocDefault) == hipSuccess;
-  for (int k = 0; k < 8 && ok; k++) ok = hipEventCreate(&B->ev[k]) == hipSuccess;
-  B->gstream[0] = B->stream;
-  for (int g = 1; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS && ok; g++) ok = hipStreamCreateWithFlags(&B->gstream[g], hipStreamNonBlocking) == hipSuccess;
-  for (int g = 0; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS && ok; g++) for (int k = 0; k < 3 && ok; k++) ok = hipEventCreateWithFlags(&B->gev[g][k], hipEventDisableTiming) == hipSuccess;
-  if (ok) ok = hipMemset(B->d_out, 0, B->out_stride * max_windows) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
-  if (!ok) { failmsg("ba_batch_create: device / pinned allocation failed"); dmvio_hip_ba_batch_destroy(B); return nullptr; }
-  if (max_windows >= 8) {
-    const unsigned int hw = std::thread::hardware_concurrency();
-    B->workers.start((int)std::min<unsigned int>(7, hw > 2 ? hw - 2 : 0), ctx->device);
-  }
-  return B;
-}
-void dmvio_hip_ba_batch_destroy(dmvio_hip_ba_batch* B) {
-  if (!B) return;
-  hipSetDevice(B->ctx->device);
-  if (B->stream) { hipStreamSynchronize(B->stream); hipStreamDestroy(B->stream); }
-  if (B->d_wins) hipFree(B->d_wins);
-  if (B->h_wins) hipHostFree(B->h_wins);
-  if (B->d_tab) hipFree(B->d_tab);
-  if (B->h_tab) hipHostFree(B->h_tab);
-  if (B->d_out) hipFree(B->d_out);
-  if (B->h_trace) hipHostFree(B->h_trace);
-  for (int k = 0; k < 8; k++) if (B->ev[k]) hipEventDestroy(B->ev[k]);
-  for (int g = 1; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS; g++) if (B->gstream[g]) { hipStreamSynchronize(B->gstream[g]); hipStreamDestroy(B->gstream[g]); }
-  for (int g = 0; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS; g++) for (int k = 0; k < 3; k++) if (B->gev[g][k]) hipEventDestroy(B->gev[g][k]);
-  delete B;
-}
-// 1: the back substitution of the 68x68 solve in the host's order (one dependent chain of n^2 / 2 subtractions: x bit-identical to BAHost::ldltSolveTransposed, ~10 us more per
-// iteration); 0 (default): column-oriented — the same terms in another association (measured |dx| <= 1e-12 relative, tests/test_ba_batch_gpu.py)
-int dmvio_hip_ba_batch_set_exact_backsub(dmvio_hip_ba_batch* B, int on) {
-  if (!B) return failmsg("ba_batch: null handle");
-  std::lock_guard<std::mutex> lk(B->mu);
-  B->exact_backsub = on ? 1 : 0;
-  return 0;
-}
-int dmvio_hip_ba_batch_last_ms(dmvio_hip_ba_batch* B, float ms3[3]) {
-  if (!B || !ms3) return failmsg("ba_batch: null argument");
-  std::lock_guard<std::mutex> lk(B->mu);
-  ms3[0] = B->last_ms[0]; ms3[1] = B->last_ms[1]; ms3[2] = B->last_ms[2];
-  return 0;
-}
-// diagnostics: in-kernel timeline of window 0's last k_ba_solve of the last call, 100 MHz ticks since the kernel started: staged + settled, delta + bM_top + diagonal, system
-// assembled, pivot order, permuted, factorised, back-substituted, x, resubstitution inputs + stepped states, exponentials, pair tables, energies
-int dmvio_hip_ba_batch_last_solve_ticks(dmvio_hip_ba_batch* B, int ticks12[12]) {
-  if (!B || !ticks12) return failmsg("ba_batch: null argument");
-  std::lock_guard<std::mutex> lk(B->mu);
-  for (int i = 0; i < 12; i++) ticks12[i] = B->h_wins[0].S.ticks[i];
-  return 0;
-}
-// diagnostics: how window w's last k_ba_solve of the last call found its pivot order — 0 = ranks of the scaled diagonal (all |values| distinct), 1 = ties replayed
-// (selection with swaps on one wavefront), 2 = a NaN on the diagonal (the literal loop)
-int dmvio_hip_ba_batch_last_pivot_branch(dmvio_hip_ba_batch* B, int w, int* branch) {
-  if (!B || !branch || w < 0 || w >= B->cap) return failmsg("ba_batch_last_pivot_branch: bad argument");
-  std::lock_guard<std::mutex> lk(B->mu);
-  *branch = B->h_wins[w].S.pivot_branch;
-  return 0;
-}
-// Tests / diagnostics: the solve of EnergyFunctional.cpp:971-973 for a GIVEN system on the device, exactly as k_ba_solve runs it (Jacobi scaling (H_ii + 10)^-1/2, Eigen's
-// pivot order, LDL^T, forward / back substitution on one 512-thread workgroup) — the device counterpart of dmvio_hip_ba_solve_ldlt.  HPassed: n x n row-major (the lower
-// triangle is read), n = 4 + 8 F <= 100.  x_out[n]; perm_out[n] (may be NULL): the index the transpositions bring to position k; branch_out (may be NULL): 0 ranks /
-// 1 ties / 2 NaN; zero_out (may be NULL): the matrix's first pivot was zero (x = 0).  exact_backsub as dmvio_hip_ba_batch_set_exact_backsub.
-int dmvio_hip_ba_debug_solve(dmvio_hip_ctx* ctx, int n, const double* HPassed, const double* b_in, int exact_backsub, double* x_out, int* perm_out, int* branch_out, int* zero_out) {
-  if (!ctx || !HPassed || !b_in || !x_out || n < 2 || n > 4 + 8 * BA_MAXF_CAP) return failmsg("ba_debug_solve: bad argument");
-  HIPCHK(hipSetDevice(ctx->device));
-  double* d = nullptr;
-  const size_t nin = (size_t)n * n + n, nout = 2 * (size_t)n + 2;
-  HIPCHK(hipMalloc((void**)&d, sizeof(double) * (nin + nout)));
-  std::vector<double> h(nin + nout, 0.0);
-  memcpy(h.data(), HPassed, sizeof(double) * n * n); memcpy(h.data() + (size_t)n * n, b_in, sizeof(double) * n);
-  hipError_t e = hipMemcpy(d, h.data(), sizeof(double) * nin, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    const bool small = n <= 4 + 8 * BA_MAXF;
-    const size_t lds = sizeof(double) * baSolveCoreLdsDoubles(n);
-    if (small) hipLaunchKernelGGL((k_ba_solve_debug<BA_MAXF>), dim3(1), dim3(BA_SOLVE_THREADS), lds, nullptr, n, d, d + (size_t)n * n, exact_backsub, d + nin);
-    else hipLaunchKernelGGL((k_ba_solve_debug<BA_MAXF_CAP>), dim3(1), dim3(BA_SOLVE_THREADS), lds, nullptr, n, d, d + (size_t)n * n, exact_backsub, d + nin);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(h.data() + nin, d + nin, sizeof(double) * nout, hipMemcpyDeviceToHost);
-  }
-  hipFree(d);
-  if (e != hipSuccess) return failmsg((std::string("ba_debug_solve: ") + hipGetErrorString(e)).c_str());
-  const double* o = h.data() + nin;
-  memcpy(x_out, o, sizeof(double) * n);
-  if (perm_out) for (int i = 0; i < n; i++) perm_out[i] = (int)o[n + i];
-  if (branch_out) *branch_out = (int)o[2 * n];
-  if (zero_out) *zero_out = (int)o[2 * n + 1];
-  return 0;
-}
-// 0 (default): a batch of >= 4 windows is cut into up to three groups on three streams (at least two windows each), their launches interleaved; k >= 1: at most k groups
-// (1 = the whole batch on one stream).  The grouping changes no result: no arithmetic crosses windows.
-int dmvio_hip_ba_batch_set_streams(dmvio_hip_ba_batch* B, int streams) {
-  if (!B || streams < 0) return failmsg("ba_batch_set_streams: bad argument");
-  std::lock_guard<std::mutex> lk(B->mu);
-  B->streams = std::min<int>(streams, dmvio_hip_ba_batch::BA_BATCH_STREAMS);
-  return 0;
-}
-// which linearisation kernel a batch of >= 4 windows runs: 1 (default) = k_ba_linearize_b1, one lane per residual; 8 = k_ba_linearize_b, eight lanes per residual (what a
-// single window runs).  Same values either way.
-int dmvio_hip_ba_batch_set_linearize_lanes(dmvio_hip_ba_batch* B, int lanes) {
-  if (!B || (lanes != 1 && lanes != 8)) return failmsg("ba_batch_set_linearize_lanes: 1 or 8");
-  std::lock_guard<std::mutex> lk(B->mu);
-  B->lin_lanes = lanes;
-  return 0;
-}
-// measurement: HIP events around the stepped linearisation of the second iteration (k_ba_linearize_b over all windows of the call) -> dmvio_hip_ba_batch_last_ms()[2]
-int dmvio_hip_ba_batch_set_profile(dmvio_hip_ba_batch* B, int on) {
-  if (!B) return failmsg("ba_batch: null handle");
-  std::lock_guard<std::mutex> lk(B->mu);
-  B->profile = on ? 1 : 0;
-  return 0;
-}
-}  // extern "C"
-
-static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba* const* hs, int mnumOptIts, float* rmse, double* finalEnergy, int* iterations, double* trace,
-                              double* x_last) {
-  const int F = hs[0]->H.F, n = hs[0]->H.n(), F2 = F * F, tot = 2 * (n * n + n);
-  if (F < 2) { for (int w = 0; w < Wn; w++) { if (rmse) rmse[w] = 0; if (iterations) iterations[w] = 0; if (finalEnergy) finalEnergy[w] = 0; } return 0; }
-  if (F < 3) mnumOptIts = 20;
-  if (F < 4) mnumOptIts = 15;
-  if (mnumOptIts < 1) return failmsg("ba_optimize_batch: mnumOptIts < 1 (the device-resident loop writes the trace's first row in its first solve)");
-  hipStream_t s = B->stream;
-  const auto t_call = std::chrono::steady_clock::now();
-  auto stamp = [&](const int k) { B->host_us[k] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count(); };
-  // the stream groups of the call (why and how they run: at the launches below)
-  const int maxG = B->streams > 0 ? B->streams : 3;   // measured (tools/ba_batch_streams.py): three groups are best at W = 16 and 64; a fourth stream shares a hardware queue
-                                                        // with another one (GPU_MAX_HW_QUEUES = 4, one of them busy with the handles' own streams) and loses
-  const int G = (Wn >= 4 && !B->profile) ? std::max(1, std::min(maxG, Wn / 2)) : 1;
-  struct Grp { hipStream_t st; int w0, cnt; };
-  Grp grp[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
-  for (int g = 0; g < G; g++) { grp[g].st = B->gstream[g]; grp[g].w0 = (int)(((long long)Wn * g) / G); grp[g].cnt = (int)(((long long)Wn * (g + 1)) / G) - grp[g].w0; }
-  auto groupOf = [&](const int w) { int g = 0; while (g + 1 < G && w >= grp[g + 1].w0) g++; return g; };
-  struct StreamSwap {   // the handles' own entry points (prepare()'s table uploads) enqueue on the stream of the window's GROUP for the duration of the call: what a group's
-                        // kernels read is then in front of them in stream order, whichever thread prepares the window and however late it does so
-    std::vector<std::pair<dmvio_hip_ba*, hipStream_t>> saved;
-    ~StreamSwap() { for (auto& kv : saved) kv.first->stream = kv.second; }
-  } swap;
-  int gx_lin = 0, gx_pt8 = 0, gx_acc = 0, gx_res = 0, gx_pts = 0;
-  const int n_gather = (tot + 256) / 256, n_stitch = F + F2;
-  for (int w = 0; w < Wn; w++) {
-    dmvio_hip_ba* b = hs[w];
-    const hipStream_t gs = grp[groupOf(w)].st;
-    if (b->stream != gs) { HIPCHK(hipStreamSynchronize(b->stream)); swap.saved.emplace_back(b, b->stream); b->stream = gs; }
-    const int nacc = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
-    gx_lin = std::max(gx_lin, b->n_lin_blocks); gx_pt8 = std::max(gx_pt8, b->n_pt8_blocks); gx_acc = std::max(gx_acc, nacc); gx_res = std::max(gx_res, (b->H.R + 255) / 256); gx_pts = std::max(gx_pts, b->H.N);
-  }
-  auto prepare = [&](const int w) -> int {
-    dmvio_hip_ba* b = hs[w];
-    BAHost& H = b->H;
-    b->vio = nullptr; b->vio_opt = nullptr; b->dynW = 1.0; H.gtsam = false;
-    b->pending_reject = false; b->pending_trace = -1; b->sums_fresh = false; b->sys_ready = false;
-    b->fullJ_applied = false;   // the batched linearisations relinearise and apply every residual without writing d_fullJ: what the buffer holds is no longer the applied state's
-    if (int r = resolveTh(b)) return r;
-    if (b->adj_dirty) { if (int r = uploadAdjoints(b)) return r; }   // on the group's stream (StreamSwap): in front of the group's first k_ba_stitch_b
-    // (the precalc table, the thresholds and the activation of all residuals travel with the batch: one upload, one launch for all windows)
-    H.getNullspaces();
-    H.prepareOrthogonalize();
-    // ---- the window's record
-    BAWinDev& V = B->h_wins[w];
-    memset(&V, 0, sizeof(V));
-    fillWindow(b);
-    V.W = b->W; V.Wb = b->W;
-    V.P = b->P; V.Rs = b->Rs;
-    V.D = makeDecide(b, 0, true, false);
-    for (int f = 0; f < BA_MAXF_CAP; f++) V.frameTH[f] = f < F ? H.fr[f].frameEnergyTH : 0.0f;
-    V.D.frameTH = B->d_wins[w].frameTH;   // (an address: the record's own copy on the device)
-    b->th_dirty = true;                    // the handle's own device copy is stale from here on; the host's values are brought up to date below
-    dynFromHost(H, V.T); V.Tb = V.T;
-    b->dyn_cur = V.T;
-    {
-      AccumArgs& A = V.A;
-      A.F = F; A.N = H.N; A.nsTop = b->nsTop; A.nsD = b->nsD; A.nsC = b->nsC;
-      A.top_begin = b->d_top_begin; A.top_members = b->d_top_members; A.scd_begin = b->d_scd_begin; A.scd_members = b->d_scd_members;
-      A.accTop = b->d_accTop; A.accD = b->d_accD; A.accE = b->d_accE; A.accC = b->d_accC; A.numTop = b->d_numTop; A.numD = b->d_numD;
-      A.ticks = nullptr;
-    }
-    V.SB = b->SB; V.adHost = b->d_adHost; V.adTarget = b->d_adTarget;
-    char* out = B->d_out + B->out_stride * (size_t)w;
-    V.sys = reinterpret_cast<double*>(out);
-    V.ctl = b->d_ctl;
-    V.n_lin_blocks = b->n_lin_blocks; V.n_pt8_blocks = b->n_pt8_blocks; V.n_acc_blocks = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
-    V.n_res_blocks = (H.R + 255) / 256; V.n_gather_blocks = n_gather; V.n_stitch_blocks = n_stitch; V.n_lin1_blocks = (H.R + LIN_THREADS - 1) / LIN_THREADS;
-    BASolveDev& S = V.S;
-    S.F = F; S.n = n; S.stepped = 0; S.iterations_done = 0; S.n_accepted = 0; S.exact_backsub = B->exact_backsub;
-    S.lambda = 1e-5;
-    S.lastL = calcLEnergy(b); S.lastM = H.calcMEnergy(); S.newL = S.lastL; S.newM = S.lastM;
-    // residuals kept linearised (dmvio_hip_ba_fix_linearization): what the three-pass accumulation and the linearised energy read, at the deltas of the state the window enters with
-    V.n_lin = b->n_lin; V.n_lin_runs = (H.N + 49) / 50; V.lin_cnt = 0;
-    if (b->n_lin > 0) {
-      V.fullJ = b->d_fullJ; V.lin = b->d_lin; V.rtz = b->d_rtz; V.linRec = b->d_linRec; V.linActive = b->d_linActive; V.topActive = b->d_topActive; V.linE = b->d_linE;
-      std::vector<float> adHT;
-      H.adHTdeltaF(adHT);
-      for (int k = 0; k < 2; k++) { memcpy(V.adHTdelta[k], adHT.data(), sizeof(float) * adHT.size()); for (int i = 0; i < 4; i++) V.cDeltaF[k][i] = H.cDeltaF[i]; }
-    }
-    for (int i = 0; i < 4; i++) { S.c_value[i] = H.c_value[i]; S.c_value_zero[i] = H.c_value_zero[i]; S.c_value_backup[i] = H.c_value[i]; S.cPrior[i] = H.cPrior[i]; S.cPriorF[i] = H.cPriorF[i]; }
-    for (int f = 0; f < F; f++) {
-      BAFrameDev& q = S.fr[f]; const BAFrameHost& h = H.fr[f];
-      q.evalPT = h.evalPT; q.ab_exposure = h.ab_exposure;
-      for (int i = 0; i < 10; i++) { q.state[i] = h.state[i]; q.state_zero[i] = h.state_zero[i]; q.state_backup[i] = h.state[i]; }
-      for (int i = 0; i < 8; i++) q.prior[i] = h.prior[i];
-    }
-    // ---- the uploaded tables: [HM | bM | basis | adHostF | adTargetF]
-    char* tab = B->h_tab + B->tab_stride * (size_t)w;
-    char* dtab = B->d_tab + B->tab_stride * (size_t)w;
-    double* tHM = reinterpret_cast<double*>(tab);
-    const bool haveM = H.HM.size() == (size_t)n * n;
-    S.haveM = haveM ? 1 : 0;
-    if (haveM) { memcpy(tHM, H.HM.data(), sizeof(double) * n * n); memcpy(tHM + (size_t)n * n, H.bM.data(), sizeof(double) * n); }
-    double* tBasis = tHM + (size_t)n * n + n;
-    S.nBasis = (int)H.orthoBasis.size();
-    for (int k = 0; k < S.nBasis; k++) memcpy(tBasis + (size_t)k * n, H.orthoBasis[k].data(), sizeof(double) * n);
-    float* tAd = reinterpret_cast<float*>(tBasis + 7 * (size_t)n);
-    memcpy(tAd, H.adHostF.data(), sizeof(float) * F2 * 64); memcpy(tAd + (size_t)F2 * 64, H.adTargetF.data(), sizeof(float) * F2 * 64);
-    S.HM = reinterpret_cast<const double*>(dtab); S.bM = S.HM + (size_t)n * n; S.basis = S.bM + n;
-    S.adHostF = reinterpret_cast<const float*>(S.basis + 7 * (size_t)n); S.adTargetF = S.adHostF + (size_t)F2 * 64;
-    BAPrecalc* tPre = reinterpret_cast<BAPrecalc*>(tAd + 2 * (size_t)F2 * 64);
-    memcpy(tPre, H.pre.data(), sizeof(BAPrecalc) * F2);
-    V.pre = reinterpret_cast<const BAPrecalc*>(S.adTargetF + (size_t)F2 * 64);
-    b->pre_static_valid = false;           // the handle's own table was not refreshed
-    S.trace = V.sys + tot + 1; S.x_last = S.trace + 256;
-    V.sysL = S.x_last + BA_BATCH_NMAX;
-    return 0;
-  };
-  stamp(0);
-  const size_t used_tab = ((size_t)n * n + n + 7 * (size_t)n) * sizeof(double) + 2 * (size_t)F2 * 64 * sizeof(float) + (size_t)F2 * sizeof(BAPrecalc);
-  if (used_tab > B->tab_stride) return failmsg("ba_optimize_batch: table slab too small");
-  const FrameStore fs = B->ctx->fs;
-  const size_t solveLds = sizeof(double) * baSolveLdsDoubles(n, F, F <= BA_MAXF ? BASolveDims<BA_MAXF>::ALIAS_HM : BASolveDims<BA_MAXF_CAP>::ALIAS_HM);
-  // Up to three groups of windows by default (at most BA_BATCH_STREAMS on request), one stream each, from 4 windows on: k_ba_solve is one workgroup per window (a 50 us latency chain on a handful of CUs), so while one
-  // group solves, the other groups' linearisations / accumulations fill the device.  The groups share nothing.  Their launches are enqueued STAGE BY STAGE (initial chain of
-  // every group, iteration 0 of every group, ...): a stream whose commands the host has not submitted yet cannot overlap with anything (measured: with the groups enqueued one
-  // after the other the second one started three iterations late).  Group g starts behind group g-1's initial linearisation, which keeps the groups out of step.  A profiled
-  // call (dmvio_hip_ba_batch_set_profile) runs as ONE group: its timed linearisation then covers all windows of the call, alone on the device.
-  // The host's per-window work is pipelined along the groups too: group g's tables are prepared, uploaded and its first chain enqueued while the device already works on the
-  // groups before it; behind the loop group g's states are written back (and its final linearisation enqueued) while the later groups still run.
-  // the eight-lane kernel hides latency (few windows); the one-lane kernel does an eighth of the lane work (a grid that fills the device)
-  const bool lin1 = B->lin_lanes == 1 && Wn >= 4;
-  const int gx_lin1 = (gx_res * 256 + LIN_THREADS - 1) / LIN_THREADS;
-  const size_t patchLds = sizeof(float) * LIN_THREADS * BA_PATCH_STRIDE;   // the one-lane linearisation's per-lane 8x8 image windows
-  auto linearize = [&](hipStream_t st, const BAWinDev* dwq, const int cnt, const int kind) {
-    if (lin1) hipLaunchKernelGGL(k_ba_linearize_b1, dim3(gx_lin1, cnt), dim3(LIN_THREADS), patchLds, st, dwq, fs, kind);
-    else hipLaunchKernelGGL(k_ba_linearize_b, dim3(gx_lin, cnt), dim3(LIN_THREADS), 0, st, dwq, fs, kind);
-  };
-  auto solve = [&](const Grp& q, const int it, const int finish) {
-    if (finish) {
-      if (F <= BA_MAXF) hipLaunchKernelGGL((k_ba_solve<BA_MAXF, true>), dim3(q.cnt), dim3(BA_SOLVE_THREADS), solveLds, q.st, B->d_wins + q.w0, it);
-      else hipLaunchKernelGGL((k_ba_solve<BA_MAXF_CAP, true>), dim3(q.cnt), dim3(BA_SOLVE_THREADS), solveLds, q.st, B->d_wins + q.w0, it);
-    } else {
-      if (F <= BA_MAXF) hipLaunchKernelGGL((k_ba_solve<BA_MAXF, false>), dim3(q.cnt), dim3(BA_SOLVE_THREADS), solveLds, q.st, B->d_wins + q.w0, it);
-      else hipLaunchKernelGGL((k_ba_solve<BA_MAXF_CAP, false>), dim3(q.cnt), dim3(BA_SOLVE_THREADS), solveLds, q.st, B->d_wins + q.w0, it);
-    }
-  };
-  // a group that holds a window with residuals kept linearised runs EnergyFunctional's three accumulations (L / A / Schur pass: accumulateLin above) for those windows; its
-  // other windows take their one ordinary accumulation in the A pass
-  bool grpLin[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
-  for (int g = 0; g < G; g++) { grpLin[g] = false; for (int w = grp[g].w0; w < grp[g].w0 + grp[g].cnt; w++) grpLin[g] = grpLin[g] || hs[w]->n_lin > 0; }
-  auto linRecords = [&](const Grp& q, const int gate, const bool sums) {   // the addPoint<1> records (and the A / L activity views); sums: + the linearised residuals' per-point sums
-    const BAWinDev* dwq = B->d_wins + q.w0;
-    hipLaunchKernelGGL(k_ba_lin_records_b, dim3(gx_res, q.cnt), dim3(256), 0, q.st, dwq, gate);
-    if (sums) hipLaunchKernelGGL(k_ba_lin_point_sums_b, dim3((gx_pts + 255) / 256, q.cnt), dim3(256), 0, q.st, dwq, gate);
-  };
-  auto chain = [&](const Grp& q, const int g, const int backup, const int apply, const int gate, const bool sums_done) {   // applyRes + per-point sums -> accumulate -> stitch -> gather: the system of the (new) state
-    const BAWinDev* dwq = B->d_wins + q.w0;
-    if (!sums_done) hipLaunchKernelGGL(k_ba_point_sums_b, dim3(gx_pt8, q.cnt), dim3(256), 0, q.st, dwq, backup, apply, gate);
-    for (int pass = grpLin[g] ? (int)BA_PASS_L : (int)BA_PASS_ALL; pass <= (grpLin[g] ? (int)BA_PASS_S : (int)BA_PASS_ALL); pass++) {
-      hipLaunchKernelGGL(k_ba_accumulate_b, dim3(gx_acc, q.cnt), dim3(256), 0, q.st, dwq, gate, pass);
-      hipLaunchKernelGGL(k_ba_stitch_b, dim3(n_stitch, q.cnt), dim3(64 * F), sizeof(StitchWave) * F, q.st, dwq, gate, pass);
-      if (F <= BA_MAXF) hipLaunchKernelGGL((k_ba_stitch_gather_b<BA_MAXF>), dim3(n_gather, q.cnt), dim3(256), 0, q.st, dwq, gate, pass);
-      else hipLaunchKernelGGL((k_ba_stitch_gather_b<BA_MAXF_CAP>), dim3(n_gather, q.cnt), dim3(256), 0, q.st, dwq, gate, pass);
-    }
-  };
-  // ---- per group: its windows' tables (host), their upload, then every residual still in the graph active again (FullSystemOptimize.cpp:431-448), initial linearisation,
-  // applyRes and the first system (:450-470).  With workers the windows are prepared in index order behind the caller's back: group g + 1's while group g is enqueued.
-  std::atomic<int> prepared[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
-  for (int g = 0; g < G; g++) prepared[g].store(0, std::memory_order_relaxed);
-  const bool async_prepare = !B->workers.th.empty() && Wn >= 8 && G > 1;
-  std::atomic<int> prepare_failed{0};   // set BEFORE the window is counted: whoever sees a group complete (acquire) sees the failure of any of its windows
-  if (async_prepare)
-    B->workers.startAsync(Wn, [&](const int w) -> int {
-      const int r = prepare(w);
-      if (r) prepare_failed.store(1, std::memory_order_relaxed);
-      prepared[groupOf(w)].fetch_add(1, std::memory_order_release);
-      return r;
-    });
-  else if (int r = B->workers.parallelFor(Wn, prepare)) return r;
-  struct AsyncGuard {   // the workers run a lambda over this frame's locals: no way out of the launch loop (HIPCHK returns) without waiting for them
-    BAWorkers& wk; bool armed;
-    ~AsyncGuard() { if (armed) wk.waitAsync(false); }
-  } asyncGuard{B->workers, async_prepare};
-  int rc_launch = 0;
-  for (int g = 0; g < G; g++) {
-    const Grp& q = grp[g];
-    const BAWinDev* dwq = B->d_wins + q.w0;
-    if (async_prepare) while (prepared[g].load(std::memory_order_acquire) < q.cnt) __builtin_ia32_pause();
-    if (g == 0) stamp(1);
-    if (async_prepare && prepare_failed.load(std::memory_order_relaxed)) { rc_launch = 1; break; }   // a window's preparation failed: nothing of it (or of the groups behind it) is launched
-    if (g == 0) { HIPCHK(hipEventRecord(B->ev[0], s)); for (int k = 1; k < G; k++) HIPCHK(hipStreamWaitEvent(grp[k].st, B->ev[0], 0)); }   // (the other streams: behind whatever the batch's stream still holds; prepare()'s own uploads need no event: they are on the group's stream)
-    HIPCHK(hipMemcpyAsync(B->d_wins + q.w0, B->h_wins + q.w0, sizeof(BAWinDev) * q.cnt, hipMemcpyHostToDevice, q.st));
-    HIPCHK(hipMemcpyAsync(B->d_tab + B->tab_stride * (size_t)q.w0, B->h_tab + B->tab_stride * (size_t)q.w0, B->tab_stride * (size_t)(q.cnt - 1) + used_tab, hipMemcpyHostToDevice, q.st));
-    if (g > 0) HIPCHK(hipStreamWaitEvent(q.st, B->gev[g - 1][0], 0));   // the stagger
-    hipLaunchKernelGGL(k_ba_reset_oob_b, dim3(gx_res, q.cnt), dim3(256), 0, q.st, dwq);
-    linearize(q.st, dwq, q.cnt, BA_LINB_INITIAL);
-    if (g + 1 < G) HIPCHK(hipEventRecord(B->gev[g][0], q.st));
-    hipLaunchKernelGGL(k_ba_apply_b, dim3(gx_res, q.cnt), dim3(256), 0, q.st, dwq, 0, (int)BA_GATE_ALWAYS);
-    if (grpLin[g]) linRecords(q, BA_GATE_ALWAYS, true);
-    chain(q, g, 1, 0, BA_GATE_ALWAYS, false);
-  }
-  if (async_prepare) {
-    asyncGuard.armed = false;
-    const int r = B->workers.waitAsync();
-    if (r || rc_launch) { for (int g = 0; g < G; g++) hipStreamSynchronize(grp[g].st); return r ? r : -1; }
-  }
-  // ---- the loop (:485-586): nothing in it waits for the host
-  for (int it = 0; it < mnumOptIts; it++)
-    for (int g = 0; g < G; g++) {
-      const Grp& q = grp[g];
-      const BAWinDev* dwq = B->d_wins + q.w0;
-      solve(q, it, 0);
-      if (grpLin[g]) hipLaunchKernelGGL(k_ba_lin_energy_b, dim3(gx_res, q.cnt), dim3(256), 0, q.st, B->d_wins + q.w0);   // E_L's linearised term of the stepped state, for the accept test
-      const bool prof = B->profile && g == 0 && it == std::min(1, mnumOptIts - 1);
-      if (prof) HIPCHK(hipEventRecord(B->ev[4], q.st));
-      if (lin1) { hipLaunchKernelGGL(k_ba_resubstitute_b, dim3(gx_pt8, q.cnt), dim3(256), 0, q.st, dwq); linearize(q.st, dwq, q.cnt, BA_LINB_STEPPED_DONE); }
-      else linearize(q.st, dwq, q.cnt, BA_LINB_STEPPED);
-      if (prof) HIPCHK(hipEventRecord(B->ev[5], q.st));
-      // rejected: restore + relinearise | accepted: applyRes + per-point sums (the last iteration's accepted step is only applied: nobody solves its system) — one launch
-      const int what = it < mnumOptIts - 1 ? 0 : 1;
-      if (grpLin[g] && what == 0) linRecords(q, BA_GATE_ACCEPTED, true);   // (the per-point sums below add the linearised residuals' Hdd / bd / Hcd)
-      const int gx_post = std::max(lin1 ? gx_lin1 : gx_lin, what == 0 ? gx_pt8 : gx_res);
-      if (lin1) hipLaunchKernelGGL((k_ba_post_decide_b<true>), dim3(gx_post, q.cnt), dim3(LIN_THREADS), patchLds, q.st, dwq, fs, what);
-      else hipLaunchKernelGGL((k_ba_post_decide_b<false>), dim3(gx_post, q.cnt), dim3(LIN_THREADS), 0, q.st, dwq, fs, what);
-      if (grpLin[g] && what == 0) linRecords(q, BA_GATE_ACCEPTED, false);  // (again behind applyRes: the A pass's activity view follows the applied states)
-      if (what == 0) chain(q, g, 1, 1, BA_GATE_ACCEPTED, true);
-    }
-  // ---- settle the last decision; every group's states and traces come back on its own stream: [resInA | trace (64 x 4) | x_last] of a window is the tail of its system
-  // slab, one strided copy per group
-  for (int g = 0; g < G; g++) {
-    const Grp& q = grp[g];
-    solve(q, mnumOptIts, 1);
-    HIPCHK(hipMemcpyAsync(B->h_wins + q.w0, B->d_wins + q.w0, sizeof(BAWinDev) * q.cnt, hipMemcpyDeviceToHost, q.st));
-    HIPCHK(hipMemcpy2DAsync(B->h_trace + (size_t)(257 + BA_BATCH_NMAX) * q.w0, sizeof(double) * (257 + BA_BATCH_NMAX),
-                            reinterpret_cast<const double*>(B->d_out + B->out_stride * (size_t)q.w0) + tot, B->out_stride, sizeof(double) * (257 + n), q.cnt, hipMemcpyDeviceToHost, q.st));
-    HIPCHK(hipEventRecord(B->gev[g][1], q.st));
-  }
-  HIPCHK(hipGetLastError());
-  stamp(2);
-  // ---- back on the host: the optimised states, then the newest keyframe's new evaluation point (:596-603) and the final fix-linearisation (:604-609)
-  const size_t tab_pre_off = ((size_t)n * n + n + 7 * (size_t)n) * sizeof(double) + 2 * (size_t)F2 * 64 * sizeof(float);
-  auto writeBack = [&](const int w) -> int {
-    dmvio_hip_ba* b = hs[w];
-    BAHost& H = b->H;
-    const BAWinDev& V = B->h_wins[w];
-    const BASolveDev& S = V.S;
-    H.calibSetValue(S.c_value);
-    for (int i = 0; i < 4; i++) H.c_value_backup[i] = S.c_value_backup[i];
-    for (int f = 0; f < F; f++) {
-      BAHost::frameSetState(H.fr[f], S.fr[f].state);
-      for (int i = 0; i < 10; i++) H.fr[f].state_backup[i] = S.fr[f].state_backup[i];
-    }
-    const double* tr = B->h_trace + (size_t)(257 + BA_BATCH_NMAX) * w + 1;
-    H.resInA = (int)tr[-1];   // the count the last accumulation left behind (ef->resInA after the loop)
-    const int done = S.iterations_done;
-    b->iterations_done = done;
-    for (int k = 0; k <= done && k < 64; k++) for (int c = 0; c < 4; c++) b->trace[k][c] = tr[4 * k + c];   // row 0: the initial state (written by the first solve)
-    b->H.lastX.assign(tr + 256, tr + 256 + n);
-    if (x_last) memcpy(x_last + (size_t)BA_BATCH_NMAX * w, tr + 256, sizeof(double) * n);
-    BAFrameHost& last = H.fr[F - 1];
-    double newStateZero[10] = {0, 0, 0, 0, 0, 0, last.state[6], last.state[7], 0, 0};
-    last.evalPT = last.w2c;
-    BAHost::frameSetState(last, newStateZero);
-    BAHost::frameSetStateZero(last, newStateZero);
-    H.setAdjointsF();
-    b->adj_dirty = true;                   // uploaded by the next consumer (nothing in this call stitches again)
-    H.setPrecalcValues();
-    memcpy(reinterpret_cast<BAPrecalc*>(B->h_tab + B->tab_stride * (size_t)w + tab_pre_off), H.pre.data(), sizeof(BAPrecalc) * F2);
-    fillWindow(b);
-    BAWinDev& V2 = B->h_wins[w];
-    V2.W = b->W;
-    dynFromHost(H, V2.T); b->dyn_cur = V2.T;
-    b->th_pending = false;                 // the thresholds live in the window's record; the newest one is read back behind the final linearisation
-    return 0;
-  };
-  // group by group, in the order they finish (the stagger): wait for the group's states, write them back (the workers share a group's windows), upload the re-anchored
-  // records / pair tables and enqueue the group's final linearisation on its stream — while the groups behind it still run their last iterations
-  for (int g = 0; g < G; g++) {
-    const Grp& q = grp[g];
-    HIPCHK(hipEventSynchronize(B->gev[g][1]));
-    if (g == 0) stamp(3);
-    if (int r = B->workers.parallelFor(q.cnt, [&](const int i) { return writeBack(q.w0 + i); }, 4)) { for (int k = 0; k < G; k++) hipStreamSynchronize(grp[k].st); return r; }
-    if (g == G - 1) stamp(4);
-    HIPCHK(hipMemcpyAsync(B->d_wins + q.w0, B->h_wins + q.w0, sizeof(BAWinDev) * q.cnt, hipMemcpyHostToDevice, q.st));
-    HIPCHK(hipMemcpy2DAsync(B->d_tab + B->tab_stride * (size_t)q.w0 + tab_pre_off, B->tab_stride, B->h_tab + B->tab_stride * (size_t)q.w0 + tab_pre_off, B->tab_stride, sizeof(BAPrecalc) * F2, q.cnt,
-                            hipMemcpyHostToDevice, q.st));   // the re-anchored pair tables
-    if (g == 0) HIPCHK(hipEventRecord(B->ev[2], q.st));
-    linearize(q.st, B->d_wins + q.w0, q.cnt, BA_LINB_FINAL);
-    hipLaunchKernelGGL(k_ba_apply_b, dim3(gx_res, q.cnt), dim3(256), 0, q.st, B->d_wins + q.w0, 1, (int)BA_GATE_ALWAYS);   // applyRes + linearizeAll(true)'s removal of inactive residuals
-    HIPCHK(hipGetLastError());
-    if (g > 0) { HIPCHK(hipEventRecord(B->gev[g][2], q.st)); HIPCHK(hipStreamWaitEvent(s, B->gev[g][2], 0)); }
-  }
-  HIPCHK(hipEventRecord(B->ev[3], s));
-  stamp(5);
-  HIPCHK(hipStreamSynchronize(s));
-  stamp(6);
-  // HIP-event times: [0] the whole call on the device (first upload .. last kernel), [1] from the first group's final linearisation to the last kernel
-  HIPCHK(hipEventElapsedTime(&B->last_ms[0], B->ev[0], B->ev[3]));
-  HIPCHK(hipEventElapsedTime(&B->last_ms[1], B->ev[2], B->ev[3]));
-  B->last_ms[0] -= B->last_ms[1];   // (callers add the two)
-  B->last_ms[2] = 0;
-  if (B->profile) HIPCHK(hipEventElapsedTime(&B->last_ms[2], B->ev[4], B->ev[5]));
-  for (int w = 0; w < Wn; w++) {
-    dmvio_hip_ba* b = hs[w];
-    BAHost& H = b->H;
-    if (b->n_lin > 0) {   // accumulateLF_MT's system of the last accumulation, for dmvio_hip_ba_get_lf_system and the host-side solve entry points
-      std::vector<double> lf((size_t)n * n + n);
-      HIPCHK(hipMemcpy(lf.data(), B->h_wins[w].sysL, sizeof(double) * lf.size(), hipMemcpyDeviceToHost));
-      H.HLraw.assign(lf.begin(), lf.begin() + (size_t)n * n); H.bLraw.assign(lf.begin() + (size_t)n * n, lf.end());
-    }
-    const double fe = b->h_res->E[0];
-    H.fr[F - 1].frameEnergyTH = b->h_res->th[0];
-    b->final_energy = fe;
-    if (rmse) rmse[w] = sqrtf((float)(fe / (8 * H.resInA)));
-    if (finalEnergy) finalEnergy[w] = fe;
-    if (iterations) iterations[w] = b->iterations_done;
-    if (trace) memcpy(trace + (size_t)256 * w, b->trace, sizeof(b->trace));
-    b->sums_fresh = false; b->sys_ready = false;
-    // the staging area of this call's uploads is free again: they went out on the group's stream in front of the group's last kernel, which `s` has waited for (gev[g][2])
-    // before the host waited for `s` above — so waiting for `s` covers them (and costs nothing more: a first host wait on each group's stream measured ~2 % of a W = 16 call)
-    if (b->bounce.used || !b->bounce.outs.empty()) HIPCHK(b->bounce.finish(s));
-  }
-  stamp(7);
-  return 0;
-}
+#include "ba_batch_host.hpp"
 
 extern "C" {
-// windows[W]: handles of the batch's context, each with its window set (set_window + set_graph), all distinct.  rmse / finalEnergy / iterations: W entries each (may be
-// NULL); trace: W x 64 x 4 doubles or NULL ([E_A, E_L, E_M, accepted] per iteration, row 0 = the initial state).  Windows with different keyframe counts run as separate
-// groups, one after the other.  Every window's result is what a batch of that window alone gives, bit for bit (no arithmetic crosses windows).
-// Diagnostics: host clock (us since the call began) at the phase boundaries of the last dmvio_hip_ba_optimize_batch group: [0] stream hand-over done, [1] per-window tables
-// prepared, [2] whole loop enqueued, [3] loop finished (first wait), [4] states written back, [5] final linearisation enqueued, [6] finished (second wait), [7] results out
-int dmvio_hip_ba_batch_last_host_us(dmvio_hip_ba_batch* B, double us8[8]) {
-  if (!B || !us8) return failmsg("ba_batch_last_host_us: null argument");
-  std::lock_guard<std::mutex> lkB(B->mu);
-  for (int k = 0; k < 8; k++) us8[k] = B->host_us[k];
-  return 0;
-}
-int dmvio_hip_ba_optimize_batch(dmvio_hip_ba_batch* B, int W, dmvio_hip_ba* const* windows, int mnumOptIts, float* rmse, double* finalEnergy, int* iterations, double* trace) {
-  if (!B || !windows || W < 1) return failmsg("ba_optimize_batch: bad argument");
-  if (W > B->cap) return failmsg("ba_optimize_batch: more windows than the batch was created for");
-  std::lock_guard<std::mutex> lkB(B->mu);
-  HIPCHK(hipSetDevice(B->ctx->device));
-  // the handles' locks, in address order (two batches sharing handles cannot deadlock)
-  std::vector<dmvio_hip_ba*> order(windows, windows + W);
-  std::sort(order.begin(), order.end());
-  for (int i = 0; i < W; i++) {
-    if (!order[i]) return failmsg("ba_optimize_batch: null window");
-    if (i > 0 && order[i] == order[i - 1]) return failmsg("ba_optimize_batch: a window appears twice");
-    if (order[i]->ctx != B->ctx) return failmsg("ba_optimize_batch: a window belongs to another context");
-  }
-  std::vector<std::unique_lock<std::recursive_mutex>> locks;
-  for (dmvio_hip_ba* b : order) locks.emplace_back(b->mu);
-  for (int i = 0; i < W; i++) {
-    dmvio_hip_ba* b = windows[i];
-    if (!b->graph_ready) return failmsg("ba_optimize_batch: set_window + set_graph first");
-    if (sharded(b)) return failmsg("ba_optimize_batch: a window sharded over ranks cannot join a batch");
-  }
-  // groups of equal keyframe count, in the caller's order
-  std::vector<char> doneW(W, 0);
-  for (int i = 0; i < W; i++) {
-    if (doneW[i]) continue;
-    std::vector<int> idx;
-    for (int j = i; j < W; j++) if (!doneW[j] && windows[j]->H.F == windows[i]->H.F) { idx.push_back(j); doneW[j] = 1; }
-    const int Wn = (int)idx.size();
-    std::vector<dmvio_hip_ba*> hs(Wn);
-    std::vector<float> r(Wn); std::vector<double> fe(Wn), tr((size_t)256 * Wn); std::vector<int> its(Wn);
-    for (int k = 0; k < Wn; k++) hs[k] = windows[idx[k]];
-    if (int rc = optimizeBatchGroup(B, Wn, hs.data(), mnumOptIts, r.data(), fe.data(), its.data(), tr.data(), nullptr)) return rc;
-    for (int k = 0; k < Wn; k++) {
-      if (rmse) rmse[idx[k]] = r[k];
-      if (finalEnergy) finalEnergy[idx[k]] = fe[k];
-      if (iterations) iterations[idx[k]] = its[k];
-      if (trace) memcpy(trace + (size_t)256 * idx[k], tr.data() + (size_t)256 * k, sizeof(double) * 256);
-    }
-  }
-  return 0;
-}
 // dmvio_hip_ba_optimize of this handle through the device-resident loop (a batch of one window, created on first use): no PCIe poll per iteration.  The host-driven loop
 // (default) stays the reference for the hook branch (dmvio_hip_ba_optimize_vio), which needs the host in every iteration anyway.
 int dmvio_hip_ba_set_device_loop(dmvio_hip_ba* b, int on) {

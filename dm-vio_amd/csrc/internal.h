@@ -163,7 +163,7 @@ struct dmvio_hip_pixel_selector;
 int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, const float** d_u, const float** d_v);
 
 // hypothesis-parallel trackNewCoarse: the element-wise fp64 sum over all ranks of a small HOST buffer, in place (set by dmvio_hip_tracker_set_comm /
-// _set_comm_callbacks in capi_ba.hip, which owns the RCCL calls; used by dmvio_hip_tracker_track_new_coarse in capi.hip)
+// _set_comm_callbacks in capi_comm.hip, next to the RCCL loader; used by dmvio_hip_tracker_track_new_coarse in capi.hip)
 struct dmvio_hip_tracker;
 int dmv_tracker_set_exchange(dmvio_hip_tracker* t, std::function<int(double*, size_t)> allreduce_sum, int rank, int world);
 dmvio_hip_ctx* dmv_tracker_ctx(dmvio_hip_tracker* t);

@@ -1,0 +1,78 @@
+#!/usr/bin/env python
+"""Is the device code of two trees the same?  Compares, kernel by kernel, the gfx950 ISA of every translation unit tools/isa_check.py knows: the instruction stream (block
+labels .LBB<n>_<m> / .Ltmp<n> renumbered in order of appearance, `;` comments stripped) and the kernel's .amdhsa_* block.  What a refactor that must not touch the kernels
+checks itself with: every kernel of A must be in B and identical, and B must not add one.
+
+usage: python tools/isa_diff.py <dirA> <dirB>        directories of <unit>.s files
+       python tools/isa_diff.py --dump <dir> [csrc]  compile the units of dm-vio_amd/csrc (or of another tree's csrc) into <dir> first (hipcc -S --cuda-device-only, the Makefile's flags)
+exit status 0: identical; 1: differences (listed)."""
+import os, re, subprocess, sys
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_check import CSRC, FLAGS, UNITS
+
+
+def dump(outdir, csrc=CSRC):
+    os.makedirs(outdir, exist_ok=True)
+    def one(u):
+        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-S", "--cuda-device-only", "-o", os.path.join(os.path.abspath(outdir), u + ".s"), u + ".hip"], cwd=csrc, check=True,
+                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    with ThreadPoolExecutor(len(UNITS)) as ex:
+        list(ex.map(one, UNITS))
+
+
+def kernels(path):
+    """{kernel symbol: (normalised instruction lines, .amdhsa_ lines)}"""
+    lines = open(path).read().splitlines()
+    hsa, sym = {}, None
+    for l in lines:   # .amdhsa_kernel <sym> ... .end_amdhsa_kernel
+        t = l.strip()
+        if t.startswith(".amdhsa_kernel "):
+            sym = t.split()[1]; hsa[sym] = []
+        elif t == ".end_amdhsa_kernel":
+            sym = None
+        elif sym and t.startswith(".amdhsa_"):
+            hsa[sym].append(t)
+    start = {l.split(":")[0]: i for i, l in enumerate(lines) if l[:1] == "_" and ":" in l}   # "<sym>:   ; @<sym>"
+    res = {}
+    for k in hsa:
+        i = start[k]
+        body, names = [], {}
+        def renum(m):
+            return names.setdefault(m.group(0), "L%d" % len(names))
+        for l in lines[i + 1:]:
+            if l.startswith(".Lfunc_end") or l.strip().startswith((".section", ".amdhsa_kernel")):   # (the descriptor block stands between the code and .Lfunc_end)
+                break
+            t = l.split(";")[0].strip()
+            if not t or t.startswith((".p2align", ".loc", ".cfi", ".file")):
+                continue
+            body.append(re.sub(r"\.(LBB\d+_\d+|Ltmp\d+)", renum, t))
+        res[k] = (body, hsa[k])
+    return res
+
+
+def main(a, b):
+    bad = 0
+    for u in UNITS:
+        ka, kb = kernels(os.path.join(a, u + ".s")), kernels(os.path.join(b, u + ".s"))
+        for k in sorted(set(ka) | set(kb)):
+            if k not in kb: what = "missing in B"
+            elif k not in ka: what = "added in B"
+            elif ka[k][0] != kb[k][0]: what = "instructions differ (%d vs %d lines)" % (len(ka[k][0]), len(kb[k][0]))
+            elif ka[k][1] != kb[k][1]: what = ".amdhsa block differs"
+            else: continue
+            bad += 1
+            print("%s: %s: %s" % (u, k, what))
+        print("%s: %d kernels in A, %d in B" % (u, len(ka), len(kb)))
+    print("identical" if not bad else "%d kernels differ" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 3 and sys.argv[1] == "--dump":
+        dump(sys.argv[2], *sys.argv[3:4])
+    elif len(sys.argv) == 3:
+        sys.exit(main(sys.argv[1], sys.argv[2]))
+    else:
+        sys.exit(__doc__)
