@@ -459,6 +459,12 @@ class CoarseTrackerHip:
         fn = self.L.dmvio_hip_tracker_set_batch_kernel; fn.argtypes = [C.c_void_p, C.c_int]; fn.restype = C.c_int
         _chk(self.L, fn(self.p, int(mode)), "tracker_set_batch_kernel")
 
+    def set_residual_only_evals(self, on=True):
+        """True (default) = the device-resident LM runs the last iteration step of a level above 0 without the 9x9 sums nothing reads; identical outputs either way
+        (dmvio_hip_tracker_set_residual_only_evals)"""
+        fn = self.L.dmvio_hip_tracker_set_residual_only_evals; fn.argtypes = [C.c_void_p, C.c_int]; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, 1 if on else 0), "tracker_set_residual_only_evals")
+
     def set_template_order(self, row_major):
         """storage order of the template from the next setCoarseTrackingRef on (dmvio_hip_tracker_set_template_order)"""
         fn = self.L.dmvio_hip_tracker_set_template_order; fn.argtypes = [C.c_void_p, C.c_int]; fn.restype = C.c_int
@@ -608,6 +614,13 @@ class CoarseTrackerHip:
     def last_work(self):
         a = C.c_longlong(0); b = C.c_longlong(0)
         _chk(self.L, self.L.dmvio_hip_tracker_last_work(self.p, C.byref(a), C.byref(b)), "last_work")
+        return a.value, b.value
+
+    def last_residual_only_work(self):
+        """(evaluations, point evaluations) of the last batch launch that ran residual-only; both are part of last_work()'s counts"""
+        a = C.c_longlong(0); b = C.c_longlong(0)
+        fn = self.L.dmvio_hip_tracker_last_residual_only_work; fn.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, C.byref(a), C.byref(b)), "last_residual_only_work")
         return a.value, b.value
 
 

@@ -90,6 +90,7 @@ struct BatchPipeline {
 struct LastRun {
   int cluster = 0, threads = 0;        // workgroups per problem, threads per workgroup
   long long evals = 0, point_evals = 0, ticks_step = 0, ticks_eval = 0;
+  long long res_evals = 0, res_point_evals = 0;   // of evals / point_evals: the residual-only ones (dmvio_hip_tracker_last_residual_only_work)
   int vio_iterations = 0;              // LM iterations of the last host-LM call
   std::vector<int> repeat_lvl;         // per problem: the level that ran twice (or -1) ...
   std::vector<double> first_pass_res;  // ... and its residual after the first pass
@@ -136,6 +137,7 @@ struct dmvio_hip_tracker {
   BatchPipeline pipe;
   LastRun last;
   int batch_kernel = 0;          // dmvio_hip_tracker_set_batch_kernel: 1 = full batches on k_track_lm_pp (control steps beside the evaluations)
+  int res_only_evals = 1;        // dmvio_hip_tracker_set_residual_only_evals: k_track_lm runs the evaluations whose 9x9 sums nothing reads as residual-only ones
   unsigned int* d_pp_next = nullptr;
   int lm_threads_override = 0, lm_cluster_override = 0;   // dmvio_hip_tracker_set_launch_shape
   float* d_cl_part = nullptr;          // cluster mode: B x 2 x C x ACC_PAD partial sums
@@ -621,6 +623,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
   if (s.refusal) return failmsg(s.refusal);
   const int C = s.C;
   ClusterArgs cl; cl.C = C; cl.part = nullptr; cl.cnt = nullptr; cl.discard = pl.d_discard; cl.log = nullptr; cl.log_n = nullptr;
+  cl.res_only = t->res_only_evals;
   if (t->debug_mode) {
     // diagnostics: 1 = record the evaluations of this launch, 2 = run the recorded evaluations again without the control steps (dmvio_hip_tracker_debug_record_replay)
     if (C != 1 || s.T != 256) return failmsg("tracker record / replay: full batches only (one 256-thread workgroup per problem)");
@@ -707,6 +710,7 @@ static int fetchLocked(dmvio_hip_tracker* t, double* pose7_out, double* aff_out,
     if (iterations) iterations[i] = o.iterations;
     run.repeat_lvl[i] = o.repeated_lvl; run.first_pass_res[i] = o.first_pass_res;
     run.evals += o.n_evals; run.point_evals += o.n_point_evals; run.ticks_step += o.ticks_step; run.ticks_eval += o.ticks_eval;
+    run.res_evals += o.n_res_evals; run.res_point_evals += o.n_res_point_evals;
   }
   t->last = std::move(run);
   return 0;
@@ -829,13 +833,13 @@ int dmvio_hip_tracker_set_single_frame_mode(dmvio_hip_tracker* t, int host_lm) {
 }
 // Measurement knobs (tools/sweep_tracking.py, profiles/): explicit calls instead of environment variables read behind the caller's back.  0 = the library's own choice.
 //   eval_blocks: workgroups per fused evaluation / evaluation server (changes how the fp32 partial sums are grouped)
-//   lm_threads: threads per workgroup of k_track_lm (256 or 512)
+//   lm_threads: threads per workgroup of k_track_lm (256, 512 or 1024)
 //   lm_waves: accepted (0, 1, 2 or 4) and without effect: every instantiation of k_track_lm that is built keeps four tap sets in flight
 //   lm_cluster: workgroups that share one alignment problem in cluster mode (2 .. 32; changes the grouping of the sums)
 int dmvio_hip_tracker_set_launch_shape(dmvio_hip_tracker* t, int eval_blocks, int lm_threads, int lm_waves, int lm_cluster) {
   if (!t) return failmsg("null tracker");
   if (eval_blocks < 0 || eval_blocks > t->max_eval_blocks) return failmsg("tracker_set_launch_shape: eval_blocks out of range");
-  if (lm_threads != 0 && lm_threads != 256 && lm_threads != 512) return failmsg("tracker_set_launch_shape: lm_threads is 0, 256 or 512");
+  if (lm_threads != 0 && lm_threads != 256 && lm_threads != 512 && lm_threads != 1024) return failmsg("tracker_set_launch_shape: lm_threads is 0, 256, 512 or 1024");
   if (lm_waves != 0 && lm_waves != 1 && lm_waves != 2 && lm_waves != 4) return failmsg("tracker_set_launch_shape: lm_waves is 0, 1, 2 or 4");
   if (lm_cluster < 0 || lm_cluster > 32) return failmsg("tracker_set_launch_shape: lm_cluster out of range");
   std::lock_guard<std::mutex> lk(t->ctx->mu);
@@ -867,6 +871,15 @@ int dmvio_hip_tracker_set_batch_kernel(dmvio_hip_tracker* t, int mode) {
   if (!t || mode < 0 || mode > 1) return failmsg("tracker_set_batch_kernel: 0 or 1");
   std::lock_guard<std::mutex> lk(t->ctx->mu);
   t->batch_kernel = mode;
+  return 0;
+}
+// 1 (default): k_track_lm runs an iteration step that is known to be its level's last (above level 0) as a residual-only evaluation — the seven statistics that decide
+// accept / reject and lastResiduals, without the 9x9 sums, which no one reads (tracker_kernels.hpp: lmWaveStep, blockEvalRes); 0: every evaluation in full.  Every output is
+// the same bit for bit either way.  k_track_lm_pp and the host-driven LM (their callbacks read H at every iteration) always evaluate in full.
+int dmvio_hip_tracker_set_residual_only_evals(dmvio_hip_tracker* t, int on) {
+  if (!t) return failmsg("null tracker");
+  std::lock_guard<std::mutex> lk(t->ctx->mu);
+  t->res_only_evals = on ? 1 : 0;
   return 0;
 }
 // 1 (default): the evaluations of a host-driven LM go to the resident evaluation server (one launch per tracked frame); 0: one fused launch per evaluation
@@ -1218,6 +1231,13 @@ int dmvio_hip_tracker_last_work(dmvio_hip_tracker* t, long long* n_evals, long l
   if (!t) return failmsg("null tracker");
   if (n_evals) *n_evals = t->last.evals;
   if (n_point_evals) *n_point_evals = t->last.point_evals;
+  return 0;
+}
+
+int dmvio_hip_tracker_last_residual_only_work(dmvio_hip_tracker* t, long long* n_evals, long long* n_point_evals) {
+  if (!t) return failmsg("null tracker");
+  if (n_evals) *n_evals = t->last.res_evals;
+  if (n_point_evals) *n_point_evals = t->last.res_point_evals;
   return 0;
 }
 

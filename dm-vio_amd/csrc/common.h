@@ -90,6 +90,7 @@ struct EvalP {
   float b0;           // lastRef_aff_g2l.b (CoarseTracker.cpp:305)
   float cutoff, maxEnergy;
   int lvl;
+  int res_only;       // 1: only the seven statistics of this evaluation are read (the LM loop's last step of a level above 0, tracker_kernels.hpp: lmWaveStep); 0 everywhere else
 };
 
 // accumulator slots of one evaluation
@@ -127,6 +128,8 @@ struct LMProblemOut {
   long long n_point_evals;
   long long ticks_step, ticks_eval;  // wall_clock64 (100 MHz) spent in LM control steps / evaluations
   double first_pass_res;   // lastResiduals[repeated_lvl] after its FIRST pass (the abort rule :731 saw that value before the repeat overwrote it)
+  long long n_res_point_evals;   // of n_point_evals: those of residual-only evaluations ...
+  int n_res_evals;               // ... and of n_evals (dmvio_hip_tracker_last_residual_only_work)
 };
 
 }  // namespace dmv

@@ -83,6 +83,23 @@ __device__ __forceinline__ float3 interp33Finish(const Taps33& t, const float x,
   return r;
 }
 
+// The intensity channel alone: the 2x2 taps p00, p10 (B.y, B.z) and p01, p11 (C.y, C.z) of the neighbourhood above in two 8-byte loads, and interp33Finish's r.x on them —
+// the same operations in the same order, hence the same bits.  For consumers that need no gradient (the tracker's residual-only evaluations).
+struct Taps22 { float2 B, C; };
+__device__ __forceinline__ void interp22Load(const float* __restrict__ img, const float x, const float y, const int width, Taps22& t) {
+  const int ix = (int)x, iy = (int)y;
+  const float* bp = img + ix + iy * width;
+  __builtin_memcpy(&t.B, bp, 8);
+  __builtin_memcpy(&t.C, bp + width, 8);
+}
+__device__ __forceinline__ float interp22Finish(const Taps22& t, const float x, const float y) {
+  const int ix = (int)x, iy = (int)y;
+  const float dx = x - ix, dy = y - iy;
+  const float dxdy = dx * dy;
+  const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
+  return w11 * t.C.y + w01 * t.C.x + w10 * t.B.y + w00 * t.B.x;
+}
+
 // dIp[lvl][idx][1], [2] of the reference at pixel (x, y) of a level plane: central differences with the reference's
 // flat-index range (rows 1..h-2) and isfinite guard (HessianBlocks.cpp:172-181).
 __device__ __forceinline__ float2 gradAt(const float* __restrict__ I, const int w, const int h, const int x, const int y) {

@@ -93,8 +93,8 @@ __device__ __forceinline__ float divBy(const float a, const Recip& R) {
   const float e2 = __builtin_fmaf(R.nb, q1, a);
   return __builtin_fmaf(e2, R.r1, q1);
 }
-template <bool TILED = false>
-__device__ __forceinline__ void projectPoint(const float4 P, const bool live, const EvalU& e, const float* __restrict__ img, PointProj& q, Taps33& taps) {
+// warp + bounds test of one template point (everything of projectPoint but the loads)
+__device__ __forceinline__ void warpPoint(const float4 P, const bool live, const EvalU& e, PointProj& q) {
   const float x = P.x, y = P.y, id = P.z;
   const float pt0 = e.RKi[0] * x + e.RKi[1] * y + e.RKi[2] * 1.0f + e.t[0] * id;
   const float pt1 = e.RKi[3] * x + e.RKi[4] * y + e.RKi[5] * 1.0f + e.t[1] * id;
@@ -106,22 +106,35 @@ __device__ __forceinline__ void projectPoint(const float4 P, const bool live, co
   q.refColor = P.w;
   q.inb = live && (Ku > 2 && Kv > 2 && Ku < e.wM3 && Kv < e.hM3 && q.new_idepth > 0);
   q.Ku = q.inb ? Ku : 2.5f; q.Kv = q.inb ? Kv : 2.5f;   // masked lanes tap a safe pixel
+}
+template <bool TILED = false>
+__device__ __forceinline__ void projectPoint(const float4 P, const bool live, const EvalU& e, const float* __restrict__ img, PointProj& q, Taps33& taps) {
+  warpPoint(P, live, e, q);
   if (TILED) interp33LoadTiled(img, q.Ku, q.Kv, e.w >> 3, taps);
   else interp33Load(img, q.Ku, q.Kv, e.w, taps);
+}
+// residual, Huber weight and the statistics of one point from its interpolated intensity (calcRes, CoarseTracker.cpp:449-476): shared by the full and the residual-only
+// evaluation, so the seven statistics of the two are the same bits.  ok: the point enters the system.
+template <bool GUARD>
+__device__ __forceinline__ void pointStats(const PointProj& q, const float hitx, const EvalU& e, EvalStats& st, float& residual, float& hw, bool& ok) {
+  const bool fin = GUARD ? (q.inb && isfinite(hitx)) : q.inb;
+  residual = hitx - (e.aff0 * q.refColor + e.aff1);
+  const float ar = fabsf(residual);
+  hw = ar < e.huberTH ? 1.0f : divBy(e.huberTH, refinedRcp(ar));
+  const bool sat = ar > e.cutoff;
+  ok = fin && !sat;
+  st.nE += fin ? 1.0f : 0.0f;
+  st.nSat += (fin && sat) ? 1.0f : 0.0f;
+  st.nW += ok ? 1.0f : 0.0f;
+  st.E += fin ? (sat ? e.maxEnergy : hw * residual * residual * (2 - hw)) : 0.0f;   // x + 0 == x: masked lanes leave E untouched
 }
 template <bool GUARD>
 __device__ __forceinline__ void finishPoint(const PointProj& q, const Taps33& taps, const EvalU& e, EvalStats& st, float (&J)[9], float& wOut) {
   const float u = q.u, v = q.v, new_idepth = q.new_idepth, refColor = q.refColor;
   const float3 hit = interp33Finish<GUARD>(taps, q.Ku, q.Kv);
-  const bool fin = GUARD ? (q.inb && isfinite(hit.x)) : q.inb;
-  const float residual = hit.x - (e.aff0 * refColor + e.aff1);
-  const float ar = fabsf(residual);
-  const float hw = ar < e.huberTH ? 1.0f : divBy(e.huberTH, refinedRcp(ar));
-  const bool sat = ar > e.cutoff, ok = fin && !sat;
-  st.nE += fin ? 1.0f : 0.0f;
-  st.nSat += (fin && sat) ? 1.0f : 0.0f;
-  st.nW += ok ? 1.0f : 0.0f;
-  st.E += fin ? (sat ? e.maxEnergy : hw * residual * residual * (2 - hw)) : 0.0f;   // x + 0 == x: masked lanes leave E untouched
+  float residual, hw;
+  bool ok;
+  pointStats<GUARD>(q, hit.x, e, st, residual, hw, ok);
   // calcGSSSE row (CoarseTracker.cpp:314-338)
   const float dx = hit.y * e.fx, dy = hit.z * e.fy;
   J[0] = ok ? new_idepth * dx : 0.0f;
@@ -134,6 +147,17 @@ __device__ __forceinline__ void finishPoint(const PointProj& q, const Taps33& ta
   J[7] = ok ? -1.0f : 0.0f;
   J[8] = ok ? residual : 0.0f;
   wOut = ok ? hw : 0.0f;
+}
+// The residual-only forms (blockEvalRes): the 2x2 intensity taps instead of the 4x4 neighbourhood, no gradients, no Jacobian row.
+__device__ __forceinline__ void projectPointRes(const float4 P, const bool live, const EvalU& e, const float* __restrict__ img, PointProj& q, Taps22& taps) {
+  warpPoint(P, live, e, q);
+  interp22Load(img, q.Ku, q.Kv, e.w, taps);
+}
+template <bool GUARD>
+__device__ __forceinline__ void finishPointRes(const PointProj& q, const Taps22& taps, const EvalU& e, EvalStats& st) {
+  float residual, hw;
+  bool ok;
+  pointStats<GUARD>(q, interp22Finish(taps, q.Ku, q.Kv), e, st, residual, hw, ok);
 }
 
 // Flow indicators of one sample point (CoarseTracker.cpp:416-447): every 32nd point of the reference's row-major list, level 0
@@ -311,6 +335,56 @@ __device__ __forceinline__ void blockEval(const EvalP& e, const LevelGeom& g, co
 #pragma unroll
       for (int wv = 0; wv < T / 64; wv++) s += s_partH[wv * 256 + r * 16 + c];
     } else if (k < ACC_N) {
+#pragma unroll
+      for (int wv = 0; wv < T / 64; wv++) s += s_partS[wv][k - 45];
+    }
+    s_tot[k] = s;
+  }
+  __syncthreads();
+}
+
+// Residual-only evaluation: the seven statistics of blockEval over the same points — same point-to-lane assignment (first, stride), same three-stage pipeline, same per-lane
+// order of additions, same reductions, so every statistic slot of s_tot holds the bits a full evaluation leaves there — without the 9x9 sums (their 45 slots are written as
+// zero): 2x2 taps instead of the 4x4 neighbourhood, no gradients, no Jacobian row, no LDS staging, no MFMA.  For the evaluations of the LM loop whose sums nothing reads
+// (lmWaveStep, EvalP::res_only); those run above level 0 only: no flow-indicator pass, no tiled planes.
+template <int T, bool GUARD = true>
+__device__ __forceinline__ void blockEvalRes(const EvalP& e, const LevelGeom& g, const float4* __restrict__ pc, const int n, const int first, const int stride,
+                                             const float* __restrict__ img, const float huberTH, float (*s_partS)[8], float* s_tot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  EvalStats st = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const EvalU eu = makeEvalU(e, g, huberTH);
+  const int base0 = first - lane;   // wave-uniform trip count, as in blockEval
+  const int nm1 = max(n - 1, 0);
+  float4 P1 = make_float4(0.f, 0.f, 0.f, 0.f);
+  PointProj q0;
+  Taps22 t0;
+  q0.u = q0.v = q0.new_idepth = q0.refColor = 0.f; q0.Ku = q0.Kv = 2.5f; q0.inb = false;
+  t0.B = t0.C = make_float2(0.f, 0.f);
+  if (n > 0) {
+    const float4 P0 = pc[min(base0 + lane, nm1)];
+    P1 = pc[min(base0 + lane + stride, nm1)];
+    projectPointRes(P0, base0 + lane < n, eu, img, q0, t0);
+  }
+  auto step = [&](const PointProj& qc, const Taps22& tc, PointProj& qn, Taps22& tn, const int base) __attribute__((always_inline)) {
+    const int i = base + lane;
+    projectPointRes(P1, i + stride < n, eu, img, qn, tn);   // next point: its taps are requested now, consumed next step
+    P1 = pc[min(i + 2 * stride, nm1)];                     // unconditional (clamped) prefetch
+    finishPointRes<GUARD>(qc, tc, eu, st);
+  };
+  PointProj q1;
+  Taps22 t1;
+  for (int base = base0; base < n; base += 2 * stride) {
+    step(q0, t0, q1, t1, base);
+    if (base + stride >= n) break;   // wave-uniform
+    step(q1, t1, q0, t0, base + stride);
+  }
+  const float stot = waveReduceStats(st, lane);
+  if (lane < 8) s_partS[wave][lane] = stot;
+  __syncthreads();
+  if (threadIdx.x < ACC_PAD) {
+    float s = 0.0f;
+    const int k = threadIdx.x;
+    if (k >= 45 && k < ACC_N) {
 #pragma unroll
       for (int wv = 0; wv < T / 64; wv++) s += s_partS[wv][k - 45];
     }
@@ -612,6 +686,7 @@ DMV_HD void makeEvalP(const TrackerDev& trk, int lvl, const Pose& T, double affA
   e.cutoff = cutoffTH;
   e.maxEnergy = 2 * trk.huberTH * cutoffTH - trk.huberTH * trk.huberTH;
   e.lvl = lvl;
+  e.res_only = 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -622,7 +697,7 @@ DMV_HD void makeEvalP(const TrackerDev& trk, int lvl, const Pose& T, double affA
 //   * the 8x8 system: lane (r*8+c) owns H(r,c); H,b from the 45 sums, damping and the pivoted LDL^T solve
 //     are wave-wide register + cross-lane operations (no scratch memory, no serial fp64 loops),
 //   * SE3 exp / pose composition by lane 0 (static indices only -> registers).
-enum { LM_LEVEL_BEGIN = 0, LM_INIT_EVAL, LM_ITER_BEGIN, LM_ITER_EVAL, LM_LEVEL_END };
+enum { LM_LEVEL_BEGIN = 0, LM_INIT_EVAL, LM_ITER_BEGIN, LM_ITER_EVAL, LM_LEVEL_END, LM_REFILL_EVAL };
 enum { ACT_DONE = 0, ACT_EVAL_CUR = 1, ACT_SOLVE = 2 };
 
 struct LMState {
@@ -636,6 +711,9 @@ struct LMState {
   int lvl, iteration, st, totalIts, nEvals;
   long long nPointEvals;
   int haveRepeated;
+  // residual-only evaluations (lmWaveStep): the evaluation in flight is one; s_H / s_b are stale (S.cur was accepted on statistics alone, its sums were never formed)
+  int resOnly, hStale, nResEvals;
+  long long nResPointEvals;
 };
 
 // H(r,c) (SCALE_*-scaled, double) of lane = r*8+c from the 45 sums — calcGSSSE's tail (CoarseTracker.cpp:340-355).
@@ -760,8 +838,17 @@ __device__ __noinline__ double waveLdltSolve8(double m, double dv, const int lan
 
 // One LM control step, executed by all 64 lanes of wave 0.  Consumes the finished evaluation in s_tot, decides,
 // and either prepares the next evaluation (s_e, returns true) or finishes the problem (returns false).
-__device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, const LMProblemIn& in, LMProblemOut& out,
-                                           const float* s_tot, double* s_H, double* s_b, double* s_x, int* s_trk, EvalP& s_e, const int lane) {
+//
+// Residual-only evaluations (RES_ONLY && res_only_on): the 9x9 sums of an evaluation are kept in two cases only — the first evaluation of a level, and an accepted iteration
+// step that another solve follows.  An iteration step above level 0 that is known to be its level's last (the increment of the solve that produced its pose is below 1e-3, or
+// the level's iteration budget ends with it: both known BEFORE the evaluation) has its sums dropped whether it is accepted or not: the level ends, the next one starts with
+// a fresh evaluation at its own resolution (the reference forms them all the same: CoarseTracker.cpp:704 calls calcGSSSE on every accept).  Such a step is asked for with
+// EvalP::res_only = 1: statistics only (blockEvalRes).  When it is accepted s_H / s_b still hold the sums of the PREVIOUS pose (S.hStale); they are read again in one case
+// only, the failure exit (out.H / out.b of a failed problem are the sums at the last accepted pose): one full evaluation at S.cur — the parameters of the accepted step, hence
+// its 45 sums — refills them first (LM_REFILL_EVAL; not counted as work of the LM loop).
+template <bool RES_ONLY = false>
+__device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, const LMProblemIn& in, LMProblemOut& out, const float* s_tot, double* s_H, double* s_b,
+                                           double* s_x, int* s_trk, EvalP& s_e, const int lane, const bool res_only_on = false) {
   const int maxIterations[5] = {10, 20, 50, 50, 50};
   const float lambdaExtrapolationLimit = 0.001f;
   int takeH = 0, action = ACT_DONE;
@@ -777,16 +864,22 @@ __device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, co
         action = ACT_EVAL_CUR;  // same pose, doubled cutoff; stay in LM_INIT_EVAL
       } else {
         takeH = 1;
+        S.hStale = 0;
         S.lambda = 0.01f;
         S.iteration = 0;
         S.st = LM_ITER_BEGIN;
       }
+    } else if (S.st == LM_REFILL_EVAL) {
+      takeH = 1;
+      S.hStale = 0;
+      S.st = LM_LEVEL_END;   // decided again below from the same S.resOld: the same failure, now with the sums of S.cur in s_H / s_b
     } else if (S.st == LM_ITER_EVAL) {
       double resNew[6];
       res6FromSums(s_tot, resNew);
       const bool accept = (resNew[0] / resNew[1]) < (S.resOld[0] / S.resOld[1]);
       if (accept) {
-        takeH = 1;
+        if (RES_ONLY && S.resOnly) S.hStale = 1;   // s_tot holds no sums: s_H / s_b keep the previous pose's
+        else takeH = 1;
         for (int i = 0; i < 6; i++) S.resOld[i] = resNew[i];
         S.affA = S.affA_n; S.affB = S.affB_n;
         S.cur = S.nxt;
@@ -812,6 +905,7 @@ __device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, co
           S.flow[0] = S.resOld[2]; S.flow[1] = S.resOld[3]; S.flow[2] = S.resOld[4];
           const bool failed = isnan(S.lastRes[S.lvl]) || (S.lastRes[S.lvl] > 1.5 * in.minRes[S.lvl]);
           if (failed) {
+            if (RES_ONLY && S.hStale) { S.st = LM_REFILL_EVAL; action = ACT_EVAL_CUR; break; }
             // reference returns false without touching lastToNew_out / aff_g2l_out (CoarseTracker.cpp:731-732)
             for (int i = 0; i < 7; i++) out.pose7[i] = in.pose7[i];
             out.aff[0] = in.aff[0]; out.aff[1] = in.aff[1];
@@ -928,11 +1022,17 @@ __device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, co
       for (int i = 0; i < 8; i++) nn += inc[i] * inc[i];
       S.incNorm = sqrt(nn);
       makeEvalP(trk, S.lvl, S.nxt, S.affA_n, S.affB_n, in.new_exposure, trk.coarseCutoffTH * S.cutoffRepeat, s_e);
+      S.resOnly = 0;
+      if (RES_ONLY && res_only_on && S.lvl > 0 && (!(S.incNorm > 1e-3) || S.iteration + 1 >= maxIterations[S.lvl])) {   // this step ends its level either way
+        S.resOnly = 1; S.nResEvals++; S.nResPointEvals += trk.pc_n[S.lvl];
+      }
+      s_e.res_only = S.resOnly;
       S.st = LM_ITER_EVAL;
     } else if (action == ACT_EVAL_CUR) {
       makeEvalP(trk, S.lvl, S.cur, S.affA, S.affB, in.new_exposure, trk.coarseCutoffTH * S.cutoffRepeat, s_e);
+      S.resOnly = 0;
     }
-    if (action != ACT_DONE) { S.nEvals++; S.nPointEvals += trk.pc_n[S.lvl]; }
+    if (action != ACT_DONE && S.st != LM_REFILL_EVAL) { S.nEvals++; S.nPointEvals += trk.pc_n[S.lvl]; }
   }
 #ifdef DMV_LM_TICKS
   if (lane == 0 && action != ACT_DONE) { const long long q4 = wall_clock64(); atomicAdd(&g_lm_ticks[1], (double)(q1 - q0)); atomicAdd(&g_lm_ticks[2], (double)(q4 - q3)); atomicAdd(&g_lm_ticks[3], (double)(q4 - q0)); atomicAdd(&g_lm_ticks[5], 1.0); }
@@ -949,7 +1049,8 @@ __device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, co
 // parity; the launch guarantees B*C <= resident workgroups, so the spin cannot deadlock.
 #define LM_LOG_EVALS 96   // evaluations per problem the diagnostic log holds (a track runs ~15; maxIterations sum to 180, the log is cut there)
 struct ClusterArgs { int C; float* part; /* B x 2 x C x ACC_PAD */ unsigned int* cnt; /* B, zeroed before the launch */ LMProblemOut* discard; /* device scratch entry */
-                     EvalP* log; /* diagnostics (dmvio_hip_tracker_debug_record_replay): B x LM_LOG_EVALS evaluation parameters, or NULL */ int* log_n; /* B */ };
+                     EvalP* log; /* diagnostics (dmvio_hip_tracker_debug_record_replay): B x LM_LOG_EVALS evaluation parameters, or NULL */ int* log_n; /* B */
+                     int res_only; /* dmvio_hip_tracker_set_residual_only_evals: evaluations whose sums nothing reads run as blockEvalRes */ };
 
 __device__ __forceinline__ void clusterExchange(float* s_tot, const ClusterArgs& cl, const int prob, const int rank, const unsigned int phase) {
   float* __restrict__ mine = cl.part + (((size_t)prob * 2 + (phase & 1u)) * cl.C + rank) * ACC_PAD;
@@ -997,6 +1098,7 @@ __global__ void __launch_bounds__(T, W) k_track_lm(const TrackerDev trk, const F
     for (int i = 0; i < 3; i++) S.flow[i] = 1000;
     S.lvl = coarsestLvl; S.st = LM_LEVEL_BEGIN; S.totalIts = 0; S.nEvals = 0; S.nPointEvals = 0; S.haveRepeated = 0;
     S.iteration = 0; S.lambda = 0.01f; S.cutoffRepeat = 1; S.incNorm = 0;
+    S.resOnly = 0; S.hStale = 0; S.nResEvals = 0; S.nResPointEvals = 0;
     pout.repeated_lvl = -1; pout.first_pass_res = __builtin_nan("");
   }
   if (threadIdx.x < 64) { s_H[threadIdx.x] = 0; if (threadIdx.x < 8) { s_b[threadIdx.x] = 0; s_x[threadIdx.x] = 0; } }
@@ -1013,7 +1115,7 @@ __global__ void __launch_bounds__(T, W) k_track_lm(const TrackerDev trk, const F
       // the control step is ONE dependent chain of ~1100 instructions on this wavefront while its three siblings wait: raised issue priority lets it through ahead of the
       // evaluation waves of the other workgroups that share the SIMD (they lose nothing they could not issue a few cycles later)
       __builtin_amdgcn_s_setprio(3);
-      const bool go = lmWaveStep(S, trk, pin, pout, s_tot, s_H, s_b, s_x, s_trk, s_e, threadIdx.x);
+      const bool go = lmWaveStep<true>(S, trk, pin, pout, s_tot, s_H, s_b, s_x, s_trk, s_e, threadIdx.x, cl.res_only != 0);
       __builtin_amdgcn_s_setprio(0);
       if (threadIdx.x == 0) s_go = go ? 1 : 0;
     }
@@ -1030,7 +1132,10 @@ __global__ void __launch_bounds__(T, W) k_track_lm(const TrackerDev trk, const F
     const int lvl = s_e.lvl;
     // the plane's address is wave-uniform (level 0 comes out of the pointer table): keep it in scalar registers
     const float* img = dmvUniformGlobal(fs.level(slot, lvl));
-    if (TL && tiled0 && lvl == 0) {   // workgroup-uniform
+    if (__builtin_amdgcn_readfirstlane(s_e.res_only)) {   // workgroup-uniform; above level 0 only (lmWaveStep)
+      if (clean) blockEvalRes<T, false>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_partS, s_tot);
+      else blockEvalRes<T, true>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_partS, s_tot);
+    } else if (TL && tiled0 && lvl == 0) {   // workgroup-uniform
       if (clean)
         blockEval<T, false, TL>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], trk.flow_mask, rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
                                 s_tot);
@@ -1054,6 +1159,8 @@ __global__ void __launch_bounds__(T, W) k_track_lm(const TrackerDev trk, const F
     pout.n_point_evals = S.nPointEvals;
     pout.ticks_step = tStep;
     pout.ticks_eval = tEval;
+    pout.n_res_evals = S.nResEvals;
+    pout.n_res_point_evals = S.nResPointEvals;
   }
   if (rank == 0) {
     if (threadIdx.x < 64) pout.H[threadIdx.x] = s_H[threadIdx.x];
@@ -1101,6 +1208,7 @@ __global__ void __launch_bounds__(256, 4) k_track_lm_pp(const TrackerDev trk, co
       for (int i = 0; i < 3; i++) Q.flow[i] = 1000;
       Q.lvl = coarsestLvl; Q.st = LM_LEVEL_BEGIN; Q.totalIts = 0; Q.nEvals = 0; Q.nPointEvals = 0; Q.haveRepeated = 0;
       Q.iteration = 0; Q.lambda = 0.01f; Q.cutoffRepeat = 1; Q.incNorm = 0;
+      Q.resOnly = 0; Q.hStale = 0; Q.nResEvals = 0; Q.nResPointEvals = 0;
       out[prob].repeated_lvl = -1; out[prob].first_pass_res = __builtin_nan("");
       s_prob[slot] = prob; s_tstep[slot] = 0; s_teval[slot] = 0;
     }
@@ -1126,6 +1234,7 @@ __global__ void __launch_bounds__(256, 4) k_track_lm_pp(const TrackerDev trk, co
         for (int i = 0; i < 3; i++) po.flow[i] = Q.flow[i];
         po.iterations = Q.totalIts; po.n_evals = Q.nEvals; po.n_point_evals = Q.nPointEvals;
         po.ticks_step = s_tstep[slot]; po.ticks_eval = s_teval[slot];
+        po.n_res_evals = 0; po.n_res_point_evals = 0;   // this kernel runs every evaluation in full (lmWaveStep<false>)
       }
       po.H[lane] = s_H[slot][lane];
       if (lane < 8) po.b[lane] = s_b[slot][lane];
@@ -1188,7 +1297,10 @@ __global__ void __launch_bounds__(T, W) k_track_replay(const TrackerDev trk, con
     __syncthreads();
     const int lvl = s_e.lvl;
     const float* img = dmvUniformGlobal(fs.level(slot, lvl));
-    if (clean) blockEval<T, false>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], trk.flow_mask, threadIdx.x, T, img, trk.huberTH, s_stage, s_partH, s_partS, s_tot);
+    if (__builtin_amdgcn_readfirstlane(s_e.res_only)) {   // as the recorded launch ran it
+      if (clean) blockEvalRes<T, false>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], threadIdx.x, T, img, trk.huberTH, s_partS, s_tot);
+      else blockEvalRes<T, true>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], threadIdx.x, T, img, trk.huberTH, s_partS, s_tot);
+    } else if (clean) blockEval<T, false>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], trk.flow_mask, threadIdx.x, T, img, trk.huberTH, s_stage, s_partH, s_partS, s_tot);
     else blockEval<T, true>(s_e, trk.g[lvl], trk.pc[lvl], trk.pc_n[lvl], trk.flow_mask, threadIdx.x, T, img, trk.huberTH, s_stage, s_partH, s_partS, s_tot);
     __syncthreads();
   }

@@ -156,7 +156,7 @@ int dmvio_hip_tracker_track(dmvio_hip_tracker* trk, int new_slot, float new_expo
  * wavefront); 0 = the device-resident LM (cluster mode).  Same evaluation sums and iteration counts either way; batches of two and more always run device-resident. */
 int dmvio_hip_tracker_set_single_frame_mode(dmvio_hip_tracker* trk, int host_lm);
 /* Measurement knobs as explicit calls (the library reads no environment variable that changes what or how it computes).  0 = the library's own choice.
- * eval_blocks: workgroups per fused evaluation / evaluation server; lm_threads (256 | 512): threads per workgroup of the device-resident LM; lm_cluster
+ * eval_blocks: workgroups per fused evaluation / evaluation server; lm_threads (256 | 512 | 1024): threads per workgroup of the device-resident LM; lm_cluster
  * (2 .. 32): workgroups sharing one alignment problem; lm_waves (1 | 2 | 4) is accepted and has no effect (every kernel that is built keeps four tap sets in flight).
  * A combination without a kernel (lm_threads = 512 with lm_cluster > 1; B * lm_cluster > 1024) is refused by the launch.  eval_blocks and lm_cluster change how the fp32 partial sums are grouped (results move in the last bits). */
 int dmvio_hip_tracker_set_launch_shape(dmvio_hip_tracker* trk, int eval_blocks, int lm_threads, int lm_waves, int lm_cluster);
@@ -167,6 +167,11 @@ int dmvio_hip_tracker_set_eval_server(dmvio_hip_tracker* trk, int on);
  * problems dealt out to a persistent grid by a device-wide counter.
  * Per problem the same arithmetic in the same order: identical results. */
 int dmvio_hip_tracker_set_batch_kernel(dmvio_hip_tracker* trk, int mode);
+/* 1 (default): the device-resident LM runs an iteration step that is known to be the last of its pyramid level (above level 0: the increment that produced its pose is below
+ * 1e-3, or the level's iteration budget ends with it) as a residual-only evaluation: calcRes's statistics, which decide accept / reject and lastResiduals, without the 9x9
+ * sums of calcGSSSE, which the next level replaces unread (the reference forms them on every accept, CoarseTracker.cpp:704).  0: every evaluation in full.  Every output is
+ * identical bit for bit either way.  The two-problems-per-workgroup batch kernel and the host-driven LM always evaluate in full. */
+int dmvio_hip_tracker_set_residual_only_evals(dmvio_hip_tracker* trk, int on);
 /* Storage order of the template points (from the next dmvio_hip_tracker_set_ref on): 0 (default) = 8x8-pixel tiles, Z-ordered inside 16x16 blocks; 1 = the reference's
  * row-major order (CoarseTracker.cpp:249-293).  Same points, same per-point arithmetic; the fp32 partial sums are grouped differently (results agree to rounding). */
 int dmvio_hip_tracker_set_template_order(dmvio_hip_tracker* trk, int row_major);
@@ -239,6 +244,9 @@ int dmvio_hip_tracker_track_new_coarse(dmvio_hip_tracker* trk, int new_slot, flo
 /* Work counters of the last batch launch: evals (calcRes+calcGS passes) and point-evaluations
  * (sum over evals of pc_n[lvl]) — the unit count behind the roofline's algorithmic bytes. */
 int dmvio_hip_tracker_last_work(dmvio_hip_tracker* trk, long long* n_evals, long long* n_point_evals);
+/* Of those counts, the share that ran as residual-only evaluations (dmvio_hip_tracker_set_residual_only_evals): dmvio_hip_tracker_last_work counts every evaluation in
+ * full whichever way it ran. */
+int dmvio_hip_tracker_last_residual_only_work(dmvio_hip_tracker* trk, long long* n_evals, long long* n_point_evals);
 /* In-kernel time split of the last batch launch, summed over problems, in 100 MHz wall_clock64 ticks:
  * LM control steps (solve, pose update, bookkeeping) vs evaluations (calcRes+calcGS). Diagnostics only. */
 int dmvio_hip_tracker_last_ticks(dmvio_hip_tracker* trk, long long* ticks_step, long long* ticks_eval);
