@@ -67,6 +67,19 @@ class PixelSelectorSettings(C.Structure):
     _fields_ = [("minGradHistCut", C.c_float), ("minGradHistAdd", C.c_float), ("gradDownweightPerLevel", C.c_float), ("selectDirectionDistribution", C.c_int)]
 
 
+class ActivationWindow(C.Structure):
+    """dmvio_hip_activation_window (include/dmvio_hip.h): one window of a batched activation call."""
+    _fields_ = [("imm", C.c_void_p), ("dm", C.c_void_p), ("n_hosts", C.c_int), ("KRKi9", c_f), ("Kt3", c_f), ("n_active", C.c_int), ("active_host_tag", c_i),
+                ("active_u", c_f), ("active_v", c_f), ("active_idepth", c_f), ("host_flagged", c_u8), ("newest_tag", C.c_int), ("minActDist", C.c_float),
+                ("minTraceQuality", C.c_float), ("n_selected", C.c_int), ("n_deleted", C.c_int)]
+
+
+class ActivationOptimize(C.Structure):
+    """dmvio_hip_activation_optimize: one window of dmvio_hip_immature_optimize_selected_batch."""
+    _fields_ = [("imm", C.c_void_p), ("F", C.c_int), ("frame_slots", c_i), ("w2c7", c_d), ("aff2", c_d), ("exposure", c_f), ("minObs", C.c_int), ("result", c_i),
+                ("idepth", c_f), ("res_state", c_i), ("n_activated", C.c_int)]
+
+
 def _sig(L):
     vp = C.c_void_p
     L.dmvio_hip_last_error.restype = C.c_char_p
@@ -213,6 +226,14 @@ def _sig(L):
     L.dmvio_hip_immature_remove_host.argtypes = [vp, C.c_int]
     L.dmvio_hip_min_act_dist_update.argtypes = [C.c_float, C.c_int, C.c_float]
     L.dmvio_hip_min_act_dist_update.restype = C.c_float
+    L.dmvio_hip_activation_batch_create.restype = vp
+    L.dmvio_hip_activation_batch_create.argtypes = [vp, C.c_int]
+    L.dmvio_hip_activation_batch_destroy.argtypes = [vp]
+    L.dmvio_hip_activation_batch_destroy.restype = None
+    L.dmvio_hip_distance_map_make_batch.argtypes = [vp, C.c_int, C.POINTER(ActivationWindow)]
+    L.dmvio_hip_immature_select_for_activation_batch.argtypes = [vp, C.c_int, C.POINTER(ActivationWindow)]
+    L.dmvio_hip_immature_optimize_selected_batch.argtypes = [vp, C.c_int, C.POINTER(ActivationOptimize), c_d]
+    L.dmvio_hip_immature_remove_marked_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), c_i]
 
 
 def load_library():
@@ -978,6 +999,134 @@ def activate_points(imm, dmap, frame_slots, w2c7, fxfycxcy, active, host_flagged
     rec = imm.get_activated()
     n = imm.remove_marked()
     return dict(activated=rec, result=result, idepth=idepth, res_state=res_state, order=order, decision=decision, n_deleted=n_del, n_points=n)
+
+
+class ActivationBatchHip:
+    """Point activation of W windows per call (dmvio_hip_activation_batch): every window is one (ImmaturePointsHip, DistanceMapHip) pair of this context and ends in the
+    state its single calls leave, so the per-handle getters (get_activation, get_marks, get_activated, DistanceMapHip.get) read the results."""
+
+    def __init__(self, ctx, max_windows):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_activation_batch_create(ctx.p, int(max_windows))
+        if not p:
+            raise HipLibraryError("dmvio_hip_activation_batch_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.max_windows = int(max_windows)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_activation_batch_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _windows(windows, select):
+        """the C records of a list of dicts (dm, KRKi, Kt, and active=dict(host, u, v, idepth) or imm, host_flagged, newest_tag, minActDist[, minTraceQuality]) and the
+        arrays that keep their memory alive"""
+        arr = (ActivationWindow * max(len(windows), 1))()
+        keep = []
+        for k, w in enumerate(windows):
+            KRKi = np.ascontiguousarray(w["KRKi"], dtype=np.float32).reshape(-1, 9); Kt = np.ascontiguousarray(w["Kt"], dtype=np.float32).reshape(-1, 3)
+            if len(Kt) != len(KRKi):
+                raise HipLibraryError("ActivationBatchHip: KRKi and Kt need one row per host")
+            r = arr[k]
+            r.dm = w["dm"].p if w.get("dm") is not None else None
+            r.imm = w["imm"].p if w.get("imm") is not None else None
+            r.n_hosts = len(KRKi); r.KRKi9 = _f(KRKi); r.Kt3 = _f(Kt)
+            keep += [KRKi, Kt]
+            if select:
+                fl = np.ascontiguousarray(w["host_flagged"], dtype=np.uint8)
+                if len(fl) != len(KRKi):
+                    raise HipLibraryError("ActivationBatchHip: host_flagged needs one entry per host")
+                r.host_flagged = fl.ctypes.data_as(c_u8); r.newest_tag = int(w["newest_tag"]); r.minActDist = float(w["minActDist"])
+                r.minTraceQuality = float(w.get("minTraceQuality", 3.0))
+                keep.append(fl)
+            else:
+                a = w["active"]
+                t = np.ascontiguousarray(a["host"], dtype=np.int32)
+                u, v, d = [np.ascontiguousarray(a[key], dtype=np.float32) for key in ("u", "v", "idepth")]
+                r.n_active = len(t); r.active_host_tag = _i(t); r.active_u = _f(u); r.active_v = _f(v); r.active_idepth = _f(d)
+                keep += [t, u, v, d]
+        return arr, keep
+
+    def make(self, windows):
+        """makeDistanceMap for every window: dicts with dm, KRKi, Kt, active"""
+        arr, keep = self._windows(windows, False)
+        _chk(self.L, self.L.dmvio_hip_distance_map_make_batch(self.p, len(windows), arr), "distance_map_make_batch")
+
+    def select(self, windows):
+        """the candidate loop for every window: dicts with imm, dm, KRKi, Kt, host_flagged, newest_tag, minActDist[, minTraceQuality] -> [(n_selected, n_deleted)]"""
+        arr, keep = self._windows(windows, True)
+        _chk(self.L, self.L.dmvio_hip_immature_select_for_activation_batch(self.p, len(windows), arr), "immature_select_for_activation_batch")
+        return [(int(arr[k].n_selected), int(arr[k].n_deleted)) for k in range(len(windows))]
+
+    def optimize_selected(self, windows, fxfycxcy):
+        """optimize_selected for every window: dicts with imm, frame_slots, w2c7[, aff, exposure, min_obs] -> [(result, idepth, res_state[n_selected, F])]"""
+        arr = (ActivationOptimize * max(len(windows), 1))()
+        keep, outs = [], []
+        for k, w in enumerate(windows):
+            imm = w["imm"]
+            slots = np.ascontiguousarray(w["frame_slots"], dtype=np.int32); F = len(slots)
+            w2c7 = np.ascontiguousarray(w["w2c7"], dtype=np.float64).reshape(F, 7)
+            a = np.zeros((F, 2)) if w.get("aff") is None else np.ascontiguousarray(w["aff"], dtype=np.float64)
+            e = np.ones(F, np.float32) if w.get("exposure") is None else np.ascontiguousarray(w["exposure"], dtype=np.float32)
+            ns = _chk(self.L, self.L.dmvio_hip_immature_get_activation(imm.p, None, None), "immature_get_activation")
+            result = np.zeros(max(ns, 1), np.int32); idepth = np.zeros(max(ns, 1), np.float32); res_state = np.zeros((max(ns, 1), F), np.int32)
+            r = arr[k]
+            r.imm = imm.p; r.F = F; r.frame_slots = _i(slots); r.w2c7 = _d(w2c7); r.aff2 = _d(a); r.exposure = _f(e); r.minObs = int(w.get("min_obs", 1))
+            r.result = _i(result); r.idepth = _f(idepth); r.res_state = _i(res_state)
+            keep += [slots, w2c7, a, e]
+            outs.append((ns, result, idepth, res_state))
+        K = np.ascontiguousarray(fxfycxcy, dtype=np.float64)
+        _chk(self.L, self.L.dmvio_hip_immature_optimize_selected_batch(self.p, len(windows), arr, _d(K)), "immature_optimize_selected_batch")
+        for k, w in enumerate(windows):
+            w["imm"].n_activated = int(arr[k].n_activated); w["imm"]._last_F = int(arr[k].F)
+        return [(result[:ns], idepth[:ns], res_state[:ns]) for ns, result, idepth, res_state in outs]
+
+    def remove_marked(self, imms):
+        """the compaction for every handle -> [new number of points]"""
+        ptrs = (C.c_void_p * max(len(imms), 1))(*[m.p for m in imms])
+        left = np.zeros(max(len(imms), 1), np.int32)
+        _chk(self.L, self.L.dmvio_hip_immature_remove_marked_batch(self.p, len(imms), ptrs, _i(left)), "immature_remove_marked_batch")
+        return left[:len(imms)].tolist()
+
+
+def _c2w_of(w2c7):
+    F = len(w2c7)
+    c2w = np.zeros((F, 7))
+    for k in range(F):
+        q = w2c7[k, 3:7]; t = w2c7[k, :3]
+        x, y, z, w = q
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        c2w[k, :3] = -R.T @ t; c2w[k, 3:6] = -q[:3]; c2w[k, 6] = q[3]
+    return c2w
+
+
+def activate_points_batch(batch, windows, fxfycxcy):
+    """activate_points for W windows of one context in four batched calls.  windows: dicts with imm, dmap, frame_slots, w2c7, active and optionally host_flagged,
+    minActDist, minTraceQuality, aff, exposure, min_obs (the arguments of activate_points).  -> one dict per window, as activate_points returns it"""
+    ws = []
+    for w in windows:
+        F = len(w["frame_slots"])
+        w2c7 = np.ascontiguousarray(w["w2c7"], dtype=np.float64).reshape(F, 7)
+        KRKi, Kt = distance_map_tables(w2c7[F - 1], _c2w_of(w2c7), fxfycxcy)
+        fl = np.zeros(F, np.uint8) if w.get("host_flagged") is None else w["host_flagged"]
+        ws.append(dict(imm=w["imm"], dm=w["dmap"], KRKi=KRKi, Kt=Kt, active=w["active"], host_flagged=fl, newest_tag=F - 1, minActDist=w.get("minActDist", 2.0),
+                       minTraceQuality=w.get("minTraceQuality", 3.0), frame_slots=w["frame_slots"], w2c7=w2c7, aff=w.get("aff"), exposure=w.get("exposure"),
+                       min_obs=w.get("min_obs", 1)))
+    batch.make(ws)
+    counts = batch.select(ws)
+    sel = [w["imm"].get_activation() for w in ws]
+    opt = batch.optimize_selected(ws, fxfycxcy)
+    recs = [w["imm"].get_activated() for w in ws]
+    left = batch.remove_marked([w["imm"] for w in ws])
+    return [dict(activated=recs[k], result=opt[k][0], idepth=opt[k][1], res_state=opt[k][2], order=sel[k][1], decision=sel[k][0], n_deleted=counts[k][1], n_points=left[k])
+            for k in range(len(ws))]
 
 
 class PixelSelectorHip:

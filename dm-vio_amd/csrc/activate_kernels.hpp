@@ -49,7 +49,7 @@ __device__ __forceinline__ bool dmProject(const float* __restrict__ KRKi, const 
 }
 
 // makeDistanceMap's seeds (:945-964): every active point projected with its host's row; the map was filled with DM_FAR before
-__global__ void __launch_bounds__(256) k_dm_seed(const int n, const int* __restrict__ host, const float* __restrict__ u, const float* __restrict__ v,
+__device__ __forceinline__ void dmSeedBody(const int n, const int* __restrict__ host, const float* __restrict__ u, const float* __restrict__ v,
                                                   const float* __restrict__ idepth, const float* __restrict__ KRKi, const float* __restrict__ Kt, const DmGeom G,
                                                   unsigned char* __restrict__ map) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -58,9 +58,14 @@ __global__ void __launch_bounds__(256) k_dm_seed(const int n, const int* __restr
   int pix; float p0;
   if (dmProject(KRKi + 9 * hI, Kt + 3 * hI, u[i], v[i], idepth[i], G, &pix, &p0)) map[pix] = 0;
 }
+__global__ void __launch_bounds__(256) k_dm_seed(const int n, const int* __restrict__ host, const float* __restrict__ u, const float* __restrict__ v,
+                                                  const float* __restrict__ idepth, const float* __restrict__ KRKi, const float* __restrict__ Kt, const DmGeom G,
+                                                  unsigned char* __restrict__ map) {
+  dmSeedBody(n, host, u, v, idepth, KRKi, Kt, G, map);
+}
 
 // one step of growDistBFS from the freshly seeded map, as a pull (see above); k odd: 8-neighbourhood, k even: 4-neighbourhood
-__global__ void __launch_bounds__(256) k_dm_grow(unsigned char* map, const DmGeom G, const int k) {
+__device__ __forceinline__ void dmGrowBody(unsigned char* map, const DmGeom G, const int k) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= G.w1 * G.h1) return;
   if ((int)map[i] <= k) return;
@@ -79,6 +84,7 @@ __global__ void __launch_bounds__(256) k_dm_grow(unsigned char* map, const DmGeo
   }
   if (hit) map[i] = (unsigned char)k;
 }
+__global__ void __launch_bounds__(256) k_dm_grow(unsigned char* map, const DmGeom G, const int k) { dmGrowBody(map, G, k); }
 
 // ------------------------------------------------------------------------------------------------------------------------
 // the map as the single-workgroup kernels see it: LDS (s_act_dyn) or global memory
@@ -161,7 +167,7 @@ struct ActArgs {
 };
 
 // FullSystem.cpp:655-716 without the order-dependent part: decision 2 = deleted, 0 = stays, 3 = passed `dist >= minActDist * my_type` on the initial map
-__global__ void __launch_bounds__(256) k_act_classify(const ImmaturePts P, const ActArgs A, const DmGeom G, const unsigned char* __restrict__ map, int* __restrict__ decision,
+__device__ __forceinline__ void actClassifyBody(const ImmaturePts P, const ActArgs A, const DmGeom G, const unsigned char* __restrict__ map, int* __restrict__ decision,
                                                        int* __restrict__ pidx, float* __restrict__ frac, float* __restrict__ thr, int* __restrict__ counts) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= A.n) return;
@@ -190,6 +196,10 @@ __global__ void __launch_bounds__(256) k_act_classify(const ImmaturePts P, const
   }
   decision[i] = dec;
 }
+__global__ void __launch_bounds__(256) k_act_classify(const ImmaturePts P, const ActArgs A, const DmGeom G, const unsigned char* __restrict__ map, int* __restrict__ decision,
+                                                       int* __restrict__ pidx, float* __restrict__ frac, float* __restrict__ thr, int* __restrict__ counts) {
+  actClassifyBody(P, A, G, map, decision, pidx, frac, thr, counts);
+}
 
 // exclusive rank of `flag` among the workgroup's threads (thread order) + the workgroup's total; s_w: one int per wave.  Two barriers.
 __device__ __forceinline__ int actBlockRank(const bool flag, int* __restrict__ s_w, int* total) {
@@ -207,7 +217,7 @@ __device__ __forceinline__ int actBlockRank(const bool flag, int* __restrict__ s
 
 // the ordered walk (see the head of this file).  One workgroup.  The final map is written back (LDS variant) / is the global map itself.
 template <bool LDS>
-__global__ void __launch_bounds__(ACT_THREADS) k_act_walk(const ImmaturePts P, const ActArgs A, const DmGeom G, unsigned char* gmap, const int map_bytes /* multiple of 16 */,
+__device__ __forceinline__ void actWalkBody(const ImmaturePts P, const ActArgs A, const DmGeom G, unsigned char* gmap, const int map_bytes /* multiple of 16 */,
                                                            int* __restrict__ decision, const int* __restrict__ pidx, const float* __restrict__ frac,
                                                            const float* __restrict__ thr, int* surv, int* __restrict__ order, unsigned char* __restrict__ select,
                                                            unsigned char* __restrict__ mark, int* __restrict__ counts) {
@@ -275,10 +285,17 @@ __global__ void __launch_bounds__(ACT_THREADS) k_act_walk(const ImmaturePts P, c
   }
   if (tid == 0) counts[ACTC_ACCEPTED] = nacc;
 }
+template <bool LDS>
+__global__ void __launch_bounds__(ACT_THREADS) k_act_walk(const ImmaturePts P, const ActArgs A, const DmGeom G, unsigned char* gmap, const int map_bytes /* multiple of 16 */,
+                                                           int* __restrict__ decision, const int* __restrict__ pidx, const float* __restrict__ frac,
+                                                           const float* __restrict__ thr, int* surv, int* __restrict__ order, unsigned char* __restrict__ select,
+                                                           unsigned char* __restrict__ mark, int* __restrict__ counts) {
+  actWalkBody<LDS>(P, A, G, gmap, map_bytes, decision, pidx, frac, thr, surv, order, select, mark, counts);
+}
 
 // FullSystem.cpp:732-756 for the optimised selection, in toOptimize order: the results gathered, the deletion marks (activated points leave the immature list, failed
 // ones and not-converged OOB ones are deleted), and the record the PointHessian constructor copies (HessianBlocks.cpp:36-58)
-__global__ void __launch_bounds__(256) k_act_gather(const ImmaturePts P, const int n_sel, const int F, const int* __restrict__ order, const int* __restrict__ result,
+__device__ __forceinline__ void actGatherBody(const ImmaturePts P, const int n_sel, const int F, const int* __restrict__ order, const int* __restrict__ result,
                                                      const float* __restrict__ idepth, const int* __restrict__ res_state, unsigned char* __restrict__ mark,
                                                      int* __restrict__ gi, float* __restrict__ gf, int* __restrict__ counts) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -294,6 +311,11 @@ __global__ void __launch_bounds__(256) k_act_gather(const ImmaturePts P, const i
   for (int t = 0; t < 8; t++) { gf[7 * n_sel + 8 * k + t] = P.color[8 * i + t]; gf[15 * n_sel + 8 * k + t] = P.weights[8 * i + t]; }
   if (res == 1 || res == -1 || (res == 0 && P.lastTraceStatus[i] == IPS_OOB)) mark[i] = 1;
   if (res == 1) atomicAdd(&counts[ACTC_ACTIVATED], 1);
+}
+__global__ void __launch_bounds__(256) k_act_gather(const ImmaturePts P, const int n_sel, const int F, const int* __restrict__ order, const int* __restrict__ result,
+                                                     const float* __restrict__ idepth, const int* __restrict__ res_state, unsigned char* __restrict__ mark,
+                                                     int* __restrict__ gi, float* __restrict__ gf, int* __restrict__ counts) {
+  actGatherBody(P, n_sel, F, order, result, idepth, res_state, mark, gi, gf, counts);
 }
 
 // the marks of FullSystem.cpp:732-756 from results computed elsewhere (result[k] of toOptimize[k])
@@ -313,7 +335,7 @@ __global__ void __launch_bounds__(256) k_rm_mark_host(const ImmaturePts P, const
 // The reference compacts every host's list with `list[i] = list.back(); pop_back(); i--` (FullSystem.cpp:759-770).  With m survivors in a list, survivors at
 // positions < m stay, and the holes below m, in ascending order, receive the survivors at positions >= m in DESCENDING order.  Both ranks are scans.  One workgroup;
 // hosts are packed in ascending tag.  newidx[i] = new handle index or -1; counts[ACTC_NEW_N] = new count, counts[ACTC_TAGS + t] = points of tag t afterwards.
-__global__ void __launch_bounds__(ACT_THREADS) k_rm_plan(const int* __restrict__ host, const unsigned char* __restrict__ mark, const int n, const int n_tags, int* newidx,
+__device__ __forceinline__ void rmPlanBody(const int* __restrict__ host, const unsigned char* __restrict__ mark, const int n, const int n_tags, int* newidx,
                                                           int* holes, int* __restrict__ counts) {
   __shared__ int s_w[ACT_THREADS / 64];
   __shared__ int s_m;
@@ -358,9 +380,13 @@ __global__ void __launch_bounds__(ACT_THREADS) k_rm_plan(const int* __restrict__
   }
   if (tid == 0) counts[ACTC_NEW_N] = outBase;
 }
+__global__ void __launch_bounds__(ACT_THREADS) k_rm_plan(const int* __restrict__ host, const unsigned char* __restrict__ mark, const int n, const int n_tags, int* newidx,
+                                                          int* holes, int* __restrict__ counts) {
+  rmPlanBody(host, mark, n, n_tags, newidx, holes, counts);
+}
 
 // drop_tag >= 0: tags above it move down by one (a marginalised keyframe leaves the window)
-__global__ void __launch_bounds__(256) k_rm_apply(const ImmaturePts S, const ImmaturePts D, const int n, const int* __restrict__ newidx, const int drop_tag) {
+__device__ __forceinline__ void rmApplyBody(const ImmaturePts S, const ImmaturePts D, const int n, const int* __restrict__ newidx, const int drop_tag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int j = newidx[i];
@@ -373,6 +399,9 @@ __global__ void __launch_bounds__(256) k_rm_apply(const ImmaturePts S, const Imm
   D.energyTH[j] = S.energyTH[i]; D.idepth_min[j] = S.idepth_min[i]; D.idepth_max[j] = S.idepth_max[i]; D.quality[j] = S.quality[i];
   D.lastTraceUV[2 * j] = S.lastTraceUV[2 * i]; D.lastTraceUV[2 * j + 1] = S.lastTraceUV[2 * i + 1];
   D.lastTracePixelInterval[j] = S.lastTracePixelInterval[i]; D.lastTraceStatus[j] = S.lastTraceStatus[i]; D.my_type[j] = S.my_type[i];
+}
+__global__ void __launch_bounds__(256) k_rm_apply(const ImmaturePts S, const ImmaturePts D, const int n, const int* __restrict__ newidx, const int drop_tag) {
+  rmApplyBody(S, D, n, newidx, drop_tag);
 }
 
 }  // namespace dmv

@@ -228,12 +228,12 @@ int dmvio_hip_immature_optimize(dmvio_hip_immature* m, int F, const int* frame_s
 }  // extern "C"
 
 int dmv_immature_optimize_launch_locked(dmvio_hip_immature* m, int F, const int* frame_slots, const double* w2c7, const double* aff2, const float* exposure,
-                                        const double fxfycxcy[4], const unsigned char* d_mask, int minObs) {
+                                        const double fxfycxcy[4], const unsigned char* d_mask, int minObs, bool stream_idle) {
   dmvio_hip_ctx* c = m->ctx;
   if (F < 2 || F > 8 || !frame_slots || !w2c7 || !aff2 || !exposure || !fxfycxcy) return failmsg("immature_optimize: bad argument");
   if (m->n == 0) return 0;
   if (m->max_tag >= F) return failmsg("immature_optimize: a point's host_tag is not a keyframe index of this window (host_tag >= F)");
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (!stream_idle) HIPCHK(hipStreamSynchronize(c->stream));
   float* tb = m->h_opt_tables;
   float *R = tb, *t = tb + 9 * 64, *aff = tb + 12 * 64;
   OptTables T;

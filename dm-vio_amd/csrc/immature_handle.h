@@ -65,6 +65,7 @@ void dmv_host_tables(const float Kleft[9], const double fxfycxcy[4], const doubl
 // the selector's status map of its last call (w*h bytes on the device; capi_select.hip)
 const unsigned char* dmv_selector_map(dmvio_hip_pixel_selector* s);
 // dmvio_hip_immature_optimize up to and including the kernel, for a mask that is already on the device (d_mask per point; results stay in d_result / d_idepth /
-// d_res_state).  The caller holds the context's mutex.
+// d_res_state).  The caller holds the context's mutex.  stream_idle: the caller has waited for the stream since this handle's tables were last uploaded (a batch of
+// handles waits once for all of them); otherwise the call waits itself before it rewrites them.
 int dmv_immature_optimize_launch_locked(dmvio_hip_immature* m, int F, const int* frame_slots, const double* w2c7, const double* aff2, const float* exposure,
-                                        const double fxfycxcy[4], const unsigned char* d_mask, int minObs);
+                                        const double fxfycxcy[4], const unsigned char* d_mask, int minObs, bool stream_idle = false);

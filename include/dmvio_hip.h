@@ -768,6 +768,61 @@ int dmvio_hip_immature_remove_host(dmvio_hip_immature* imm, int tag);
 /* currentMinActDist after the controller of FullSystem.cpp:608-627 (nPoints = ef->nPoints, desiredDensity = setting_desiredPointDensity).  Host only. */
 float dmvio_hip_min_act_dist_update(float cur, int nPoints, float desiredDensity);
 
+/* ------------------------------------------------------------------------------------------------------------------------
+ * Point activation of W sliding windows per call (a server that also runs dmvio_hip_ba_optimize_batch): the steps above for W independent pairs of an immature handle
+ * and a distance map, all of one context.  Every window afterwards holds exactly what its single call leaves (maps, decisions, toOptimize order, marks, compacted lists,
+ * the handle's selection state), so single and batched calls may be mixed on a handle.  The ordered walk of a window stays one workgroup; a batch is W of them side by
+ * side.  Each call uploads one slab of per-window records, runs under the context's lock on the context's stream and waits for the stream once.
+ * A call is refused as a whole, before anything is enqueued or any handle touched, when W < 0 or W > max_windows, a handle is NULL or belongs to another context, an
+ * immature handle or a map appears twice, a needed array is NULL, a map has not been made (select) or a point's host_tag has no table row.  W == 0 returns 0. */
+typedef struct dmvio_hip_activation_batch dmvio_hip_activation_batch;
+/* owns the record slab, its pinned mirror and the per-window counters; max_windows >= 1 */
+dmvio_hip_activation_batch* dmvio_hip_activation_batch_create(dmvio_hip_ctx* ctx, int max_windows);
+void dmvio_hip_activation_batch_destroy(dmvio_hip_activation_batch* batch);
+/* one window of a batch; the arrays stay the caller's.  make_batch reads dm, n_hosts, KRKi9, Kt3 and the active points (the arguments of dmvio_hip_distance_map_make);
+ * select_batch reads imm, dm, n_hosts, KRKi9, Kt3 and the four parameters of dmvio_hip_immature_select_for_activation and writes n_selected and n_deleted */
+typedef struct dmvio_hip_activation_window {
+  dmvio_hip_immature* imm;
+  dmvio_hip_distance_map* dm;
+  int n_hosts;
+  const float* KRKi9;
+  const float* Kt3;
+  int n_active;
+  const int* active_host_tag;
+  const float* active_u;
+  const float* active_v;
+  const float* active_idepth;          /* PointHessian::idepth_scaled */
+  const unsigned char* host_flagged;   /* n_hosts */
+  int newest_tag;
+  float minActDist, minTraceQuality;
+  int n_selected, n_deleted;           /* out */
+} dmvio_hip_activation_window;
+/* CoarseDistanceMap::makeDistanceMap (CoarseTracker.cpp:931-967) with growDistBFS (CoarseTracker.cpp:979-1073) for every window: 39 growth launches for all W maps */
+int dmvio_hip_distance_map_make_batch(dmvio_hip_activation_batch* batch, int W, dmvio_hip_activation_window* win);
+/* the candidate loop of FullSystem::activatePointsMT (FullSystem.cpp:646-717) for every window, each window's walk with addIntoDistFinal (CoarseTracker.cpp:1076-1082)
+ * one workgroup.  If any handle of the call has dmvio_hip_immature_set_activation_walk set to 1, or the map does not fit into LDS, every window walks in global memory. */
+int dmvio_hip_immature_select_for_activation_batch(dmvio_hip_activation_batch* batch, int W, dmvio_hip_activation_window* win);
+/* FullSystem::optimizeImmaturePoint and the result loop (FullSystem.cpp:723-756) for the selection of every window, as dmvio_hip_immature_optimize_selected: F keyframes
+ * per window (frame_slots, w2c7 F x 7, aff2 F x 2, exposure F), one camera for all.  result / idepth / res_state (n_selected, n_selected, n_selected * F entries, toOptimize
+ * order, each may be NULL) and n_activated are written per window. */
+typedef struct dmvio_hip_activation_optimize {
+  dmvio_hip_immature* imm;
+  int F;
+  const int* frame_slots;
+  const double* w2c7;
+  const double* aff2;
+  const float* exposure;
+  int minObs;
+  int* result;
+  float* idepth;
+  int* res_state;
+  int n_activated;                     /* out */
+} dmvio_hip_activation_optimize;
+int dmvio_hip_immature_optimize_selected_batch(dmvio_hip_activation_batch* batch, int W, dmvio_hip_activation_optimize* win, const double fxfycxcy[4]);
+/* the compaction of FullSystem.cpp:759-770 for every handle, as dmvio_hip_immature_remove_marked; n_left[w] (may be NULL) = the new number of points.  Every handle needs
+ * a selection, which the call consumes. */
+int dmvio_hip_immature_remove_marked_batch(dmvio_hip_activation_batch* batch, int W, dmvio_hip_immature* const* imm, int* n_left);
+
 #ifdef __cplusplus
 }
 #endif

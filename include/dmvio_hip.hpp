@@ -482,5 +482,40 @@ class ImmaturePoints {
   bool own_;
 };
 
+/* FullSystem::activatePointsMT for several windows per call (dmvio_hip_activation_batch): W pairs of ImmaturePoints and DistanceMap of one context.  Every window ends in
+ * the state its single calls leave; the results are read with the windows' own getters (ImmaturePoints::activation, DistanceMap::get).  A call is refused as a whole
+ * (lastError()) before any window is touched. */
+class ActivationBatch {
+ public:
+  ActivationBatch(dmvio_hip_ctx* ctx, int maxWindows) : b_(dmvio_hip_activation_batch_create(ctx, maxWindows)) {}
+  ~ActivationBatch() { if (b_) dmvio_hip_activation_batch_destroy(b_); }
+  ActivationBatch(const ActivationBatch&) = delete;
+  ActivationBatch& operator=(const ActivationBatch&) = delete;
+  bool valid() const { return b_ != nullptr; }
+  /* makeDistanceMap (CoarseTracker.cpp:931-967) of every window: dm, n_hosts, the tables and the active points of each record */
+  bool makeDistanceMaps(std::vector<dmvio_hip_activation_window>& windows) {
+    return b_ && dmvio_hip_distance_map_make_batch(b_, (int)windows.size(), windows.data()) == 0;
+  }
+  /* the candidate loop (FullSystem.cpp:646-717) of every window; n_selected / n_deleted of each record are written */
+  bool selectForActivation(std::vector<dmvio_hip_activation_window>& windows) {
+    return b_ && dmvio_hip_immature_select_for_activation_batch(b_, (int)windows.size(), windows.data()) == 0;
+  }
+  /* optimizeImmaturePoint of every window's selection (FullSystem.cpp:723-756); the result arrays of each record are the caller's */
+  bool optimizeSelected(std::vector<dmvio_hip_activation_optimize>& windows, const double fxfycxcy[4]) {
+    return b_ && dmvio_hip_immature_optimize_selected_batch(b_, (int)windows.size(), windows.data(), fxfycxcy) == 0;
+  }
+  /* the compaction (FullSystem.cpp:759-770) of every handle: nLeft[i] = new number of points */
+  bool removeMarked(const std::vector<ImmaturePoints*>& points, std::vector<int>& nLeft) {
+    if (!b_) return false;
+    std::vector<dmvio_hip_immature*> hs(points.size());
+    for (size_t i = 0; i < points.size(); i++) { if (!points[i]) return false; hs[i] = points[i]->handle(); }
+    nLeft.assign(points.size(), 0);
+    return dmvio_hip_immature_remove_marked_batch(b_, (int)hs.size(), hs.data(), nLeft.data()) == 0;
+  }
+
+ private:
+  dmvio_hip_activation_batch* b_;
+};
+
 }  // namespace dmvio_hip
 #endif
