@@ -67,6 +67,17 @@ class PixelSelectorSettings(C.Structure):
     _fields_ = [("minGradHistCut", C.c_float), ("minGradHistAdd", C.c_float), ("gradDownweightPerLevel", C.c_float), ("selectDirectionDistribution", C.c_int)]
 
 
+class PixelSelectorWindow(C.Structure):
+    """dmvio_hip_pixel_selector_window (include/dmvio_hip.h): one window of a batched makeMaps call."""
+    _fields_ = [("sel", C.c_void_p), ("slot", C.c_int), ("B_lut256", c_f), ("density", C.c_float), ("recursions_left", C.c_int), ("th_factor", C.c_float),
+                ("map_out_host", c_f), ("n_selected", C.c_int), ("counts3", C.c_int * 3)]
+
+
+class NewTracesWindow(C.Structure):
+    """dmvio_hip_new_traces_window: one window of dmvio_hip_immature_add_selected_batch."""
+    _fields_ = [("imm", C.c_void_p), ("host_tag", C.c_int), ("host_slot", C.c_int), ("sel", C.c_void_p), ("first", C.c_int)]
+
+
 class ActivationWindow(C.Structure):
     """dmvio_hip_activation_window (include/dmvio_hip.h): one window of a batched activation call."""
     _fields_ = [("imm", C.c_void_p), ("dm", C.c_void_p), ("n_hosts", C.c_int), ("KRKi9", c_f), ("Kt3", c_f), ("n_active", C.c_int), ("active_host_tag", c_i),
@@ -202,6 +213,12 @@ def _sig(L):
     L.dmvio_hip_pixel_selector_get_passes.argtypes = [vp, C.c_int, c_i, c_i]
     L.dmvio_hip_pixel_selector_get_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.dmvio_hip_immature_add_selected.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.dmvio_hip_pixel_selector_batch_create.restype = vp
+    L.dmvio_hip_pixel_selector_batch_create.argtypes = [vp, C.c_int]
+    L.dmvio_hip_pixel_selector_batch_destroy.argtypes = [vp]
+    L.dmvio_hip_pixel_selector_batch_destroy.restype = None
+    L.dmvio_hip_pixel_selector_make_maps_batch.argtypes = [vp, C.c_int, C.POINTER(PixelSelectorWindow)]
+    L.dmvio_hip_immature_add_selected_batch.argtypes = [vp, C.c_int, C.POINTER(NewTracesWindow)]
     L.dmvio_hip_distance_map_create.restype = vp
     L.dmvio_hip_distance_map_create.argtypes = [vp]
     L.dmvio_hip_distance_map_destroy.argtypes = [vp]
@@ -1198,6 +1215,65 @@ class PixelSelectorHip:
         s = (C.c_longlong * 4)()
         _chk(self.L, self.L.dmvio_hip_pixel_selector_get_stats(self.p, s), "pixel_selector_get_stats")
         return dict(exact_path_runs=int(s[0]), passes=int(s[1]), n_selected=int(s[2]), n_window=int(s[3]))
+
+
+class PixelSelectorBatchHip:
+    """makeMaps and the point loop of makeNewTraces for W windows per call (dmvio_hip_pixel_selector_batch): every window is one PixelSelectorHip (and one
+    ImmaturePointsHip) of this context and ends in the state its single calls leave, so the per-handle getters (get_selection, get_passes, get_thresholds, stats,
+    currentPotential, get_static ...) read the results."""
+
+    def __init__(self, ctx, max_windows):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_pixel_selector_batch_create(ctx.p, int(max_windows))
+        if not p:
+            raise HipLibraryError("dmvio_hip_pixel_selector_batch_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.max_windows = int(max_windows)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_pixel_selector_batch_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def make_maps(self, windows):
+        """windows: dicts with sel, slot, density and optionally recursionsLeft (1), thFactor (1.0), B (None), want_map (True)
+        -> [(return value of makeMaps, status map uint8 [h, w] or None)]; every selector's .counts = (n2, n3, n4) of its last select"""
+        arr = (PixelSelectorWindow * max(len(windows), 1))()
+        keep, maps = [], []
+        for k, w in enumerate(windows):
+            r = arr[k]
+            sel = w.get("sel")
+            r.sel = sel.p if sel is not None else None
+            r.slot = int(w["slot"]); r.density = float(w["density"]); r.recursions_left = int(w.get("recursionsLeft", 1)); r.th_factor = float(w.get("thFactor", 1.0))
+            if w.get("B") is not None:
+                B = np.ascontiguousarray(w["B"], dtype=np.float32)
+                r.B_lut256 = _f(B); keep.append(B)
+            m = np.zeros(self.ctx.w * self.ctx.h, np.float32) if w.get("want_map", True) else None
+            if m is not None:
+                r.map_out_host = _f(m)
+            maps.append(m)
+        _chk(self.L, self.L.dmvio_hip_pixel_selector_make_maps_batch(self.p, len(windows), arr), "pixel_selector_make_maps_batch")
+        out = []
+        for k, w in enumerate(windows):
+            w["sel"].counts = tuple(int(x) for x in arr[k].counts3)
+            out.append((int(arr[k].n_selected), None if maps[k] is None else maps[k].astype(np.uint8).reshape(self.ctx.h, self.ctx.w)))
+        return out
+
+    def add_selected(self, windows):
+        """windows: dicts with imm, host_tag, host_slot, sel -> [index of the first new point]"""
+        arr = (NewTracesWindow * max(len(windows), 1))()
+        for k, w in enumerate(windows):
+            r = arr[k]
+            r.imm = w["imm"].p if w.get("imm") is not None else None
+            r.sel = w["sel"].p if w.get("sel") is not None else None
+            r.host_tag = int(w["host_tag"]); r.host_slot = int(w["host_slot"])
+        _chk(self.L, self.L.dmvio_hip_immature_add_selected_batch(self.p, len(windows), arr), "immature_add_selected_batch")
+        return [int(arr[k].first) for k in range(len(windows))]
 
 
 class BundleAdjusterBatch:

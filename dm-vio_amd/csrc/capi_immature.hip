@@ -105,6 +105,68 @@ int dmvio_hip_immature_add_selected(dmvio_hip_immature* m, int host_tag, int hos
   return first;
 }
 
+// the same loop for W windows: one record upload, one launch sequence (coordinate copy + constructor, then the types from the map); like the single call it does not wait
+int dmvio_hip_immature_add_selected_batch(dmvio_hip_pixel_selector_batch* batch, int W, dmvio_hip_new_traces_window* win) {
+  dmvio_hip_ctx* c = nullptr;
+  int max_windows = 0;
+  char* d_records = nullptr;
+  if (int r = dmv_selector_batch_traces(batch, sizeof(NewTracesWin), &c, &max_windows, &d_records)) return r;
+  if (W < 0 || W > max_windows) return failmsg("immature_add_selected_batch: W is negative or larger than the batch's max_windows");
+  if (W > 0 && !win) return failmsg("immature_add_selected_batch: the window array is NULL");
+  if (W == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  // every refusal before anything is enqueued or any handle touched
+  std::vector<int> nn(W);
+  std::vector<const float*> du(W), dv(W);
+  for (int k = 0; k < W; k++) {
+    const dmvio_hip_new_traces_window& V = win[k];
+    if (!V.imm) return failmsg("immature_add_selected_batch: an immature handle is NULL");
+    if (!V.sel) return failmsg("immature_add_selected_batch: a selector handle is NULL");
+    if (V.imm->ctx != c) return failmsg("immature_add_selected_batch: an immature handle belongs to another context");
+    for (int j = 0; j < k; j++) if (win[j].imm == V.imm) return failmsg("immature_add_selected_batch: an immature handle appears twice");
+    dmvio_hip_ctx* sc = nullptr;
+    nn[k] = dmv_selector_window_list(V.sel, &sc, &du[k], &dv[k]);
+    if (nn[k] < 0) return nn[k];
+    if (sc != c) return failmsg("immature_add_selected_batch: a selector belongs to another context");
+    if (V.imm->n + nn[k] > V.imm->capacity) return failmsg("immature_add_selected_batch: capacity exceeded");
+    if (V.host_slot < 0 || V.host_slot >= c->n_slots || V.host_tag < 0 || V.host_tag >= IMM_MAX_HOSTS) return failmsg("immature_add_selected_batch: slot / tag out of range");
+  }
+  for (int k = 0; k < W; k++) if (int r = dmv_ensure_row_major_locked(c, win[k].host_slot)) return r;
+  int nmax = 0;
+  for (int k = 0; k < W; k++) nmax = std::max(nmax, nn[k]);
+  if (nmax > 0) {
+    // the records are staged in the context's pinned memory, which stays intact until the next wait on the stream
+    size_t off;
+    HIPCHK(c->bounce.reserve(sizeof(NewTracesWin) * (size_t)W, c->stream, &off));
+    NewTracesWin* R = reinterpret_cast<NewTracesWin*>(c->bounce.h + off);
+    for (int k = 0; k < W; k++) {
+      const dmvio_hip_new_traces_window& V = win[k];
+      NewTracesWin r{};
+      r.I = c->levelPtr(V.host_slot, 0); r.wu = du[k]; r.wv = dv[k]; r.map = dmv_selector_map(V.sel);
+      r.P = V.imm->P; r.P.n = V.imm->n + nn[k];
+      r.S = V.imm->S;
+      r.w = c->w; r.first = V.imm->n; r.n = nn[k]; r.host_tag = V.host_tag;
+      memcpy(&R[k], &r, sizeof(r));
+    }
+    HIPCHK(hipMemcpyAsync(d_records, R, sizeof(NewTracesWin) * (size_t)W, hipMemcpyHostToDevice, c->stream));
+    const NewTracesWin* D = reinterpret_cast<const NewTracesWin*>(d_records);
+    // the window (3 <= x < w-4, 3 <= y < h-4) lies inside the margin the constructor needs (dmvio_hip_immature_add_points)
+    hipLaunchKernelGGL(k_immature_init_b, dim3((nmax + 255) / 256, W), dim3(256), 0, c->stream, D);
+    hipLaunchKernelGGL(k_immature_types_from_map_b, dim3((nmax + 255) / 256, W), dim3(256), 0, c->stream, D);
+    HIPCHK(hipGetLastError());
+  }
+  for (int k = 0; k < W; k++) {
+    dmvio_hip_immature* m = win[k].imm;
+    win[k].first = m->n;
+    if (nn[k] == 0) continue;   // as the single call: nothing added, nothing changed
+    m->P.n = m->n + nn[k];
+    m->n += nn[k];
+    m->max_tag = std::max(m->max_tag, win[k].host_tag);
+  }
+  return 0;
+}
+
 int dmvio_hip_immature_get_static(dmvio_hip_immature* m, float* u, float* v, int* host_tag, float* color8, float* weights8, float* gradH4, float* energyTH) {
   IMM_READY(m);
   hipStream_t s = m->ctx->stream;

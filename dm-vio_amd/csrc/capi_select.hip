@@ -6,6 +6,7 @@
 #include "../../include/dmvio_hip.h"
 #include "internal.h"
 #include "select_kernels.hpp"
+#include "select_batch_kernels.hpp"
 
 using namespace dmv;
 
@@ -50,11 +51,17 @@ static int salloc(dmvio_hip_pixel_selector* s, T** p, size_t n) {
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 #define SEL_READY(s) do { if (!(s)) return failmsg("null pixel selector handle"); HIPCHK(hipSetDevice((s)->ctx->device)); } while (0)
 
-// one select() pass (PixelSelector2.cpp:311-454) at potential `pot` on the stream; the counters are copied into h_counts and waited for
-static int selectPass(dmvio_hip_pixel_selector* s, int slot, int pot, float thFactor) {
+// geometry and scratch layout of one select() pass at potential `pot`: what the single call and a window of a batch share.  Sets s->d_counters / s->d_map.
+struct SelLayout {
+  SelGeom G;
+  unsigned int* d_mask;
+  unsigned long long *d_key2, *d_key3, *d_key4;
+  size_t bytes;   // of d_zero, cleared before the pass
+};
+static int selectLayout(dmvio_hip_pixel_selector* s, int pot, float thFactor, SelLayout& L) {
   dmvio_hip_ctx* c = s->ctx;
   const int w = s->w, h = s->h, wh = w * h;
-  SelGeom G;
+  SelGeom& G = L.G;
   G.w = w; G.h = h; G.w1 = c->wl[1]; G.w2 = c->wl[2];
   G.pot = std::min(pot, std::max(w, h));
   G.nb4x = (w + 4 * G.pot - 1) / (4 * G.pot);
@@ -69,14 +76,27 @@ static int selectPass(dmvio_hip_pixel_selector* s, int slot, int pot, float thFa
   const size_t N = G.ncell;
   size_t off = 0;
   s->d_counters = reinterpret_cast<int*>(s->d_zero + off); off += up256(sizeof(int) * SELC_COUNT);
-  unsigned int* d_mask = reinterpret_cast<unsigned int*>(s->d_zero + off); off += up256(sizeof(unsigned int) * N);
+  L.d_mask = reinterpret_cast<unsigned int*>(s->d_zero + off); off += up256(sizeof(unsigned int) * N);
   // the three key arrays lie back to back: k_sel_pick addresses them as one (N is a multiple of 16)
-  unsigned long long* d_key2 = reinterpret_cast<unsigned long long*>(s->d_zero + off); off += up256(sizeof(unsigned long long) * (N + N / 4 + N / 16));
-  unsigned long long *d_key3 = d_key2 + N, *d_key4 = d_key3 + N / 4;
+  L.d_key2 = reinterpret_cast<unsigned long long*>(s->d_zero + off); off += up256(sizeof(unsigned long long) * (N + N / 4 + N / 16));
+  L.d_key3 = L.d_key2 + N; L.d_key4 = L.d_key3 + N / 4;
   s->d_map = reinterpret_cast<unsigned char*>(s->d_zero + off); off += up256((size_t)wh);
   if (off > s->zero_cap) return failmsg("pixel_selector: internal: scratch layout exceeds its allocation");
+  L.bytes = off;
+  return 0;
+}
+
+// one select() pass (PixelSelector2.cpp:311-454) at potential `pot` on the stream; the counters are copied into h_counts and waited for
+static int selectPass(dmvio_hip_pixel_selector* s, int slot, int pot, float thFactor) {
+  dmvio_hip_ctx* c = s->ctx;
+  const int w = s->w, h = s->h, wh = w * h;
+  SelLayout L;
+  if (int r = selectLayout(s, pot, thFactor, L)) return r;
+  const SelGeom& G = L.G;
+  unsigned int* d_mask = L.d_mask;
+  unsigned long long *d_key2 = L.d_key2, *d_key3 = L.d_key3, *d_key4 = L.d_key4;
   hipStream_t st = c->stream;
-  HIPCHK(hipMemsetAsync(s->d_zero, 0, off, st));
+  HIPCHK(hipMemsetAsync(s->d_zero, 0, L.bytes, st));
   const float* I0 = c->levelPtr(slot, 0);
   const float *ag0 = s->d_ag, *ag1 = ag0 + wh, *ag2 = ag1 + c->wl[1] * c->hl[1];
   hipLaunchKernelGGL(k_sel_cellmask, dim3((wh + 255) / 256), dim3(256), 0, st, I0, ag0, (const float*)s->d_thsS, G, d_mask);
@@ -97,6 +117,36 @@ static int selectPass(dmvio_hip_pixel_selector* s, int slot, int pot, float thFa
   HIPCHK(hipMemcpyAsync(s->h_counts, s->d_counters, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
+}
+
+// The decision step of makeMaps' recursion (:203-245) after one select pass with counters n[]: records the pass, and either moves currentPotential and asks for another
+// pass (true) or ends the recursion (false).  The single call and every window of a batched call run this one function.
+struct SelRecursion {
+  float numWant = 0, quotia = 0;
+  int idealPotential = 0, recursionsLeft = 0;
+};
+static bool selectDecide(dmvio_hip_pixel_selector* s, const int* n, SelRecursion& R) {
+  s->pass_pot.push_back(s->currentPotential);
+  for (int k = 0; k < 3; k++) { s->pass_counts.push_back(n[k]); s->last_counts[k] = n[k]; }
+  if (n[SELC_EXACT]) s->exact_runs++;
+  const float numHave = (float)(n[0] + n[1] + n[2]);
+  R.quotia = R.numWant / numHave;
+  const float K = numHave * (s->currentPotential + 1) * (s->currentPotential + 1);
+  R.idealPotential = (int)(sqrtf(K / R.numWant) - 1);   // round down
+  if (R.idealPotential < 1) R.idealPotential = 1;
+  if (R.recursionsLeft > 0 && (double)R.quotia > 1.25 && s->currentPotential > 1) {
+    if (R.idealPotential >= s->currentPotential) R.idealPotential = s->currentPotential - 1;
+    s->currentPotential = R.idealPotential;
+    R.recursionsLeft--;
+    return true;
+  }
+  if (R.recursionsLeft > 0 && (double)R.quotia < 0.25) {
+    if (R.idealPotential <= s->currentPotential) R.idealPotential = s->currentPotential + 1;
+    s->currentPotential = R.idealPotential;
+    R.recursionsLeft--;
+    return true;
+  }
+  return false;
 }
 
 extern "C" {
@@ -180,35 +230,14 @@ int dmvio_hip_pixel_selector_make_maps(dmvio_hip_pixel_selector* s, int slot, co
 
   // makeMaps (:158-273); its recursion is this loop
   s->pass_pot.clear(); s->pass_counts.clear();
-  const float numWant = density;
-  float numHave = 0, quotia = 0;
-  int idealPotential = s->currentPotential;
-  int recursionsLeft = recursions_left;
+  SelRecursion R;
+  R.numWant = density; R.idealPotential = s->currentPotential; R.recursionsLeft = recursions_left;
   for (;;) {
     if (int r = selectPass(s, slot, s->currentPotential, th_factor)) return r;
-    const int* n = s->h_counts;
-    s->pass_pot.push_back(s->currentPotential);
-    for (int k = 0; k < 3; k++) { s->pass_counts.push_back(n[k]); s->last_counts[k] = n[k]; }
-    if (n[SELC_EXACT]) s->exact_runs++;
-    numHave = (float)(n[0] + n[1] + n[2]);
-    quotia = numWant / numHave;
-    const float K = numHave * (s->currentPotential + 1) * (s->currentPotential + 1);
-    idealPotential = (int)(sqrtf(K / numWant) - 1);   // round down
-    if (idealPotential < 1) idealPotential = 1;
-    if (recursionsLeft > 0 && (double)quotia > 1.25 && s->currentPotential > 1) {
-      if (idealPotential >= s->currentPotential) idealPotential = s->currentPotential - 1;
-      s->currentPotential = idealPotential;
-      recursionsLeft--;
-      continue;
-    }
-    if (recursionsLeft > 0 && (double)quotia < 0.25) {
-      if (idealPotential <= s->currentPotential) idealPotential = s->currentPotential + 1;
-      s->currentPotential = idealPotential;
-      recursionsLeft--;
-      continue;
-    }
-    break;
+    if (!selectDecide(s, s->h_counts, R)) break;
   }
+  const float quotia = R.quotia;
+  const int idealPotential = R.idealPotential;
   // sub-selection (:247-265), compaction in raster order, the makeNewTraces window
   SelScanArgs A;
   A.n = wh; A.w = w; A.h = h; A.charTH = 255;
@@ -288,6 +317,217 @@ int dmvio_hip_pixel_selector_get_stats(dmvio_hip_pixel_selector* s, long long st
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------------------------------ W keyframes per call
+// makeMaps for W selectors of one context.  The recursion stays on the host, in rounds: round r runs one select pass for every window that is still recursing, each at its
+// own potential; the counters of all windows come back in one copy behind one stream wait, and selectDecide() moves every window on.  The final phase (sub-selection,
+// raster compaction, makeNewTraces list) runs once for all windows.  Every round writes one pinned slab [SelWin x W | B tables] and uploads it in one copy; the slab is
+// rewritten only after the wait that ends the round before.
+struct dmvio_hip_pixel_selector_batch {
+  dmvio_hip_ctx* ctx = nullptr;
+  int max_windows = 0;
+  char *h_slab = nullptr, *d_slab = nullptr;      // max_windows x (SelWin | 256 floats), sized at creation
+  size_t slab_bytes = 0, b_off = 0;
+  int *h_counts = nullptr, *d_counts = nullptr;   // max_windows x SELC_COUNT ints
+  char* d_traces = nullptr;                       // max_windows records of dmvio_hip_immature_add_selected_batch (capi_immature.hip)
+  size_t traces_bytes = 0;
+};
+enum { SEL_TRACES_RECORD = 512 };   // bytes reserved per window in d_traces (capi_immature.hip checks its record against it)
+
+static int selBatchHead(dmvio_hip_pixel_selector_batch* b, int W, const void* arr, const char* what) {
+  if (!b) return failmsg(std::string(what) + ": null batch handle");
+  if (W < 0 || W > b->max_windows) return failmsg(std::string(what) + ": W is negative or larger than the batch's max_windows");
+  if (W > 0 && !arr) return failmsg(std::string(what) + ": the window array is NULL");
+  return 0;
+}
+// the record of window `k` for a select pass at its selector's current potential (active) or for a phase it only watches (inactive: the layout of its last pass stays)
+static int selRecord(dmvio_hip_pixel_selector_batch* b, SelWin& R, int k, const dmvio_hip_pixel_selector_window& V, bool pass) {
+  dmvio_hip_pixel_selector* s = V.sel;
+  dmvio_hip_ctx* c = b->ctx;
+  memset(&R, 0, sizeof(R));
+  R.I0 = c->levelPtr(V.slot, 0); R.I1 = c->levelPtr(V.slot, 1); R.I2 = c->levelPtr(V.slot, 2);
+  if (V.B_lut256) {
+    memcpy(b->h_slab + b->b_off + (size_t)k * 1024, V.B_lut256, sizeof(float) * 256);
+    R.B = reinterpret_cast<const float*>(b->d_slab + b->b_off + (size_t)k * 1024);
+  }
+  R.ag = s->d_ag; R.ths = s->d_ths; R.thsS = s->d_thsS; R.pattern = s->d_pattern;
+  R.counters = b->d_counts + (size_t)k * SELC_COUNT;
+  R.n2ex = s->d_n2ex; R.tiles = s->d_tiles; R.rn = s->d_rn; R.lu = s->d_lu; R.lv = s->d_lv; R.lt = s->d_lt; R.wu = s->d_wu; R.wv = s->d_wv;
+  R.h1 = c->hl[1]; R.h2 = c->hl[2]; R.nbH = s->nbH;
+  R.histCut = s->S.minGradHistCut; R.histAdd = s->S.minGradHistAdd;
+  R.G.w = s->w; R.G.h = s->h; R.G.w1 = c->wl[1]; R.G.w2 = c->wl[2]; R.G.nbW = s->nbW;
+  R.A.w = s->w; R.A.h = s->h; R.A.charTH = 255;
+  if (pass) {
+    SelLayout L;
+    if (int r = selectLayout(s, s->currentPotential, V.th_factor, L)) return r;
+    R.G = L.G;
+    R.zero = reinterpret_cast<uint4*>(s->d_zero); R.zero_words = (int)(L.bytes / 16);
+    R.mask = L.d_mask; R.keys = L.d_key2;
+    R.A.n = L.G.ncell;
+    R.active = 1;
+  }
+  R.map = s->d_map;
+  return 0;
+}
+
+extern "C" {
+
+dmvio_hip_pixel_selector_batch* dmvio_hip_pixel_selector_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
+  if (!ctx) { failmsg("pixel_selector_batch_create: null context"); return nullptr; }
+  if (max_windows < 1 || max_windows > 65535) { failmsg("pixel_selector_batch_create: max_windows out of range (1..65535)"); return nullptr; }
+  HIPCHKP(hipSetDevice(ctx->device));
+  dmvio_hip_pixel_selector_batch* b = new dmvio_hip_pixel_selector_batch();
+  b->ctx = ctx; b->max_windows = max_windows;
+  b->b_off = up256(sizeof(SelWin) * (size_t)max_windows);
+  b->slab_bytes = b->b_off + (size_t)1024 * max_windows;
+  b->traces_bytes = (size_t)SEL_TRACES_RECORD * max_windows;
+  const size_t cb = sizeof(int) * SELC_COUNT * (size_t)max_windows;
+  if (hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&b->d_slab, b->slab_bytes) != hipSuccess ||
+      hipHostMalloc((void**)&b->h_counts, cb, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&b->d_counts, cb) != hipSuccess ||
+      hipMalloc((void**)&b->d_traces, b->traces_bytes) != hipSuccess) {
+    failmsg("pixel_selector_batch_create: allocation failed");
+    if (b->h_slab) hipHostFree(b->h_slab);
+    if (b->d_slab) hipFree(b->d_slab);
+    if (b->h_counts) hipHostFree(b->h_counts);
+    if (b->d_counts) hipFree(b->d_counts);
+    delete b;
+    return nullptr;
+  }
+  return b;
+}
+void dmvio_hip_pixel_selector_batch_destroy(dmvio_hip_pixel_selector_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
+  hipHostFree(b->h_slab); hipFree(b->d_slab); hipHostFree(b->h_counts); hipFree(b->d_counts); hipFree(b->d_traces);
+  delete b;
+}
+
+int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, int W, dmvio_hip_pixel_selector_window* win) {
+  if (int r = selBatchHead(b, W, win, "pixel_selector_make_maps_batch")) return r;
+  if (W == 0) return 0;
+  dmvio_hip_ctx* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  // every refusal before anything is enqueued or any handle touched
+  for (int k = 0; k < W; k++) {
+    const dmvio_hip_pixel_selector_window& V = win[k];
+    if (!V.sel) return failmsg("pixel_selector_make_maps_batch: a selector handle is NULL");
+    if (V.sel->ctx != c) return failmsg("pixel_selector_make_maps_batch: a selector belongs to another context");
+    for (int j = 0; j < k; j++) if (win[j].sel == V.sel) return failmsg("pixel_selector_make_maps_batch: a selector appears twice");
+    if (V.slot < 0 || V.slot >= c->n_slots) return failmsg("pixel_selector_make_maps_batch: frame slot out of range");
+  }
+  for (int k = 0; k < W; k++) if (int r = dmv_ensure_row_major_locked(c, win[k].slot)) return r;
+  hipStream_t st = c->stream;
+  const int w = c->w, h = c->h, wh = w * h;
+  SelWin* R = reinterpret_cast<SelWin*>(b->h_slab);
+  const SelWin* D = reinterpret_cast<const SelWin*>(b->d_slab);
+  const size_t up_bytes = b->b_off + (size_t)1024 * W, cnt_bytes = sizeof(int) * SELC_COUNT * (size_t)W;
+  std::vector<SelRecursion> rec(W);
+  std::vector<char> running(W, 1);
+  for (int k = 0; k < W; k++) {
+    dmvio_hip_pixel_selector* s = win[k].sel;
+    s->pass_pot.clear(); s->pass_counts.clear();
+    rec[k].numWant = win[k].density; rec[k].idealPotential = s->currentPotential; rec[k].recursionsLeft = win[k].recursions_left;
+  }
+  // makeMaps (:158-273): its recursion is this loop, one round per pass of the window that recurses longest
+  for (int round = 0;; round++) {
+    int zmax = 0, tmax = 0, cmax = 0;
+    for (int k = 0; k < W; k++) {
+      if (int r = selRecord(b, R[k], k, win[k], running[k] != 0)) return r;
+      if (!running[k]) continue;
+      zmax = std::max(zmax, R[k].zero_words); tmax = std::max(tmax, (R[k].A.n + SEL_TILE - 1) / SEL_TILE); cmax = std::max(cmax, R[k].G.ncell);
+    }
+    HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, up_bytes, hipMemcpyHostToDevice, st));
+    if (round == 0) {
+      // FrameHessian::makeImages' absSquaredGrad and makeHists of every window
+      const int nag = wh + c->wl[1] * c->hl[1] + c->wl[2] * c->hl[2];
+      const int nb = (w / 16) * (h / 16);
+      hipLaunchKernelGGL(k_sel_absgrad_b, dim3((nag + 255) / 256, W), dim3(256), 0, st, D);
+      hipLaunchKernelGGL(k_sel_hist_b, dim3(nb, W), dim3(256), 0, st, D);
+      hipLaunchKernelGGL(k_sel_smooth_b, dim3((nb + 255) / 256, W), dim3(256), 0, st, D);
+    }
+    // the scratch clear of all active windows is one fill
+    hipLaunchKernelGGL(k_sel_clear_b, dim3((zmax + 255) / 256, W), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_sel_cellmask_b, dim3((wh + 255) / 256, W), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_sel_scanA_b<SEL_MODE_CELL>, dim3(tmax, W), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_sel_scanB_b, dim3(W), dim3(256), 0, st, D, (int)SEL_MODE_CELL, (int)SELC_N2, (int)SELC_MIXED);
+    hipLaunchKernelGGL(k_sel_scanC_b<SEL_MODE_CELL>, dim3(tmax, W), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_sel_scan_exact_b, dim3(W), dim3(64), 0, st, D);
+    hipLaunchKernelGGL(k_sel_pick_b, dim3((wh + 255) / 256, W), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_sel_write_b, dim3((cmax + 1023) / 1024, W), dim3(1024), 0, st, D);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, cnt_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));   // the one wait of the round
+    bool any = false;
+    for (int k = 0; k < W; k++) {
+      if (!running[k]) continue;
+      running[k] = selectDecide(win[k].sel, b->h_counts + (size_t)k * SELC_COUNT, rec[k]) ? 1 : 0;
+      any = any || running[k];
+    }
+    if (!any) break;
+  }
+  // sub-selection (:247-265) for the windows with quotia < 0.95, compaction in raster order, the makeNewTraces window: once for all windows
+  bool anySub = false;
+  int nmaps = 0;
+  for (int k = 0; k < W; k++) {
+    if (int r = selRecord(b, R[k], k, win[k], false)) return r;
+    R[k].A.n = wh;
+    if ((double)rec[k].quotia < 0.95) {
+      R[k].A.charTH = (int)(unsigned char)(255 * rec[k].quotia);
+      R[k].sub = 1;
+      anySub = true;
+    }
+    if (win[k].map_out_host) nmaps++;
+  }
+  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, up_bytes, hipMemcpyHostToDevice, st));
+  const int ntiles = (wh + SEL_TILE - 1) / SEL_TILE;
+  if (anySub) {
+    hipLaunchKernelGGL(k_sel_scanA_b<SEL_MODE_NZ>, dim3(ntiles, W), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_sel_scanB_b, dim3(W), dim3(256), 0, st, D, (int)SEL_MODE_NZ, (int)SELC_NZ, -1);
+    hipLaunchKernelGGL(k_sel_scanC_b<SEL_MODE_NZ>, dim3(ntiles, W), dim3(256), 0, st, D);
+  }
+  hipLaunchKernelGGL(k_sel_scanA_b<SEL_MODE_SURV>, dim3(ntiles, W), dim3(256), 0, st, D);
+  hipLaunchKernelGGL(k_sel_scanB_b, dim3(W), dim3(256), 0, st, D, (int)SEL_MODE_SURV, (int)SELC_NSEL, (int)SELC_NWIN);
+  hipLaunchKernelGGL(k_sel_scanC_b<SEL_MODE_SURV>, dim3(ntiles, W), dim3(256), 0, st, D);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, cnt_bytes, hipMemcpyDeviceToHost, st));
+  // the status maps the caller asked for come back through the bounce buffer: ONE reservation (a second one could drain and rewind the staging area under the first)
+  size_t moff = 0;
+  const size_t mstep = up256((size_t)wh);
+  if (nmaps) {
+    HIPCHK(c->bounce.reserve(mstep * nmaps, st, &moff));
+    int j = 0;
+    for (int k = 0; k < W; k++)
+      if (win[k].map_out_host) HIPCHK(hipMemcpyAsync(c->bounce.h + moff + mstep * (j++), win[k].sel->d_map, (size_t)wh, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c->bounce.finish(st));   // the one wait of the final phase
+  int j = 0;
+  for (int k = 0; k < W; k++) {
+    dmvio_hip_pixel_selector* s = win[k].sel;
+    if (win[k].map_out_host) {
+      const unsigned char* m = reinterpret_cast<const unsigned char*>(c->bounce.h + moff + mstep * (j++));
+      for (int i = 0; i < wh; i++) win[k].map_out_host[i] = (float)m[i];
+    }
+    const int* hc = b->h_counts + (size_t)k * SELC_COUNT;
+    s->currentPotential = rec[k].idealPotential;   // :273
+    s->n_selected = hc[SELC_NSEL];
+    s->n_window = hc[SELC_NWIN];
+    s->last_slot = win[k].slot;
+    win[k].n_selected = s->n_selected;
+    for (int q = 0; q < 3; q++) win[k].counts3[q] = s->last_counts[q];
+  }
+  return 0;
+}
+
+}  // extern "C"
+
+// the batch's context, size and record area for dmvio_hip_immature_add_selected_batch (capi_immature.hip): `bytes` per window must fit SEL_TRACES_RECORD
+int dmv_selector_batch_traces(dmvio_hip_pixel_selector_batch* b, size_t record_bytes, dmvio_hip_ctx** ctx, int* max_windows, char** d_records) {
+  if (!b) return failmsg("immature_add_selected_batch: null batch handle");
+  if (record_bytes > (size_t)SEL_TRACES_RECORD) return failmsg("immature_add_selected_batch: internal: record larger than the batch reserves");
+  *ctx = b->ctx; *max_windows = b->max_windows; *d_records = b->d_traces;
+  return 0;
+}
 int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, const float** d_u, const float** d_v) {
   if (!s) return failmsg("null pixel selector handle");
   if (s->last_slot < 0) return failmsg("immature_add_selected: the selector has no selection yet (dmvio_hip_pixel_selector_make_maps)");

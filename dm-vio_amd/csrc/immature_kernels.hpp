@@ -66,11 +66,7 @@ __device__ __forceinline__ float3 interp33Any(const float* __restrict__ I, const
 
 // ImmaturePoint constructor: thread per point.  getInterpolatedElement33BiLin (globalFuncs.h:203-227) only reads the intensity
 // channel (forward differences of the bilinear cell).
-__global__ void __launch_bounds__(256) k_immature_init(const float* __restrict__ I, const int w, const int first, const int n, const ImmaturePts P,
-                                                        const int host_tag, const ImmatureSettings S) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const int i = first + k;
+__device__ __forceinline__ void immInitBody(const float* __restrict__ I, const int w, const int i, const ImmaturePts& P, const int host_tag, const ImmatureSettings& S) {
   const float uf = P.u[i], vf = P.v[i];
   float g00 = 0.f, g01 = 0.f, g10 = 0.f, g11 = 0.f;
   bool bad = false;
@@ -100,13 +96,64 @@ __global__ void __launch_bounds__(256) k_immature_init(const float* __restrict__
   P.lastTraceStatus[i] = IPS_UNINITIALIZED;
   P.my_type[i] = 1.f;
 }
+__global__ void __launch_bounds__(256) k_immature_init(const float* __restrict__ I, const int w, const int first, const int n, const ImmaturePts P,
+                                                        const int host_tag, const ImmatureSettings S) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  immInitBody(I, w, first + k, P, host_tag, S);
+}
 
 // my_type of the points [first, first + n) from the selector's status map (FullSystem::makeNewTraces passes selectionMap[i], FullSystem.cpp:1660)
+__device__ __forceinline__ void immTypeBody(const unsigned char* __restrict__ map, const int w, const int i, const ImmaturePts& P) {
+  P.my_type[i] = (float)map[(int)P.u[i] + (int)P.v[i] * w];
+}
 __global__ void __launch_bounds__(256) k_immature_types_from_map(const unsigned char* __restrict__ map, const int w, const int first, const int n, const ImmaturePts P) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const int i = first + k;
-  P.my_type[i] = (float)map[(int)P.u[i] + (int)P.v[i] * w];
+  immTypeBody(map, w, first + k, P);
+}
+
+// ---- the point loop of makeNewTraces for W windows per launch (dmvio_hip_immature_add_selected_batch): window = blockIdx.y, grid.x = the largest count of the batch; the
+// bodies are the single call's, so a handle of a batch holds the bytes its single call would have left
+struct NewTracesWin {
+  const float* I;              // level 0 of the host frame
+  const float *wu, *wv;        // the selector's makeNewTraces window list
+  const unsigned char* map;    // the selector's status map
+  ImmaturePts P;
+  ImmatureSettings S;
+  int w, first, n, host_tag;
+};
+// A pointer read from a record in memory is a generic pointer to the compiler and every access through it a flat_* instruction (activate_batch_kernels.hpp: actGl); read
+// through an lvalue whose pointee type carries the global address space it stays a global one.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wincompatible-pointer-types-discards-qualifiers"
+template <class T> __device__ __forceinline__ T* immGl(T* const& member) {
+  return (T*)(*reinterpret_cast<__attribute__((address_space(1))) T* const*>(&member));
+}
+#pragma clang diagnostic pop
+__device__ __forceinline__ ImmaturePts immPts(const ImmaturePts& g) {
+  ImmaturePts v;
+  v.n = g.n;
+  v.u = immGl(g.u); v.v = immGl(g.v); v.host = immGl(g.host); v.color = immGl(g.color); v.weights = immGl(g.weights); v.gradH = immGl(g.gradH); v.energyTH = immGl(g.energyTH);
+  v.idepth_min = immGl(g.idepth_min); v.idepth_max = immGl(g.idepth_max); v.quality = immGl(g.quality); v.lastTraceUV = immGl(g.lastTraceUV);
+  v.lastTracePixelInterval = immGl(g.lastTracePixelInterval); v.lastTraceStatus = immGl(g.lastTraceStatus); v.my_type = immGl(g.my_type);
+  return v;
+}
+// the coordinate copy from the selector's list is folded in: the thread that constructs point first + k copies its position first
+__global__ void __launch_bounds__(256) k_immature_init_b(const NewTracesWin* __restrict__ wins) {
+  const NewTracesWin& V = wins[blockIdx.y];
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= V.n) return;
+  const ImmaturePts P = immPts(V.P);
+  const int i = V.first + k;
+  P.u[i] = immGl(V.wu)[k]; P.v[i] = immGl(V.wv)[k];
+  immInitBody(immGl(V.I), V.w, i, P, V.host_tag, V.S);
+}
+__global__ void __launch_bounds__(256) k_immature_types_from_map_b(const NewTracesWin* __restrict__ wins) {
+  const NewTracesWin& V = wins[blockIdx.y];
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= V.n) return;
+  immTypeBody(immGl(V.map), V.w, V.first + k, immPts(V.P));
 }
 
 // first-minimum argmin over the wave: (value, index) with the reference's strict '<' scan order (smallest index among equal minima)

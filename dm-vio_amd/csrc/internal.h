@@ -162,6 +162,10 @@ struct dmvio_hip_graph {
 // dmvio_hip_immature_add_selected in capi_immature.hip): pixel positions as floats, raster order.  Returns the number of entries or <0.
 struct dmvio_hip_pixel_selector;
 int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, const float** d_u, const float** d_v);
+// what dmvio_hip_immature_add_selected_batch (capi_immature.hip) needs of a selector batch (capi_select.hip): its context, its size and the device memory for the
+// call's records (record_bytes per window, checked against what the batch reserves).  0 or <0.
+struct dmvio_hip_pixel_selector_batch;
+int dmv_selector_batch_traces(dmvio_hip_pixel_selector_batch* b, size_t record_bytes, dmvio_hip_ctx** ctx, int* max_windows, char** d_records);
 
 // hypothesis-parallel trackNewCoarse: the element-wise fp64 sum over all ranks of a small HOST buffer, in place (set by dmvio_hip_tracker_set_comm /
 // _set_comm_callbacks in capi_comm.hip, next to the RCCL loader; used by dmvio_hip_tracker_track_new_coarse in capi.hip, which keeps the two accessors below because

@@ -25,6 +25,7 @@
 //   k_sel_write          thread per cell: decodes the keys into the status map, counts n3 / n4
 //   k_sel_scanA/B/C      raster-order scans of the map: the random sub-selection's running count (:250-264), then the compacted (u, v, type) list and the list
 //                        restricted to the window FullSystem::makeNewTraces walks (FullSystem.cpp:1653-1654)
+// Every kernel's body is a __device__ function (selAbsgradBody ... selWriteBody) that the batched forms of select_batch_kernels.hpp call as well.
 // Cells are stored in a PADDED walk order: cell (cx, cy) of the pot grid lives at ((by4*nb4x + bx4)*4 + sub3)*4 + sub2, cells the image clips away keep mask 0.
 #pragma once
 #include "common.h"
@@ -73,8 +74,8 @@ __device__ __forceinline__ void selKeyMax(unsigned long long* p, const unsigned 
 }
 
 // absSquaredGrad[0..2] of FrameHessian::makeImages (HessianBlocks.cpp:169-189), the arithmetic of k_abs_squared_grad; out = [level 0 | level 1 | level 2]
-__global__ void __launch_bounds__(256) k_sel_absgrad(const float* __restrict__ I0, const float* __restrict__ I1, const float* __restrict__ I2, const int w0, const int h0,
-                                                     const int w1, const int h1, const int w2, const int h2, const float* __restrict__ B, float* __restrict__ out) {
+__device__ __forceinline__ void selAbsgradBody(const float* __restrict__ I0, const float* __restrict__ I1, const float* __restrict__ I2, const int w0, const int h0,
+                                               const int w1, const int h1, const int w2, const int h2, const float* __restrict__ B, float* __restrict__ out) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int n0 = w0 * h0, n1 = w1 * h1, n2 = w2 * h2;
   if (gid >= n0 + n1 + n2) return;
@@ -95,10 +96,14 @@ __global__ void __launch_bounds__(256) k_sel_absgrad(const float* __restrict__ I
   }
   out[gid] = v;
 }
+__global__ void __launch_bounds__(256) k_sel_absgrad(const float* __restrict__ I0, const float* __restrict__ I1, const float* __restrict__ I2, const int w0, const int h0,
+                                                     const int w1, const int h1, const int w2, const int h2, const float* __restrict__ B, float* __restrict__ out) {
+  selAbsgradBody(I0, I1, I2, w0, h0, w1, h1, w2, h2, B, out);
+}
 
 // makeHists, first loop (:106-125) + computeHistQuantil (:82-91): one workgroup per 16x16 block
-__global__ void __launch_bounds__(256) k_sel_hist(const float* __restrict__ ag0, const int w, const int h, const int nbW, const float histCut, const float histAdd,
-                                                  float* __restrict__ ths) {
+__device__ __forceinline__ void selHistBody(const float* __restrict__ ag0, const int w, const int h, const int nbW, const float histCut, const float histAdd,
+                                            float* __restrict__ ths) {
   __shared__ int s_hist[50];
   const int bx = blockIdx.x % nbW, by = blockIdx.x / nbW;
   if (threadIdx.x < 50) s_hist[threadIdx.x] = 0;
@@ -122,9 +127,13 @@ __global__ void __launch_bounds__(256) k_sel_hist(const float* __restrict__ ag0,
     ths[blockIdx.x] = q + histAdd;
   }
 }
+__global__ void __launch_bounds__(256) k_sel_hist(const float* __restrict__ ag0, const int w, const int h, const int nbW, const float histCut, const float histAdd,
+                                                  float* __restrict__ ths) {
+  selHistBody(ag0, w, h, nbW, histCut, histAdd, ths);
+}
 
 // makeHists, second loop (:127-151): the sum order of the reference
-__global__ void __launch_bounds__(256) k_sel_smooth(const float* __restrict__ ths, const int w32, const int h32, float* __restrict__ thsSmoothed) {
+__device__ __forceinline__ void selSmoothBody(const float* __restrict__ ths, const int w32, const int h32, float* __restrict__ thsSmoothed) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= w32 * h32) return;
   const int x = i % w32, y = i / w32;
@@ -144,10 +153,13 @@ __global__ void __launch_bounds__(256) k_sel_smooth(const float* __restrict__ th
   num++; sum += ths[x + y * w32];
   thsSmoothed[i] = (sum / num) * (sum / num);
 }
+__global__ void __launch_bounds__(256) k_sel_smooth(const float* __restrict__ ths, const int w32, const int h32, float* __restrict__ thsSmoothed) {
+  selSmoothBody(ths, w32, h32, thsSmoothed);
+}
 
 // bit d of a cell's mask: some pixel of the cell passes the level-0 threshold and scores > 0 against direction d
-__global__ void __launch_bounds__(256) k_sel_cellmask(const float* __restrict__ I, const float* __restrict__ ag0, const float* __restrict__ thsS, const SelGeom G,
-                                                      unsigned int* __restrict__ mask) {
+__device__ __forceinline__ void selCellmaskBody(const float* __restrict__ I, const float* __restrict__ ag0, const float* __restrict__ thsS, const SelGeom& G,
+                                                unsigned int* __restrict__ mask) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   unsigned int m = 0;
   int c = -1;
@@ -177,6 +189,10 @@ __global__ void __launch_bounds__(256) k_sel_cellmask(const float* __restrict__ 
   } else if (m) {
     atomicOr(&mask[c], m);
   }
+}
+__global__ void __launch_bounds__(256) k_sel_cellmask(const float* __restrict__ I, const float* __restrict__ ag0, const float* __restrict__ thsS, const SelGeom G,
+                                                      unsigned int* __restrict__ mask) {
+  selCellmaskBody(I, ag0, thsS, G, mask);
 }
 
 // ---- two-level exclusive scans of two counters per element.  MODE_CELL: (cell selects, cell is mixed) over the padded walk order; MODE_NZ: (map != 0, -) in raster
@@ -223,8 +239,8 @@ __device__ __forceinline__ int2 selBlockScan(int2 v, int2* total) {
   return selAdd(v, before);
 }
 
-template <int MODE> __global__ void __launch_bounds__(256) k_sel_scanA(const SelScanArgs A, const unsigned int* __restrict__ mask, const unsigned char* __restrict__ map,
-                                                                        const int* __restrict__ rn, const unsigned char* __restrict__ pattern, int2* __restrict__ tiles) {
+template <int MODE> __device__ __forceinline__ void selScanABody(const SelScanArgs& A, const unsigned int* __restrict__ mask, const unsigned char* __restrict__ map,
+                                                                 const int* __restrict__ rn, const unsigned char* __restrict__ pattern, int2* __restrict__ tiles) {
   const int base = blockIdx.x * SEL_TILE + threadIdx.x * 4;
   int2 s = make_int2(0, 0);
 #pragma unroll
@@ -233,8 +249,12 @@ template <int MODE> __global__ void __launch_bounds__(256) k_sel_scanA(const Sel
   selBlockScan(s, &total);
   if (threadIdx.x == 0) tiles[blockIdx.x] = total;
 }
+template <int MODE> __global__ void __launch_bounds__(256) k_sel_scanA(const SelScanArgs A, const unsigned int* __restrict__ mask, const unsigned char* __restrict__ map,
+                                                                        const int* __restrict__ rn, const unsigned char* __restrict__ pattern, int2* __restrict__ tiles) {
+  selScanABody<MODE>(A, mask, map, rn, pattern, tiles);
+}
 // one workgroup: tile sums -> exclusive, in place; the totals into counters[slot_x] / [slot_y] (slot < 0: not stored)
-__global__ void __launch_bounds__(256) k_sel_scanB(int2* __restrict__ tiles, const int ntiles, int* __restrict__ counters, const int slot_x, const int slot_y) {
+__device__ __forceinline__ void selScanBBody(int2* __restrict__ tiles, const int ntiles, int* __restrict__ counters, const int slot_x, const int slot_y) {
   int2 carry = make_int2(0, 0);
   for (int base = 0; base < ntiles; base += 256) {
     const int i = base + threadIdx.x;
@@ -249,11 +269,14 @@ __global__ void __launch_bounds__(256) k_sel_scanB(int2* __restrict__ tiles, con
     if (slot_y >= 0) counters[slot_y] = carry.y;
   }
 }
+__global__ void __launch_bounds__(256) k_sel_scanB(int2* __restrict__ tiles, const int ntiles, int* __restrict__ counters, const int slot_x, const int slot_y) {
+  selScanBBody(tiles, ntiles, counters, slot_x, slot_y);
+}
 // CELL: n2ex[i] (and n2ex[n]); NZ: rn[i]; SURV: clears the dropped entries, writes the compacted lists
-template <int MODE> __global__ void __launch_bounds__(256) k_sel_scanC(const SelScanArgs A, const unsigned int* __restrict__ mask, unsigned char* __restrict__ map,
-                                                                        const int* __restrict__ rn, const unsigned char* __restrict__ pattern, const int2* __restrict__ tiles,
-                                                                        int* __restrict__ out, int* __restrict__ lu, int* __restrict__ lv, int* __restrict__ lt,
-                                                                        float* __restrict__ wu, float* __restrict__ wv) {
+template <int MODE> __device__ __forceinline__ void selScanCBody(const SelScanArgs& A, const unsigned int* __restrict__ mask, unsigned char* __restrict__ map,
+                                                                 const int* __restrict__ rn, const unsigned char* __restrict__ pattern, const int2* __restrict__ tiles,
+                                                                 int* __restrict__ out, int* __restrict__ lu, int* __restrict__ lv, int* __restrict__ lt,
+                                                                 float* __restrict__ wu, float* __restrict__ wv) {
   const int base = blockIdx.x * SEL_TILE + threadIdx.x * 4;
   int2 v[4];
   int2 s = make_int2(0, 0);
@@ -287,13 +310,19 @@ template <int MODE> __global__ void __launch_bounds__(256) k_sel_scanC(const Sel
     ex = selAdd(ex, v[k]);
   }
 }
+template <int MODE> __global__ void __launch_bounds__(256) k_sel_scanC(const SelScanArgs A, const unsigned int* __restrict__ mask, unsigned char* __restrict__ map,
+                                                                        const int* __restrict__ rn, const unsigned char* __restrict__ pattern, const int2* __restrict__ tiles,
+                                                                        int* __restrict__ out, int* __restrict__ lu, int* __restrict__ lv, int* __restrict__ lt,
+                                                                        float* __restrict__ wu, float* __restrict__ wv) {
+  selScanCBody<MODE>(A, mask, map, rn, pattern, tiles, out, lu, lv, lt, wu, wv);
+}
 
 // The recurrence itself, when a cell's selection depends on its direction: one wave, 64 cells per step, the next step's masks already in flight.  A group whose masks
 // are all 0 / 0xFFFF advances by its popcount.  In a mixed group every lane tests its cell against the current direction; the first cell that selects ends the
 // stretch (all cells up to it have their n2), n2 moves, the next direction comes out of a 128-entry window of randomPattern held in registers, and the rest of the group
 // is tested again: one round per selection, none per cell.  Bounded by the cell count; waits on nothing.
-__global__ void __launch_bounds__(64) k_sel_scan_exact(const unsigned int* __restrict__ mask, const int ncell, const unsigned char* __restrict__ pattern, const int npattern,
-                                                       int* __restrict__ n2ex, int* __restrict__ counters) {
+__device__ __forceinline__ void selScanExactBody(const unsigned int* __restrict__ mask, const int ncell, const unsigned char* __restrict__ pattern, const int npattern,
+                                                 int* __restrict__ n2ex, int* __restrict__ counters) {
   if (counters[SELC_MIXED] == 0) return;
   const int lane = threadIdx.x;
   int n2 = 0, wbase = 0;                                    // wave-uniform; window: lane j holds randomPattern[wbase + j] and [wbase + 64 + j]
@@ -345,6 +374,10 @@ __global__ void __launch_bounds__(64) k_sel_scan_exact(const unsigned int* __res
   }
   if (lane == 0) { n2ex[ncell] = n2; counters[SELC_N2] = n2; counters[SELC_EXACT] = 1; }
 }
+__global__ void __launch_bounds__(64) k_sel_scan_exact(const unsigned int* __restrict__ mask, const int ncell, const unsigned char* __restrict__ pattern, const int npattern,
+                                                       int* __restrict__ n2ex, int* __restrict__ counters) {
+  selScanExactBody(mask, ncell, pattern, npattern, n2ex, counters);
+}
 
 // MAX of the keys of the lanes that share a target (id >= 0; lanes with the same id lie next to each other: a wave is 64 consecutive pixels of a row): a segmented
 // scan, then one atomic per run instead of one per pixel
@@ -362,9 +395,9 @@ __device__ __forceinline__ void selRunMax(unsigned long long key, const int id, 
 }
 
 // thread per pixel: its candidacies at the three levels.  keys = [key2: ncell | key3: ncell/4 | key4: ncell/16]
-__global__ void __launch_bounds__(256) k_sel_pick(const float* __restrict__ I, const float* __restrict__ ag0, const float* __restrict__ ag1, const float* __restrict__ ag2,
-                                                  const float* __restrict__ thsS, const unsigned char* __restrict__ pattern, const int* __restrict__ n2ex, const SelGeom G,
-                                                  unsigned long long* __restrict__ keys) {
+__device__ __forceinline__ void selPickBody(const float* __restrict__ I, const float* __restrict__ ag0, const float* __restrict__ ag1, const float* __restrict__ ag2,
+                                            const float* __restrict__ thsS, const unsigned char* __restrict__ pattern, const int* __restrict__ n2ex, const SelGeom& G,
+                                            unsigned long long* __restrict__ keys) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   // a pixel competes at level 0 (its cell selects) or at level 1 (its 2pot block holds no level-0 point), never both: one target; level 2 is a second one
   unsigned long long kA = 0ull, kB = 0ull;
@@ -405,10 +438,15 @@ __global__ void __launch_bounds__(256) k_sel_pick(const float* __restrict__ I, c
   selRunMax(kA, idA, keys);
   if (__ballot(idB >= 0) != 0ull) selRunMax(kB, idB, keys);
 }
+__global__ void __launch_bounds__(256) k_sel_pick(const float* __restrict__ I, const float* __restrict__ ag0, const float* __restrict__ ag1, const float* __restrict__ ag2,
+                                                  const float* __restrict__ thsS, const unsigned char* __restrict__ pattern, const int* __restrict__ n2ex, const SelGeom G,
+                                                  unsigned long long* __restrict__ keys) {
+  selPickBody(I, ag0, ag1, ag2, thsS, pattern, n2ex, G, keys);
+}
 
 // thread per cell: keys -> status map (:429-449), n3 / n4
-__global__ void __launch_bounds__(1024) k_sel_write(const int* __restrict__ n2ex, const unsigned long long* __restrict__ key2, const unsigned long long* __restrict__ key3,
-                                                   const unsigned long long* __restrict__ key4, const SelGeom G, unsigned char* __restrict__ map, int* __restrict__ counters) {
+__device__ __forceinline__ void selWriteBody(const int* __restrict__ n2ex, const unsigned long long* __restrict__ key2, const unsigned long long* __restrict__ key3,
+                                             const unsigned long long* __restrict__ key4, const SelGeom& G, unsigned char* __restrict__ map, int* __restrict__ counters) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = c < G.ncell;
   const unsigned int pot = (unsigned int)G.pot, pp = pot * pot;
@@ -459,6 +497,10 @@ __global__ void __launch_bounds__(1024) k_sel_write(const int* __restrict__ n2ex
     if (s_n[0]) atomicAdd(&counters[SELC_N3], s_n[0]);
     if (s_n[1]) atomicAdd(&counters[SELC_N4], s_n[1]);
   }
+}
+__global__ void __launch_bounds__(1024) k_sel_write(const int* __restrict__ n2ex, const unsigned long long* __restrict__ key2, const unsigned long long* __restrict__ key3,
+                                                   const unsigned long long* __restrict__ key4, const SelGeom G, unsigned char* __restrict__ map, int* __restrict__ counters) {
+  selWriteBody(n2ex, key2, key3, key4, G, map, counters);
 }
 
 }  // namespace dmv

@@ -703,6 +703,47 @@ int dmvio_hip_pixel_selector_get_stats(dmvio_hip_pixel_selector* sel, long long 
 int dmvio_hip_immature_add_selected(dmvio_hip_immature* imm, int host_tag, int host_slot, dmvio_hip_pixel_selector* sel);
 
 /* ------------------------------------------------------------------------------------------------------------------------
+ * Pixel selection of W keyframes per call, for a caller that runs W sliding windows on one device (W selectors, W immature handles of ONE context):
+ *   PixelSelector::makeMaps        src/dso/FullSystem/PixelSelector2.cpp:158-307  -> dmvio_hip_pixel_selector_make_maps_batch
+ *     (with makeHists PixelSelector2.cpp:94-157 and select PixelSelector2.cpp:311-454)
+ *   FullSystem::makeNewTraces      src/dso/FullSystem/FullSystem.cpp:1640-1666    -> dmvio_hip_pixel_selector_make_maps_batch + dmvio_hip_immature_add_selected_batch
+ *     (its point loop, FullSystem.cpp:1653-1663, is dmvio_hip_immature_add_selected_batch)
+ * The contract is the one of batched activation: after a batched call every window's selector holds exactly what dmvio_hip_pixel_selector_make_maps leaves (status map,
+ * ths / thsSmoothed, the pass list with the counts of every pass, currentPotential, the compacted list, the makeNewTraces list, the stats), and every immature handle
+ * exactly what dmvio_hip_immature_add_selected leaves.  Single and batched calls may be mixed on a handle; every dmvio_hip_pixel_selector_get_* call works unchanged.
+ * The recursion of makeMaps stays on the host, per window, in rounds: round r runs one select pass for every window that is still recursing, each at its own
+ * potential, and the counters of all windows come back in one copy behind one stream wait; a call waits (largest pass count of its windows) + 1 times, whatever W is.
+ * A call runs under the context's lock on the context's stream.  It is refused as a whole, with a message, before anything is enqueued or any handle is changed:
+ * W < 0 or W > max_windows; a NULL batch, window array, selector or immature handle; a handle of another context; a selector twice in one make_maps_batch or an immature
+ * handle twice in one add_selected_batch (one selector may feed two immature handles); a slot or tag out of range; capacity exceeded in any window; a selector
+ * without a selection (add_selected_batch).  W == 0 returns 0. */
+typedef struct dmvio_hip_pixel_selector_batch dmvio_hip_pixel_selector_batch;
+dmvio_hip_pixel_selector_batch* dmvio_hip_pixel_selector_batch_create(dmvio_hip_ctx* ctx, int max_windows);
+void dmvio_hip_pixel_selector_batch_destroy(dmvio_hip_pixel_selector_batch* batch);
+
+typedef struct dmvio_hip_pixel_selector_window {
+  dmvio_hip_pixel_selector* sel;   /* one selector per window: currentPotential and settings are per FullSystem */
+  int slot;                        /* the new keyframe's resident frame */
+  const float* B_lut256;           /* may be NULL, per window */
+  float density;
+  int recursions_left;
+  float th_factor;
+  float* map_out_host;             /* may be NULL */
+  int n_selected;                  /* out: makeMaps' return value */
+  int counts3[3];                  /* out: (n2, n3, n4) of the last select */
+} dmvio_hip_pixel_selector_window;
+int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* batch, int W, dmvio_hip_pixel_selector_window* win);
+
+typedef struct dmvio_hip_new_traces_window {
+  dmvio_hip_immature* imm;
+  int host_tag, host_slot;
+  dmvio_hip_pixel_selector* sel;
+  int first;                       /* out: index of the first new point (imm's count when nothing was added) */
+} dmvio_hip_new_traces_window;
+/* one record upload and one launch sequence for all windows; like dmvio_hip_immature_add_selected it does not wait for the stream */
+int dmvio_hip_immature_add_selected_batch(dmvio_hip_pixel_selector_batch* batch, int W, dmvio_hip_new_traces_window* win);
+
+/* ------------------------------------------------------------------------------------------------------------------------
  * Point activation: which immature points become active points, chosen on the device.
  *   CoarseDistanceMap::makeK            src/dso/FullSystem/CoarseTracker.cpp:1086-1115  -> dmvio_hip_distance_map_tables_from_poses
  *   CoarseDistanceMap::makeDistanceMap  src/dso/FullSystem/CoarseTracker.cpp:931-967    -> dmvio_hip_distance_map_make

@@ -398,6 +398,31 @@ class PixelSelector {
   dmvio_hip_pixel_selector* s_;
 };
 
+/* PixelSelector::makeMaps and the point loop of FullSystem::makeNewTraces for several windows per call (dmvio_hip_pixel_selector_batch): W PixelSelector objects and W
+ * immature handles of one context.  Every window ends in the state its single calls leave; the results are read from the records and with the windows' own getters
+ * (PixelSelector::selection, currentPotential).  A call is refused as a whole (lastError()) before any window is touched. */
+class PixelSelectorBatch {
+ public:
+  PixelSelectorBatch(dmvio_hip_ctx* ctx, int maxWindows) : b_(dmvio_hip_pixel_selector_batch_create(ctx, maxWindows)) {}
+  ~PixelSelectorBatch() { if (b_) dmvio_hip_pixel_selector_batch_destroy(b_); }
+  PixelSelectorBatch(const PixelSelectorBatch&) = delete;
+  PixelSelectorBatch& operator=(const PixelSelectorBatch&) = delete;
+  bool valid() const { return b_ != nullptr; }
+  /* makeMaps (PixelSelector2.cpp:158-307) of every window: sel, slot, B_lut256, density, recursions_left, th_factor and map_out_host of each record; n_selected and
+   * counts3 are written */
+  bool makeMaps(std::vector<dmvio_hip_pixel_selector_window>& windows) {
+    return b_ && dmvio_hip_pixel_selector_make_maps_batch(b_, (int)windows.size(), windows.data()) == 0;
+  }
+  /* the point loop of makeNewTraces (FullSystem.cpp:1653-1663) of every window; `first` of each record is written */
+  bool makeNewTraces(std::vector<dmvio_hip_new_traces_window>& windows) {
+    return b_ && dmvio_hip_immature_add_selected_batch(b_, (int)windows.size(), windows.data()) == 0;
+  }
+  dmvio_hip_pixel_selector_batch* handle() const { return b_; }
+
+ private:
+  dmvio_hip_pixel_selector_batch* b_;
+};
+
 /* CoarseDistanceMap (FullSystem/CoarseTracker.h) at pyramid level 1 over dmvio_hip_distance_map_*: the map FullSystem::activatePointsMT tests its candidates against. */
 class DistanceMap {
  public:
