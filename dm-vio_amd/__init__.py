@@ -78,6 +78,17 @@ class NewTracesWindow(C.Structure):
     _fields_ = [("imm", C.c_void_p), ("host_tag", C.c_int), ("host_slot", C.c_int), ("sel", C.c_void_p), ("first", C.c_int)]
 
 
+class TraceTablesWindow(C.Structure):
+    """dmvio_hip_trace_tables_window (include/dmvio_hip.h): one window of dmvio_hip_immature_trace_batch."""
+    _fields_ = [("imm", C.c_void_p), ("new_slot", C.c_int), ("n_hosts", C.c_int), ("KRKi9", c_f), ("Kt3", c_f), ("aff2", c_f)]
+
+
+class TraceWindow(C.Structure):
+    """dmvio_hip_trace_window: one window of dmvio_hip_trace_new_coarse_batch."""
+    _fields_ = [("imm", C.c_void_p), ("new_slot", C.c_int), ("new_w2c7", C.c_double * 7), ("new_aff", C.c_double * 2), ("new_exposure", C.c_float), ("n_hosts", C.c_int),
+                ("host_c2w7", c_d), ("host_aff2", c_d), ("host_exposure", c_f), ("counts6", C.c_int * 6)]
+
+
 class ActivationWindow(C.Structure):
     """dmvio_hip_activation_window (include/dmvio_hip.h): one window of a batched activation call."""
     _fields_ = [("imm", C.c_void_p), ("dm", C.c_void_p), ("n_hosts", C.c_int), ("KRKi9", c_f), ("Kt3", c_f), ("n_active", C.c_int), ("active_host_tag", c_i),
@@ -157,6 +168,12 @@ def _sig(L):
     L.dmvio_hip_immature_trace.argtypes = [vp, C.c_int, C.c_int, c_f, c_f, c_f]
     L.dmvio_hip_immature_optimize.argtypes = [vp, C.c_int, c_i, c_d, c_d, c_f, c_d, C.c_char_p, C.c_int, c_i, c_f, c_i]
     L.dmvio_hip_trace_new_coarse.argtypes = [vp, C.c_int, c_d, c_d, C.c_float, C.c_int, c_d, c_d, c_f, c_d, c_i]
+    L.dmvio_hip_trace_batch_create.restype = vp
+    L.dmvio_hip_trace_batch_create.argtypes = [vp, C.c_int]
+    L.dmvio_hip_trace_batch_destroy.argtypes = [vp]
+    L.dmvio_hip_trace_batch_destroy.restype = None
+    L.dmvio_hip_immature_trace_batch.argtypes = [vp, C.c_int, C.POINTER(TraceTablesWindow)]
+    L.dmvio_hip_trace_new_coarse_batch.argtypes = [vp, C.c_int, C.POINTER(TraceWindow), c_d, C.c_int]
     L.dmvio_hip_ba_set_frame_state.argtypes = [vp, C.c_int, c_d]
     L.dmvio_hip_ba_marginalize_frame.argtypes = [vp, C.c_int, c_d, c_d]
     L.dmvio_hip_ba_get_marg_prior.argtypes = [vp, c_d, c_d]
@@ -1144,6 +1161,86 @@ def activate_points_batch(batch, windows, fxfycxcy):
     left = batch.remove_marked([w["imm"] for w in ws])
     return [dict(activated=recs[k], result=opt[k][0], idepth=opt[k][1], res_state=opt[k][2], order=sel[k][1], decision=sel[k][0], n_deleted=counts[k][1], n_points=left[k])
             for k in range(len(ws))]
+
+
+STATUS_NAMES = ("good", "oob", "outlier", "skipped", "badcondition", "uninitialized")
+
+
+class TraceBatchHip:
+    """ImmaturePoint::traceOn / FullSystem::traceNewCoarse for W windows per call (dmvio_hip_trace_batch): every window is one ImmaturePointsHip of this context traced
+    against its own new frame, and ends in the state its single call leaves, so get_state reads the results."""
+
+    def __init__(self, ctx, max_windows):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_trace_batch_create(ctx.p, int(max_windows))
+        if not p:
+            raise HipLibraryError("dmvio_hip_trace_batch_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.max_windows = int(max_windows)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_trace_batch_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _tables_windows(windows):
+        """the C records of a list of dicts (imm, new_slot, KRKi, Kt, aff) and the arrays that keep their memory alive"""
+        arr = (TraceTablesWindow * max(len(windows), 1))()
+        keep = []
+        for k, w in enumerate(windows):
+            KRKi = np.ascontiguousarray(w["KRKi"], dtype=np.float32).reshape(-1, 9); Kt = np.ascontiguousarray(w["Kt"], dtype=np.float32).reshape(-1, 3)
+            aff = np.ascontiguousarray(w["aff"], dtype=np.float32).reshape(-1, 2)
+            if len(Kt) != len(KRKi) or len(aff) != len(KRKi):
+                raise HipLibraryError("TraceBatchHip: KRKi, Kt and aff need one row per host")
+            r = arr[k]
+            r.imm = w["imm"].p if w.get("imm") is not None else None
+            r.new_slot = int(w["new_slot"]); r.n_hosts = len(KRKi); r.KRKi9 = _f(KRKi); r.Kt3 = _f(Kt); r.aff2 = _f(aff)
+            keep += [KRKi, Kt, aff]
+        return arr, keep
+
+    @staticmethod
+    def _coarse_windows(windows):
+        """the C records of a list of dicts (imm, new_slot, new_w2c7, host_c2w7[, new_aff, new_exposure, host_aff, host_exposure]) and the arrays behind them"""
+        arr = (TraceWindow * max(len(windows), 1))()
+        keep = []
+        for k, w in enumerate(windows):
+            c2w = np.ascontiguousarray(w["host_c2w7"], dtype=np.float64).reshape(-1, 7)
+            H = len(c2w)
+            ha = np.zeros((H, 2)) if w.get("host_aff") is None else np.ascontiguousarray(w["host_aff"], dtype=np.float64).reshape(-1, 2)
+            he = np.ones(H, np.float32) if w.get("host_exposure") is None else np.ascontiguousarray(w["host_exposure"], dtype=np.float32).reshape(-1)
+            if len(ha) != H or len(he) != H:
+                raise HipLibraryError("TraceBatchHip: host_aff and host_exposure need one entry per host")
+            r = arr[k]
+            r.imm = w["imm"].p if w.get("imm") is not None else None
+            r.new_slot = int(w["new_slot"])
+            r.new_w2c7[:] = [float(x) for x in np.asarray(w["new_w2c7"], dtype=np.float64).reshape(7)]
+            r.new_aff[:] = [float(x) for x in w.get("new_aff", (0.0, 0.0))]
+            r.new_exposure = float(w.get("new_exposure", 1.0)); r.n_hosts = H
+            r.host_c2w7 = _d(c2w); r.host_aff2 = _d(ha); r.host_exposure = _f(he)
+            keep += [c2w, ha, he]
+        return arr, keep
+
+    def trace(self, windows):
+        """traceOn for every window: dicts with imm, new_slot, KRKi, Kt, aff (one row per host).  Does not wait for the stream."""
+        arr, keep = self._tables_windows(windows)
+        _chk(self.L, self.L.dmvio_hip_immature_trace_batch(self.p, len(windows), arr), "immature_trace_batch")
+
+    def trace_new_coarse(self, windows, fxfycxcy, want_counts=True):
+        """traceNewCoarse for every window: dicts with imm, new_slot, new_w2c7, host_c2w7 and optionally new_aff ((0, 0)), new_exposure (1), host_aff, host_exposure (the
+        arguments of ImmaturePointsHip.traceNewCoarse) -> one count dict per window, behind the call's one wait; with want_counts=False the call does not wait and
+        returns None"""
+        arr, keep = self._coarse_windows(windows)
+        K = np.ascontiguousarray(fxfycxcy, dtype=np.float64)
+        _chk(self.L, self.L.dmvio_hip_trace_new_coarse_batch(self.p, len(windows), arr, _d(K), 1 if want_counts else 0), "trace_new_coarse_batch")
+        if not want_counts:
+            return None
+        return [dict(zip(STATUS_NAMES, [int(x) for x in arr[k].counts6])) for k in range(len(windows))]
 
 
 class PixelSelectorHip:

@@ -10,6 +10,78 @@
 
 using namespace dmv;
 
+// ---- W windows per call: the slab of dmvio_hip_trace_batch (immature_handle.h) ----
+static size_t tracePad(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t traceRecordBytes(int W) { return tracePad(sizeof(TraceWin) * (size_t)W); }
+static size_t traceTableBytes(int n_hosts) { return tracePad(sizeof(float) * 14 * (size_t)n_hosts); }
+static void traceBatchFree(dmvio_hip_trace_batch* b) {
+  for (int k = 0; k < 2; k++) {
+    if (b->uploaded[k]) hipEventDestroy(b->uploaded[k]);
+    if (b->h_slab[k]) hipHostFree(b->h_slab[k]);
+  }
+  if (b->h_counts) hipHostFree(b->h_counts);
+  if (b->d_slab) hipFree(b->d_slab);
+  delete b;
+}
+static int traceBatchHead(dmvio_hip_trace_batch* b, int W, const void* arr, const char* what) {
+  if (!b) return failmsg(std::string(what) + ": null batch handle");
+  if (W < 0 || W > b->max_windows) return failmsg(std::string(what) + ": W is negative or larger than the batch's max_windows");
+  if (W > 0 && !arr) return failmsg(std::string(what) + ": the window array is NULL");
+  return 0;
+}
+// The body of both batched calls; the caller holds the context's mutex.  Every refusal comes before anything is enqueued or any handle touched.  counts: NULL, or 6 ints per
+// window; then the histogram follows the trace and the stream is waited for once.
+static int traceBatchLocked(dmvio_hip_trace_batch* b, int W, const dmvio_hip_trace_tables_window* win, int* counts, const char* what) {
+  dmvio_hip_ctx* c = b->ctx;
+  const std::string pre = std::string(what) + ": ";
+  int nmax = 0;
+  for (int k = 0; k < W; k++) {
+    const dmvio_hip_trace_tables_window& V = win[k];
+    if (!V.imm) return failmsg(pre + "an immature handle is NULL");
+    if (V.imm->ctx != c) return failmsg(pre + "an immature handle belongs to another context");
+    for (int j = 0; j < k; j++) if (win[j].imm == V.imm) return failmsg(pre + "an immature handle appears twice");
+    if (V.new_slot < 0 || V.new_slot >= c->n_slots) return failmsg(pre + "frame slot out of range");
+    if (V.n_hosts < 1 || V.n_hosts > IMM_MAX_HOSTS) return failmsg(pre + "n_hosts out of range (1..64)");
+    if (!V.KRKi9 || !V.Kt3 || !V.aff2) return failmsg(pre + "a table is NULL");
+    if (V.imm->n > 0 && V.imm->max_tag >= V.n_hosts) return failmsg(pre + "a point's host_tag has no table row (host_tag >= n_hosts)");
+    nmax = std::max(nmax, V.imm->n);
+  }
+  for (int k = 0; k < W; k++) if (int r = dmv_ensure_row_major_locked(c, win[k].new_slot)) return r;
+  if (counts) memset(counts, 0, sizeof(int) * 6 * (size_t)W);
+  if (nmax == 0) return 0;   // every window is empty: nothing to launch
+  const int mi = b->next;
+  if (b->in_flight[mi]) { HIPCHK(hipEventSynchronize(b->uploaded[mi])); b->in_flight[mi] = false; }   // this mirror's last upload, two calls ago: not the stream
+  char* H = b->h_slab[mi];
+  size_t off = traceRecordBytes(W);
+  for (int k = 0; k < W; k++) {
+    const dmvio_hip_trace_tables_window& V = win[k];
+    dmvio_hip_immature* m = V.imm;
+    const size_t nh = V.n_hosts;
+    float* t = reinterpret_cast<float*>(H + off);
+    const float* dt = reinterpret_cast<const float*>(b->d_slab + off);
+    memcpy(t, V.KRKi9, sizeof(float) * 9 * nh); memcpy(t + 9 * nh, V.Kt3, sizeof(float) * 3 * nh); memcpy(t + 12 * nh, V.aff2, sizeof(float) * 2 * nh);
+    off += traceTableBytes(V.n_hosts);
+    m->P.n = m->n;
+    TraceWin r{};
+    r.I = c->levelPtr(V.new_slot, 0); r.P = m->P; r.S = m->S;
+    r.KRKi = dt; r.Kt = dt + 9 * nh; r.aff = dt + 12 * nh;
+    r.w = c->w; r.h = c->h;
+    memcpy(H + sizeof(TraceWin) * (size_t)k, &r, sizeof(r));
+  }
+  HIPCHK(hipMemcpyAsync(b->d_slab, H, off, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipEventRecord(b->uploaded[mi], c->stream));
+  b->in_flight[mi] = true; b->next = mi ^ 1;
+  const TraceWin* D = reinterpret_cast<const TraceWin*>(b->d_slab);
+  hipLaunchKernelGGL(k_immature_trace_b, dim3((nmax + 3) / 4, W), dim3(256), 0, c->stream, D);
+  if (counts) hipLaunchKernelGGL(k_status_hist_b, dim3(W), dim3(1024), 0, c->stream, D, b->h_counts);
+  HIPCHK(hipGetLastError());
+  if (counts) {
+    HIPCHK(hipStreamSynchronize(c->stream));   // the call's one wait
+    memcpy(counts, b->h_counts, sizeof(int) * 6 * (size_t)W);
+  }
+  return 0;
+}
+
 extern "C" {
 
 dmvio_hip_immature* dmvio_hip_immature_create(dmvio_hip_ctx* ctx, int capacity) {
@@ -266,6 +338,78 @@ int dmvio_hip_trace_new_coarse(dmvio_hip_immature* m, int new_slot, const double
       for (int k = 0; k < 6; k++) counts6[k] = m->h_counts[k];
     }
   }
+  return 0;
+}
+
+// ---- W windows per call ----
+dmvio_hip_trace_batch* dmvio_hip_trace_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
+  if (!ctx) { failmsg("trace_batch_create: null context"); return nullptr; }
+  if (max_windows < 1 || max_windows > 65535) { failmsg("trace_batch_create: max_windows out of range (1..65535)"); return nullptr; }
+  HIPCHKP(hipSetDevice(ctx->device));
+  dmvio_hip_trace_batch* b = new dmvio_hip_trace_batch();
+  b->ctx = ctx; b->max_windows = max_windows;
+  b->slab_bytes = traceRecordBytes(max_windows) + (size_t)max_windows * traceTableBytes(IMM_MAX_HOSTS);
+  bool ok = hipMalloc((void**)&b->d_slab, b->slab_bytes) == hipSuccess && hipHostMalloc((void**)&b->h_counts, sizeof(int) * 6 * (size_t)max_windows, hipHostMallocDefault) == hipSuccess;
+  for (int k = 0; k < 2 && ok; k++)
+    ok = hipHostMalloc((void**)&b->h_slab[k], b->slab_bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&b->uploaded[k], hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    failmsg("trace_batch_create: allocation failed");
+    traceBatchFree(b);
+    return nullptr;
+  }
+  return b;
+}
+void dmvio_hip_trace_batch_destroy(dmvio_hip_trace_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
+  traceBatchFree(b);
+}
+
+// traceOn of every point of every window: as dmvio_hip_immature_trace it does not wait
+int dmvio_hip_immature_trace_batch(dmvio_hip_trace_batch* b, int W, const dmvio_hip_trace_tables_window* win) {
+  if (int r = traceBatchHead(b, W, win, "immature_trace_batch")) return r;
+  if (W == 0) return 0;
+  HIPCHK(hipSetDevice(b->ctx->device));
+  std::lock_guard<std::mutex> lk(b->ctx->mu);
+  return traceBatchLocked(b, W, win, nullptr, "immature_trace_batch");
+}
+
+// FullSystem::traceNewCoarse (FullSystem.cpp:541-584) for every window: the tables of each window from its poses by the single call's host functions, one trace launch, and
+// with want_counts one histogram launch and the call's only wait
+int dmvio_hip_trace_new_coarse_batch(dmvio_hip_trace_batch* b, int W, dmvio_hip_trace_window* win, const double fxfycxcy[4], int want_counts) {
+  if (int r = traceBatchHead(b, W, win, "trace_new_coarse_batch")) return r;
+  if (!fxfycxcy) return failmsg("trace_new_coarse_batch: fxfycxcy is NULL");
+  if (W == 0) return 0;
+  size_t rows = 0;
+  for (int k = 0; k < W; k++) {
+    const dmvio_hip_trace_window& V = win[k];
+    if (V.n_hosts < 1 || V.n_hosts > IMM_MAX_HOSTS) return failmsg("trace_new_coarse_batch: n_hosts out of range (1..64)");
+    if (!V.host_c2w7 || !V.host_aff2 || !V.host_exposure) return failmsg("trace_new_coarse_batch: a pose, affine or exposure array is NULL");
+    rows += V.n_hosts;
+  }
+  std::vector<float> tab(14 * rows);
+  std::vector<dmvio_hip_trace_tables_window> tw(W);
+  const float K[9] = {(float)fxfycxcy[0], 0, (float)fxfycxcy[2], 0, (float)fxfycxcy[1], (float)fxfycxcy[3], 0, 0, 1};
+  float* t = tab.data();
+  for (int k = 0; k < W; k++) {
+    const dmvio_hip_trace_window& V = win[k];
+    float *KRKi = t, *Kt = t + 9 * V.n_hosts, *aff = t + 12 * V.n_hosts;
+    t += 14 * V.n_hosts;
+    dmv_host_tables(K, fxfycxcy, V.new_w2c7, V.n_hosts, V.host_c2w7, KRKi, Kt);
+    for (int hI = 0; hI < V.n_hosts; hI++) {
+      double ab[2];
+      affFromTo(V.host_exposure[hI], V.new_exposure, V.host_aff2[2 * hI], V.host_aff2[2 * hI + 1], V.new_aff[0], V.new_aff[1], ab);
+      aff[2 * hI] = (float)ab[0]; aff[2 * hI + 1] = (float)ab[1];
+    }
+    tw[k].imm = V.imm; tw[k].new_slot = V.new_slot; tw[k].n_hosts = V.n_hosts; tw[k].KRKi9 = KRKi; tw[k].Kt3 = Kt; tw[k].aff2 = aff;
+  }
+  HIPCHK(hipSetDevice(b->ctx->device));
+  std::lock_guard<std::mutex> lk(b->ctx->mu);
+  if (!want_counts) return traceBatchLocked(b, W, tw.data(), nullptr, "trace_new_coarse_batch");
+  std::vector<int> counts(6 * (size_t)W);
+  if (int r = traceBatchLocked(b, W, tw.data(), counts.data(), "trace_new_coarse_batch")) return r;
+  for (int k = 0; k < W; k++) memcpy(win[k].counts6, &counts[6 * (size_t)k], sizeof(int) * 6);
   return 0;
 }
 

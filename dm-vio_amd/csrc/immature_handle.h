@@ -59,6 +59,21 @@ static int dmv_immature_alloc_pts(dmvio_hip_immature* m, dmv::ImmaturePts& P) {
          ialloc(m, &P.lastTracePixelInterval, c) || ialloc(m, &P.lastTraceStatus, c) || ialloc(m, &P.my_type, c);
 }
 
+// traceNewCoarse of W windows per call (capi_immature.hip).  One slab per call: [TraceWin x W | every window's table rows KRKi 9H, Kt 3H, aff 2H], filled in a pinned
+// mirror and uploaded in one copy.  A call that does not wait leaves that copy in flight, so the batch alternates between two mirrors and records an event behind each
+// upload; before a mirror is filled again only its own event is waited for (the upload before the previous one), never the stream.
+struct dmvio_hip_trace_batch {
+  dmvio_hip_ctx* ctx = nullptr;
+  int max_windows = 0;
+  size_t slab_bytes = 0;       // max_windows records + max_windows x 64 x 14 floats
+  char* d_slab = nullptr;
+  char* h_slab[2] = {nullptr, nullptr};      // pinned
+  hipEvent_t uploaded[2] = {nullptr, nullptr};
+  bool in_flight[2] = {false, false};
+  int next = 0;                // the mirror the next call fills
+  int* h_counts = nullptr;     // pinned, 6 x max_windows: k_status_hist_b stores straight into it
+};
+
 // per-host tables hostToNew: KRKi = Kleft * R * K0^-1, Kt = Kleft * t (floats, the reference's product order; FullSystem.cpp:548-552 with Kleft = K0,
 // CoarseTracker.cpp:949-951 with Kleft = K[1]); K0 from fxfycxcy, its inverse as Eigen's 3x3 cofactor inverse
 void dmv_host_tables(const float Kleft[9], const double fxfycxcy[4], const double new_w2c7[7], int n_hosts, const double* host_c2w7, float* KRKi9, float* Kt3);

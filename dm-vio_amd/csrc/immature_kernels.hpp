@@ -15,7 +15,7 @@ namespace dmv {
 
 // status histogram of FullSystem::traceNewCoarse's printout / bookkeeping (FullSystem.cpp:562-583): one workgroup, counts stored straight into
 // pinned host memory (out6)
-__global__ void __launch_bounds__(1024) k_status_hist(const int* __restrict__ status, const int n, int* __restrict__ out6) {
+__device__ __forceinline__ void statusHistBody(const int* __restrict__ status, const int n, int* __restrict__ out6) {
   __shared__ int s_c[6];
   if (threadIdx.x < 6) s_c[threadIdx.x] = 0;
   __syncthreads();
@@ -34,6 +34,7 @@ __global__ void __launch_bounds__(1024) k_status_hist(const int* __restrict__ st
   __syncthreads();
   if (threadIdx.x < 6) out6[threadIdx.x] = s_c[threadIdx.x];
 }
+__global__ void __launch_bounds__(1024) k_status_hist(const int* __restrict__ status, const int n, int* __restrict__ out6) { statusHistBody(status, n, out6); }
 
 struct TraceTables { const float *KRKi /* H x 9 */, *Kt /* H x 3 */, *aff /* H x 2 */; };
 // the same tables by value, for windows of up to 16 host keyframes: they travel as kernel arguments (896 B) — no upload, no staging buffer
@@ -171,12 +172,11 @@ __device__ __forceinline__ float waveMin(float v) {
   return v;
 }
 
-// traceOn: one wavefront per point (4 points per 256-thread workgroup); TT = TraceTables (device memory) or TraceTablesArg (kernel arguments)
+// traceOn of point i by one wavefront; TT = TraceTables (device memory) or TraceTablesArg (kernel arguments).  No barrier inside: a wave whose point does not exist
+// returns on its own.
 template <class TT>
-__global__ void __launch_bounds__(256) k_immature_trace(const float* __restrict__ I, const int w, const int h, const ImmaturePts P, const TT T,
-                                                         const ImmatureSettings S) {
+__device__ __forceinline__ void immTraceBody(const float* __restrict__ I, const int w, const int h, const ImmaturePts& P, const TT& T, const ImmatureSettings& S, const int i) {
   const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= P.n) return;
   int status = P.lastTraceStatus[i];
   if (status == IPS_OOB) return;
@@ -376,6 +376,35 @@ __global__ void __launch_bounds__(256) k_immature_trace(const float* __restrict_
     P.quality[i] = quality;
     if (writeInterval) { P.idepth_min[i] = idepth_min; P.idepth_max[i] = idepth_max; }
   }
+}
+// one wavefront per point (4 points per 256-thread workgroup)
+template <class TT>
+__global__ void __launch_bounds__(256) k_immature_trace(const float* __restrict__ I, const int w, const int h, const ImmaturePts P, const TT T,
+                                                         const ImmatureSettings S) {
+  immTraceBody(I, w, h, P, T, S, blockIdx.x * 4 + (threadIdx.x >> 6));
+}
+
+// ---- traceNewCoarse for W windows per launch (dmvio_hip_immature_trace_batch, dmvio_hip_trace_new_coarse_batch): window = blockIdx.y, grid.x = the largest point count
+// of the call in workgroups of 4 points; the bodies are the single call's, so a handle of a batch holds the bytes its single call would have left
+struct TraceWin {
+  const float* I;                  // level 0 of the window's new frame
+  ImmaturePts P;                   // n = the handle's count; 0: no work
+  ImmatureSettings S;
+  const float *KRKi, *Kt, *aff;    // the window's rows in the call's slab (n_hosts x 9 | x 3 | x 2)
+  int w, h;
+};
+__global__ void __launch_bounds__(256) k_immature_trace_b(const TraceWin* __restrict__ wins) {
+  const TraceWin& V = wins[blockIdx.y];
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= V.P.n) return;
+  TraceTables T;
+  T.KRKi = immGl(V.KRKi); T.Kt = immGl(V.Kt); T.aff = immGl(V.aff);
+  immTraceBody(immGl(V.I), V.w, V.h, immPts(V.P), T, V.S, i);
+}
+// one workgroup per window; out6: six counts per window (an empty window: six zeros)
+__global__ void __launch_bounds__(1024) k_status_hist_b(const TraceWin* __restrict__ wins, int* __restrict__ out6) {
+  const TraceWin& V = wins[blockIdx.x];
+  statusHistBody(immGl(V.P.lastTraceStatus), V.P.n, out6 + 6 * blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -635,6 +635,50 @@ int dmvio_hip_immature_optimize(dmvio_hip_immature* imm, int F, const int* frame
 int dmvio_hip_trace_new_coarse(dmvio_hip_immature* imm, int new_slot, const double new_w2c7[7], const double new_aff[2], float new_exposure, int n_hosts,
                                const double* host_c2w7, const double* host_aff2, const float* host_exposure, const double fxfycxcy[4], int counts6[6]);
 
+/* Tracing of W sliding windows per call, for a caller that runs W windows on one device (W immature handles of ONE context, each with its own new frame):
+ *   FullSystem::traceNewCoarse     src/dso/FullSystem/FullSystem.cpp:541-584    -> dmvio_hip_trace_new_coarse_batch
+ *   ImmaturePoint::traceOn         src/dso/FullSystem/ImmaturePoint.cpp:76-437  -> dmvio_hip_immature_trace_batch
+ * traceNewCoarse runs for every frame, keyframe or not; a batch is one upload, one trace launch and, when the counts are wanted, one histogram launch and one wait.
+ * The contract is the one of the activation and selector batches: every window ends holding exactly the bytes its single call leaves (idepth_min / idepth_max, quality,
+ * lastTraceUV, lastTracePixelInterval, lastTraceStatus, and the counts), single and batched calls may be mixed on a handle and every getter works unchanged.  A call runs
+ * under the context's lock on the context's stream.  dmvio_hip_immature_trace_batch does not wait for the stream, nor does dmvio_hip_trace_new_coarse_batch with
+ * want_counts == 0; with want_counts != 0 it waits exactly once, whatever W is.  Two windows may name the same new_slot (the frame is only read).  A window whose handle
+ * holds no points gets no work and zero counts; if every window is empty nothing is launched.  The pose-level entry builds each window's tables with the host functions of
+ * dmvio_hip_trace_new_coarse, so they carry the same bits.
+ * A call is refused as a whole, with a message, before anything is enqueued or any handle touched: W < 0 or W > max_windows; a NULL batch, window array, handle, table or
+ * pose array; a handle of another context; the same immature handle twice; new_slot out of range; n_hosts < 1 or > 64; a point whose host_tag >= the window's n_hosts;
+ * fxfycxcy NULL.  W == 0 returns 0. */
+typedef struct dmvio_hip_trace_batch dmvio_hip_trace_batch;
+/* owns the device slab of the per-window records and table rows, its pinned mirrors and the pinned counters; max_windows >= 1 */
+dmvio_hip_trace_batch* dmvio_hip_trace_batch_create(dmvio_hip_ctx* ctx, int max_windows);
+void dmvio_hip_trace_batch_destroy(dmvio_hip_trace_batch* batch);
+
+/* as dmvio_hip_immature_trace, one window */
+typedef struct dmvio_hip_trace_tables_window {
+  dmvio_hip_immature* imm;
+  int new_slot;
+  int n_hosts;
+  const float* KRKi9;
+  const float* Kt3;
+  const float* aff2;
+} dmvio_hip_trace_tables_window;
+int dmvio_hip_immature_trace_batch(dmvio_hip_trace_batch* batch, int W, const dmvio_hip_trace_tables_window* win);
+
+/* as dmvio_hip_trace_new_coarse, one window */
+typedef struct dmvio_hip_trace_window {
+  dmvio_hip_immature* imm;
+  int new_slot;
+  double new_w2c7[7];
+  double new_aff[2];
+  float new_exposure;
+  int n_hosts;
+  const double* host_c2w7;
+  const double* host_aff2;
+  const float* host_exposure;
+  int counts6[6];                 /* out, written only when want_counts != 0 */
+} dmvio_hip_trace_window;
+int dmvio_hip_trace_new_coarse_batch(dmvio_hip_trace_batch* batch, int W, dmvio_hip_trace_window* win, const double fxfycxcy[4], int want_counts);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * Initializer: CoarseInitializer::calcResAndGS  src/dso/FullSystem/CoarseInitializer.cpp:331-624.
  * The handle holds the point set of one pyramid level (struct Pnt, CoarseInitializer.h:44-83); every call evaluates the 8-pixel

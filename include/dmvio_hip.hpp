@@ -542,5 +542,28 @@ class ActivationBatch {
   dmvio_hip_activation_batch* b_;
 };
 
+/* FullSystem::traceNewCoarse for several windows per call (dmvio_hip_trace_batch): W ImmaturePoints of one context, each against its own new frame.  Every window ends in
+ * the state its single call leaves; the points are read with the windows' own getters.  A call is refused as a whole (lastError()) before any window is touched. */
+class TraceBatch {
+ public:
+  TraceBatch(dmvio_hip_ctx* ctx, int maxWindows) : b_(dmvio_hip_trace_batch_create(ctx, maxWindows)) {}
+  ~TraceBatch() { if (b_) dmvio_hip_trace_batch_destroy(b_); }
+  TraceBatch(const TraceBatch&) = delete;
+  TraceBatch& operator=(const TraceBatch&) = delete;
+  bool valid() const { return b_ != nullptr; }
+  /* ImmaturePoint::traceOn (ImmaturePoint.cpp:76-437) of every window's points with the caller's tables; does not wait for the stream */
+  bool trace(const std::vector<dmvio_hip_trace_tables_window>& windows) {
+    return b_ && dmvio_hip_immature_trace_batch(b_, (int)windows.size(), windows.data()) == 0;
+  }
+  /* traceNewCoarse (FullSystem.cpp:541-584) of every window from its poses; wantCounts: counts6 of each record is written behind the call's one wait, otherwise the
+   * call does not wait */
+  bool traceNewCoarse(std::vector<dmvio_hip_trace_window>& windows, const double fxfycxcy[4], bool wantCounts = true) {
+    return b_ && dmvio_hip_trace_new_coarse_batch(b_, (int)windows.size(), windows.data(), fxfycxcy, wantCounts ? 1 : 0) == 0;
+  }
+
+ private:
+  dmvio_hip_trace_batch* b_;
+};
+
 }  // namespace dmvio_hip
 #endif
