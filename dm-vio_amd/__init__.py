@@ -764,7 +764,8 @@ class CoarseInitializerHip:
         self.n = len(u)
 
     def calcResAndGS(self, lvl, first_slot, new_slot, Ki9, fxfycxcy_lvl, refToNew7, aff_ab, idepth_new, alphaW=150 * 150, alphaK=2.5 * 2.5, couplingWeight=1.0,
-                     priorY=0.0, priorX=0.0):
+                     priorY=0.0, priorX=0.0, per_point=True):
+        """per_point=False passes NULL for the five per-point outputs (the C ABI then skips their download); the returned dict holds the reductions only."""
         n = self.n
         o = dict(H=np.zeros((8, 8), np.float32), b=np.zeros(8, np.float32), Hsc=np.zeros((8, 8), np.float32), bsc=np.zeros(8, np.float32), res3=np.zeros(3, np.float32),
                  energy_new=np.zeros((n, 2), np.float32), isGood_new=np.zeros(n, np.uint8), maxstep=np.zeros(n, np.float32), lastHessian_new=np.zeros(n, np.float32),
@@ -772,11 +773,14 @@ class CoarseInitializerHip:
         c_u8 = C.POINTER(C.c_ubyte)
         idn = np.ascontiguousarray(idepth_new, dtype=np.float32)
         K = np.ascontiguousarray(fxfycxcy_lvl, dtype=np.float32)
+        pp = [_f(o["energy_new"]), o["isGood_new"].ctypes.data_as(c_u8), _f(o["maxstep"]), _f(o["lastHessian_new"]), _f(o["JbBuffer_new"])] if per_point else [None] * 5
         _chk(self.L, self.L.dmvio_hip_initializer_calc_res_and_gs(self.p, lvl, first_slot, new_slot, _d(np.ascontiguousarray(Ki9, dtype=np.float64)), _f(K),
                                                                   _d(np.ascontiguousarray(refToNew7, dtype=np.float64)), _d(np.array(aff_ab, dtype=np.float64)), _f(idn),
                                                                   alphaW, alphaK, couplingWeight, priorY, priorX, _f(o["H"]), _f(o["b"]), _f(o["Hsc"]), _f(o["bsc"]),
-                                                                  _f(o["res3"]), _f(o["energy_new"]), o["isGood_new"].ctypes.data_as(c_u8), _f(o["maxstep"]),
-                                                                  _f(o["lastHessian_new"]), _f(o["JbBuffer_new"])), "initializer_calc_res_and_gs")
+                                                                  _f(o["res3"]), *pp), "initializer_calc_res_and_gs")
+        if not per_point:
+            for k in ("energy_new", "isGood_new", "maxstep", "lastHessian_new", "JbBuffer_new"):
+                del o[k]
         return o
 
 

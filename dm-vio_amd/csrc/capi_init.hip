@@ -2,6 +2,7 @@
 #include <vector>
 #include <cmath>
 #include <cstring>
+#include <cstdio>
 #include "../../include/dmvio_hip.h"
 #include "internal.h"
 #include "lie_dev.h"
@@ -96,8 +97,23 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   std::lock_guard<std::mutex> lk(c->mu);
   if (!Ki9 || !fxfycxcy_lvl || !refToNew7 || !aff_ab || !idepth_new || !H_out64 || !b_out8 || !H_sc64 || !b_sc8 || !res3) return failmsg("initializer_calc: null argument");
   if (lvl < 0 || lvl >= c->levels || first_slot < 0 || first_slot >= c->n_slots || new_slot < 0 || new_slot >= c->n_slots) return failmsg("initializer_calc: level / slot out of range");
-  if (lvl == 0) { if (int r = dmv_ensure_row_major_locked(c, first_slot)) return r; if (int r = dmv_ensure_row_major_locked(c, new_slot)) return r; }
   const int n = m->n;
+  {
+    // k_init_partial reads the first image at (u + dx, v + dy), dx, dy in [-2, 2], and one pixel right / below, without a test: CoarseInitializer::setFirst never
+    // places a point where that leaves the level, and a point set that does is refused here (the staging slab still holds u, v and isGood of the last set_points)
+    const size_t P = padn(n);
+    const float *u = m->h_in, *v = m->h_in + P;
+    const unsigned char* good = reinterpret_cast<const unsigned char*>(m->h_in + 7 * P);
+    const float umax = (float)(c->wl[lvl] - 3), vmax = (float)(c->hl[lvl] - 3);
+    for (int i = 0; i < n; i++)
+      if (good[i] && !(u[i] >= 2.0f && u[i] < umax && v[i] >= 2.0f && v[i] < vmax)) {
+        char msg[192];
+        snprintf(msg, sizeof(msg), "initializer_calc: good point %d at (%g, %g) outside [2, %d) x [2, %d) of level %d", i, (double)u[i], (double)v[i], c->wl[lvl] - 3,
+                 c->hl[lvl] - 3, lvl);
+        return failmsg(msg);
+      }
+  }
+  if (lvl == 0) { if (int r = dmv_ensure_row_major_locked(c, first_slot)) return r; if (int r = dmv_ensure_row_major_locked(c, new_slot)) return r; }
   hipStream_t s = c->stream;
   const Pose T = poseFrom7(refToNew7);
   InitArgs A;
@@ -138,9 +154,15 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   m->upload_pending = false;
   if (energy_new2) memcpy(energy_new2, m->h_res, sizeof(float) * 2 * n);
   if (maxstep) memcpy(maxstep, m->h_res + 2 * PN, sizeof(float) * n);
-  if (lastHessian_new) memcpy(lastHessian_new, m->h_res + 3 * PN, sizeof(float) * n);
   if (JbBuffer_new10) memcpy(JbBuffer_new10, m->h_res + 4 * PN, sizeof(float) * 10 * n);
   if (isGood_new) memcpy(isGood_new, m->h_res + 14 * PN, n);
+  if (lastHessian_new) {
+    // written for accepted points only, like the reference's member (CoarseInitializer.cpp:560): the kernel leaves the other entries of the slab as an earlier call,
+    // laid out for another n, left them, so they are not the caller's to see
+    const float* lh = m->h_res + 3 * PN;
+    const unsigned char* acc = reinterpret_cast<const unsigned char*>(m->h_res + 14 * PN);
+    for (int i = 0; i < n; i++) if (acc[i]) lastHessian_new[i] = lh[i];
+  }
   // unpack the two upper triangles, then the tail of calcResAndGS (:582-613)
   float M[2][9][9];
   for (int w = 0; w < 2; w++) {

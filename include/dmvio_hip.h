@@ -685,7 +685,11 @@ int dmvio_hip_trace_new_coarse_batch(dmvio_hip_trace_batch* batch, int W, dmvio_
  * pattern of all points at (refToNew, aff) for the current idepth_new and returns the 8x8 system H_out, b_out, its Schur part
  * H_out_sc, b_out_sc (row-major floats, Mat88f / Vec8f), res3 = (energy, alphaEnergy, num) and — for non-NULL pointers — the
  * per-point fields calcResAndGS writes (energy_new[2n], isGood_new, maxstep, lastHessian_new, JbBuffer_new[10n]).
- * Ki9: the level's inverse intrinsics (Mat33 Ki[lvl], row-major double); fxfycxcy_lvl: fx[lvl] .. cy[lvl]; aff_ab = (a, b) of refToNew_aff. */
+ * Ki9: the level's inverse intrinsics (Mat33 Ki[lvl], row-major double); fxfycxcy_lvl: fx[lvl] .. cy[lvl]; aff_ab = (a, b) of refToNew_aff.
+ * Point positions: the first image is read at (u + dx, v + dy), |dx|, |dy| <= 2, bilinearly and without a border test, as in the reference, whose setFirst
+ * keeps every point well inside.  calc_res_and_gs therefore refuses (returns non-zero, dmvio_hip_last_error names the point) a set with a good point outside
+ * [2, w_lvl - 3) x [2, h_lvl - 3) of the level it is asked to evaluate, before anything is launched or a slot is touched.  Points that are not good may lie anywhere.
+ * lastHessian_new is written for accepted points (isGood_new != 0) only, as the reference writes its member; the caller's other entries keep their values. */
 typedef struct dmvio_hip_initializer dmvio_hip_initializer;
 dmvio_hip_initializer* dmvio_hip_initializer_create(dmvio_hip_ctx* ctx, int capacity);
 void dmvio_hip_initializer_destroy(dmvio_hip_initializer* ini);

@@ -33,11 +33,13 @@ extern "C" {
 
 // Point arrays mirror struct Pnt (CoarseInitializer.h:44-83).  Outputs: H_out / H_sc 8x8 row-major, b_out / b_sc 8, res3 = (E.A, alphaEnergy, E.num),
 // per point: energy_new[2n], isGood_new[n], maxstep[n], lastHessian_new[n] (only written for good points), JbBuffer_new[10n].
-void orc_init_calc_res_and_gs(const float* dI_ref, const float* dI_new, int wl, int hl, const double* Ki9, float fxl, float fyl, float cxl, float cyl,
+// rows (may be NULL): the residual rows that entered H, rows[n][8][9] = per pattern index the eight dp values and r; all zero for points that are not accepted.
+void orc_init_calc_res_and_gs_rows(const float* dI_ref, const float* dI_new, int wl, int hl, const double* Ki9, float fxl, float fyl, float cxl, float cyl,
                               const double* refToNew7, double aff_a, double aff_b, int npts, const float* pu, const float* pv, const float* idepth_new,
                               const float* iR, const unsigned char* isGood, const float* energy /*2n*/, const float* outlierTH, float alphaW, float alphaK,
                               float couplingWeight, double priorY, double priorX, float* H_out, float* b_out, float* H_sc, float* b_sc, float* res3,
-                              float* energy_new, unsigned char* isGood_new, float* maxstep_out, float* lastHessian_new, float* JbBuffer_new) {
+                              float* energy_new, unsigned char* isGood_new, float* maxstep_out, float* lastHessian_new, float* JbBuffer_new, float* rows) {
+  if (rows) memset(rows, 0, sizeof(float) * 72 * (size_t)npts);
   orc::SE3 T; T.t[0] = refToNew7[0]; T.t[1] = refToNew7[1]; T.t[2] = refToNew7[2];
   T.q = orc::qimport(orc::Quat{refToNew7[6], refToNew7[3], refToNew7[4], refToNew7[5]});
   double Rd[9], RKid[9];
@@ -115,6 +117,12 @@ void orc_init_calc_res_and_gs(const float* dI_ref, const float* dI_new, int wl, 
       J[8] = _mm_load_ps(&r[k4]);
       acc9.updateSSE(J);
     }
+    if (rows)
+      for (int idx = 0; idx < patternNum; idx++) {
+        float* row = rows + 72 * (size_t)i + 9 * idx;
+        for (int k = 0; k < 8; k++) row[k] = dp[k][idx];
+        row[8] = r[idx];
+      }
   }
   acc9.finish();
   E.finish();
@@ -155,6 +163,16 @@ void orc_init_calc_res_and_gs(const float* dI_ref, const float* dI_new, int wl, 
   H_out[9] += priorY; b_out[1] += priorY * T.t[1];
   H_out[0] += priorX; b_out[0] += priorX * T.t[0];
   res3[0] = E.A; res3[1] = alphaEnergy; res3[2] = (float)Enum;
+}
+
+void orc_init_calc_res_and_gs(const float* dI_ref, const float* dI_new, int wl, int hl, const double* Ki9, float fxl, float fyl, float cxl, float cyl,
+                              const double* refToNew7, double aff_a, double aff_b, int npts, const float* pu, const float* pv, const float* idepth_new,
+                              const float* iR, const unsigned char* isGood, const float* energy /*2n*/, const float* outlierTH, float alphaW, float alphaK,
+                              float couplingWeight, double priorY, double priorX, float* H_out, float* b_out, float* H_sc, float* b_sc, float* res3,
+                              float* energy_new, unsigned char* isGood_new, float* maxstep_out, float* lastHessian_new, float* JbBuffer_new) {
+  orc_init_calc_res_and_gs_rows(dI_ref, dI_new, wl, hl, Ki9, fxl, fyl, cxl, cyl, refToNew7, aff_a, aff_b, npts, pu, pv, idepth_new, iR, isGood, energy, outlierTH, alphaW,
+                                alphaK, couplingWeight, priorY, priorX, H_out, b_out, H_sc, b_sc, res3, energy_new, isGood_new, maxstep_out, lastHessian_new, JbBuffer_new,
+                                nullptr);
 }
 
 }  // extern "C"

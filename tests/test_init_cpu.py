@@ -1,17 +1,20 @@
-"""CPU tests of the initializer oracle (CoarseInitializer::calcResAndGS, oracle/init_oracle.cpp)."""
+"""CPU tests of the initializer oracle (CoarseInitializer::calcResAndGS, oracle/init_oracle.cpp); the inputs, float64 sums and rounding bound shared with the GPU
+matrix of tests/test_init_gpu.py live in tests/init_matrix.py."""
 import numpy as np
+import pytest
+
+from init_matrix import XI_SMALL, XI_LARGE, matrix_case, oracle_run, sums64, chains_oracle, check_sums
 
 
-def init_case(synth, oracle, w=320, h=256, lvl=1, n=800, seed=12):
+def init_case(synth, oracle, w=320, h=256, lvl=1, n=800, seed=12, xi=(0.05, -0.02, 0.01, 0.004, -0.006, 0.002), aff_render=(0.02, 1.5)):
     """First frame at identity, new frame slightly moved; initializer-style points (u = x + 0.1, idepth around the true value rescaled
     to mean 1 like the initializer's convention is NOT needed for the algebra test: true inverse depths are used)."""
     world = synth.PlaneWorld(synth.SEED + seed, fmax=14.0)
     K4 = synth.default_intrinsics(w, h)
     rng = np.random.RandomState(seed)
     img0, id0 = world.render(K4, np.eye(3), np.zeros(3), w, h)
-    xi = np.array([0.05, -0.02, 0.01, 0.004, -0.006, 0.002])
-    R, t = synth.se3_exp(xi)
-    img1, _ = world.render(K4, R, t, w, h, aff=(0.02, 1.5))
+    R, t = synth.se3_exp(np.array(xi, dtype=np.float64))
+    img1, _ = world.render(K4, R, t, w, h, aff=aff_render)
     wl, hl = w >> lvl, h >> lvl
     s = 2.0 ** lvl
     fx, fy = K4[0] / s, K4[1] / s
@@ -68,3 +71,40 @@ def test_gauss_newton_direction_reduces_energy(oracle, synth):
     new_pose = oracle.se3_mul(oracle.se3_exp(x[:6]), start)
     o1 = oracle.init_calc_res_and_gs(dI0[lvl], dI1[lvl], c["wl"], c["hl"], c["Ki"], c["K_lvl"], new_pose, (c["aff"][0] + x[6], c["aff"][1] + x[7]), c["pts"], idn, **kw)
     assert o1["res3"][0] < o0["res3"][0]
+
+
+# ------------------------------------------------------------------------------------------------ CPU tests of the rows entry and of the bound
+MATRIX_CPU = [dict(lvl=0), dict(lvl=1, priorY=0.3, priorX=0.1), dict(lvl=2), dict(lvl=1, alphaW=0.0), dict(lvl=0, xi=XI_LARGE), dict(lvl=1, n=257), dict(lvl=1, n=1)]
+
+
+@pytest.mark.parametrize("case", MATRIX_CPU, ids=lambda d: "-".join("%s=%s" % (k, "large" if k == "xi" else v) for k, v in d.items()))
+def test_rows_entry_matches_plain_entry_bit_for_bit(oracle, synth, case):
+    """orc_init_calc_res_and_gs_rows writes every output of orc_init_calc_res_and_gs with the same bits; its rows are zero exactly for the points that are not accepted
+    and carry r[7] = -hw (never zero) for the others."""
+    case = dict(case)
+    c = matrix_case(synth, oracle, case.pop("lvl"), n=case.pop("n", 700), xi=case.pop("xi", XI_SMALL))
+    a = oracle_run(oracle, c, rows=False, **case); b = oracle_run(oracle, c, rows=True, **case)
+    for k in a:
+        assert np.array_equal(np.ascontiguousarray(a[k]).view(np.uint8), np.ascontiguousarray(b[k]).view(np.uint8)), k
+    acc = b["isGood_new"].astype(bool)
+    assert b["rows"].shape == (c["n"], 8, 9) and not b["rows"][~acc].any() and np.all(b["rows"][acc][:, :, 7] != 0)
+
+
+@pytest.mark.parametrize("case", MATRIX_CPU, ids=lambda d: "-".join("%s=%s" % (k, "large" if k == "xi" else v) for k, v in d.items()))
+def test_oracle_sums_meet_the_rounding_bound(oracle, synth, case):
+    """The oracle's own fp32 sums against the float64 sums of its rows, inside c 2^-24 S with c read off acc9.h (chains_oracle): the bound the GPU matrix applies to the
+    kernel (with the kernel's c) is one a correct fp32 summation meets.  Largest |err| / (2^-24 S) over these cases: H 7.0, Hsc 12.5, E 8.5, against c = 1008 / 653 / 705 at n = 700 (646 accepted)."""
+    case = dict(case)
+    c = matrix_case(synth, oracle, case.pop("lvl"), n=case.pop("n", 700), xi=case.pop("xi", XI_SMALL))
+    o = oracle_run(oracle, c, **case)
+    s = sums64(oracle, o, c, **{k: v for k, v in case.items() if k in ("alphaW", "alphaK", "priorY", "priorX")})
+    ratios = check_sums(o, s, chains_oracle(c["n"], s["n_acc"]), label=str(case))
+    print("oracle ratios", case, c["n"], {k: round(v, 3) for k, v in ratios.items()})
+    # the bound is not vacuous: one residual row less is outside it
+    o2 = {k: np.array(v, copy=True) for k, v in o.items()}
+    acc = np.flatnonzero(o["isGood_new"])
+    if len(acc) > 1:
+        o2["rows"][acc[len(acc) // 2], 7] = 0
+        s2 = sums64(oracle, o2, c, **{k: v for k, v in case.items() if k in ("alphaW", "alphaK", "priorY", "priorX")})
+        with pytest.raises(AssertionError):
+            check_sums(o, s2, chains_oracle(c["n"], s["n_acc"]))

@@ -487,6 +487,67 @@ def test_initializer_calc_res_and_gs_bitwise(O, synth, lvl):
         assert same(r["lastHessian_new"][good], o["lastHessian_new"][good]) and same(r["JbBuffer_new"][good], o["JbBuffer_new"][good])
 
 
+def _alpha_poses(synth):
+    """(name, pose7, alphaOpt expected non-zero): the small translation of an initializer frame before the snap (alphaW |t|^2 = 0.47 < alphaK = 6.25), and two poses
+    whose translation lies 1e-3 below and above the switch |t| = sqrt(alphaK / alphaW) = 2.5 / 150."""
+    from init_matrix import XI_SMALL
+    Rm, t = synth.se3_exp(np.array(XI_SMALL))
+    d = np.array([0.6, -0.64, 0.48]) * (2.5 / 150.0)
+    return [("small", synth.pose7(Rm, t), True), ("below", synth.pose7(Rm, d * (1 - 1e-3)), True), ("above", synth.pose7(Rm, d * (1 + 1e-3)), False)]
+
+
+@pytest.mark.parametrize("lvl", [0, 1, 2])
+def test_initializer_alpha_regimes_bitwise(O, synth, lvl):
+    """The regime every initializer frame before the snap runs in, alphaOpt = alphaW != 0 (CoarseInitializer.cpp:520-535): JbBuffer_new then carries alphaOpt (id - 1) and
+    alphaOpt and no coupling term, H[k,k] and b[k], k < 3, carry alphaOpt n and log(T).head<3>() alphaOpt n.  Same assertions as the test above, on the small-translation
+    pose with and without the priors and on both sides of the switch alphaW |t|^2 n <> alphaK n; that the branch was taken is shown against the same call at alphaW = 0."""
+    from test_init_cpu import init_case
+    from init_matrix import ALPHA_W, ALPHA_K
+    c = init_case(synth, O, lvl=lvl, n=700, seed=12 + lvl)
+    K4 = synth.default_intrinsics(c["w"], c["h"])
+    K_lvl, Ki = R.init_make_k(c["w"], c["h"], K4, lvl)
+    dI0 = O.make_images(c["img0"], c["w"], c["h"])[0]; dI1 = O.make_images(c["img1"], c["w"], c["h"])[0]
+    n = 700
+    for name, pose7, nonzero in _alpha_poses(synth):
+        for pri in ((dict(), dict(priorY=3.0, priorX=0.5)) if name == "small" else (dict(),)):
+            out = {}
+            for aW in (ALPHA_W, 0.0):
+                kw = dict(alphaW=aW, **pri)
+                r = R.init_calc_res_and_gs(c["img0"], c["img1"], c["w"], c["h"], K4, lvl, pose7, c["aff"], c["pts"], c["idepth_new"], **kw)
+                o = O.init_calc_res_and_gs(dI0[lvl], dI1[lvl], c["wl"], c["hl"], Ki, K_lvl, pose7, c["aff"], c["pts"], c["idepth_new"], **kw)
+                good = o["isGood_new"].astype(bool)
+                assert np.array_equal(r["isGood_new"], o["isGood_new"]) and good.sum() > 400
+                for k in ("Hsc", "bsc", "energy_new", "maxstep"):
+                    assert same(r[k], o[k]), (k, name, kw, float(np.abs(r[k] - o[k]).max()))
+                assert same(r["res3"][1:], o["res3"][1:]) and same(r["res3"][1], o["res3"][1])
+                sc = np.sqrt(np.outer(np.abs(np.diag(o["H"])), np.abs(np.diag(o["H"])))) + 1e-30
+                assert np.max(np.abs(r["H"] - o["H"]) / sc) < 2e-5 and np.allclose(r["b"], o["b"], rtol=1e-4, atol=1e-5 * np.abs(o["b"]).max())
+                assert abs(r["res3"][0] - o["res3"][0]) <= 1e-5 * o["res3"][0]
+                assert same(r["lastHessian_new"][good], o["lastHessian_new"][good]) and same(r["JbBuffer_new"][good], o["JbBuffer_new"][good])
+                out[aW] = (r, o)
+            tlog = O.se3_log(pose7)[:3]
+            an = ALPHA_W * n if nonzero else 0.0
+            for r_o in (0, 1):                                            # the reference, then the oracle
+                a, z = out[ALPHA_W][r_o], out[0.0][r_o]
+                if nonzero:
+                    assert a["res3"][1] < ALPHA_K * n and a["res3"][1] > 0 and z["res3"][1] == 0
+                else:
+                    assert a["res3"][1] == np.float32(ALPHA_K * n)
+                for k in range(3):
+                    # the tolerances of the direct comparison above, once per sum: the reference's two runs each sum H and b in an order of their own
+                    tolH = 4e-5 * max(abs(float(a["H"][k, k])), abs(float(z["H"][k, k])))
+                    tolb = 2e-4 * max(abs(float(a["b"][k])), abs(float(z["b"][k]))) + 2e-5 * max(np.abs(a["b"]).max(), np.abs(z["b"]).max())
+                    assert abs(float(a["H"][k, k]) - float(z["H"][k, k]) - an) <= tolH, (name, k)
+                    assert abs(float(a["b"][k]) - float(z["b"][k]) - tlog[k] * an) <= tolb, (name, k)
+                    if nonzero:                                           # ... and the terms are far above them: their absence would fail
+                        assert an > 100 * tolH and abs(tlog[k] * an) > 10 * tolb, (name, k, an, tolH, tlog[k] * an, tolb)
+                acc = a["isGood_new"].astype(bool)
+                if nonzero:     # the Schur rows: alphaOpt in the weight instead of the coupling weight 1
+                    assert not same(a["JbBuffer_new"][acc], z["JbBuffer_new"][acc]) and np.all(a["JbBuffer_new"][acc, 9] < 1.0 / ALPHA_W)
+                else:           # alphaOpt = 0 either way: identical
+                    assert same(a["JbBuffer_new"][acc], z["JbBuffer_new"][acc]) and same(a["Hsc"], z["Hsc"])
+
+
 # ---------------------------------------------------------------------------------------------------------------- result.txt
 def test_print_result_bytes(O, synth, tmp_path):
     """FullSystem::printResult (FullSystem.cpp:256-298) of a live run of the reference (keyframes with their optimised camToWorld, the other frames re-based on their
