@@ -133,6 +133,13 @@ def _sig(L):
     L.dmvio_hip_tracker_eval.argtypes = [vp, C.c_int, C.c_int, C.c_float, c_d, c_d, C.c_float, c_d, c_d, c_d]
     L.dmvio_hip_tracker_track.argtypes = [vp, C.c_int, C.c_float, c_d, c_d, C.c_int, c_d, c_d, c_d, c_d, c_d, c_i]
     L.dmvio_hip_tracker_track_batch.argtypes = [vp, C.c_int, c_i, c_f, c_d, c_d, C.c_int, c_d, c_d, c_d, c_d, c_d, c_i, c_i]
+    L.dmvio_hip_track_multi_create.argtypes = [vp, C.c_int, C.c_int]; L.dmvio_hip_track_multi_create.restype = vp
+    L.dmvio_hip_track_multi_destroy.argtypes = [vp]; L.dmvio_hip_track_multi_destroy.restype = None
+    L.dmvio_hip_tracker_track_multi.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.c_int, c_i, c_i, c_f, c_d, c_d, C.c_int, c_d, c_d, c_d, c_d, c_d, c_i, c_i]
+    L.dmvio_hip_track_multi_set_launch_shape.argtypes = [vp, C.c_int]
+    L.dmvio_hip_track_multi_set_residual_only_evals.argtypes = [vp, C.c_int]
+    L.dmvio_hip_track_multi_last_launch.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.dmvio_hip_track_multi_last_work.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.dmvio_hip_tracker_track_batch_stage.argtypes = [vp, C.c_int, c_i, c_f, c_d, c_d, C.c_int, c_d]
     L.dmvio_hip_tracker_track_batch_launch.argtypes = [vp]
     L.dmvio_hip_tracker_track_batch_fetch_begin.argtypes = [vp]
@@ -676,6 +683,65 @@ class CoarseTrackerHip:
         a = C.c_longlong(0); b = C.c_longlong(0)
         fn = self.L.dmvio_hip_tracker_last_residual_only_work; fn.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]; fn.restype = C.c_int
         _chk(self.L, fn(self.p, C.byref(a), C.byref(b)), "last_residual_only_work")
+        return a.value, b.value
+
+
+class TrackMultiHip:
+    """CoarseTracker::trackNewestCoarse for the frames of W windows in one launch (dmvio_hip_track_multi): problem i is aligned against the reference of
+    trackers[window_of[i]].  The trackers are only read; every problem returns, bit for bit, what its own tracker's track_batch returns for it at the same launch shape
+    (set_launch_shape(0, 256, 0, C) with C from last_launch())."""
+
+    def __init__(self, ctx, max_windows, max_problems):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_track_multi_create(ctx.p, int(max_windows), int(max_problems))
+        if not p:
+            raise HipLibraryError("dmvio_hip_track_multi_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.max_windows, self.max_problems = int(max_windows), int(max_problems)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_track_multi_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def track(self, trackers, window_of, slots, poses, affs, coarsestLvl=None, minRes=None, exposures=None):
+        """trackers: CoarseTrackerHip objects of this context; the other arguments as CoarseTrackerHip.track_batch takes them, one entry per problem -> the same dict"""
+        B = len(slots)
+        hs = (C.c_void_p * max(len(trackers), 1))(*[t.p for t in trackers])
+        win = np.ascontiguousarray(window_of, dtype=np.int32)
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(B, 7).copy()
+        affs = np.ascontiguousarray(affs, dtype=np.float64).reshape(B, 2).copy()
+        exposures = np.ones(B, dtype=np.float32) if exposures is None else np.ascontiguousarray(exposures, dtype=np.float32)
+        mr = np.full((B, 5), np.nan) if minRes is None else np.ascontiguousarray(minRes, dtype=np.float64).reshape(B, 5)
+        if coarsestLvl is None:
+            coarsestLvl = self.ctx.levels - 1
+        lr = np.zeros((B, 5)); fl = np.zeros((B, 3)); H = np.zeros((B, 64)); b = np.zeros((B, 8))
+        good = np.zeros(B, dtype=np.int32); its = np.zeros(B, dtype=np.int32)
+        _chk(self.L, self.L.dmvio_hip_tracker_track_multi(self.p, len(trackers), hs, B, _i(win), _i(slots), _f(exposures), _d(poses), _d(affs), coarsestLvl, _d(mr),
+                                                          _d(lr), _d(fl), _d(H), _d(b), _i(good), _i(its)), "track_multi")
+        return dict(good=good, pose7=poses, aff=affs, lastResiduals=lr, flow=fl, H=H.reshape(B, 8, 8), b=b, iterations=its)
+
+    def set_launch_shape(self, lm_cluster=0):
+        """workgroups per problem (0 = the library's choice): dmvio_hip_track_multi_set_launch_shape"""
+        _chk(self.L, self.L.dmvio_hip_track_multi_set_launch_shape(self.p, int(lm_cluster)), "track_multi_set_launch_shape")
+
+    def set_residual_only_evals(self, on=True):
+        _chk(self.L, self.L.dmvio_hip_track_multi_set_residual_only_evals(self.p, 1 if on else 0), "track_multi_set_residual_only_evals")
+
+    def last_launch(self):
+        a = C.c_int(0); b = C.c_int(0)
+        _chk(self.L, self.L.dmvio_hip_track_multi_last_launch(self.p, C.byref(a), C.byref(b)), "track_multi_last_launch")
+        return a.value, b.value
+
+    def last_work(self):
+        a = C.c_longlong(0); b = C.c_longlong(0)
+        _chk(self.L, self.L.dmvio_hip_track_multi_last_work(self.p, C.byref(a), C.byref(b)), "track_multi_last_work")
         return a.value, b.value
 
 

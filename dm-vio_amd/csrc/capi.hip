@@ -1267,4 +1267,167 @@ int dmvio_hip_write_result_txt(const char* path, int n, const double* timestamps
   return 0;
 }
 
+// ------------------------------------------------------------------ W windows' frames against their own references in one launch
+// dmvio_hip_tracker_track_multi: every problem names its window, the kernel (k_track_lm_w) takes that window's reference out of a table in device memory.  The handle owns
+// what a call needs besides the trackers it reads — its own pipeline of pinned problem / result records, the cluster exchange buffers, the table with its pinned mirror —
+// so single and multi calls on the same trackers may be mixed freely.
+// Cluster mode spins on a device-scope barrier: every workgroup of the launch must be resident.  k_track_lm_w<256, 4, *> keeps four workgroups per CU (resource figures in
+// DESIGN.md, "k_track_lm_w"), 256 CUs: the same bound as dmvio_hip_tracker_track_batch's.
+enum { MULTI_RESIDENT_WORKGROUPS = 1024 };
+struct dmvio_hip_track_multi {
+  dmvio_hip_ctx* ctx = nullptr;
+  int max_windows = 0, max_problems = 0;
+  BatchPipeline pipe;
+  float* d_cl_part = nullptr;          // MULTI_RESIDENT_WORKGROUPS x 2 x ACC_PAD partial sums (B x 2 x C x ACC_PAD of a launch, B * C within the bound)
+  unsigned int* d_cl_cnt = nullptr;    // arrive counters, one per problem of a cluster launch
+  char *h_table = nullptr, *d_table = nullptr;   // packed per call: W TrackerDev records, then ref_of[B]
+  int lm_cluster = 0, res_only = 1;
+  int last_cluster = 0, last_threads = 0;
+  long long last_evals = 0, last_point_evals = 0;
+};
+
+dmvio_hip_track_multi* dmvio_hip_track_multi_create(dmvio_hip_ctx* c, int max_windows, int max_problems) {
+  if (!c) { failmsg("track_multi_create: null context"); return nullptr; }
+  if (max_windows < 1 || max_problems < 1) { failmsg("track_multi_create: max_windows and max_problems must be positive"); return nullptr; }
+  HIPCHKP(hipSetDevice(c->device));
+  dmvio_hip_track_multi* m = new dmvio_hip_track_multi();
+  m->ctx = c; m->max_windows = max_windows; m->max_problems = max_problems;
+  const size_t table_bytes = sizeof(TrackerDev) * (size_t)max_windows + sizeof(int) * (size_t)max_problems;
+  auto init = [&]() -> int {
+    if (int r = m->pipe.reserve(max_problems, c->stream)) return r;
+    HIPCHK(hipMalloc((void**)&m->d_cl_part, sizeof(float) * (size_t)MULTI_RESIDENT_WORKGROUPS * 2 * ACC_PAD));
+    HIPCHK(hipMalloc((void**)&m->d_cl_cnt, sizeof(unsigned int) * MULTI_RESIDENT_WORKGROUPS));
+    HIPCHK(hipMalloc((void**)&m->d_table, table_bytes));
+    HIPCHK(hipHostMalloc((void**)&m->h_table, table_bytes, hipHostMallocDefault));
+    return 0;
+  };
+  if (init()) { dmvio_hip_track_multi_destroy(m); return nullptr; }
+  return m;
+}
+
+void dmvio_hip_track_multi_destroy(dmvio_hip_track_multi* m) {
+  if (!m) return;
+  hipSetDevice(m->ctx->device);
+  hipStreamSynchronize(m->ctx->stream);
+  m->pipe.release();
+  if (m->d_cl_part) hipFree(m->d_cl_part);
+  if (m->d_cl_cnt) hipFree(m->d_cl_cnt);
+  if (m->d_table) hipFree(m->d_table);
+  if (m->h_table) hipHostFree(m->h_table);
+  delete m;
+}
+
+int dmvio_hip_track_multi_set_launch_shape(dmvio_hip_track_multi* m, int lm_cluster) {
+  if (!m) return failmsg("track_multi_set_launch_shape: null handle");
+  if (lm_cluster < 0 || lm_cluster > 32) return failmsg("track_multi_set_launch_shape: lm_cluster out of range");
+  std::lock_guard<std::mutex> lk(m->ctx->mu);
+  m->lm_cluster = lm_cluster;
+  return 0;
+}
+int dmvio_hip_track_multi_set_residual_only_evals(dmvio_hip_track_multi* m, int on) {
+  if (!m) return failmsg("track_multi_set_residual_only_evals: null handle");
+  std::lock_guard<std::mutex> lk(m->ctx->mu);
+  m->res_only = on ? 1 : 0;
+  return 0;
+}
+int dmvio_hip_track_multi_last_launch(dmvio_hip_track_multi* m, int* workgroups_per_problem, int* threads_per_workgroup) {
+  if (!m) return failmsg("track_multi_last_launch: null handle");
+  std::lock_guard<std::mutex> lk(m->ctx->mu);
+  if (workgroups_per_problem) *workgroups_per_problem = m->last_cluster;
+  if (threads_per_workgroup) *threads_per_workgroup = m->last_threads;
+  return 0;
+}
+int dmvio_hip_track_multi_last_work(dmvio_hip_track_multi* m, long long* n_evals, long long* n_point_evals) {
+  if (!m) return failmsg("track_multi_last_work: null handle");
+  std::lock_guard<std::mutex> lk(m->ctx->mu);
+  if (n_evals) *n_evals = m->last_evals;
+  if (n_point_evals) *n_point_evals = m->last_point_evals;
+  return 0;
+}
+
+int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tracker* const* trackers, int B, const int* window_of, const int* new_slots,
+                                  const float* new_exposures, double* pose7_io, double* aff_io, int coarsestLvl, const double* minRes, double* lastResiduals,
+                                  double* lastFlow, double* H, double* b, int* good, int* iterations) {
+  // every refusal stands before the first enqueue and before the first write to a caller's array
+  if (!m) return failmsg("track_multi: null handle");
+  if (!trackers || !window_of || !new_slots || !pose7_io || !aff_io) return failmsg("track_multi: null argument");
+  if (W < 1 || W > m->max_windows) return failmsg("track_multi: W outside 1 .. max_windows");
+  if (B < 0 || B > m->max_problems) return failmsg("track_multi: B outside 0 .. max_problems");
+  dmvio_hip_ctx* c = m->ctx;
+  for (int w = 0; w < W; w++) {
+    if (!trackers[w]) return failmsg("track_multi: null tracker");
+    if (trackers[w]->ctx != c) return failmsg("track_multi: a tracker belongs to another context");
+  }
+  if (coarsestLvl < 0 || coarsestLvl >= c->levels || coarsestLvl >= 5) return failmsg("track_multi: coarsestLvl out of range");
+  std::lock_guard<std::mutex> lk(c->mu);
+  for (int w = 0; w < W; w++)
+    if (!trackers[w]->haveK || !trackers[w]->haveRef) return failmsg("track_multi: makeK / setCoarseTrackingRef not called on a tracker");
+  int pc0 = 0;
+  bool any_tiled = false;
+  for (int i = 0; i < B; i++) {
+    if (window_of[i] < 0 || window_of[i] >= W) return failmsg("track_multi: window_of entry out of range");
+    if (new_slots[i] < 0 || new_slots[i] >= c->n_slots) return failmsg("track_multi: frame slot out of range");
+    pc0 = std::max(pc0, trackers[window_of[i]]->dev.pc_n[0]);
+    any_tiled = any_tiled || c->h_tiled[new_slots[i]] != 0;
+  }
+  if (B == 0) return 0;
+  const int C = m->lm_cluster > 0 ? m->lm_cluster : clusterSize(B, pc0);
+  if (C > 1 && (long)B * C > MULTI_RESIDENT_WORKGROUPS)
+    return failmsg("track_multi: cluster size too large for the batch (B*C must be <= 1024 resident workgroups)");
+  HIPCHK(hipSetDevice(c->device));
+  BatchPipeline& pl = m->pipe;
+  if (int r = pl.reserve(B, c->stream)) return r;
+  int half;
+  if (int r = pl.stageInto(&half)) return r;
+  // the table as the trackers stand now (a set_ref since the last call is seen), then which record each problem reads
+  TrackerDev* h_refs = reinterpret_cast<TrackerDev*>(m->h_table);
+  int* h_ref_of = reinterpret_cast<int*>(m->h_table + sizeof(TrackerDev) * (size_t)W);
+  for (int w = 0; w < W; w++) h_refs[w] = trackers[w]->dev;
+  LMProblemIn* in = pl.in(half);
+  for (int i = 0; i < B; i++) {
+    h_ref_of[i] = window_of[i];
+    LMProblemIn& p = in[i];
+    memcpy(p.pose7, pose7_io + 7 * i, sizeof(double) * 7);
+    p.aff[0] = aff_io[2 * i]; p.aff[1] = aff_io[2 * i + 1];
+    for (int k = 0; k < 5; k++) p.minRes[k] = minRes ? minRes[5 * i + k] : NAN;
+    p.new_slot = new_slots[i];
+    p.new_exposure = new_exposures ? new_exposures[i] : 1.0f;
+  }
+  pl.stageDone(half, B, coarsestLvl);
+  HIPCHK(hipMemcpyAsync(m->d_table, m->h_table, sizeof(TrackerDev) * (size_t)W + sizeof(int) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+  ClusterArgs cl; cl.C = C; cl.part = nullptr; cl.cnt = nullptr; cl.discard = pl.d_discard; cl.log = nullptr; cl.log_n = nullptr;
+  cl.res_only = m->res_only;
+  if (C > 1) {
+    HIPCHK(hipMemsetAsync(m->d_cl_cnt, 0, sizeof(unsigned int) * B, c->stream));
+    cl.part = m->d_cl_part; cl.cnt = m->d_cl_cnt;
+  }
+  const TrackerDev* d_refs = reinterpret_cast<const TrackerDev*>(m->d_table);
+  const int* d_ref_of = reinterpret_cast<const int*>(m->d_table + sizeof(TrackerDev) * (size_t)W);
+  LMProblemOut* pout = pl.out(half);
+  pl.unlaunched = false;
+  auto lm = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B * C), dim3(256), 0, c->stream, d_refs, d_ref_of, c->fs, (const LMProblemIn*)in, pout, coarsestLvl, cl); };
+  if (any_tiled) lm(k_track_lm_w<256, 4, true>); else lm(k_track_lm_w<256, 4, false>);
+  HIPCHK(hipGetLastError());
+  m->last_cluster = C; m->last_threads = 256;
+  if (int r = pl.launched(c->stream)) return r;
+  int nB;
+  if (int r = pl.take(&half, &nB)) return r;
+  const LMProblemOut* out = pl.out(half);
+  long long evals = 0, point_evals = 0;
+  for (int i = 0; i < B; i++) {
+    const LMProblemOut& o = out[i];
+    memcpy(pose7_io + 7 * i, o.pose7, sizeof(double) * 7);
+    aff_io[2 * i] = o.aff[0]; aff_io[2 * i + 1] = o.aff[1];
+    if (lastResiduals) memcpy(lastResiduals + 5 * i, o.lastRes, sizeof(double) * 5);
+    if (lastFlow) memcpy(lastFlow + 3 * i, o.flow, sizeof(double) * 3);
+    if (H) memcpy(H + 64 * i, o.H, sizeof(double) * 64);
+    if (b) memcpy(b + 8 * i, o.b, sizeof(double) * 8);
+    if (good) good[i] = o.good;
+    if (iterations) iterations[i] = o.iterations;
+    evals += o.n_evals; point_evals += o.n_point_evals;
+  }
+  m->last_evals = evals; m->last_point_evals = point_evals;
+  return 0;
+}
+
 }  // extern "C"

@@ -232,6 +232,31 @@ int dmvio_hip_tracker_track_batch_launch(dmvio_hip_tracker* trk);
 int dmvio_hip_tracker_track_batch_fetch_begin(dmvio_hip_tracker* trk);
 int dmvio_hip_tracker_track_batch_fetch(dmvio_hip_tracker* trk, double* pose7_out, double* aff_out, double* lastResiduals,
                                         double* lastFlow, double* H, double* b, int* good, int* iterations);
+/* The same device-resident LM (CoarseTracker::trackNewestCoarse, CoarseTracker.cpp:539-770; the hypothesis list of FullSystem::trackNewCoarse, FullSystem.cpp:364-402) for the
+ * frames of W sliding windows in ONE launch: problem i is aligned against the reference that trackers[window_of[i]] holds when the call is made.  The handle owns everything
+ * a call needs besides the trackers (pinned problem / result records, the cluster exchange buffers, the device table of the W references); of the trackers it only reads
+ * the reference (template, exposure, affine, intrinsics) and the settings — their own batch pipeline, last_* counters, launch-shape overrides and residual-only switch are
+ * neither used nor changed, so calls of either kind may be mixed freely.  One call is one upload of the table, one launch (plus the clear of the arrive counters in cluster
+ * mode) and one wait, under the context's lock on the context's stream, whatever W and B are.
+ * Launch shape: 256 threads per workgroup; C workgroups per problem = lm_cluster (dmvio_hip_track_multi_set_launch_shape) or, by default, what dmvio_hip_tracker_track_batch
+ * would choose for B problems on the largest template among the named windows up to 128 problems and 1 above; B * C <= 1024 in cluster mode (all workgroups must be
+ * resident).  Frames whose level 0 is stored in 8x4 tiles are gathered from as they are.
+ * Problem i returns, bit for bit, what dmvio_hip_tracker_track_batch on trackers[window_of[i]] returns for that problem when it runs the device-resident LM at the same shape
+ * (dmvio_hip_tracker_set_launch_shape(trk, 0, 256, 0, C)): pose7, aff, lastResiduals, lastFlow, H, b, good and iterations; what else the batch holds does not enter.
+ * Arrays are B-major as in dmvio_hip_tracker_track_batch; new_exposures, minResForAbort and the outputs from lastResiduals on may be NULL.  The call is refused as a whole,
+ * with a message and before anything is enqueued or written: a NULL handle, tracker array, window_of, new_slots, pose7_io or aff_io; W outside 1 .. max_windows; B outside
+ * 0 .. max_problems; a window_of entry outside [0, W); a tracker of another context, without dmvio_hip_tracker_make_k or without a reference; a slot out of range;
+ * coarsestLvl outside the pyramid; a cluster shape beyond the residency bound.  B == 0 returns 0.  A tracker may stand twice in `trackers`; problems may share a window and a slot. */
+typedef struct dmvio_hip_track_multi dmvio_hip_track_multi;
+dmvio_hip_track_multi* dmvio_hip_track_multi_create(dmvio_hip_ctx* ctx, int max_windows, int max_problems);
+void dmvio_hip_track_multi_destroy(dmvio_hip_track_multi* m);
+int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tracker* const* trackers, int B, const int* window_of,
+                                  const int* new_slots, const float* new_exposures, double* pose7_io, double* aff_io, int coarsestLvl,
+                                  const double* minResForAbort, double* lastResiduals, double* lastFlow, double* H, double* b, int* good, int* iterations);
+int dmvio_hip_track_multi_set_launch_shape(dmvio_hip_track_multi* m, int lm_cluster);       /* 0 = the library's choice */
+int dmvio_hip_track_multi_set_residual_only_evals(dmvio_hip_track_multi* m, int on);        /* default 1; outputs identical either way */
+int dmvio_hip_track_multi_last_launch(dmvio_hip_track_multi* m, int* workgroups_per_problem, int* threads_per_workgroup);
+int dmvio_hip_track_multi_last_work(dmvio_hip_track_multi* m, long long* n_evals, long long* n_point_evals);
 /* FullSystem::trackNewCoarse (FullSystem.cpp:300-539), visual-only path without IMU hint:
  *  - dmvio_hip_make_track_hypotheses builds lastF_2_fh_tries (:364-402: constant / double / half / zero motion, zero motion from the
  *    keyframe, 26 small rotations) from the camToWorld poses of the last two frames and of the reference keyframe; returns the count (31);

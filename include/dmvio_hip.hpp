@@ -146,6 +146,8 @@ class CoarseTracker {
   }
   int lastEvaluations = 0;   /* calcRes + calcGSSSE passes of the last hand-off track */
   int pc_n(int lvl) const { return trk_ ? dmvio_hip_tracker_pc_n(trk_, lvl) : 0; }
+  /* the C handle, for calls that take several trackers (TrackMulti::track); stays owned by this object */
+  dmvio_hip_tracker* handle() const { return trk_; }
 
   /* CoarseTracker.h:83-91 */
   double lastResiduals[5];
@@ -563,6 +565,68 @@ class TraceBatch {
 
  private:
   dmvio_hip_trace_batch* b_;
+};
+
+/* CoarseTracker::trackNewestCoarse for the frames of several windows per call (dmvio_hip_track_multi): problem i is aligned against the reference its own tracker
+ * holds, all of them in one launch.  The trackers are only read; every problem returns what CoarseTracker's own batch call returns for it at the same launch shape.  A call
+ * is refused as a whole (lastError()) before anything is written. */
+class TrackMulti {
+ public:
+  TrackMulti(dmvio_hip_ctx* ctx, int maxWindows, int maxProblems) : m_(dmvio_hip_track_multi_create(ctx, maxWindows, maxProblems)) {}
+  ~TrackMulti() { if (m_) dmvio_hip_track_multi_destroy(m_); }
+  TrackMulti(const TrackMulti&) = delete;
+  TrackMulti& operator=(const TrackMulti&) = delete;
+  bool valid() const { return m_ != nullptr; }
+  struct Problem {
+    int window;               /* index into the tracker list */
+    int newSlot;
+    float new_ab_exposure;
+    SE3 lastToNew;            /* in / out */
+    AffLight aff_g2l;         /* in / out */
+    double minResForAbort[5]; /* NAN = no abort rule */
+    double lastResiduals[5], lastFlowIndicators[3], H[64], b[8];
+    bool good;
+    int iterations;
+  };
+  bool track(const std::vector<const CoarseTracker*>& trackers, std::vector<Problem>& problems, int coarsestLvl) {
+    if (!m_) return false;
+    const size_t W = trackers.size(), B = problems.size();
+    std::vector<dmvio_hip_tracker*> hs(W);
+    for (size_t w = 0; w < W; w++) { if (!trackers[w]) return false; hs[w] = trackers[w]->handle(); }
+    std::vector<int> win(B), slots(B), good(B), its(B);
+    std::vector<float> ex(B);
+    std::vector<double> pose(7 * B), aff(2 * B), mr(5 * B), lr(5 * B), fl(3 * B), H(64 * B), b(8 * B);
+    for (size_t i = 0; i < B; i++) {
+      const Problem& p = problems[i];
+      win[i] = p.window; slots[i] = p.newSlot; ex[i] = p.new_ab_exposure;
+      p.lastToNew.toPose7(&pose[7 * i]);
+      aff[2 * i] = p.aff_g2l.a; aff[2 * i + 1] = p.aff_g2l.b;
+      for (int k = 0; k < 5; k++) mr[5 * i + k] = p.minResForAbort[k];
+    }
+    if (dmvio_hip_tracker_track_multi(m_, (int)W, hs.data(), (int)B, win.data(), slots.data(), ex.data(), pose.data(), aff.data(), coarsestLvl, mr.data(), lr.data(), fl.data(),
+                                      H.data(), b.data(), good.data(), its.data()) != 0)
+      return false;
+    for (size_t i = 0; i < B; i++) {
+      Problem& p = problems[i];
+      p.lastToNew.fromPose7(&pose[7 * i]);
+      p.aff_g2l = AffLight(aff[2 * i], aff[2 * i + 1]);
+      for (int k = 0; k < 5; k++) p.lastResiduals[k] = lr[5 * i + k];
+      for (int k = 0; k < 3; k++) p.lastFlowIndicators[k] = fl[3 * i + k];
+      for (int k = 0; k < 64; k++) p.H[k] = H[64 * i + k];
+      for (int k = 0; k < 8; k++) p.b[k] = b[8 * i + k];
+      p.good = good[i] != 0; p.iterations = its[i];
+    }
+    return true;
+  }
+  /* workgroups per problem: 0 = the library's choice */
+  bool setLaunchShape(int lmCluster) { return m_ && dmvio_hip_track_multi_set_launch_shape(m_, lmCluster) == 0; }
+  bool setResidualOnlyEvals(bool on) { return m_ && dmvio_hip_track_multi_set_residual_only_evals(m_, on ? 1 : 0) == 0; }
+  bool lastLaunch(int& workgroupsPerProblem, int& threadsPerWorkgroup) const { return m_ && dmvio_hip_track_multi_last_launch(m_, &workgroupsPerProblem, &threadsPerWorkgroup) == 0; }
+  bool lastWork(long long& evals, long long& pointEvals) const { return m_ && dmvio_hip_track_multi_last_work(m_, &evals, &pointEvals) == 0; }
+  dmvio_hip_track_multi* handle() const { return m_; }
+
+ private:
+  dmvio_hip_track_multi* m_;
 };
 
 }  // namespace dmvio_hip
