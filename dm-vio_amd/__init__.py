@@ -102,6 +102,12 @@ class ActivationOptimize(C.Structure):
                 ("idepth", c_f), ("res_state", c_i), ("n_activated", C.c_int)]
 
 
+class SetRefWindow(C.Structure):
+    """dmvio_hip_set_ref_window (include/dmvio_hip.h): one window of dmvio_hip_tracker_set_ref_batch."""
+    _fields_ = [("trk", C.c_void_p), ("ref_slot", C.c_int), ("ref_exposure", C.c_float), ("ref_aff_a", C.c_double), ("ref_aff_b", C.c_double), ("n", C.c_int),
+                ("u", c_f), ("v", c_f), ("idepth", c_f), ("hdiF", c_f)]
+
+
 def _sig(L):
     vp = C.c_void_p
     L.dmvio_hip_last_error.restype = C.c_char_p
@@ -140,6 +146,10 @@ def _sig(L):
     L.dmvio_hip_track_multi_set_residual_only_evals.argtypes = [vp, C.c_int]
     L.dmvio_hip_track_multi_last_launch.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.dmvio_hip_track_multi_last_work.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.dmvio_hip_set_ref_batch_create.argtypes = [vp, C.c_int, C.c_int]; L.dmvio_hip_set_ref_batch_create.restype = vp
+    L.dmvio_hip_set_ref_batch_destroy.argtypes = [vp]; L.dmvio_hip_set_ref_batch_destroy.restype = None
+    L.dmvio_hip_tracker_set_ref_batch.argtypes = [vp, C.c_int, C.POINTER(SetRefWindow)]
+    L.dmvio_hip_set_ref_batch_last_work.argtypes = [vp, c_i, c_i, c_i, c_i]
     L.dmvio_hip_tracker_track_batch_stage.argtypes = [vp, C.c_int, c_i, c_f, c_d, c_d, C.c_int, c_d]
     L.dmvio_hip_tracker_track_batch_launch.argtypes = [vp]
     L.dmvio_hip_tracker_track_batch_fetch_begin.argtypes = [vp]
@@ -743,6 +753,54 @@ class TrackMultiHip:
         a = C.c_longlong(0); b = C.c_longlong(0)
         _chk(self.L, self.L.dmvio_hip_track_multi_last_work(self.p, C.byref(a), C.byref(b)), "track_multi_last_work")
         return a.value, b.value
+
+
+class SetRefBatchHip:
+    """CoarseTracker::setCoarseTrackingRef + makeCoarseDepthL0 of W trackers of one context in one pass (dmvio_hip_set_ref_batch): every tracker ends, bit for bit, as its
+    own setCoarseTrackingRef would have left it; one upload, a W-independent number of launches, one download and one wait per call (last_work())."""
+
+    def __init__(self, ctx, max_windows, max_points_per_window):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_set_ref_batch_create(ctx.p, int(max_windows), int(max_points_per_window))
+        if not p:
+            raise HipLibraryError("dmvio_hip_set_ref_batch_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.max_windows, self.max_points_per_window = int(max_windows), int(max_points_per_window)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_set_ref_batch_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def pack(windows):
+        """windows: one dict per tracker with trk (a CoarseTrackerHip), ref_slot, u, v, idepth, hdiF and optionally ref_exposure (1.0) and ref_aff ((0, 0)), the
+        arguments of CoarseTrackerHip.setCoarseTrackingRef -> (array of dmvio_hip_set_ref_window, the arrays it points into)"""
+        arr = (SetRefWindow * max(len(windows), 1))()
+        keep = []
+        for x, d in zip(arr, windows):
+            pts = [np.ascontiguousarray(d[k], dtype=np.float32) for k in ("u", "v", "idepth", "hdiF")]
+            keep.append(pts)
+            aff = d.get("ref_aff", (0.0, 0.0))
+            x.trk = d["trk"].p; x.ref_slot = int(d["ref_slot"]); x.ref_exposure = float(d.get("ref_exposure", 1.0)); x.ref_aff_a = float(aff[0]); x.ref_aff_b = float(aff[1])
+            x.n = len(pts[0]); x.u, x.v, x.idepth, x.hdiF = [_f(a) for a in pts]
+        return arr, keep
+
+    def set_ref(self, windows):
+        """one dmvio_hip_tracker_set_ref_batch call over `windows` (see pack())"""
+        arr, keep = self.pack(windows)
+        _chk(self.L, self.L.dmvio_hip_tracker_set_ref_batch(self.p, len(windows), arr), "set_ref_batch")
+
+    def last_work(self):
+        """(kernel launches, uploads, downloads, stream waits) of the last call"""
+        v = [C.c_int(0) for _ in range(4)]
+        _chk(self.L, self.L.dmvio_hip_set_ref_batch_last_work(self.p, *[C.byref(x) for x in v]), "set_ref_batch_last_work")
+        return tuple(x.value for x in v)
 
 
 def set_raw_batch_layout(ctx, tiled):

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "lie_dev.h"
 #include "ref_kernels.hpp"
+#include "ref_batch_kernels.hpp"
 #include "tracker_kernels.hpp"
 
 using namespace dmv;
@@ -85,6 +86,30 @@ struct BatchPipeline {
   }
 };
 
+// setCoarseTrackingRef: the rank of every point among the points of its level-0 pixel, in index order, by open addressing on the host (k_ref_scatter adds ranks 0 and 1
+// together and every further rank in a launch of its own).  Points outside the image get rank 0 (the scatter drops them).  Returns the largest rank, capped at 255.
+struct RefRanker {
+  std::vector<int> keys, cnt;
+  int rank(const int w0, const int h0, const int n, const float* u, const float* v, unsigned char* out) {
+    int maxRank = 0;
+    size_t cap = 64;
+    while (cap < 2 * (size_t)n + 16) cap <<= 1;
+    keys.assign(cap, -1); cnt.assign(cap, 0);
+    for (int i = 0; i < n; i++) {
+      const int ui = (int)(u[i] + 0.5f), vi = (int)(v[i] + 0.5f);
+      if (ui < 0 || vi < 0 || ui >= w0 || vi >= h0) { out[i] = 0; continue; }
+      const int key = ui + w0 * vi;
+      size_t hpos = ((unsigned)key * 2654435761u) & (cap - 1);
+      while (keys[hpos] != -1 && keys[hpos] != key) hpos = (hpos + 1) & (cap - 1);
+      keys[hpos] = key;
+      const int r = cnt[hpos]++;
+      out[i] = (unsigned char)std::min(r, 255);
+      maxRank = std::max(maxRank, std::min(r, 255));
+    }
+    return maxRank;
+  }
+};
+
 // what the "last launch" queries report (dmvio_hip_tracker_last_launch / _last_work / _last_ticks) and what the try loop of trackNewCoarse reads per problem; a fetch and
 // a host-LM call assign it whole, a launch sets its shape
 struct LastRun {
@@ -110,7 +135,7 @@ struct dmvio_hip_tracker {
   float4** d_pc_ptrs = nullptr;
   float* d_pts = nullptr;
   int pts_cap = 0;
-  std::vector<int> h_rank_keys, h_rank_cnt;    // set_ref: host-side ranking of the points that share a pixel
+  RefRanker ranker;                            // set_ref: host-side ranking of the points that share a pixel
   std::vector<unsigned char> h_rank;
   // fused evaluation (k_eval_fused)
   float *d_partials = nullptr, *h_tot = nullptr;
@@ -289,25 +314,9 @@ int dmvio_hip_tracker_set_ref(dmvio_hip_tracker* t, int ref_slot, float ref_expo
     HIPCHK(c->bounce.h2d(t->d_pts + 1 * (size_t)t->pts_cap, v, sizeof(float) * n, s));
     HIPCHK(c->bounce.h2d(t->d_pts + 2 * (size_t)t->pts_cap, idepth, sizeof(float) * n, s));
     HIPCHK(c->bounce.h2d(t->d_pts + 3 * (size_t)t->pts_cap, hdiF, sizeof(float) * n, s));
-    // rank of every point among the points of its pixel (index order), by open addressing on the host: pixels with more than two points are scattered
-    // rank by rank (k_ref_scatter)
-    int maxRank = 0;
-    {
-      size_t cap = 64;
-      while (cap < 2 * (size_t)n + 16) cap <<= 1;
-      t->h_rank_keys.assign(cap, -1); t->h_rank_cnt.assign(cap, 0); t->h_rank.resize(n);
-      for (int i = 0; i < n; i++) {
-        const int ui = (int)(u[i] + 0.5f), vi = (int)(v[i] + 0.5f);
-        if (ui < 0 || vi < 0 || ui >= R.w[0] || vi >= R.h[0]) { t->h_rank[i] = 0; continue; }
-        const int key = ui + R.w[0] * vi;
-        size_t hpos = ((unsigned)key * 2654435761u) & (cap - 1);
-        while (t->h_rank_keys[hpos] != -1 && t->h_rank_keys[hpos] != key) hpos = (hpos + 1) & (cap - 1);
-        t->h_rank_keys[hpos] = key;
-        const int r = t->h_rank_cnt[hpos]++;
-        t->h_rank[i] = (unsigned char)std::min(r, 255);
-        maxRank = std::max(maxRank, std::min(r, 255));
-      }
-    }
+    // rank of every point among the points of its pixel (index order): pixels with more than two points are scattered rank by rank (k_ref_scatter)
+    t->h_rank.resize(n);
+    const int maxRank = t->ranker.rank(R.w[0], R.h[0], n, u, v, t->h_rank.data());
     const unsigned char* d_rank = nullptr;
     if (maxRank >= 2) {
       HIPCHK(c->bounce.h2d(t->d_pts + 4 * (size_t)t->pts_cap, t->h_rank.data(), (size_t)n, s));
@@ -1427,6 +1436,157 @@ int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tra
     evals += o.n_evals; point_evals += o.n_point_evals;
   }
   m->last_evals = evals; m->last_point_evals = point_evals;
+  return 0;
+}
+
+// ------------------------------------------------------------------ W trackers' reference templates in one pass
+// dmvio_hip_tracker_set_ref_batch: setCoarseTrackingRef + makeCoarseDepthL0 (CoarseTracker.cpp:524-538, 138-295) of W trackers of one context.  The handle owns what a call
+// needs besides the trackers' own buffers: a slab in pinned memory with its device copy (W RefWin records, the four point arrays of every window, their rank bytes: one
+// upload), the [W][levels] pc_n table with its pinned mirror (one download) and the ranking tables.  Every kernel runs over all W windows (ref_batch_kernels.hpp); the
+// trackers' scratch for the single call (d_pts) is not touched, so single and batched calls on one tracker may be mixed freely.
+struct dmvio_hip_set_ref_batch {
+  dmvio_hip_ctx* ctx = nullptr;
+  int max_windows = 0, max_points = 0;
+  size_t slab_bytes = 0;
+  char *h_slab = nullptr, *d_slab = nullptr;
+  int *h_pcn = nullptr, *d_pcn = nullptr;      // [max_windows][DMV_MAX_LEVELS]; a call uses [W][levels]
+  RefRanker ranker;
+  std::vector<const dmvio_hip_tracker*> seen;  // the duplicate test
+  int last_launches = 0, last_uploads = 0, last_downloads = 0, last_waits = 0;
+};
+// the slab: records, then floats, then bytes; every part starts on a 16-byte boundary
+static size_t refSlabPointsOff(int W) { return (sizeof(RefWin) * (size_t)W + 15) & ~(size_t)15; }
+static size_t refSlabRanksOff(int W, size_t total_points) { return (refSlabPointsOff(W) + sizeof(float) * 4 * total_points + 15) & ~(size_t)15; }
+
+dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* c, int max_windows, int max_points_per_window) {
+  if (!c) { failmsg("set_ref_batch_create: null context"); return nullptr; }
+  if (max_windows < 1 || max_points_per_window < 1) { failmsg("set_ref_batch_create: max_windows and max_points_per_window must be positive"); return nullptr; }
+  HIPCHKP(hipSetDevice(c->device));
+  dmvio_hip_set_ref_batch* b = new dmvio_hip_set_ref_batch();
+  b->ctx = c; b->max_windows = max_windows; b->max_points = max_points_per_window;
+  const size_t total = (size_t)max_windows * (size_t)max_points_per_window;
+  b->slab_bytes = refSlabRanksOff(max_windows, total) + total;
+  auto init = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&b->d_slab, b->slab_bytes));
+    HIPCHK(hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&b->d_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows));
+    HIPCHK(hipHostMalloc((void**)&b->h_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows, hipHostMallocDefault));
+    return 0;
+  };
+  if (init()) { dmvio_hip_set_ref_batch_destroy(b); return nullptr; }
+  return b;
+}
+
+void dmvio_hip_set_ref_batch_destroy(dmvio_hip_set_ref_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
+  if (b->d_slab) hipFree(b->d_slab);
+  if (b->h_slab) hipHostFree(b->h_slab);
+  if (b->d_pcn) hipFree(b->d_pcn);
+  if (b->h_pcn) hipHostFree(b->h_pcn);
+  delete b;
+}
+
+int dmvio_hip_set_ref_batch_last_work(dmvio_hip_set_ref_batch* b, int* launches, int* uploads, int* downloads, int* waits) {
+  if (!b) return failmsg("set_ref_batch_last_work: null handle");
+  std::lock_guard<std::mutex> lk(b->ctx->mu);
+  if (launches) *launches = b->last_launches;
+  if (uploads) *uploads = b->last_uploads;
+  if (downloads) *downloads = b->last_downloads;
+  if (waits) *waits = b->last_waits;
+  return 0;
+}
+
+int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmvio_hip_set_ref_window* win) {
+  // every refusal stands before the first enqueue and before the first write to a tracker
+  if (!b) return failmsg("tracker_set_ref_batch: null handle");
+  if (W < 0 || W > b->max_windows) return failmsg("tracker_set_ref_batch: W outside 0 .. max_windows");
+  if (W > 0 && !win) return failmsg("tracker_set_ref_batch: null window array");
+  dmvio_hip_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  b->seen.clear();
+  size_t total = 0;
+  int max_n = 0;
+  for (int w = 0; w < W; w++) {
+    const dmvio_hip_set_ref_window& x = win[w];
+    if (!x.trk) return failmsg("tracker_set_ref_batch: null tracker");
+    if (x.trk->ctx != c) return failmsg("tracker_set_ref_batch: a tracker belongs to another context");
+    if (x.ref_slot < 0 || x.ref_slot >= c->n_slots) return failmsg("tracker_set_ref_batch: slot out of range");
+    if (x.n < 0 || x.n > b->max_points) return failmsg("tracker_set_ref_batch: n outside 0 .. max_points_per_window");
+    if (x.n > 0 && (!x.u || !x.v || !x.idepth || !x.hdiF)) return failmsg("tracker_set_ref_batch: null point array");
+    b->seen.push_back(x.trk);
+    total += (size_t)x.n;
+    max_n = std::max(max_n, x.n);
+  }
+  std::sort(b->seen.begin(), b->seen.end());
+  if (std::adjacent_find(b->seen.begin(), b->seen.end()) != b->seen.end())
+    return failmsg("tracker_set_ref_batch: the same tracker is named twice (two windows would write one set of buffers)");
+  b->last_launches = b->last_uploads = b->last_downloads = b->last_waits = 0;
+  if (W == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  // reference slots whose level 0 is stored in 8x4 tiles go back to row-major first, as in the single call (their launches are not part of last_work's figures)
+  for (int w = 0; w < W; w++) if (int r = dmv_ensure_row_major_locked(c, win[w].ref_slot)) return r;
+  hipStream_t s = c->stream;
+  RefLevels R = win[0].trk->R;   // the geometry is the context's, the same for every tracker; the storage order is the tracker's and travels in its record
+  R.order = 0;
+  const int n_tiles = win[0].trk->n_tiles, flow_words = (int)win[0].trk->flow_words;
+  const int n0 = R.w[0] * R.h[0];
+  // the slab: caller arrays are copied into the handle's pinned memory (internal.h: DmvBounce has the reason) and go up in one copy
+  RefWin* h_wins = reinterpret_cast<RefWin*>(b->h_slab);
+  size_t pts = refSlabPointsOff(W) / sizeof(float), ranks = refSlabRanksOff(W, total);
+  int max_rank = 0;
+  for (int w = 0; w < W; w++) {
+    const dmvio_hip_set_ref_window& x = win[w];
+    dmvio_hip_tracker* t = x.trk;
+    RefWin& V = h_wins[w];
+    V.idp = t->d_idp; V.wsp = t->d_wsp; V.idp2 = t->d_idp2; V.wsp2 = t->d_wsp2; V.dense = t->d_dense;
+    V.tile_count = t->d_tile_count; V.tile_base = t->d_tile_base; V.seg = t->d_seg; V.pc_n = t->d_pc_n;
+    V.pc = t->d_pc_ptrs; V.flow_mask = t->d_flow_mask;
+    V.pc_n_row = b->d_pcn + (size_t)w * R.levels;
+    V.pts_off = pts; V.rank_off = ranks;
+    V.ref_slot = x.ref_slot; V.n = x.n; V.order = t->R.order; V.max_rank = 0;
+    if (x.n > 0) {
+      float* hp = reinterpret_cast<float*>(b->h_slab) + pts;
+      memcpy(hp, x.u, sizeof(float) * x.n); memcpy(hp + x.n, x.v, sizeof(float) * x.n);
+      memcpy(hp + 2 * (size_t)x.n, x.idepth, sizeof(float) * x.n); memcpy(hp + 3 * (size_t)x.n, x.hdiF, sizeof(float) * x.n);
+      V.max_rank = b->ranker.rank(R.w[0], R.h[0], x.n, x.u, x.v, reinterpret_cast<unsigned char*>(b->h_slab) + ranks);
+    }
+    max_rank = std::max(max_rank, V.max_rank);
+    pts += 4 * (size_t)x.n; ranks += (size_t)x.n;
+  }
+  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, ranks, hipMemcpyHostToDevice, s));
+  b->last_uploads = 1;
+  const RefWin* d_wins = reinterpret_cast<const RefWin*>(b->d_slab);
+  const float* d_slab = reinterpret_cast<const float*>(b->d_slab);
+  int launches = 0;
+  const unsigned gw = (unsigned)W;
+  hipLaunchKernelGGL(k_ref_clear_w, dim3((unsigned)(((n0 + 3) / 4 + 255) / 256), gw), dim3(256), 0, s, d_wins, n0, flow_words); launches++;
+  // ranks 0 and 1 together, then every further rank of the batch behind them: a window whose own largest rank is below the launch's leaves at once
+  const unsigned gs = (unsigned)std::max(1, (max_n + 255) / 256);
+  for (int r = 1; r <= std::max(max_rank, 1); r++) {
+    hipLaunchKernelGGL(k_ref_scatter_w, dim3(gs, gw), dim3(256), 0, s, d_wins, d_slab, R.w[0], R.h[0], r == 1 ? 0 : r, r); launches++;
+  }
+  if (R.levels > 1) {
+    const size_t npool = R.total - R.off[1];
+    hipLaunchKernelGGL(k_ref_pool_w, dim3((unsigned)((npool + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
+  }
+  hipLaunchKernelGGL(k_ref_dilate_w, dim3((unsigned)((R.total + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
+  hipLaunchKernelGGL(k_ref_count_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->fs); launches++;
+  hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
+  hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->fs); launches++;
+  HIPCHK(hipGetLastError());
+  b->last_launches = launches;
+  HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * R.levels, hipMemcpyDeviceToHost, s));
+  b->last_downloads = 1;
+  HIPCHK(hipStreamSynchronize(s));
+  b->last_waits = 1;
+  for (int w = 0; w < W; w++) {
+    dmvio_hip_tracker* t = win[w].trk;
+    for (int l = 0; l < R.levels; l++) { t->dev.pc_n[l] = b->h_pcn[(size_t)w * R.levels + l]; t->dev.pc[l] = t->d_pc[l]; }
+    t->dev.ref_exposure = win[w].ref_exposure; t->dev.ref_aff_a = win[w].ref_aff_a; t->dev.ref_aff_b = win[w].ref_aff_b;
+    t->haveRef = true;
+  }
   return 0;
 }
 

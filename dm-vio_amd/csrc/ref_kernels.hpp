@@ -30,10 +30,12 @@ struct RefLevels {
 // The reference adds the points of a pixel one after the other (CoarseTracker.cpp:151-165).  Two float atomics on one pixel commute (0 + a + b); a third
 // would make the sum depend on the arrival order, so the host ranks the points of every pixel by index (`rank`, NULL when no pixel holds more than two) and
 // launches ranks [0,1] together and every further rank as its own launch behind them: sequential order, no data race.
-__global__ void __launch_bounds__(256) k_ref_scatter(const int n, const float* __restrict__ u, const float* __restrict__ v,
-                                                      const float* __restrict__ idepth, const float* __restrict__ hdiF,
-                                                      float* __restrict__ id0, float* __restrict__ ws0, const int w0, const int h0,
-                                                      const unsigned char* __restrict__ rank, const int rank_lo, const int rank_hi) {
+// (every stage below is a __device__ body that its single-window kernel here and its W-window kernel in ref_batch_kernels.hpp both call: the arithmetic and its operand
+// order exist once)
+__device__ __forceinline__ void refScatterBody(const int n, const float* __restrict__ u, const float* __restrict__ v,
+                                               const float* __restrict__ idepth, const float* __restrict__ hdiF,
+                                               float* __restrict__ id0, float* __restrict__ ws0, const int w0, const int h0,
+                                               const unsigned char* __restrict__ rank, const int rank_lo, const int rank_hi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (rank) { const int r = rank[i]; if (r < rank_lo || r > rank_hi) return; }
@@ -43,6 +45,12 @@ __global__ void __launch_bounds__(256) k_ref_scatter(const int n, const float* _
   const float weight = sqrtf((float)(1e-3 / ((double)hdiF[i] + 1e-12)));
   atomicAdd(&id0[ui + w0 * vi], idepth[i] * weight);
   atomicAdd(&ws0[ui + w0 * vi], weight);
+}
+__global__ void __launch_bounds__(256) k_ref_scatter(const int n, const float* __restrict__ u, const float* __restrict__ v,
+                                                      const float* __restrict__ idepth, const float* __restrict__ hdiF,
+                                                      float* __restrict__ id0, float* __restrict__ ws0, const int w0, const int h0,
+                                                      const unsigned char* __restrict__ rank, const int rank_lo, const int rank_hi) {
+  refScatterBody(n, u, v, idepth, hdiF, id0, ws0, w0, h0, rank, rank_lo, rank_hi);
 }
 
 // nested 2x2 sums in the reference's operand order: ((a + b) + c) + d, level by level
@@ -67,7 +75,7 @@ __device__ __forceinline__ float pooledSum(const float* __restrict__ p0, const i
 }
 
 // all levels >= 1 in one launch; idx runs over the concatenated pixels of levels 1..L-1
-__global__ void __launch_bounds__(256) k_ref_pool(const RefLevels R, float* __restrict__ idp, float* __restrict__ wsp) {
+__device__ __forceinline__ void refPoolBody(const RefLevels& R, float* __restrict__ idp, float* __restrict__ wsp) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x + R.off[1];
   if (idx >= R.total) return;
   int lvl = 1;
@@ -85,11 +93,12 @@ __global__ void __launch_bounds__(256) k_ref_pool(const RefLevels R, float* __re
   idp[idx] = a;
   wsp[idx] = b;
 }
+__global__ void __launch_bounds__(256) k_ref_pool(const RefLevels R, float* __restrict__ idp, float* __restrict__ wsp) { refPoolBody(R, idp, wsp); }
 
 // dilation: reads the un-dilated planes (the reference's weightSums_bak + never-overwritten idepth
 // entries), writes new planes — race free by construction.
-__global__ void __launch_bounds__(256) k_ref_dilate(const RefLevels R, const float* __restrict__ idp, const float* __restrict__ wsp,
-                                                     float* __restrict__ idp2, float* __restrict__ wsp2) {
+__device__ __forceinline__ void refDilateBody(const RefLevels& R, const float* __restrict__ idp, const float* __restrict__ wsp,
+                                              float* __restrict__ idp2, float* __restrict__ wsp2) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= R.total) return;
   int lvl = 0;
@@ -113,6 +122,10 @@ __global__ void __launch_bounds__(256) k_ref_dilate(const RefLevels R, const flo
   }
   idp2[idx] = oid;
   wsp2[idx] = ows;
+}
+__global__ void __launch_bounds__(256) k_ref_dilate(const RefLevels R, const float* __restrict__ idp, const float* __restrict__ wsp,
+                                                     float* __restrict__ idp2, float* __restrict__ wsp2) {
+  refDilateBody(R, idp, wsp, idp2, wsp2);
 }
 
 // normalise; returns whether pixel (x,y) of level lvl becomes a template point, and its record
@@ -148,8 +161,8 @@ __device__ __forceinline__ void blockToPixel(const RefLevels& R, const int blk, 
 }
 
 // pass 1: per-block counts (+ per (row, 8-px segment) counts on level 0)
-__global__ void __launch_bounds__(256) k_ref_count(const RefLevels R, const float* __restrict__ idp2, const float* __restrict__ wsp2,
-                                                    const FrameStore fs, const int ref_slot, int* __restrict__ blk_count, int* __restrict__ seg_count) {
+__device__ __forceinline__ void refCountBody(const RefLevels& R, const float* __restrict__ idp2, const float* __restrict__ wsp2,
+                                             const FrameStore& fs, const int ref_slot, int* __restrict__ blk_count, int* __restrict__ seg_count) {
   int lvl, x, y;
   blockToPixel(R, blockIdx.x, lvl, x, y);
   bool flag = false;
@@ -165,6 +178,10 @@ __global__ void __launch_bounds__(256) k_ref_count(const RefLevels R, const floa
   if (inside && (lane & 7) == 0) seg_count[R.seg_off[lvl] + y * R.seg_x[lvl] + (x >> 3)] = __popcll((m >> (lane & 56)) & 0xffull);
   __syncthreads();
   if (threadIdx.x == 0) blk_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+__global__ void __launch_bounds__(256) k_ref_count(const RefLevels R, const float* __restrict__ idp2, const float* __restrict__ wsp2,
+                                                    const FrameStore fs, const int ref_slot, int* __restrict__ blk_count, int* __restrict__ seg_count) {
+  refCountBody(R, idp2, wsp2, fs, ref_slot, blk_count, seg_count);
 }
 
 // block-wide exclusive scan helper over 1024 threads (value per thread) ; returns exclusive prefix, total via s_total
@@ -186,8 +203,9 @@ __device__ __forceinline__ int scan1024(const int c, int* s_wave, int& total) {
 
 // pass 2: blockIdx.x < levels: exclusive scan of the block counts of that level -> blk_base, pc_n[lvl].
 //         blockIdx.x >= levels: row-major rank tables of level blockIdx.x - levels: seg_count -> exclusive prefix in row-major order (in place).
-__global__ void __launch_bounds__(1024) k_ref_scan(const RefLevels R, const int* __restrict__ blk_count, int* __restrict__ blk_base,
-                                                    int* __restrict__ pc_n, int* __restrict__ seg_count) {
+// pc_n_row (may be NULL): a second place for pc_n[lvl], the window's row of a batch's [W][levels] table
+__device__ __forceinline__ void refScanBody(const RefLevels& R, const int* __restrict__ blk_count, int* __restrict__ blk_base,
+                                            int* __restrict__ pc_n, int* __restrict__ seg_count, int* __restrict__ pc_n_row) {
   __shared__ int s_wave[16];
   int carry = 0;
   if ((int)blockIdx.x < R.levels) {
@@ -201,7 +219,7 @@ __global__ void __launch_bounds__(1024) k_ref_scan(const RefLevels R, const int*
       if (t < t1) blk_base[t] = carry + ex;
       carry += total;
     }
-    if (threadIdx.x == 0) pc_n[lvl] = carry;
+    if (threadIdx.x == 0) { pc_n[lvl] = carry; if (pc_n_row) pc_n_row[lvl] = carry; }
   } else {
     const int lvl = blockIdx.x - R.levels;
     const int n = R.h[lvl] * R.seg_x[lvl];  // row-major (y, segment) order == raster order of the segments
@@ -216,13 +234,23 @@ __global__ void __launch_bounds__(1024) k_ref_scan(const RefLevels R, const int*
     }
   }
 }
+__global__ void __launch_bounds__(1024) k_ref_scan(const RefLevels R, const int* __restrict__ blk_count, int* __restrict__ blk_base,
+                                                    int* __restrict__ pc_n, int* __restrict__ seg_count) {
+  refScanBody(R, blk_count, blk_base, pc_n, seg_count, nullptr);
+}
 
 // pass 3: ranked write of the template records in tile order, the dense normalised idepth map (debugPlotIDepthMap)
 // and, on level 0, the flow-sample bit of every entry whose ROW-MAJOR rank is a multiple of 32.
-__global__ void __launch_bounds__(256) k_ref_write(const RefLevels R, const float* __restrict__ idp2, const float* __restrict__ wsp2,
-                                                    const FrameStore fs, const int ref_slot, const int* __restrict__ blk_base,
-                                                    const int* __restrict__ seg_prefix, float4* const* __restrict__ pc,
-                                                    float* __restrict__ idepth_dense, unsigned long long* __restrict__ flow_mask) {
+// GL = false, the single-window kernel: the storage order is R.order and the entry pc[lvl] a generic pointer (its one flat store).  GL = true, the W-window kernel: the
+// order is `win_order`, from the window's record (the geometry it is handed is the context's, the order the tracker's), and pc[lvl] is read as a global pointer
+// (ba_batch_kernels.hpp: gl()).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wincompatible-pointer-types-discards-qualifiers"
+template <bool GL>
+__device__ __forceinline__ void refWriteBody(const RefLevels& R, const int win_order, const float* __restrict__ idp2, const float* __restrict__ wsp2,
+                                             const FrameStore& fs, const int ref_slot, const int* __restrict__ blk_base,
+                                             const int* __restrict__ seg_prefix, float4* const* __restrict__ pc,
+                                             float* __restrict__ idepth_dense, unsigned long long* __restrict__ flow_mask) {
   int lvl, x, y;
   blockToPixel(R, blockIdx.x, lvl, x, y);
   bool flag = false;
@@ -240,11 +268,19 @@ __global__ void __launch_bounds__(256) k_ref_write(const RefLevels R, const floa
   if (flag) {
     const unsigned long long rowbits = (m >> (lane & 56)) & 0xffull;
     const int raster = seg_prefix[R.seg_off[lvl] + y * R.seg_x[lvl] + (x >> 3)] + __popcll(rowbits & ((1ull << (lane & 7)) - 1ull));   // rank in the reference's row-major list
-    const int pos = R.order ? raster : blk_base[blockIdx.x] + woff + __popcll(m & ((1ull << lane) - 1ull));
-    pc[lvl][pos] = rec;
+    const int pos = (GL ? win_order : R.order) ? raster : blk_base[blockIdx.x] + woff + __popcll(m & ((1ull << lane) - 1ull));
+    if constexpr (GL) ((float4*)(*reinterpret_cast<__attribute__((address_space(1))) float4* const*>(&pc[lvl])))[pos] = rec;
+    else pc[lvl][pos] = rec;
     if (lvl == 0 && (raster & 31) == 0) atomicOr(&flow_mask[pos >> 6], 1ull << (pos & 63));
   }
   if (inside) idepth_dense[R.off[lvl] + x + y * R.w[lvl]] = idn;
+}
+#pragma clang diagnostic pop
+__global__ void __launch_bounds__(256) k_ref_write(const RefLevels R, const float* __restrict__ idp2, const float* __restrict__ wsp2,
+                                                    const FrameStore fs, const int ref_slot, const int* __restrict__ blk_base,
+                                                    const int* __restrict__ seg_prefix, float4* const* __restrict__ pc,
+                                                    float* __restrict__ idepth_dense, unsigned long long* __restrict__ flow_mask) {
+  refWriteBody<false>(R, 0, idp2, wsp2, fs, ref_slot, blk_base, seg_prefix, pc, idepth_dense, flow_mask);
 }
 
 }  // namespace dmv

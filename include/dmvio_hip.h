@@ -257,6 +257,34 @@ int dmvio_hip_track_multi_set_launch_shape(dmvio_hip_track_multi* m, int lm_clus
 int dmvio_hip_track_multi_set_residual_only_evals(dmvio_hip_track_multi* m, int on);        /* default 1; outputs identical either way */
 int dmvio_hip_track_multi_last_launch(dmvio_hip_track_multi* m, int* workgroups_per_problem, int* threads_per_workgroup);
 int dmvio_hip_track_multi_last_work(dmvio_hip_track_multi* m, long long* n_evals, long long* n_point_evals);
+/* CoarseTracker::setCoarseTrackingRef + makeCoarseDepthL0 (CoarseTracker.cpp:524-538, 138-295) for W trackers of one context in one pass: window i is what
+ * dmvio_hip_tracker_set_ref(win[i].trk, win[i].ref_slot, ...) is, and after the call every named tracker holds exactly the bytes that call would have left — the template
+ * lists of every level in the tracker's own storage order (dmvio_hip_tracker_set_template_order is per tracker, so the order is per window), pc_n, the flow-sample mask, the
+ * dilated planes and the dense idepth map behind dmvio_hip_tracker_get_idepth_map, ref_exposure, the affine pair, and the reference counts as set.  The handle owns what a
+ * call needs besides the trackers' own buffers (a pinned slab for the windows' records, point arrays and rank bytes with its device copy, the [W][levels] pc_n table); single
+ * and batched calls may be mixed freely on a tracker, and every getter, dmvio_hip_tracker_track, _track_batch, _track_vio and _track_multi work unchanged afterwards.
+ * A call runs under the context's lock on the context's stream and consists, whatever W is, of ONE packed upload, a number of kernel launches that does not depend on W —
+ * one clear, max(1, R) scatters where R is the largest number of further points on one level-0 pixel (rank, in index order: ranks 0 and 1 go together, every further rank
+ * in a launch of its own, as in the single call) over all windows, then pool (pyramids of two and more levels), dilate, count, scan and write: 6 + max(1, R) — ONE download of
+ * the pc_n table and ONE wait; dmvio_hip_set_ref_batch_last_work reports these four figures of the last call (all 0 after a call with W == 0; any pointer may be NULL).
+ * A reference slot whose level 0 is stored in 8x4 tiles is converted to row-major first, as the single call does; those launches and their wait are NOT counted.
+ * The call is refused as a whole, with a message and before anything is enqueued or any tracker touched: a NULL handle, window array or tracker; W < 0 or W > max_windows;
+ * a tracker of another context; the same tracker named twice (two windows would write one set of buffers); ref_slot out of range; n < 0 or n > max_points_per_window;
+ * n > 0 with a NULL point array.  W == 0 returns 0.  A window with n == 0 is legal and ends with an empty template, as in the single call.  Windows may share a ref_slot. */
+typedef struct dmvio_hip_set_ref_batch dmvio_hip_set_ref_batch;
+dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* ctx, int max_windows, int max_points_per_window);
+void dmvio_hip_set_ref_batch_destroy(dmvio_hip_set_ref_batch* b);
+typedef struct dmvio_hip_set_ref_window {   /* as dmvio_hip_tracker_set_ref, one window */
+  dmvio_hip_tracker* trk;
+  int ref_slot;
+  float ref_exposure;
+  double ref_aff_a, ref_aff_b;
+  int n;
+  const float *u, *v, *idepth, *hdiF;
+} dmvio_hip_set_ref_window;
+int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmvio_hip_set_ref_window* win);
+/* what the last call enqueued: kernel launches, host-to-device copies, device-to-host copies, stream waits */
+int dmvio_hip_set_ref_batch_last_work(dmvio_hip_set_ref_batch* b, int* launches, int* uploads, int* downloads, int* waits);
 /* FullSystem::trackNewCoarse (FullSystem.cpp:300-539), visual-only path without IMU hint:
  *  - dmvio_hip_make_track_hypotheses builds lastF_2_fh_tries (:364-402: constant / double / half / zero motion, zero motion from the
  *    keyframe, 26 small rotations) from the camToWorld poses of the last two frames and of the reference keyframe; returns the count (31);

@@ -629,5 +629,41 @@ class TrackMulti {
   dmvio_hip_track_multi* m_;
 };
 
+/* CoarseTracker::setCoarseTrackingRef + makeCoarseDepthL0 for several trackers of one context per call (dmvio_hip_set_ref_batch): every tracker ends as its own
+ * single call would have left it; one upload, a number of launches that does not depend on the number of windows, one download, one wait.  A call is refused as a whole
+ * (lastError()) before any tracker is touched. */
+class SetRefBatch {
+ public:
+  SetRefBatch(dmvio_hip_ctx* ctx, int maxWindows, int maxPointsPerWindow) : b_(dmvio_hip_set_ref_batch_create(ctx, maxWindows, maxPointsPerWindow)) {}
+  ~SetRefBatch() { if (b_) dmvio_hip_set_ref_batch_destroy(b_); }
+  SetRefBatch(const SetRefBatch&) = delete;
+  SetRefBatch& operator=(const SetRefBatch&) = delete;
+  bool valid() const { return b_ != nullptr; }
+  struct Window {
+    const CoarseTracker* tracker;
+    int refSlot;
+    float ref_ab_exposure;
+    AffLight ref_aff_g2l;
+    std::vector<float> u, v, idepth, hdiF;   /* the window's points projected into the new reference, as dmvio_hip_tracker_set_ref takes them */
+  };
+  bool setCoarseTrackingRef(const std::vector<Window>& windows) {
+    if (!b_) return false;
+    std::vector<dmvio_hip_set_ref_window> win(windows.size());
+    for (size_t i = 0; i < windows.size(); i++) {
+      const Window& w = windows[i];
+      if (!w.tracker || w.v.size() != w.u.size() || w.idepth.size() != w.u.size() || w.hdiF.size() != w.u.size()) return false;
+      win[i].trk = w.tracker->handle(); win[i].ref_slot = w.refSlot; win[i].ref_exposure = w.ref_ab_exposure;
+      win[i].ref_aff_a = w.ref_aff_g2l.a; win[i].ref_aff_b = w.ref_aff_g2l.b;
+      win[i].n = (int)w.u.size(); win[i].u = w.u.data(); win[i].v = w.v.data(); win[i].idepth = w.idepth.data(); win[i].hdiF = w.hdiF.data();
+    }
+    return dmvio_hip_tracker_set_ref_batch(b_, (int)win.size(), win.data()) == 0;
+  }
+  bool lastWork(int& launches, int& uploads, int& downloads, int& waits) const { return b_ && dmvio_hip_set_ref_batch_last_work(b_, &launches, &uploads, &downloads, &waits) == 0; }
+  dmvio_hip_set_ref_batch* handle() const { return b_; }
+
+ private:
+  dmvio_hip_set_ref_batch* b_;
+};
+
 }  // namespace dmvio_hip
 #endif
