@@ -1,4 +1,6 @@
-// libdmvio_hip.so — C ABI implementation (include/dmvio_hip.h), the coarse tracker.  gfx950 only.
+// libdmvio_hip.so — C ABI implementation (include/dmvio_hip.h), the coarse tracker: the handle's life, the evaluation server, the batched LM pipeline, the host LM, the
+// try loop of trackNewCoarse and the multi-window launch.  gfx950 only.  The only unit that compiles tracker_kernels.hpp, so every launch of one of its kernels is here; the
+// reference template is capi_ref.hip's.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -14,163 +16,11 @@
 #include "../../include/dmvio_hip.h"
 #include "common.h"
 #include "lie_dev.h"
-#include "ref_kernels.hpp"
-#include "ref_batch_kernels.hpp"
 #include "tracker_kernels.hpp"
 
 using namespace dmv;
 
-#include "internal.h"
-
-// The double-buffered batch pipeline of _track_batch_stage / _launch / _fetch_begin / _fetch.  Problems and results live in two halves of pinned host memory used
-// alternately (the kernel reads its 120 B per problem and writes its results there directly); an event follows every launch.  The rules, as transitions:
-//   * a batch is staged into the half the LAST launch did not use, once the launch before the last one (same half) has completed;
-//   * one batch may be staged behind results marked by fetchBegin(), not two (the kernel would overwrite results nobody has read);
-//   * the halves cannot grow while such results are pending;
-//   * between stageDone() and the launch `unlaunched` holds: a single-frame call must not slip in front of that batch.
-struct BatchPipeline {
-  LMProblemIn* h_in = nullptr;
-  LMProblemOut* h_out = nullptr;
-  LMProblemOut* d_discard = nullptr;   // one device entry: where the non-leading workgroups of cluster mode put their result
-  hipEvent_t done[2] = {nullptr, nullptr};   // recorded behind each launch: the results of that half are in host memory once it has completed
-  int cap = 0;                         // problems per half
-  int cur = 0;                         // half of the last launch
-  int staged_half = 0, staged_B = 0, staged_coarsest = 0;
-  bool unlaunched = false;
-  int fetch_half = 0, fetch_B = 0;     // fetchBegin(): the half and size a later take() refers to (0 = none pending)
-
-  LMProblemIn* in(int half) const { return h_in + (size_t)half * cap; }
-  LMProblemOut* out(int half) const { return h_out + (size_t)half * cap; }
-
-  int reserve(int B, hipStream_t s) {
-    if (B <= cap) return 0;
-    if (fetch_B > 0) return failmsg("track_batch_stage: a larger batch cannot be staged while the results of the previous one are still to be fetched");
-    if (h_in) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(d_discard)); HIPCHK(hipHostFree(h_in)); HIPCHK(hipHostFree(h_out)); }
-    cap = std::max(B, 64);
-    HIPCHK(hipMalloc((void**)&d_discard, sizeof(LMProblemOut)));
-    HIPCHK(hipHostMalloc((void**)&h_in, sizeof(LMProblemIn) * 2 * cap, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&h_out, sizeof(LMProblemOut) * 2 * cap, hipHostMallocDefault));
-    return 0;
-  }
-  // the half the next batch is written into, free to be overwritten when this returns 0
-  int stageInto(int* half) {
-    *half = cur ^ 1;
-    if (fetch_B > 0 && *half == fetch_half)
-      return failmsg("track_batch_stage: the results marked by track_batch_fetch_begin have not been fetched yet (one batch may be staged behind them, not two)");
-    if (done[*half]) HIPCHK(hipEventSynchronize(done[*half]));
-    return 0;
-  }
-  void stageDone(int half, int B, int coarsest) { staged_half = half; staged_B = B; staged_coarsest = coarsest; unlaunched = true; }
-  // a kernel that works on the staged half has been enqueued on `s` (the host may still be unpacking the other half: fetchBegin pipeline)
-  int launched(hipStream_t s) {
-    cur = staged_half;
-    if (!done[cur]) HIPCHK(hipEventCreateWithFlags(&done[cur], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(done[cur], s));
-    return 0;
-  }
-  // nothing to enqueue: the next launch goes into the other half and take() waits for this launch's event only
-  void fetchBegin() { fetch_B = staged_B; fetch_half = cur; }
-  // waits for the results to unpack: those marked by fetchBegin() (they belong to the launch before the last one) or else the last launch's
-  int take(int* half, int* B) {
-    *B = staged_B; *half = cur;
-    if (fetch_B > 0) { *B = fetch_B; fetch_B = 0; *half = fetch_half; }
-    if (!done[*half]) return failmsg("track_batch_fetch: nothing launched");
-    HIPCHK(hipEventSynchronize(done[*half]));
-    return 0;
-  }
-  void release() {
-    hipFree(d_discard);
-    for (hipEvent_t e : done) if (e) hipEventDestroy(e);
-    if (h_in) hipHostFree(h_in);
-    if (h_out) hipHostFree(h_out);
-  }
-};
-
-// setCoarseTrackingRef: the rank of every point among the points of its level-0 pixel, in index order, by open addressing on the host (k_ref_scatter adds ranks 0 and 1
-// together and every further rank in a launch of its own).  Points outside the image get rank 0 (the scatter drops them).  Returns the largest rank, capped at 255.
-struct RefRanker {
-  std::vector<int> keys, cnt;
-  int rank(const int w0, const int h0, const int n, const float* u, const float* v, unsigned char* out) {
-    int maxRank = 0;
-    size_t cap = 64;
-    while (cap < 2 * (size_t)n + 16) cap <<= 1;
-    keys.assign(cap, -1); cnt.assign(cap, 0);
-    for (int i = 0; i < n; i++) {
-      const int ui = (int)(u[i] + 0.5f), vi = (int)(v[i] + 0.5f);
-      if (ui < 0 || vi < 0 || ui >= w0 || vi >= h0) { out[i] = 0; continue; }
-      const int key = ui + w0 * vi;
-      size_t hpos = ((unsigned)key * 2654435761u) & (cap - 1);
-      while (keys[hpos] != -1 && keys[hpos] != key) hpos = (hpos + 1) & (cap - 1);
-      keys[hpos] = key;
-      const int r = cnt[hpos]++;
-      out[i] = (unsigned char)std::min(r, 255);
-      maxRank = std::max(maxRank, std::min(r, 255));
-    }
-    return maxRank;
-  }
-};
-
-// what the "last launch" queries report (dmvio_hip_tracker_last_launch / _last_work / _last_ticks) and what the try loop of trackNewCoarse reads per problem; a fetch and
-// a host-LM call assign it whole, a launch sets its shape
-struct LastRun {
-  int cluster = 0, threads = 0;        // workgroups per problem, threads per workgroup
-  long long evals = 0, point_evals = 0, ticks_step = 0, ticks_eval = 0;
-  long long res_evals = 0, res_point_evals = 0;   // of evals / point_evals: the residual-only ones (dmvio_hip_tracker_last_residual_only_work)
-  int vio_iterations = 0;              // LM iterations of the last host-LM call
-  std::vector<int> repeat_lvl;         // per problem: the level that ran twice (or -1) ...
-  std::vector<double> first_pass_res;  // ... and its residual after the first pass
-};
-
-struct dmvio_hip_tracker {
-  dmvio_hip_ctx* ctx = nullptr;
-  TrackerDev dev{};
-  bool haveK = false, haveRef = false;
-  RefLevels R{};
-  int n_tiles = 0;
-  float *d_idp = nullptr, *d_wsp = nullptr, *d_idp2 = nullptr, *d_wsp2 = nullptr, *d_dense = nullptr;
-  int *d_tile_count = nullptr, *d_tile_base = nullptr, *d_pc_n = nullptr, *d_seg = nullptr;
-  unsigned long long* d_flow_mask = nullptr;
-  size_t flow_words = 0;
-  float4* d_pc[DMV_MAX_LEVELS] = {};
-  float4** d_pc_ptrs = nullptr;
-  float* d_pts = nullptr;
-  int pts_cap = 0;
-  RefRanker ranker;                            // set_ref: host-side ranking of the points that share a pixel
-  std::vector<unsigned char> h_rank;
-  // fused evaluation (k_eval_fused)
-  float *d_partials = nullptr, *h_tot = nullptr;
-  unsigned int* d_arrive = nullptr;   // arrive counter of k_eval_fused (zero between launches)
-  unsigned int eval_ticket = 0;       // ticket of the last fused evaluation; the kernel stores it behind the sums in h_tot
-  int eval_blocks_override = 0;
-  int max_eval_blocks = 1024;
-  // evaluation server (k_eval_server): one launch per tracked frame, requests through a mailbox in host-coherent memory
-  unsigned int* d_leave = nullptr;    // the launch (by its first ticket) whose workgroups have been told to leave by an idle time-out
-  unsigned int* h_mail = nullptr;     // EVAL_MAIL_DWORDS dwords: [0] request ticket, [1..] EvalP, [last] the ticket again (written before [0])
-  float* h_rec = nullptr;             // EVAL_SERVER_MAX_BLOCKS records of EVAL_RECORD_FLOATS floats: every server workgroup stores its partial sums + the ticket into its own
-  bool server_on = false;             // a server kernel was launched for server_slot and has not been told to quit
-  int server_slot = -1, server_G = 0;
-  unsigned int server_session = 0;    // identity of the current serverStart .. serverStop session (mailbox dword EVAL_MAIL_SESSION, kernel argument)
-  long long server_idle_ticks = 500000;   // the server leaves after this long without a request (100 MHz ticks: 5 ms); dmvio_hip_tracker_set_server_idle_us
-  int use_server = 1;                 // dmvio_hip_tracker_set_eval_server(0): one k_eval_fused launch per evaluation instead
-  int single_host_lm = 1;             // dmvio_hip_tracker_set_single_frame_mode(0): a single alignment problem runs the device-resident LM (cluster mode) instead of the host LM + server
-  // hypothesis-parallel trackNewCoarse: the tries after the first are split over `xworld` ranks, their per-try records summed over the ranks (every record is written by
-  // exactly one rank, the others add zeros) by `xchg`
-  std::function<int(double*, size_t)> xchg;
-  int xrank = 0, xworld = 0;
-  bool debug_split1 = false;          // dmvio_hip_tracker_debug_split_single_rank: a group of ONE rank still takes the split path (tests of the transport on a one-device box)
-  // batched device-resident LM
-  BatchPipeline pipe;
-  LastRun last;
-  int batch_kernel = 0;          // dmvio_hip_tracker_set_batch_kernel: 1 = full batches on k_track_lm_pp (control steps beside the evaluations)
-  int res_only_evals = 1;        // dmvio_hip_tracker_set_residual_only_evals: k_track_lm runs the evaluations whose 9x9 sums nothing reads as residual-only ones
-  unsigned int* d_pp_next = nullptr;
-  int lm_threads_override = 0, lm_cluster_override = 0;   // dmvio_hip_tracker_set_launch_shape
-  float* d_cl_part = nullptr;          // cluster mode: B x 2 x C x ACC_PAD partial sums
-  unsigned int* d_cl_cnt = nullptr;    // cluster mode: arrive counters
-  size_t cl_part_cap = 0; int cl_cnt_cap = 0;
-  int debug_mode = 0, log_cap = 0, log_B = 0;   // dmvio_hip_tracker_debug_record_replay
-  EvalP* d_log = nullptr; int* d_log_n = nullptr; float* d_log_sink = nullptr;
-};
+#include "tracker_handle.h"
 
 extern "C" {
 
@@ -288,115 +138,6 @@ int dmvio_hip_tracker_make_k(dmvio_hip_tracker* t, const float k[4]) {
     Ki[6] = (0.0f * 0.0f - e * 0.0f) * invdet; Ki[7] = (0.0f * 0.0f - a * 0.0f) * invdet; Ki[8] = (a * e - 0.0f * 0.0f) * invdet;
   }
   t->haveK = true;
-  return 0;
-}
-
-int dmvio_hip_tracker_set_ref(dmvio_hip_tracker* t, int ref_slot, float ref_exposure, double aff_a, double aff_b,
-                              int n, const float* u, const float* v, const float* idepth, const float* hdiF) {
-  if (!t) return failmsg("tracker_set_ref: null tracker");
-  dmvio_hip_ctx* c = t->ctx;
-  if (ref_slot < 0 || ref_slot >= c->n_slots) return failmsg("tracker_set_ref: slot out of range");
-  if (n < 0 || (n > 0 && (!u || !v || !idepth || !hdiF))) return failmsg("tracker_set_ref: bad point arrays");
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIPCHK(hipSetDevice(c->device));
-  if (int r = dmv_ensure_row_major_locked(c, ref_slot)) return r;
-  hipStream_t s = c->stream;
-  if (n > t->pts_cap) {
-    if (t->d_pts) HIPCHK(hipFree(t->d_pts));
-    t->pts_cap = std::max(n, 4096);
-    HIPCHK(hipMalloc((void**)&t->d_pts, sizeof(float) * 5 * t->pts_cap));   // u, v, idepth, hdiF, [per-pixel rank bytes]
-  }
-  const RefLevels& R = t->R;
-  HIPCHK(hipMemsetAsync(t->d_idp, 0, sizeof(float) * R.w[0] * R.h[0], s));
-  HIPCHK(hipMemsetAsync(t->d_wsp, 0, sizeof(float) * R.w[0] * R.h[0], s));
-  if (n > 0) {
-    HIPCHK(c->bounce.h2d(t->d_pts + 0 * (size_t)t->pts_cap, u, sizeof(float) * n, s));      // through the library's pinned memory (internal.h: DmvBounce)
-    HIPCHK(c->bounce.h2d(t->d_pts + 1 * (size_t)t->pts_cap, v, sizeof(float) * n, s));
-    HIPCHK(c->bounce.h2d(t->d_pts + 2 * (size_t)t->pts_cap, idepth, sizeof(float) * n, s));
-    HIPCHK(c->bounce.h2d(t->d_pts + 3 * (size_t)t->pts_cap, hdiF, sizeof(float) * n, s));
-    // rank of every point among the points of its pixel (index order): pixels with more than two points are scattered rank by rank (k_ref_scatter)
-    t->h_rank.resize(n);
-    const int maxRank = t->ranker.rank(R.w[0], R.h[0], n, u, v, t->h_rank.data());
-    const unsigned char* d_rank = nullptr;
-    if (maxRank >= 2) {
-      HIPCHK(c->bounce.h2d(t->d_pts + 4 * (size_t)t->pts_cap, t->h_rank.data(), (size_t)n, s));
-      d_rank = (const unsigned char*)(t->d_pts + 4 * (size_t)t->pts_cap);
-    }
-    for (int r = 1; r <= std::max(maxRank, 1); r++)
-      hipLaunchKernelGGL(k_ref_scatter, dim3((n + 255) / 256), dim3(256), 0, s, n, t->d_pts, t->d_pts + t->pts_cap, t->d_pts + 2 * (size_t)t->pts_cap,
-                         t->d_pts + 3 * (size_t)t->pts_cap, t->d_idp, t->d_wsp, R.w[0], R.h[0], d_rank, r == 1 ? 0 : r, r);
-  }
-  if (R.levels > 1) {
-    const size_t npool = R.total - R.off[1];
-    hipLaunchKernelGGL(k_ref_pool, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp);
-  }
-  hipLaunchKernelGGL(k_ref_dilate, dim3((unsigned)((R.total + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp, t->d_idp2, t->d_wsp2);
-  HIPCHK(hipMemsetAsync(t->d_flow_mask, 0, sizeof(unsigned long long) * t->flow_words, s));
-  hipLaunchKernelGGL(k_ref_count, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->fs, ref_slot, t->d_tile_count, t->d_seg);
-  hipLaunchKernelGGL(k_ref_scan, dim3(2 * R.levels), dim3(1024), 0, s, R, t->d_tile_count, t->d_tile_base, t->d_pc_n, t->d_seg);
-  hipLaunchKernelGGL(k_ref_write, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->fs, ref_slot, t->d_tile_base, t->d_seg, t->d_pc_ptrs,
-                     t->d_dense, t->d_flow_mask);
-  HIPCHK(hipGetLastError());
-  int pcn[DMV_MAX_LEVELS] = {};
-  HIPCHK(c->bounce.d2h(pcn, t->d_pc_n, sizeof(int) * R.levels, s));
-  HIPCHK(c->bounce.finish(s));
-  for (int l = 0; l < R.levels; l++) { t->dev.pc_n[l] = pcn[l]; t->dev.pc[l] = t->d_pc[l]; }
-  t->dev.ref_exposure = ref_exposure; t->dev.ref_aff_a = aff_a; t->dev.ref_aff_b = aff_b;
-  t->haveRef = true;
-  return 0;
-}
-
-int dmvio_hip_tracker_pc_n(dmvio_hip_tracker* t, int lvl) {
-  if (!t || lvl < 0 || lvl >= t->ctx->levels) return failmsg("tracker_pc_n: bad argument");
-  return t->dev.pc_n[lvl];
-}
-
-int dmvio_hip_tracker_get_pc(dmvio_hip_tracker* t, int lvl, float* u, float* v, float* idepth, float* color) {
-  if (!t || lvl < 0 || lvl >= t->ctx->levels) return failmsg("tracker_get_pc: bad argument");
-  dmvio_hip_ctx* c = t->ctx;
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIPCHK(hipSetDevice(c->device));
-  const int n = t->dev.pc_n[lvl];
-  std::vector<float4> tmp(n);
-  HIPCHK(c->bounce.d2h(tmp.data(), t->d_pc[lvl], sizeof(float4) * n, c->stream));
-  HIPCHK(c->bounce.finish(c->stream));
-  // the device keeps the template in tile order; hand it out in the reference's row-major order (y, then x)
-  std::sort(tmp.begin(), tmp.end(), [](const float4& a, const float4& b) { return a.y < b.y || (a.y == b.y && a.x < b.x); });
-  for (int i = 0; i < n; i++) { u[i] = tmp[i].x; v[i] = tmp[i].y; idepth[i] = tmp[i].z; color[i] = tmp[i].w; }
-  return 0;
-}
-
-// The dense maps CoarseTracker keeps next to the template: idepth[lvl] and weightSums[lvl] as makeCoarseDepthL0 leaves them (CoarseTracker.cpp:249-293; read by
-// debugPlotIDepthMap / debugPlotIDepthMapFloat, :772-880, when output wrappers exist).  Debug path: the dilated planes come back from the device and the normalisation loop is
-// replayed on the host; whether a pixel with weight became a template point (finite reference colour, idepth > 0) is taken from the template itself.
-int dmvio_hip_tracker_get_idepth_map(dmvio_hip_tracker* t, int lvl, float* idepth_out, float* weightSums_out) {
-  if (!t || lvl < 0 || lvl >= t->ctx->levels || !idepth_out) return failmsg("tracker_get_idepth_map: bad argument");
-  if (!t->haveRef) return failmsg("tracker_get_idepth_map: setCoarseTrackingRef not called");
-  dmvio_hip_ctx* c = t->ctx;
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIPCHK(hipSetDevice(c->device));
-  const RefLevels& R = t->R;
-  const int wl = R.w[lvl], hl = R.h[lvl], n = t->dev.pc_n[lvl];
-  const size_t npx = (size_t)wl * hl;
-  std::vector<float> ws(npx);
-  std::vector<float4> pc(n);
-  HIPCHK(c->bounce.d2h(idepth_out, t->d_idp2 + R.off[lvl], sizeof(float) * npx, c->stream));
-  HIPCHK(c->bounce.d2h(ws.data(), t->d_wsp2 + R.off[lvl], sizeof(float) * npx, c->stream));
-  if (n) HIPCHK(c->bounce.d2h(pc.data(), t->d_pc[lvl], sizeof(float4) * n, c->stream));
-  HIPCHK(c->bounce.finish(c->stream));
-  std::vector<unsigned char> kept(npx, 0);
-  for (int i = 0; i < n; i++) kept[(size_t)pc[i].x + (size_t)pc[i].y * wl] = 1;
-  for (int y = 2; y < hl - 2; y++)
-    for (int x = 2; x < wl - 2; x++) {
-      const size_t i = (size_t)x + (size_t)y * wl;
-      if (ws[i] > 0) {
-        idepth_out[i] /= ws[i];
-        if (!kept[i]) { idepth_out[i] = -1; continue; }   // the reference's "just skip if something is wrong": weightSums keeps its value
-      } else
-        idepth_out[i] = -1;
-      ws[i] = 1;
-    }
-  if (weightSums_out) memcpy(weightSums_out, ws.data(), sizeof(float) * npx);
   return 0;
 }
 
@@ -532,16 +273,13 @@ static int stageChecks(dmvio_hip_tracker* t, int B, const int* new_slots, const 
   return 0;
 }
 
-static int stageLocked(dmvio_hip_tracker* t, int B, const int* new_slots, const float* new_exposures, const double* pose7_in, const double* aff_in, int coarsestLvl,
-                       const double* minRes) {
-  dmvio_hip_ctx* c = t->ctx;
-  BatchPipeline& pl = t->pipe;
-  if (int r = pl.reserve(B, c->stream)) return r;
-  int half;
-  if (int r = pl.stageInto(&half)) return r;
-  LMProblemIn* in = pl.in(half);
+// Cluster mode spins on a device-scope barrier, so every workgroup of such a launch must be resident at once: 256 CUs x 4 workgroups of 256 threads (k_track_lm, k_track_lm_w
+// and k_track_lm_pp all keep four per CU; resource figures in DESIGN.md).  One workgroup per problem has no such limit: batches beyond the resident slots simply queue.
+enum { LM_RESIDENT_WORKGROUPS = 1024 };
+
+// the caller's arrays -> the problem records the LM kernels read (minRes NULL: no abort thresholds, NaN; new_exposures NULL: 1)
+static void packProblems(LMProblemIn* in, int B, const int* new_slots, const float* new_exposures, const double* pose7_in, const double* aff_in, const double* minRes) {
   for (int i = 0; i < B; i++) {
-    if (new_slots[i] < 0 || new_slots[i] >= c->n_slots) return failmsg("track: frame slot out of range");
     LMProblemIn& p = in[i];
     memcpy(p.pose7, pose7_in + 7 * i, sizeof(double) * 7);
     p.aff[0] = aff_in[2 * i]; p.aff[1] = aff_in[2 * i + 1];
@@ -549,6 +287,42 @@ static int stageLocked(dmvio_hip_tracker* t, int B, const int* new_slots, const 
     p.new_slot = new_slots[i];
     p.new_exposure = new_exposures ? new_exposures[i] : 1.0f;
   }
+}
+// the result records -> the caller's arrays (every one optional); returns the evaluations and point evaluations of the batch
+struct LmWork { long long evals = 0, point_evals = 0; };
+static LmWork unpackResults(const LMProblemOut* out, int B, double* pose7_out, double* aff_out, double* lastResiduals, double* lastFlow, double* H, double* b, int* good,
+                            int* iterations) {
+  LmWork w;
+  for (int i = 0; i < B; i++) {
+    const LMProblemOut& o = out[i];
+    if (pose7_out) memcpy(pose7_out + 7 * i, o.pose7, sizeof(double) * 7);
+    if (aff_out) { aff_out[2 * i] = o.aff[0]; aff_out[2 * i + 1] = o.aff[1]; }
+    if (lastResiduals) memcpy(lastResiduals + 5 * i, o.lastRes, sizeof(double) * 5);
+    if (lastFlow) memcpy(lastFlow + 3 * i, o.flow, sizeof(double) * 3);
+    if (H) memcpy(H + 64 * i, o.H, sizeof(double) * 64);
+    if (b) memcpy(b + 8 * i, o.b, sizeof(double) * 8);
+    if (good) good[i] = o.good;
+    if (iterations) iterations[i] = o.iterations;
+    w.evals += o.n_evals; w.point_evals += o.n_point_evals;
+  }
+  return w;
+}
+// the launch argument of the k_track_lm kernels for C workgroups per problem; a cluster launch (C > 1) adds its exchange buffers
+static ClusterArgs clusterArgs(int C, LMProblemOut* discard, int res_only) {
+  ClusterArgs cl; cl.C = C; cl.part = nullptr; cl.cnt = nullptr; cl.discard = discard; cl.log = nullptr; cl.log_n = nullptr;
+  cl.res_only = res_only;
+  return cl;
+}
+
+static int stageLocked(dmvio_hip_tracker* t, int B, const int* new_slots, const float* new_exposures, const double* pose7_in, const double* aff_in, int coarsestLvl,
+                       const double* minRes) {
+  dmvio_hip_ctx* c = t->ctx;
+  BatchPipeline& pl = t->pipe;
+  if (int r = pl.reserve(B, c->stream)) return r;
+  int half;
+  if (int r = pl.stageInto(&half)) return r;
+  for (int i = 0; i < B; i++) if (new_slots[i] < 0 || new_slots[i] >= c->n_slots) return failmsg("track: frame slot out of range");
+  packProblems(pl.in(half), B, new_slots, new_exposures, pose7_in, aff_in, minRes);
   pl.stageDone(half, B, coarsestLvl);
   return 0;
 }
@@ -599,9 +373,7 @@ static LaunchShape chooseLaunchShape(int B, int pc0, int lm_threads, int lm_clus
   LaunchShape s;
   if (lm_cluster > 0) s.C = lm_cluster;
   else if (!lm_threads) s.C = clusterSize(B, pc0);
-  // cluster mode synchronises the workgroups of a problem with a device-scope barrier: all of them must be resident at once (256 CUs x 4); one
-  // workgroup per problem has no such limit — batches beyond the resident slots simply queue
-  if (s.C > 1 && (long)B * s.C > 1024) { s.refusal = "track_batch_launch: cluster size too large for the batch (B*C must be <= 1024 resident workgroups)"; return s; }
+  if (s.C > 1 && (long)B * s.C > LM_RESIDENT_WORKGROUPS) { s.refusal = "track_batch_launch: cluster size too large for the batch (B*C must be <= 1024 resident workgroups)"; return s; }
   // threads per workgroup: 256 in cluster mode and for full batches (four workgroups per CU); batches that cannot fill the CUs that way
   // (129..512 problems) take 512 threads per problem (measured: B=256 0.47 -> 0.40 ms, B=512 0.62 -> 0.58 ms)
   s.T = lm_threads ? lm_threads : (s.C > 1 ? 256 : (B <= 128 ? 1024 : (B <= 512 ? 512 : 256)));
@@ -631,8 +403,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
   const LaunchShape s = chooseLaunchShape(B, t->dev.pc_n[0], t->lm_threads_override, t->lm_cluster_override, t->batch_kernel == 1 && !t->debug_mode, any_tiled);
   if (s.refusal) return failmsg(s.refusal);
   const int C = s.C;
-  ClusterArgs cl; cl.C = C; cl.part = nullptr; cl.cnt = nullptr; cl.discard = pl.d_discard; cl.log = nullptr; cl.log_n = nullptr;
-  cl.res_only = t->res_only_evals;
+  ClusterArgs cl = clusterArgs(C, pl.d_discard, t->res_only_evals);
   if (t->debug_mode) {
     // diagnostics: 1 = record the evaluations of this launch, 2 = run the recorded evaluations again without the control steps (dmvio_hip_tracker_debug_record_replay)
     if (C != 1 || s.T != 256) return failmsg("tracker record / replay: full batches only (one 256-thread workgroup per problem)");
@@ -671,7 +442,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
     case LM_PP: {
       if (!t->d_pp_next) HIPCHK(hipMalloc((void**)&t->d_pp_next, sizeof(unsigned int)));
       HIPCHK(hipMemsetAsync(t->d_pp_next, 0, sizeof(unsigned int), c->stream));
-      const int grid = std::min((B + 1) / 2, 1024);   // 256 CUs x 4 resident workgroups at 128 registers
+      const int grid = std::min((B + 1) / 2, (int)LM_RESIDENT_WORKGROUPS);   // persistent: no more workgroups than are resident at 128 registers
       hipLaunchKernelGGL(k_track_lm_pp, dim3(grid), dim3(256), 0, c->stream, t->dev, c->fs, pin, pout, pl.staged_coarsest, B, t->d_pp_next);
       break;
     }
@@ -707,18 +478,12 @@ static int fetchLocked(dmvio_hip_tracker* t, double* pose7_out, double* aff_out,
   run.cluster = t->last.cluster; run.threads = t->last.threads; run.vio_iterations = t->last.vio_iterations;   // those belong to the launch / the last host-LM call
   run.repeat_lvl = std::move(t->last.repeat_lvl); run.first_pass_res = std::move(t->last.first_pass_res);     // (their storage, not their contents)
   run.repeat_lvl.resize(B); run.first_pass_res.resize(B);
+  const LmWork work = unpackResults(out, B, pose7_out, aff_out, lastResiduals, lastFlow, H, b, good, iterations);
+  run.evals = work.evals; run.point_evals = work.point_evals;
   for (int i = 0; i < B; i++) {
     const LMProblemOut& o = out[i];
-    if (pose7_out) memcpy(pose7_out + 7 * i, o.pose7, sizeof(double) * 7);
-    if (aff_out) { aff_out[2 * i] = o.aff[0]; aff_out[2 * i + 1] = o.aff[1]; }
-    if (lastResiduals) memcpy(lastResiduals + 5 * i, o.lastRes, sizeof(double) * 5);
-    if (lastFlow) memcpy(lastFlow + 3 * i, o.flow, sizeof(double) * 3);
-    if (H) memcpy(H + 64 * i, o.H, sizeof(double) * 64);
-    if (b) memcpy(b + 8 * i, o.b, sizeof(double) * 8);
-    if (good) good[i] = o.good;
-    if (iterations) iterations[i] = o.iterations;
     run.repeat_lvl[i] = o.repeated_lvl; run.first_pass_res[i] = o.first_pass_res;
-    run.evals += o.n_evals; run.point_evals += o.n_point_evals; run.ticks_step += o.ticks_step; run.ticks_eval += o.ticks_eval;
+    run.ticks_step += o.ticks_step; run.ticks_eval += o.ticks_eval;
     run.res_evals += o.n_res_evals; run.res_point_evals += o.n_res_point_evals;
   }
   t->last = std::move(run);
@@ -862,15 +627,6 @@ int dmvio_hip_tracker_debug_record_replay(dmvio_hip_tracker* t, int mode) {
   if (!t || mode < 0 || mode > 2) return failmsg("tracker_debug_record_replay: bad argument");
   std::lock_guard<std::mutex> lk(t->ctx->mu);
   t->debug_mode = mode;
-  return 0;
-}
-// Order in which setCoarseTrackingRef stores the template points of every level: 0 (default) = 8x8-pixel tiles, Z-ordered inside 16x16 blocks; 1 = the reference's
-// row-major order (CoarseTracker.cpp:249-293).  Takes effect with the next dmvio_hip_tracker_set_ref.  The sums of an evaluation are formed per 64-point group and then in
-// group order, so the two orders group the fp32 additions differently (results agree to rounding, like cluster sizes do); profiles/r05_tracker_floor.md has the measurement.
-int dmvio_hip_tracker_set_template_order(dmvio_hip_tracker* t, int row_major) {
-  if (!t) return failmsg("null tracker");
-  std::lock_guard<std::mutex> lk(t->ctx->mu);
-  t->R.order = row_major ? 1 : 0;
   return 0;
 }
 // Kernel of FULL batches (>= 512 problems, one 256-thread evaluation group per problem): 0 = k_track_lm (four wavefronts per problem: they evaluate, then three wait
@@ -1172,24 +928,6 @@ int dmvio_hip_tracker_track_new_coarse(dmvio_hip_tracker* t, int new_slot, float
   return 0;
 }
 
-}  // extern "C"
-
-int dmv_tracker_set_exchange(dmvio_hip_tracker* t, std::function<int(double*, size_t)> allreduce_sum, int rank, int world) {
-  if (!t) return failmsg("null tracker");
-  // dmvio_hip_tracker_debug_split_single_rank(t, 1) (tests): a group of ONE rank still takes the split path — every try is "mine", the all-reduce is the identity — so
-  // that the exchange (RCCL on the context's stream included) runs on a one-device box.  An explicit call on THIS tracker, never the environment.
-  const bool force1 = world == 1 && allreduce_sum && t->debug_split1;
-  if ((world <= 1 && !force1) || !allreduce_sum) { t->xchg = nullptr; t->xrank = 0; t->xworld = 0; return 0; }
-  if (rank < 0 || rank >= world) return failmsg("tracker_set_comm: 0 <= rank < world");
-  std::lock_guard<std::mutex> lk(t->ctx->mu);
-  t->xchg = std::move(allreduce_sum); t->xrank = rank; t->xworld = world;
-  return 0;
-}
-dmvio_hip_ctx* dmv_tracker_ctx(dmvio_hip_tracker* t) { return t ? t->ctx : nullptr; }
-bool dmv_tracker_debug_split1(dmvio_hip_tracker* t) { return t && t->debug_split1; }
-
-extern "C" {
-
 int dmvio_hip_tracker_debug_split_single_rank(dmvio_hip_tracker* t, int on) {
   if (!t) return failmsg("null tracker");
   t->debug_split1 = on != 0;
@@ -1250,44 +988,16 @@ int dmvio_hip_tracker_last_residual_only_work(dmvio_hip_tracker* t, long long* n
   return 0;
 }
 
-// FullSystem::printResult (FullSystem.cpp:256-298): one line "timestamp tx ty tz qx qy qz qw" per frame with a valid pose, 15
-// significant digits, poses relative to the first frame (camToFirst = firstPose^-1 * camToWorld); frames that are not keyframes are
-// re-based on their tracking reference's CURRENT pose when tracking_ref / camToTrackingRef7 are given (useCamToTrackingRef).
-// Host-only (no device work): the on-disk edge of the path, so that trajectories of both pipelines compare file against file.
-int dmvio_hip_write_result_txt(const char* path, int n, const double* timestamps, const double* camToWorld7, const unsigned char* pose_valid,
-                               const int* tracking_ref, const double* camToTrackingRef7, const double firstPose7[7]) {
-  if (!path || n < 0 || (n > 0 && (!timestamps || !camToWorld7)) || !firstPose7) return failmsg("write_result_txt: bad argument");
-  if (tracking_ref && !camToTrackingRef7) return failmsg("write_result_txt: tracking_ref without camToTrackingRef7");
-  FILE* f = fopen(path, "w");
-  if (!f) return failmsg("write_result_txt: cannot open the file");
-  const Pose firstInv = poseInv(poseFrom7(firstPose7));
-  for (int i = 0; i < n; i++) {
-    if (pose_valid && !pose_valid[i]) continue;
-    Pose c2w = poseFrom7(camToWorld7 + 7 * i);
-    if (tracking_ref && tracking_ref[i] >= 0) {
-      if (tracking_ref[i] >= n) { fclose(f); return failmsg("write_result_txt: tracking_ref out of range"); }
-      c2w = poseMul(poseFrom7(camToWorld7 + 7 * tracking_ref[i]), poseFrom7(camToTrackingRef7 + 7 * i));
-    }
-    double p[7];
-    poseTo7(poseMul(firstInv, c2w), p);
-    fprintf(f, "%.15g %.15g %.15g %.15g %.15g %.15g %.15g %.15g\n", timestamps[i], p[0], p[1], p[2], p[3], p[4], p[5], p[6]);
-  }
-  if (fclose(f) != 0) return failmsg("write_result_txt: write failed");
-  return 0;
-}
-
 // ------------------------------------------------------------------ W windows' frames against their own references in one launch
 // dmvio_hip_tracker_track_multi: every problem names its window, the kernel (k_track_lm_w) takes that window's reference out of a table in device memory.  The handle owns
 // what a call needs besides the trackers it reads — its own pipeline of pinned problem / result records, the cluster exchange buffers, the table with its pinned mirror —
 // so single and multi calls on the same trackers may be mixed freely.
-// Cluster mode spins on a device-scope barrier: every workgroup of the launch must be resident.  k_track_lm_w<256, 4, *> keeps four workgroups per CU (resource figures in
-// DESIGN.md, "k_track_lm_w"), 256 CUs: the same bound as dmvio_hip_tracker_track_batch's.
-enum { MULTI_RESIDENT_WORKGROUPS = 1024 };
+// Cluster launches stay within LM_RESIDENT_WORKGROUPS like dmvio_hip_tracker_track_batch's (k_track_lm_w<256, 4, *> keeps four workgroups per CU too).
 struct dmvio_hip_track_multi {
   dmvio_hip_ctx* ctx = nullptr;
   int max_windows = 0, max_problems = 0;
   BatchPipeline pipe;
-  float* d_cl_part = nullptr;          // MULTI_RESIDENT_WORKGROUPS x 2 x ACC_PAD partial sums (B x 2 x C x ACC_PAD of a launch, B * C within the bound)
+  float* d_cl_part = nullptr;          // LM_RESIDENT_WORKGROUPS x 2 x ACC_PAD partial sums (B x 2 x C x ACC_PAD of a launch, B * C within the bound)
   unsigned int* d_cl_cnt = nullptr;    // arrive counters, one per problem of a cluster launch
   char *h_table = nullptr, *d_table = nullptr;   // packed per call: W TrackerDev records, then ref_of[B]
   int lm_cluster = 0, res_only = 1;
@@ -1304,8 +1014,8 @@ dmvio_hip_track_multi* dmvio_hip_track_multi_create(dmvio_hip_ctx* c, int max_wi
   const size_t table_bytes = sizeof(TrackerDev) * (size_t)max_windows + sizeof(int) * (size_t)max_problems;
   auto init = [&]() -> int {
     if (int r = m->pipe.reserve(max_problems, c->stream)) return r;
-    HIPCHK(hipMalloc((void**)&m->d_cl_part, sizeof(float) * (size_t)MULTI_RESIDENT_WORKGROUPS * 2 * ACC_PAD));
-    HIPCHK(hipMalloc((void**)&m->d_cl_cnt, sizeof(unsigned int) * MULTI_RESIDENT_WORKGROUPS));
+    HIPCHK(hipMalloc((void**)&m->d_cl_part, sizeof(float) * (size_t)LM_RESIDENT_WORKGROUPS * 2 * ACC_PAD));
+    HIPCHK(hipMalloc((void**)&m->d_cl_cnt, sizeof(unsigned int) * LM_RESIDENT_WORKGROUPS));
     HIPCHK(hipMalloc((void**)&m->d_table, table_bytes));
     HIPCHK(hipHostMalloc((void**)&m->h_table, table_bytes, hipHostMallocDefault));
     return 0;
@@ -1381,7 +1091,7 @@ int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tra
   }
   if (B == 0) return 0;
   const int C = m->lm_cluster > 0 ? m->lm_cluster : clusterSize(B, pc0);
-  if (C > 1 && (long)B * C > MULTI_RESIDENT_WORKGROUPS)
+  if (C > 1 && (long)B * C > LM_RESIDENT_WORKGROUPS)
     return failmsg("track_multi: cluster size too large for the batch (B*C must be <= 1024 resident workgroups)");
   HIPCHK(hipSetDevice(c->device));
   BatchPipeline& pl = m->pipe;
@@ -1392,20 +1102,12 @@ int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tra
   TrackerDev* h_refs = reinterpret_cast<TrackerDev*>(m->h_table);
   int* h_ref_of = reinterpret_cast<int*>(m->h_table + sizeof(TrackerDev) * (size_t)W);
   for (int w = 0; w < W; w++) h_refs[w] = trackers[w]->dev;
+  memcpy(h_ref_of, window_of, sizeof(int) * (size_t)B);
   LMProblemIn* in = pl.in(half);
-  for (int i = 0; i < B; i++) {
-    h_ref_of[i] = window_of[i];
-    LMProblemIn& p = in[i];
-    memcpy(p.pose7, pose7_io + 7 * i, sizeof(double) * 7);
-    p.aff[0] = aff_io[2 * i]; p.aff[1] = aff_io[2 * i + 1];
-    for (int k = 0; k < 5; k++) p.minRes[k] = minRes ? minRes[5 * i + k] : NAN;
-    p.new_slot = new_slots[i];
-    p.new_exposure = new_exposures ? new_exposures[i] : 1.0f;
-  }
+  packProblems(in, B, new_slots, new_exposures, pose7_io, aff_io, minRes);
   pl.stageDone(half, B, coarsestLvl);
   HIPCHK(hipMemcpyAsync(m->d_table, m->h_table, sizeof(TrackerDev) * (size_t)W + sizeof(int) * (size_t)B, hipMemcpyHostToDevice, c->stream));
-  ClusterArgs cl; cl.C = C; cl.part = nullptr; cl.cnt = nullptr; cl.discard = pl.d_discard; cl.log = nullptr; cl.log_n = nullptr;
-  cl.res_only = m->res_only;
+  ClusterArgs cl = clusterArgs(C, pl.d_discard, m->res_only);
   if (C > 1) {
     HIPCHK(hipMemsetAsync(m->d_cl_cnt, 0, sizeof(unsigned int) * B, c->stream));
     cl.part = m->d_cl_part; cl.cnt = m->d_cl_cnt;
@@ -1421,172 +1123,8 @@ int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tra
   if (int r = pl.launched(c->stream)) return r;
   int nB;
   if (int r = pl.take(&half, &nB)) return r;
-  const LMProblemOut* out = pl.out(half);
-  long long evals = 0, point_evals = 0;
-  for (int i = 0; i < B; i++) {
-    const LMProblemOut& o = out[i];
-    memcpy(pose7_io + 7 * i, o.pose7, sizeof(double) * 7);
-    aff_io[2 * i] = o.aff[0]; aff_io[2 * i + 1] = o.aff[1];
-    if (lastResiduals) memcpy(lastResiduals + 5 * i, o.lastRes, sizeof(double) * 5);
-    if (lastFlow) memcpy(lastFlow + 3 * i, o.flow, sizeof(double) * 3);
-    if (H) memcpy(H + 64 * i, o.H, sizeof(double) * 64);
-    if (b) memcpy(b + 8 * i, o.b, sizeof(double) * 8);
-    if (good) good[i] = o.good;
-    if (iterations) iterations[i] = o.iterations;
-    evals += o.n_evals; point_evals += o.n_point_evals;
-  }
-  m->last_evals = evals; m->last_point_evals = point_evals;
-  return 0;
-}
-
-// ------------------------------------------------------------------ W trackers' reference templates in one pass
-// dmvio_hip_tracker_set_ref_batch: setCoarseTrackingRef + makeCoarseDepthL0 (CoarseTracker.cpp:524-538, 138-295) of W trackers of one context.  The handle owns what a call
-// needs besides the trackers' own buffers: a slab in pinned memory with its device copy (W RefWin records, the four point arrays of every window, their rank bytes: one
-// upload), the [W][levels] pc_n table with its pinned mirror (one download) and the ranking tables.  Every kernel runs over all W windows (ref_batch_kernels.hpp); the
-// trackers' scratch for the single call (d_pts) is not touched, so single and batched calls on one tracker may be mixed freely.
-struct dmvio_hip_set_ref_batch {
-  dmvio_hip_ctx* ctx = nullptr;
-  int max_windows = 0, max_points = 0;
-  size_t slab_bytes = 0;
-  char *h_slab = nullptr, *d_slab = nullptr;
-  int *h_pcn = nullptr, *d_pcn = nullptr;      // [max_windows][DMV_MAX_LEVELS]; a call uses [W][levels]
-  RefRanker ranker;
-  std::vector<const dmvio_hip_tracker*> seen;  // the duplicate test
-  int last_launches = 0, last_uploads = 0, last_downloads = 0, last_waits = 0;
-};
-// the slab: records, then floats, then bytes; every part starts on a 16-byte boundary
-static size_t refSlabPointsOff(int W) { return (sizeof(RefWin) * (size_t)W + 15) & ~(size_t)15; }
-static size_t refSlabRanksOff(int W, size_t total_points) { return (refSlabPointsOff(W) + sizeof(float) * 4 * total_points + 15) & ~(size_t)15; }
-
-dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* c, int max_windows, int max_points_per_window) {
-  if (!c) { failmsg("set_ref_batch_create: null context"); return nullptr; }
-  if (max_windows < 1 || max_points_per_window < 1) { failmsg("set_ref_batch_create: max_windows and max_points_per_window must be positive"); return nullptr; }
-  HIPCHKP(hipSetDevice(c->device));
-  dmvio_hip_set_ref_batch* b = new dmvio_hip_set_ref_batch();
-  b->ctx = c; b->max_windows = max_windows; b->max_points = max_points_per_window;
-  const size_t total = (size_t)max_windows * (size_t)max_points_per_window;
-  b->slab_bytes = refSlabRanksOff(max_windows, total) + total;
-  auto init = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&b->d_slab, b->slab_bytes));
-    HIPCHK(hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&b->d_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows));
-    HIPCHK(hipHostMalloc((void**)&b->h_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows, hipHostMallocDefault));
-    return 0;
-  };
-  if (init()) { dmvio_hip_set_ref_batch_destroy(b); return nullptr; }
-  return b;
-}
-
-void dmvio_hip_set_ref_batch_destroy(dmvio_hip_set_ref_batch* b) {
-  if (!b) return;
-  hipSetDevice(b->ctx->device);
-  hipStreamSynchronize(b->ctx->stream);
-  if (b->d_slab) hipFree(b->d_slab);
-  if (b->h_slab) hipHostFree(b->h_slab);
-  if (b->d_pcn) hipFree(b->d_pcn);
-  if (b->h_pcn) hipHostFree(b->h_pcn);
-  delete b;
-}
-
-int dmvio_hip_set_ref_batch_last_work(dmvio_hip_set_ref_batch* b, int* launches, int* uploads, int* downloads, int* waits) {
-  if (!b) return failmsg("set_ref_batch_last_work: null handle");
-  std::lock_guard<std::mutex> lk(b->ctx->mu);
-  if (launches) *launches = b->last_launches;
-  if (uploads) *uploads = b->last_uploads;
-  if (downloads) *downloads = b->last_downloads;
-  if (waits) *waits = b->last_waits;
-  return 0;
-}
-
-int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmvio_hip_set_ref_window* win) {
-  // every refusal stands before the first enqueue and before the first write to a tracker
-  if (!b) return failmsg("tracker_set_ref_batch: null handle");
-  if (W < 0 || W > b->max_windows) return failmsg("tracker_set_ref_batch: W outside 0 .. max_windows");
-  if (W > 0 && !win) return failmsg("tracker_set_ref_batch: null window array");
-  dmvio_hip_ctx* c = b->ctx;
-  std::lock_guard<std::mutex> lk(c->mu);
-  b->seen.clear();
-  size_t total = 0;
-  int max_n = 0;
-  for (int w = 0; w < W; w++) {
-    const dmvio_hip_set_ref_window& x = win[w];
-    if (!x.trk) return failmsg("tracker_set_ref_batch: null tracker");
-    if (x.trk->ctx != c) return failmsg("tracker_set_ref_batch: a tracker belongs to another context");
-    if (x.ref_slot < 0 || x.ref_slot >= c->n_slots) return failmsg("tracker_set_ref_batch: slot out of range");
-    if (x.n < 0 || x.n > b->max_points) return failmsg("tracker_set_ref_batch: n outside 0 .. max_points_per_window");
-    if (x.n > 0 && (!x.u || !x.v || !x.idepth || !x.hdiF)) return failmsg("tracker_set_ref_batch: null point array");
-    b->seen.push_back(x.trk);
-    total += (size_t)x.n;
-    max_n = std::max(max_n, x.n);
-  }
-  std::sort(b->seen.begin(), b->seen.end());
-  if (std::adjacent_find(b->seen.begin(), b->seen.end()) != b->seen.end())
-    return failmsg("tracker_set_ref_batch: the same tracker is named twice (two windows would write one set of buffers)");
-  b->last_launches = b->last_uploads = b->last_downloads = b->last_waits = 0;
-  if (W == 0) return 0;
-  HIPCHK(hipSetDevice(c->device));
-  // reference slots whose level 0 is stored in 8x4 tiles go back to row-major first, as in the single call (their launches are not part of last_work's figures)
-  for (int w = 0; w < W; w++) if (int r = dmv_ensure_row_major_locked(c, win[w].ref_slot)) return r;
-  hipStream_t s = c->stream;
-  RefLevels R = win[0].trk->R;   // the geometry is the context's, the same for every tracker; the storage order is the tracker's and travels in its record
-  R.order = 0;
-  const int n_tiles = win[0].trk->n_tiles, flow_words = (int)win[0].trk->flow_words;
-  const int n0 = R.w[0] * R.h[0];
-  // the slab: caller arrays are copied into the handle's pinned memory (internal.h: DmvBounce has the reason) and go up in one copy
-  RefWin* h_wins = reinterpret_cast<RefWin*>(b->h_slab);
-  size_t pts = refSlabPointsOff(W) / sizeof(float), ranks = refSlabRanksOff(W, total);
-  int max_rank = 0;
-  for (int w = 0; w < W; w++) {
-    const dmvio_hip_set_ref_window& x = win[w];
-    dmvio_hip_tracker* t = x.trk;
-    RefWin& V = h_wins[w];
-    V.idp = t->d_idp; V.wsp = t->d_wsp; V.idp2 = t->d_idp2; V.wsp2 = t->d_wsp2; V.dense = t->d_dense;
-    V.tile_count = t->d_tile_count; V.tile_base = t->d_tile_base; V.seg = t->d_seg; V.pc_n = t->d_pc_n;
-    V.pc = t->d_pc_ptrs; V.flow_mask = t->d_flow_mask;
-    V.pc_n_row = b->d_pcn + (size_t)w * R.levels;
-    V.pts_off = pts; V.rank_off = ranks;
-    V.ref_slot = x.ref_slot; V.n = x.n; V.order = t->R.order; V.max_rank = 0;
-    if (x.n > 0) {
-      float* hp = reinterpret_cast<float*>(b->h_slab) + pts;
-      memcpy(hp, x.u, sizeof(float) * x.n); memcpy(hp + x.n, x.v, sizeof(float) * x.n);
-      memcpy(hp + 2 * (size_t)x.n, x.idepth, sizeof(float) * x.n); memcpy(hp + 3 * (size_t)x.n, x.hdiF, sizeof(float) * x.n);
-      V.max_rank = b->ranker.rank(R.w[0], R.h[0], x.n, x.u, x.v, reinterpret_cast<unsigned char*>(b->h_slab) + ranks);
-    }
-    max_rank = std::max(max_rank, V.max_rank);
-    pts += 4 * (size_t)x.n; ranks += (size_t)x.n;
-  }
-  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, ranks, hipMemcpyHostToDevice, s));
-  b->last_uploads = 1;
-  const RefWin* d_wins = reinterpret_cast<const RefWin*>(b->d_slab);
-  const float* d_slab = reinterpret_cast<const float*>(b->d_slab);
-  int launches = 0;
-  const unsigned gw = (unsigned)W;
-  hipLaunchKernelGGL(k_ref_clear_w, dim3((unsigned)(((n0 + 3) / 4 + 255) / 256), gw), dim3(256), 0, s, d_wins, n0, flow_words); launches++;
-  // ranks 0 and 1 together, then every further rank of the batch behind them: a window whose own largest rank is below the launch's leaves at once
-  const unsigned gs = (unsigned)std::max(1, (max_n + 255) / 256);
-  for (int r = 1; r <= std::max(max_rank, 1); r++) {
-    hipLaunchKernelGGL(k_ref_scatter_w, dim3(gs, gw), dim3(256), 0, s, d_wins, d_slab, R.w[0], R.h[0], r == 1 ? 0 : r, r); launches++;
-  }
-  if (R.levels > 1) {
-    const size_t npool = R.total - R.off[1];
-    hipLaunchKernelGGL(k_ref_pool_w, dim3((unsigned)((npool + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
-  }
-  hipLaunchKernelGGL(k_ref_dilate_w, dim3((unsigned)((R.total + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
-  hipLaunchKernelGGL(k_ref_count_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->fs); launches++;
-  hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
-  hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->fs); launches++;
-  HIPCHK(hipGetLastError());
-  b->last_launches = launches;
-  HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * R.levels, hipMemcpyDeviceToHost, s));
-  b->last_downloads = 1;
-  HIPCHK(hipStreamSynchronize(s));
-  b->last_waits = 1;
-  for (int w = 0; w < W; w++) {
-    dmvio_hip_tracker* t = win[w].trk;
-    for (int l = 0; l < R.levels; l++) { t->dev.pc_n[l] = b->h_pcn[(size_t)w * R.levels + l]; t->dev.pc[l] = t->d_pc[l]; }
-    t->dev.ref_exposure = win[w].ref_exposure; t->dev.ref_aff_a = win[w].ref_aff_a; t->dev.ref_aff_b = win[w].ref_aff_b;
-    t->haveRef = true;
-  }
+  const LmWork work = unpackResults(pl.out(half), B, pose7_io, aff_io, lastResiduals, lastFlow, H, b, good, iterations);
+  m->last_evals = work.evals; m->last_point_evals = work.point_evals;
   return 0;
 }
 

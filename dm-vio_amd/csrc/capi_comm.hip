@@ -7,7 +7,7 @@
 #include <string>
 
 #include "../../include/dmvio_hip.h"
-#include "internal.h"
+#include "tracker_handle.h"
 #include "rccl_api.h"
 
 RcclApi& rccl() {
@@ -26,6 +26,20 @@ RcclApi& rccl() {
     api.ok = all;
   });
   return api;
+}
+
+// hypothesis-parallel trackNewCoarse: the element-wise fp64 sum over all ranks of a small HOST buffer, in place; dmvio_hip_tracker_track_new_coarse
+// (capi.hip) calls it
+static int dmv_tracker_set_exchange(dmvio_hip_tracker* t, std::function<int(double*, size_t)> allreduce_sum, int rank, int world) {
+  if (!t) return failmsg("null tracker");
+  // dmvio_hip_tracker_debug_split_single_rank(t, 1) (tests): a group of ONE rank still takes the split path — every try is "mine", the all-reduce is the identity — so
+  // that the exchange (RCCL on the context's stream included) runs on a one-device box.  An explicit call on THIS tracker, never the environment.
+  const bool force1 = world == 1 && allreduce_sum && t->debug_split1;
+  if ((world <= 1 && !force1) || !allreduce_sum) { t->xchg = nullptr; t->xrank = 0; t->xworld = 0; return 0; }
+  if (rank < 0 || rank >= world) return failmsg("tracker_set_comm: 0 <= rank < world");
+  std::lock_guard<std::mutex> lk(t->ctx->mu);
+  t->xchg = std::move(allreduce_sum); t->xrank = rank; t->xworld = world;
+  return 0;
 }
 
 extern "C" {
@@ -51,9 +65,9 @@ int dmvio_hip_comm_init_rank(dmvio_hip_ctx* ctx, const unsigned char id128[128],
 }
 // ---- hypothesis-parallel FullSystem::trackNewCoarse (include/dmvio_hip.h): the per-try records of dmvio_hip_tracker_track_new_coarse summed over the ranks
 int dmvio_hip_tracker_set_comm(dmvio_hip_tracker* t, void* nccl_comm, int rank, int world) {
-  dmvio_hip_ctx* c = dmv_tracker_ctx(t);
-  if (!c) return failmsg("null tracker");
-  const bool force1 = world == 1 && nccl_comm && dmv_tracker_debug_split1(t);   // test hook (dmvio_hip_tracker_debug_split_single_rank), see dmv_tracker_set_exchange
+  if (!t) return failmsg("null tracker");
+  dmvio_hip_ctx* c = t->ctx;
+  const bool force1 = world == 1 && nccl_comm && t->debug_split1;   // test hook (dmvio_hip_tracker_debug_split_single_rank), see dmv_tracker_set_exchange
   if (!nccl_comm || (world <= 1 && !force1)) return dmv_tracker_set_exchange(t, nullptr, 0, 0);
   ncclComm_t comm = (ncclComm_t)nccl_comm;
   RCCL_READY();
@@ -82,7 +96,7 @@ int dmvio_hip_tracker_set_comm(dmvio_hip_tracker* t, void* nccl_comm, int rank, 
   }, rank, world);
 }
 int dmvio_hip_tracker_set_comm_callbacks(dmvio_hip_tracker* t, const dmvio_hip_comm_callbacks* cb, int rank, int world) {
-  if (!dmv_tracker_ctx(t)) return failmsg("null tracker");
+  if (!t) return failmsg("null tracker");
   if (!cb || world <= 1) return dmv_tracker_set_exchange(t, nullptr, 0, 0);
   if (!cb->allreduce_sum_f64) return failmsg("tracker_set_comm_callbacks: allreduce_sum_f64 is required");
   const dmvio_hip_comm_callbacks k = *cb;

@@ -1,0 +1,289 @@
+// libdmvio_hip.so — C ABI implementation (include/dmvio_hip.h), the coarse tracker's reference template: setCoarseTrackingRef of one tracker and of W trackers per call, and
+// the queries of what it left.  gfx950 only.  The only unit that compiles ref_kernels.hpp and ref_batch_kernels.hpp.
+#include <hip/hip_runtime.h>
+#include <cstring>
+#include <mutex>
+#include <vector>
+#include <algorithm>
+
+#include "../../include/dmvio_hip.h"
+#include "common.h"
+#include "ref_kernels.hpp"
+#include "ref_batch_kernels.hpp"
+
+using namespace dmv;
+
+#include "tracker_handle.h"
+
+// what ends a setCoarseTrackingRef, single or batched: the template the kernels left (pcn: its points per level) becomes the tracker's reference
+static void refPublish(dmvio_hip_tracker* t, const int* pcn, float ref_exposure, double aff_a, double aff_b) {
+  for (int l = 0; l < t->R.levels; l++) { t->dev.pc_n[l] = pcn[l]; t->dev.pc[l] = t->d_pc[l]; }
+  t->dev.ref_exposure = ref_exposure; t->dev.ref_aff_a = aff_a; t->dev.ref_aff_b = aff_b;
+  t->haveRef = true;
+}
+
+extern "C" {
+
+int dmvio_hip_tracker_set_ref(dmvio_hip_tracker* t, int ref_slot, float ref_exposure, double aff_a, double aff_b,
+                              int n, const float* u, const float* v, const float* idepth, const float* hdiF) {
+  if (!t) return failmsg("tracker_set_ref: null tracker");
+  dmvio_hip_ctx* c = t->ctx;
+  if (ref_slot < 0 || ref_slot >= c->n_slots) return failmsg("tracker_set_ref: slot out of range");
+  if (n < 0 || (n > 0 && (!u || !v || !idepth || !hdiF))) return failmsg("tracker_set_ref: bad point arrays");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(hipSetDevice(c->device));
+  if (int r = dmv_ensure_row_major_locked(c, ref_slot)) return r;
+  hipStream_t s = c->stream;
+  if (n > t->pts_cap) {
+    if (t->d_pts) HIPCHK(hipFree(t->d_pts));
+    t->pts_cap = std::max(n, 4096);
+    HIPCHK(hipMalloc((void**)&t->d_pts, sizeof(float) * 5 * t->pts_cap));   // u, v, idepth, hdiF, [per-pixel rank bytes]
+  }
+  const RefLevels& R = t->R;
+  HIPCHK(hipMemsetAsync(t->d_idp, 0, sizeof(float) * R.w[0] * R.h[0], s));
+  HIPCHK(hipMemsetAsync(t->d_wsp, 0, sizeof(float) * R.w[0] * R.h[0], s));
+  if (n > 0) {
+    HIPCHK(c->bounce.h2d(t->d_pts + 0 * (size_t)t->pts_cap, u, sizeof(float) * n, s));      // through the library's pinned memory (internal.h: DmvBounce)
+    HIPCHK(c->bounce.h2d(t->d_pts + 1 * (size_t)t->pts_cap, v, sizeof(float) * n, s));
+    HIPCHK(c->bounce.h2d(t->d_pts + 2 * (size_t)t->pts_cap, idepth, sizeof(float) * n, s));
+    HIPCHK(c->bounce.h2d(t->d_pts + 3 * (size_t)t->pts_cap, hdiF, sizeof(float) * n, s));
+    // rank of every point among the points of its pixel (index order): pixels with more than two points are scattered rank by rank (k_ref_scatter)
+    t->h_rank.resize(n);
+    const int maxRank = t->ranker.rank(R.w[0], R.h[0], n, u, v, t->h_rank.data());
+    const unsigned char* d_rank = nullptr;
+    if (maxRank >= 2) {
+      HIPCHK(c->bounce.h2d(t->d_pts + 4 * (size_t)t->pts_cap, t->h_rank.data(), (size_t)n, s));
+      d_rank = (const unsigned char*)(t->d_pts + 4 * (size_t)t->pts_cap);
+    }
+    for (int r = 1; r <= std::max(maxRank, 1); r++)
+      hipLaunchKernelGGL(k_ref_scatter, dim3((n + 255) / 256), dim3(256), 0, s, n, t->d_pts, t->d_pts + t->pts_cap, t->d_pts + 2 * (size_t)t->pts_cap,
+                         t->d_pts + 3 * (size_t)t->pts_cap, t->d_idp, t->d_wsp, R.w[0], R.h[0], d_rank, r == 1 ? 0 : r, r);
+  }
+  if (R.levels > 1) {
+    const size_t npool = R.total - R.off[1];
+    hipLaunchKernelGGL(k_ref_pool, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp);
+  }
+  hipLaunchKernelGGL(k_ref_dilate, dim3((unsigned)((R.total + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp, t->d_idp2, t->d_wsp2);
+  HIPCHK(hipMemsetAsync(t->d_flow_mask, 0, sizeof(unsigned long long) * t->flow_words, s));
+  hipLaunchKernelGGL(k_ref_count, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->fs, ref_slot, t->d_tile_count, t->d_seg);
+  hipLaunchKernelGGL(k_ref_scan, dim3(2 * R.levels), dim3(1024), 0, s, R, t->d_tile_count, t->d_tile_base, t->d_pc_n, t->d_seg);
+  hipLaunchKernelGGL(k_ref_write, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->fs, ref_slot, t->d_tile_base, t->d_seg, t->d_pc_ptrs,
+                     t->d_dense, t->d_flow_mask);
+  HIPCHK(hipGetLastError());
+  int pcn[DMV_MAX_LEVELS] = {};
+  HIPCHK(c->bounce.d2h(pcn, t->d_pc_n, sizeof(int) * R.levels, s));
+  HIPCHK(c->bounce.finish(s));
+  refPublish(t, pcn, ref_exposure, aff_a, aff_b);
+  return 0;
+}
+
+int dmvio_hip_tracker_pc_n(dmvio_hip_tracker* t, int lvl) {
+  if (!t || lvl < 0 || lvl >= t->ctx->levels) return failmsg("tracker_pc_n: bad argument");
+  return t->dev.pc_n[lvl];
+}
+
+int dmvio_hip_tracker_get_pc(dmvio_hip_tracker* t, int lvl, float* u, float* v, float* idepth, float* color) {
+  if (!t || lvl < 0 || lvl >= t->ctx->levels) return failmsg("tracker_get_pc: bad argument");
+  dmvio_hip_ctx* c = t->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(hipSetDevice(c->device));
+  const int n = t->dev.pc_n[lvl];
+  std::vector<float4> tmp(n);
+  HIPCHK(c->bounce.d2h(tmp.data(), t->d_pc[lvl], sizeof(float4) * n, c->stream));
+  HIPCHK(c->bounce.finish(c->stream));
+  // the device keeps the template in tile order; hand it out in the reference's row-major order (y, then x)
+  std::sort(tmp.begin(), tmp.end(), [](const float4& a, const float4& b) { return a.y < b.y || (a.y == b.y && a.x < b.x); });
+  for (int i = 0; i < n; i++) { u[i] = tmp[i].x; v[i] = tmp[i].y; idepth[i] = tmp[i].z; color[i] = tmp[i].w; }
+  return 0;
+}
+
+// The dense maps CoarseTracker keeps next to the template: idepth[lvl] and weightSums[lvl] as makeCoarseDepthL0 leaves them (CoarseTracker.cpp:249-293; read by
+// debugPlotIDepthMap / debugPlotIDepthMapFloat, :772-880, when output wrappers exist).  Debug path: the dilated planes come back from the device and the normalisation loop is
+// replayed on the host; whether a pixel with weight became a template point (finite reference colour, idepth > 0) is taken from the template itself.
+int dmvio_hip_tracker_get_idepth_map(dmvio_hip_tracker* t, int lvl, float* idepth_out, float* weightSums_out) {
+  if (!t || lvl < 0 || lvl >= t->ctx->levels || !idepth_out) return failmsg("tracker_get_idepth_map: bad argument");
+  if (!t->haveRef) return failmsg("tracker_get_idepth_map: setCoarseTrackingRef not called");
+  dmvio_hip_ctx* c = t->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(hipSetDevice(c->device));
+  const RefLevels& R = t->R;
+  const int wl = R.w[lvl], hl = R.h[lvl], n = t->dev.pc_n[lvl];
+  const size_t npx = (size_t)wl * hl;
+  std::vector<float> ws(npx);
+  std::vector<float4> pc(n);
+  HIPCHK(c->bounce.d2h(idepth_out, t->d_idp2 + R.off[lvl], sizeof(float) * npx, c->stream));
+  HIPCHK(c->bounce.d2h(ws.data(), t->d_wsp2 + R.off[lvl], sizeof(float) * npx, c->stream));
+  if (n) HIPCHK(c->bounce.d2h(pc.data(), t->d_pc[lvl], sizeof(float4) * n, c->stream));
+  HIPCHK(c->bounce.finish(c->stream));
+  std::vector<unsigned char> kept(npx, 0);
+  for (int i = 0; i < n; i++) kept[(size_t)pc[i].x + (size_t)pc[i].y * wl] = 1;
+  for (int y = 2; y < hl - 2; y++)
+    for (int x = 2; x < wl - 2; x++) {
+      const size_t i = (size_t)x + (size_t)y * wl;
+      if (ws[i] > 0) {
+        idepth_out[i] /= ws[i];
+        if (!kept[i]) { idepth_out[i] = -1; continue; }   // the reference's "just skip if something is wrong": weightSums keeps its value
+      } else
+        idepth_out[i] = -1;
+      ws[i] = 1;
+    }
+  if (weightSums_out) memcpy(weightSums_out, ws.data(), sizeof(float) * npx);
+  return 0;
+}
+// Order in which setCoarseTrackingRef stores the template points of every level: 0 (default) = 8x8-pixel tiles, Z-ordered inside 16x16 blocks; 1 = the reference's
+// row-major order (CoarseTracker.cpp:249-293).  Takes effect with the next dmvio_hip_tracker_set_ref.  The sums of an evaluation are formed per 64-point group and then in
+// group order, so the two orders group the fp32 additions differently (results agree to rounding, like cluster sizes do); profiles/r05_tracker_floor.md has the measurement.
+int dmvio_hip_tracker_set_template_order(dmvio_hip_tracker* t, int row_major) {
+  if (!t) return failmsg("null tracker");
+  std::lock_guard<std::mutex> lk(t->ctx->mu);
+  t->R.order = row_major ? 1 : 0;
+  return 0;
+}
+
+// ------------------------------------------------------------------ W trackers' reference templates in one pass
+// dmvio_hip_tracker_set_ref_batch: setCoarseTrackingRef + makeCoarseDepthL0 (CoarseTracker.cpp:524-538, 138-295) of W trackers of one context.  The handle owns what a call
+// needs besides the trackers' own buffers: a slab in pinned memory with its device copy (W RefWin records, the four point arrays of every window, their rank bytes: one
+// upload), the [W][levels] pc_n table with its pinned mirror (one download) and the ranking tables.  Every kernel runs over all W windows (ref_batch_kernels.hpp); the
+// trackers' scratch for the single call (d_pts) is not touched, so single and batched calls on one tracker may be mixed freely.
+struct dmvio_hip_set_ref_batch {
+  dmvio_hip_ctx* ctx = nullptr;
+  int max_windows = 0, max_points = 0;
+  size_t slab_bytes = 0;
+  char *h_slab = nullptr, *d_slab = nullptr;
+  int *h_pcn = nullptr, *d_pcn = nullptr;      // [max_windows][DMV_MAX_LEVELS]; a call uses [W][levels]
+  RefRanker ranker;
+  std::vector<const dmvio_hip_tracker*> seen;  // the duplicate test
+  int last_launches = 0, last_uploads = 0, last_downloads = 0, last_waits = 0;
+};
+// the slab: records, then floats, then bytes; every part starts on a 16-byte boundary
+static size_t refSlabPointsOff(int W) { return (sizeof(RefWin) * (size_t)W + 15) & ~(size_t)15; }
+static size_t refSlabRanksOff(int W, size_t total_points) { return (refSlabPointsOff(W) + sizeof(float) * 4 * total_points + 15) & ~(size_t)15; }
+
+dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* c, int max_windows, int max_points_per_window) {
+  if (!c) { failmsg("set_ref_batch_create: null context"); return nullptr; }
+  if (max_windows < 1 || max_points_per_window < 1) { failmsg("set_ref_batch_create: max_windows and max_points_per_window must be positive"); return nullptr; }
+  HIPCHKP(hipSetDevice(c->device));
+  dmvio_hip_set_ref_batch* b = new dmvio_hip_set_ref_batch();
+  b->ctx = c; b->max_windows = max_windows; b->max_points = max_points_per_window;
+  const size_t total = (size_t)max_windows * (size_t)max_points_per_window;
+  b->slab_bytes = refSlabRanksOff(max_windows, total) + total;
+  auto init = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&b->d_slab, b->slab_bytes));
+    HIPCHK(hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&b->d_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows));
+    HIPCHK(hipHostMalloc((void**)&b->h_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows, hipHostMallocDefault));
+    return 0;
+  };
+  if (init()) { dmvio_hip_set_ref_batch_destroy(b); return nullptr; }
+  return b;
+}
+
+void dmvio_hip_set_ref_batch_destroy(dmvio_hip_set_ref_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
+  if (b->d_slab) hipFree(b->d_slab);
+  if (b->h_slab) hipHostFree(b->h_slab);
+  if (b->d_pcn) hipFree(b->d_pcn);
+  if (b->h_pcn) hipHostFree(b->h_pcn);
+  delete b;
+}
+
+int dmvio_hip_set_ref_batch_last_work(dmvio_hip_set_ref_batch* b, int* launches, int* uploads, int* downloads, int* waits) {
+  if (!b) return failmsg("set_ref_batch_last_work: null handle");
+  std::lock_guard<std::mutex> lk(b->ctx->mu);
+  if (launches) *launches = b->last_launches;
+  if (uploads) *uploads = b->last_uploads;
+  if (downloads) *downloads = b->last_downloads;
+  if (waits) *waits = b->last_waits;
+  return 0;
+}
+
+int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmvio_hip_set_ref_window* win) {
+  // every refusal stands before the first enqueue and before the first write to a tracker
+  if (!b) return failmsg("tracker_set_ref_batch: null handle");
+  if (W < 0 || W > b->max_windows) return failmsg("tracker_set_ref_batch: W outside 0 .. max_windows");
+  if (W > 0 && !win) return failmsg("tracker_set_ref_batch: null window array");
+  dmvio_hip_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  b->seen.clear();
+  size_t total = 0;
+  int max_n = 0;
+  for (int w = 0; w < W; w++) {
+    const dmvio_hip_set_ref_window& x = win[w];
+    if (!x.trk) return failmsg("tracker_set_ref_batch: null tracker");
+    if (x.trk->ctx != c) return failmsg("tracker_set_ref_batch: a tracker belongs to another context");
+    if (x.ref_slot < 0 || x.ref_slot >= c->n_slots) return failmsg("tracker_set_ref_batch: slot out of range");
+    if (x.n < 0 || x.n > b->max_points) return failmsg("tracker_set_ref_batch: n outside 0 .. max_points_per_window");
+    if (x.n > 0 && (!x.u || !x.v || !x.idepth || !x.hdiF)) return failmsg("tracker_set_ref_batch: null point array");
+    b->seen.push_back(x.trk);
+    total += (size_t)x.n;
+    max_n = std::max(max_n, x.n);
+  }
+  std::sort(b->seen.begin(), b->seen.end());
+  if (std::adjacent_find(b->seen.begin(), b->seen.end()) != b->seen.end())
+    return failmsg("tracker_set_ref_batch: the same tracker is named twice (two windows would write one set of buffers)");
+  b->last_launches = b->last_uploads = b->last_downloads = b->last_waits = 0;
+  if (W == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  // reference slots whose level 0 is stored in 8x4 tiles go back to row-major first, as in the single call (their launches are not part of last_work's figures)
+  for (int w = 0; w < W; w++) if (int r = dmv_ensure_row_major_locked(c, win[w].ref_slot)) return r;
+  hipStream_t s = c->stream;
+  RefLevels R = win[0].trk->R;   // the geometry is the context's, the same for every tracker; the storage order is the tracker's and travels in its record
+  R.order = 0;
+  const int n_tiles = win[0].trk->n_tiles, flow_words = (int)win[0].trk->flow_words;
+  const int n0 = R.w[0] * R.h[0];
+  // the slab: caller arrays are copied into the handle's pinned memory (internal.h: DmvBounce has the reason) and go up in one copy
+  RefWin* h_wins = reinterpret_cast<RefWin*>(b->h_slab);
+  size_t pts = refSlabPointsOff(W) / sizeof(float), ranks = refSlabRanksOff(W, total);
+  int max_rank = 0;
+  for (int w = 0; w < W; w++) {
+    const dmvio_hip_set_ref_window& x = win[w];
+    dmvio_hip_tracker* t = x.trk;
+    RefWin& V = h_wins[w];
+    V.idp = t->d_idp; V.wsp = t->d_wsp; V.idp2 = t->d_idp2; V.wsp2 = t->d_wsp2; V.dense = t->d_dense;
+    V.tile_count = t->d_tile_count; V.tile_base = t->d_tile_base; V.seg = t->d_seg; V.pc_n = t->d_pc_n;
+    V.pc = t->d_pc_ptrs; V.flow_mask = t->d_flow_mask;
+    V.pc_n_row = b->d_pcn + (size_t)w * R.levels;
+    V.pts_off = pts; V.rank_off = ranks;
+    V.ref_slot = x.ref_slot; V.n = x.n; V.order = t->R.order; V.max_rank = 0;
+    if (x.n > 0) {
+      float* hp = reinterpret_cast<float*>(b->h_slab) + pts;
+      memcpy(hp, x.u, sizeof(float) * x.n); memcpy(hp + x.n, x.v, sizeof(float) * x.n);
+      memcpy(hp + 2 * (size_t)x.n, x.idepth, sizeof(float) * x.n); memcpy(hp + 3 * (size_t)x.n, x.hdiF, sizeof(float) * x.n);
+      V.max_rank = b->ranker.rank(R.w[0], R.h[0], x.n, x.u, x.v, reinterpret_cast<unsigned char*>(b->h_slab) + ranks);
+    }
+    max_rank = std::max(max_rank, V.max_rank);
+    pts += 4 * (size_t)x.n; ranks += (size_t)x.n;
+  }
+  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, ranks, hipMemcpyHostToDevice, s));
+  b->last_uploads = 1;
+  const RefWin* d_wins = reinterpret_cast<const RefWin*>(b->d_slab);
+  const float* d_slab = reinterpret_cast<const float*>(b->d_slab);
+  int launches = 0;
+  const unsigned gw = (unsigned)W;
+  hipLaunchKernelGGL(k_ref_clear_w, dim3((unsigned)(((n0 + 3) / 4 + 255) / 256), gw), dim3(256), 0, s, d_wins, n0, flow_words); launches++;
+  // ranks 0 and 1 together, then every further rank of the batch behind them: a window whose own largest rank is below the launch's leaves at once
+  const unsigned gs = (unsigned)std::max(1, (max_n + 255) / 256);
+  for (int r = 1; r <= std::max(max_rank, 1); r++) {
+    hipLaunchKernelGGL(k_ref_scatter_w, dim3(gs, gw), dim3(256), 0, s, d_wins, d_slab, R.w[0], R.h[0], r == 1 ? 0 : r, r); launches++;
+  }
+  if (R.levels > 1) {
+    const size_t npool = R.total - R.off[1];
+    hipLaunchKernelGGL(k_ref_pool_w, dim3((unsigned)((npool + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
+  }
+  hipLaunchKernelGGL(k_ref_dilate_w, dim3((unsigned)((R.total + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
+  hipLaunchKernelGGL(k_ref_count_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->fs); launches++;
+  hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
+  hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->fs); launches++;
+  HIPCHK(hipGetLastError());
+  b->last_launches = launches;
+  HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * R.levels, hipMemcpyDeviceToHost, s));
+  b->last_downloads = 1;
+  HIPCHK(hipStreamSynchronize(s));
+  b->last_waits = 1;
+  for (int w = 0; w < W; w++) refPublish(win[w].trk, b->h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
+  return 0;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // internals shared by the translation units of libdmvio_hip.so.  capi_frames.hip defines the error string, the context (dmvio_hip_ctx) with its frame store and
-// dmv_ensure_row_major*; capi.hip is the coarse tracker (the definition of dmvio_hip_tracker stays private to it); every other unit is one handle type of its own.
+// dmv_ensure_row_major*; capi.hip is the coarse tracker and capi_ref.hip its reference template (their handle: tracker_handle.h); every other unit is one handle type of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -166,11 +166,3 @@ int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, c
 // call's records (record_bytes per window, checked against what the batch reserves).  0 or <0.
 struct dmvio_hip_pixel_selector_batch;
 int dmv_selector_batch_traces(dmvio_hip_pixel_selector_batch* b, size_t record_bytes, dmvio_hip_ctx** ctx, int* max_windows, char** d_records);
-
-// hypothesis-parallel trackNewCoarse: the element-wise fp64 sum over all ranks of a small HOST buffer, in place (set by dmvio_hip_tracker_set_comm /
-// _set_comm_callbacks in capi_comm.hip, next to the RCCL loader; used by dmvio_hip_tracker_track_new_coarse in capi.hip, which keeps the two accessors below because
-// the tracker's definition needs kernel headers that no second unit may compile)
-struct dmvio_hip_tracker;
-int dmv_tracker_set_exchange(dmvio_hip_tracker* t, std::function<int(double*, size_t)> allreduce_sum, int rank, int world);
-dmvio_hip_ctx* dmv_tracker_ctx(dmvio_hip_tracker* t);
-bool dmv_tracker_debug_split1(dmvio_hip_tracker* t);

@@ -14,19 +14,6 @@
 
 namespace dmv {
 
-struct RefLevels {
-  int levels;
-  int w[DMV_MAX_LEVELS], h[DMV_MAX_LEVELS];
-  size_t off[DMV_MAX_LEVELS];      // offset of the level inside the concatenated per-pixel float planes
-  int tile_off[DMV_MAX_LEVELS + 1];  // first 16x16 block of each level
-  int blocks_x[DMV_MAX_LEVELS];      // 16x16 blocks per row of the level
-  int seg_x0;                        // level 0: 8-pixel segments per row (row-major rank reconstruction)
-  int seg_x[DMV_MAX_LEVELS];         // 8-pixel segments per row of every level, and where the level's (row, segment) counts start in seg_count
-  int seg_off[DMV_MAX_LEVELS + 1];
-  int order;                         // 0: the template is stored in tile order; 1: in the reference's row-major order (dmvio_hip_tracker_set_template_order)
-  size_t total;                    // total pixels over all levels
-};
-
 // The reference adds the points of a pixel one after the other (CoarseTracker.cpp:151-165).  Two float atomics on one pixel commute (0 + a + b); a third
 // would make the sum depend on the arrival order, so the host ranks the points of every pixel by index (`rank`, NULL when no pixel holds more than two) and
 // launches ranks [0,1] together and every further rank as its own launch behind them: sequential order, no data race.

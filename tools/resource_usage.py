@@ -8,7 +8,7 @@ args = [a for a in sys.argv[1:] if not a.startswith("--")]
 flt = None
 if "--filter" in sys.argv:
     flt = sys.argv[sys.argv.index("--filter") + 1]; args = [a for a in args if a != flt]
-srcs = args or ["capi.hip", "capi_frames.hip", "capi_ba.hip", "capi_immature.hip", "capi_init.hip"]
+srcs = args or ["capi.hip", "capi_ref.hip", "capi_frames.hip", "capi_ba.hip", "capi_immature.hip", "capi_init.hip"]
 flags = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp".split()
 print("| kernel | SGPRs | VGPRs | AGPRs | spilled SGPRs | spilled VGPRs | scratch B/lane | waves/SIMD | LDS B |"); print("|---|---|---|---|---|---|---|---|---|")
 for s in srcs:
