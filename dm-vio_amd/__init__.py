@@ -96,6 +96,12 @@ class ActivationWindow(C.Structure):
                 ("minTraceQuality", C.c_float), ("n_selected", C.c_int), ("n_deleted", C.c_int)]
 
 
+class BAMargWindow(C.Structure):
+    """dmvio_hip_ba_marg_window: one window of dmvio_hip_ba_marginalize_points_batch."""
+    _fields_ = [("ba", C.c_void_p), ("candidates", C.c_void_p), ("decision", C.c_void_p), ("Hadd", C.c_void_p), ("badd", C.c_void_p), ("resInM", C.c_int),
+                ("update_prior", C.c_int)]
+
+
 class ActivationOptimize(C.Structure):
     """dmvio_hip_activation_optimize: one window of dmvio_hip_immature_optimize_selected_batch."""
     _fields_ = [("imm", C.c_void_p), ("F", C.c_int), ("frame_slots", c_i), ("w2c7", c_d), ("aff2", c_d), ("exposure", c_f), ("minObs", C.c_int), ("result", c_i),
@@ -1535,6 +1541,43 @@ class BundleAdjusterBatch:
         rm = np.zeros(W, np.float32); fe = np.zeros(W); it = np.zeros(W, np.int32); tr = np.zeros((W, 64, 4))
         _chk(self.L, self.L.dmvio_hip_ba_optimize_batch(self.p, W, hs, its, rm.ctypes.data, fe.ctypes.data, it.ctypes.data, tr.ctypes.data), "ba_optimize_batch")
         return [dict(rmse=float(rm[k]), finalEnergy=float(fe[k]), iterations=int(it[k]), trace=tr[k, :it[k] + 1].copy()) for k in range(W)]
+
+    def marginalize_points(self, windows, candidates, update_prior=False, want_system=True):
+        """dmvio_hip_ba_marginalize_points_batch: BundleAdjusterHip.marginalize_points for W windows in one call.  candidates: one array per window; update_prior /
+        want_system: one flag for all windows or one per window (want_system False passes Hadd / badd as NULL).  Returns [(decision[N], Hadd, badd, resInM)] per window
+        (Hadd / badd None where not wanted)."""
+        W = len(windows)
+        up = list(update_prior) if isinstance(update_prior, (list, tuple)) else [update_prior] * W
+        ws = list(want_system) if isinstance(want_system, (list, tuple)) else [want_system] * W
+        fn = self.L.dmvio_hip_ba_marginalize_points_batch; fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(BAMargWindow)]; fn.restype = C.c_int
+        arr = (BAMargWindow * max(W, 1))()
+        keep = []
+        for k, w in enumerate(windows):
+            cand = np.ascontiguousarray(candidates[k], dtype=np.uint8)
+            assert cand.size == w.N, (cand.size, w.N)
+            dec = np.zeros(w.N, np.uint8)
+            H = np.zeros((w.n, w.n)) if ws[k] else None
+            b = np.zeros(w.n) if ws[k] else None
+            keep.append((cand, dec, H, b))
+            arr[k].ba = w.p.value if isinstance(w.p, C.c_void_p) else w.p; arr[k].candidates = cand.ctypes.data; arr[k].decision = dec.ctypes.data
+            arr[k].Hadd = H.ctypes.data if ws[k] else None; arr[k].badd = b.ctypes.data if ws[k] else None
+            arr[k].resInM = -1; arr[k].update_prior = 1 if up[k] else 0
+        _chk(self.L, fn(self.p, W, arr), "ba_marginalize_points_batch")
+        return [(keep[k][1], keep[k][2], keep[k][3], int(arr[k].resInM)) for k in range(W)]
+
+    def last_marg_ms(self):
+        """with set_profile(True): HIP-event time (ms) of the last marginalize_points call's device work, first upload to the download"""
+        ms = C.c_float(0)
+        fn = self.L.dmvio_hip_ba_batch_last_marg_ms; fn.argtypes = [C.c_void_p, C.POINTER(C.c_float)]; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, C.byref(ms)), "ba_batch_last_marg_ms")
+        return float(ms.value)
+
+    def last_marg_work(self):
+        """what the last marginalize_points call enqueued: dict(launches, uploads, downloads, waits)"""
+        v = [C.c_int(0) for _ in range(4)]
+        fn = self.L.dmvio_hip_ba_batch_last_marg_work; fn.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, *[C.byref(x) for x in v]), "ba_batch_last_marg_work")
+        return dict(launches=v[0].value, uploads=v[1].value, downloads=v[2].value, waits=v[3].value)
 
     def last_ms(self):
         ms = np.zeros(3, np.float32)

@@ -117,6 +117,20 @@ struct BatchLayout {
   size_t outStride() const { return padded(sizeof(double) * (outSysL() + sysLDoubles())); }
   size_t mirrorUsed() const { return MIRROR_XLAST + n; }
   bool fitsIn(const BatchLayout& cap) const { return tabUsed() <= cap.tabStride() && outStride() <= cap.outStride() && mirrorUsed() <= MIRROR_STRIDE; }
+  // ---- dmvio_hip_ba_marginalize_points_batch in the same slabs (a call owns them from its first line to its last wait: the batch's lock)
+  //   tables (byte offsets)              [pre F2 | adHost F2 x 64 | adTarget F2 x 64 doubles]: the adjoints only of a window whose device copy is stale
+  //   marginalisation buffer (bytes)     [candidates of every window, N bytes each, padded] then per window [sys 2 (n x n + n) | resInA doubles | decisions N bytes, padded]:
+  //                                      the first part goes up in one copy, the second comes back in one
+  size_t margTabPre() const { return 0; }
+  size_t margTabAdBytes() const { return sizeof(double) * F2 * 64; }
+  size_t margTabAdHost() const { return padded(tabPreBytes()); }
+  size_t margTabAdTarget() const { return margTabAdHost() + margTabAdBytes(); }
+  size_t margTabUsed(const bool adjoints) const { return adjoints ? margTabAdTarget() + margTabAdBytes() : tabPreBytes(); }
+  size_t margSysDoubles() const { return outResInA() + 1; }
+  static size_t margCandBytes(const size_t N) { return padded(N); }
+  size_t margOutDecision() const { return sizeof(double) * margSysDoubles(); }
+  size_t margOutBytes(const size_t N) const { return padded(margOutDecision() + N); }
+  bool margFitsIn(const BatchLayout& cap) const { return margTabUsed(true) <= cap.tabStride(); }
 };
 struct dmvio_hip_ba_batch {
   BAWorkers workers;
@@ -148,6 +162,14 @@ struct dmvio_hip_ba_batch {
   int lin_lanes = 1;               // dmvio_hip_ba_batch_set_linearize_lanes: 1 = k_ba_linearize_b1 (one lane per residual) from 4 windows on, 8 = always the eight-lane kernel
   int streams = 0;                 // dmvio_hip_ba_batch_set_streams: 0 = automatic, k >= 1 = at most k groups (1: the whole batch on one stream)
   int profile = 0;                 // dmvio_hip_ba_batch_set_profile: events around the stepped linearisation of iteration 1 (k_ba_linearize_b of all windows)
+  // dmvio_hip_ba_marginalize_points_batch: the candidates / systems / decisions of a call (BatchLayout), device and pinned, grown on demand and kept; the event that puts a
+  // handle's own pending work in front of the call; what the last call enqueued
+  char* d_marg = nullptr;
+  char* h_marg = nullptr;
+  size_t marg_cap = 0;
+  hipEvent_t marg_ev = nullptr;
+  int marg_work[4] = {0, 0, 0, 0};   // launches, uploads, downloads, waits
+  float marg_ms = 0;                 // with `profile`: HIP events around the last call's device work (first upload .. the download)
 };
 extern "C" {
 dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
@@ -184,6 +206,9 @@ void dmvio_hip_ba_batch_destroy(dmvio_hip_ba_batch* B) {
   if (B->h_tab) hipHostFree(B->h_tab);
   if (B->d_out) hipFree(B->d_out);
   if (B->h_trace) hipHostFree(B->h_trace);
+  if (B->d_marg) hipFree(B->d_marg);
+  if (B->h_marg) hipHostFree(B->h_marg);
+  if (B->marg_ev) hipEventDestroy(B->marg_ev);
   for (int k = 0; k < 8; k++) if (B->ev[k]) hipEventDestroy(B->ev[k]);
   for (int g = 1; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS; g++) if (B->gstream[g]) { hipStreamSynchronize(B->gstream[g]); hipStreamDestroy(B->gstream[g]); }
   for (int g = 0; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS; g++) for (int k = 0; k < 3; k++) if (B->gev[g][k]) hipEventDestroy(B->gev[g][k]);
@@ -641,7 +666,223 @@ static int optimizeBatchGroup(dmvio_hip_ba_batch* B, const int Wn, dmvio_hip_ba*
   return c.collect(rmse, finalEnergy, iterations, trace);
 }
 
+// ================================================================================================= point marginalisation, W windows per call
+// dmvio_hip_ba_marginalize_points (capi_ba.hip) for W windows: FullSystem::flagPointsForRemoval's relinearisation (FullSystem.cpp:829-859) + marginalizePointsF
+// (EnergyFunctional.cpp:678-742).  The windows are ordered by keyframe count (the stitch kernels want one F per launch; the caller's order inside a count), every window's
+// record, pair table, candidates and — where the device copy is stale — adjoints are filled in the pinned slabs and go up in three copies; per count six launches
+// (ba_batch_kernels.hpp); the systems and decisions come back in one copy behind one wait; then the host tail of the single call per window.  What the single call does to
+// the handle beyond its results is done here too (the window's kernel arguments refreshed, the isLinearized bookkeeping of FullSystem.cpp:840-843); what it merely
+// refreshes on the device (the handle's own pair table, threshold and adjoint copies) keeps its dirty flag instead and is refreshed by the next single call that needs it.
+struct MargBatchCall {
+  dmvio_hip_ba_batch* const B;
+  const int W;
+  dmvio_hip_ba_marg_window* const win;
+  std::vector<int> order;                    // record k holds window order[k]
+  struct Grp { int w0, cnt, F; };
+  std::vector<Grp> grp;
+  std::vector<size_t> candOff, outOff;       // per record, into the marginalisation buffer
+  size_t inBytes = 0, outBytes = 0;
+  bool anyAdjoints = false;
+  MargBatchCall(dmvio_hip_ba_batch* B_, const int W_, dmvio_hip_ba_marg_window* win_) : B(B_), W(W_), win(win_) {}
+
+  int plan() {
+    std::vector<char> done(W, 0);
+    for (int i = 0; i < W; i++) {
+      if (done[i]) continue;
+      Grp g{(int)order.size(), 0, win[i].ba->H.F};
+      for (int j = i; j < W; j++) if (!done[j] && win[j].ba->H.F == g.F) { order.push_back(j); done[j] = 1; g.cnt++; }
+      grp.push_back(g);
+    }
+    candOff.resize(W); outOff.resize(W);
+    for (int k = 0; k < W; k++) { candOff[k] = inBytes; inBytes += BatchLayout::margCandBytes((size_t)win[order[k]].ba->H.N); }
+    for (int k = 0; k < W; k++) {
+      const dmvio_hip_ba* b = win[order[k]].ba;
+      const BatchLayout L(b->H.n(), b->H.F);
+      if (!L.margFitsIn(B->slab)) return failmsg("ba_marginalize_points_batch: table slab too small");
+      outOff[k] = inBytes + outBytes; outBytes += L.margOutBytes((size_t)b->H.N);
+      anyAdjoints = anyAdjoints || b->adj_dirty;
+    }
+    if (inBytes + outBytes > B->marg_cap) {
+      if (B->d_marg) { hipFree(B->d_marg); B->d_marg = nullptr; }
+      if (B->h_marg) { hipHostFree(B->h_marg); B->h_marg = nullptr; }
+      B->marg_cap = 0;
+      const size_t cap = (inBytes + outBytes) * 2;
+      HIPCHK(hipMalloc((void**)&B->d_marg, cap));
+      HIPCHK(hipHostMalloc((void**)&B->h_marg, cap, hipHostMallocDefault));
+      B->marg_cap = cap;
+    }
+    if (!B->marg_ev) HIPCHK(hipEventCreateWithFlags(&B->marg_ev, hipEventDisableTiming));
+    return 0;
+  }
+
+  // ---- the host side of record k before the launches: the handle's part of the single call, the window's record and its tables in the pinned slabs
+  int prepareWindow(const int k) {
+    dmvio_hip_ba_marg_window& q = win[order[k]];
+    dmvio_hip_ba* b = q.ba;
+    BAHost& H = b->H;
+    const int F = H.F, F2 = F * F, N = H.N, R = H.R;
+    const BatchLayout L(H.n(), F);
+    b->stateChanged();
+    if (int r = resolveTh(b)) return r;
+    fillWindow(b);
+    BAWinDev& V = B->h_wins[k];
+    memset(&V, 0, sizeof(V));
+    V.W = b->W; V.Wb = b->W;
+    V.D = makeDecide(b, -1, false, false);   // masked relinearisation: no energy / threshold / accept pass
+    for (int f = 0; f < BA_MAXF_CAP; f++) V.frameTH[f] = f < F ? H.fr[f].frameEnergyTH : 0.0f;
+    V.D.frameTH = B->d_wins[k].frameTH;
+    // FullSystem.cpp:840-843: a candidate point's residuals are relinearised with isLinearized = false (the device clears its flags in k_ba_marg_apply_fix_b; the masked
+    // kernels in front of it do not read them)
+    if (b->n_lin > 0) {
+      V.margLinClear = b->d_lin;
+      for (int ri = 0; ri < R; ri++) if (q.candidates[b->h_point[ri]] && b->h_lin[ri]) { b->h_lin[ri] = 0; b->n_lin--; }
+      b->n_lin_global = b->n_lin;
+      if (b->n_lin == 0) { b->Rs.lin = nullptr; b->P.lHdd = b->P.lbd = b->P.lHcd = nullptr; b->P.HcdAF = nullptr; b->H.HLraw.clear(); b->H.bLraw.clear(); }
+    }
+    V.P = b->P; V.Rs = b->Rs;
+    {
+      AccumArgs& A = V.A;
+      A.F = F; A.N = N; A.nsTop = b->nsTop; A.nsD = b->nsD; A.nsC = b->nsC;
+      A.top_begin = b->d_top_begin; A.top_members = b->d_top_members; A.scd_begin = b->d_scd_begin; A.scd_members = b->d_scd_members;
+      A.accTop = b->d_accTop; A.accD = b->d_accD; A.accE = b->d_accE; A.accC = b->d_accC; A.numTop = b->d_numTop; A.numD = b->d_numD;
+      A.ticks = nullptr;
+    }
+    V.SB = b->SB; V.ctl = b->d_ctl;
+    V.n_lin_blocks = b->n_lin_blocks; V.n_pt8_blocks = b->n_pt8_blocks; V.n_pt_blocks = b->n_pt_blocks; V.n_acc_blocks = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
+    V.n_res_blocks = (R + 255) / 256; V.n_gather_blocks = (int)((L.margSysDoubles() + 255) / 256); V.n_stitch_blocks = F + F2; V.n_lin1_blocks = (R + LIN_THREADS - 1) / LIN_THREADS;
+    // deltas at the current state (EnergyFunctional::setDeltaF, EnergyFunctional.cpp:175-198)
+    std::vector<float> adHT;
+    H.adHTdeltaF(adHT);
+    memcpy(V.adHTdelta[0], adHT.data(), sizeof(float) * adHT.size());
+    for (int i = 0; i < 4; i++) V.cDeltaF[0][i] = H.cDeltaF[i];
+    // the uploaded tables: the pair table of the current state; the adjoints where the handle's device copy is stale (it stays stale: adj_dirty is kept)
+    char* tab = B->hTab(k);
+    char* dtab = B->dTab(k);
+    memcpy(tab + L.margTabPre(), H.pre.data(), L.tabPreBytes());
+    V.pre = reinterpret_cast<const BAPrecalc*>(dtab + L.margTabPre());
+    if (b->adj_dirty) {
+      memcpy(tab + L.margTabAdHost(), H.adHost.data(), L.margTabAdBytes()); memcpy(tab + L.margTabAdTarget(), H.adTarget.data(), L.margTabAdBytes());
+      V.adHost = reinterpret_cast<const double*>(dtab + L.margTabAdHost()); V.adTarget = reinterpret_cast<const double*>(dtab + L.margTabAdTarget());
+    } else { V.adHost = b->d_adHost; V.adTarget = b->d_adTarget; }
+    memcpy(B->h_marg + candOff[k], q.candidates, (size_t)N);
+    V.margCand = reinterpret_cast<const unsigned char*>(B->d_marg + candOff[k]);
+    V.margSys = reinterpret_cast<double*>(B->d_marg + outOff[k]);
+    V.margDecision = reinterpret_cast<unsigned char*>(B->d_marg + outOff[k] + L.margOutDecision());
+    V.margFullJ = b->d_fullJ; V.margRec = b->d_margRec; V.margActive = b->d_margActive;
+    V.mHdiF = b->d_mHdiF; V.mbdSumF = b->d_mbdSumF; V.mHcd = b->d_mHcd;
+    return 0;
+  }
+
+  int enqueue() {
+    const hipStream_t s = B->stream;
+    int* const work = B->marg_work;
+    // a handle's own stream may still hold work (its entry points return on a ticket, not on an empty stream): in front of the call
+    for (int k = 0; k < W; k++) {
+      dmvio_hip_ba* b = win[order[k]].ba;
+      if (b->stream == s || hipStreamQuery(b->stream) == hipSuccess) continue;
+      HIPCHK(hipEventRecord(B->marg_ev, b->stream));
+      HIPCHK(hipStreamWaitEvent(s, B->marg_ev, 0));
+    }
+    (void)hipGetLastError();   // (hipErrorNotReady of the query above is no error)
+    if (B->profile) HIPCHK(hipEventRecord(B->ev[6], s));
+    HIPCHK(hipMemcpyAsync(B->d_wins, B->h_wins, sizeof(BAWinDev) * W, hipMemcpyHostToDevice, s));
+    size_t tabWidth = 0;
+    for (const Grp& g : grp) tabWidth = std::max(tabWidth, BatchLayout(4 + 8 * g.F, g.F).margTabUsed(anyAdjoints));
+    HIPCHK(hipMemcpy2DAsync(B->dTab(0), B->slab.tabStride(), B->hTab(0), B->slab.tabStride(), tabWidth, W, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(B->d_marg, B->h_marg, inBytes, hipMemcpyHostToDevice, s));
+    work[1] = 3;
+    const FrameStore fs = B->ctx->fs;
+    for (const Grp& g : grp) {
+      int gx_lin = 0, gx_res = 0, gx_pt = 0, gx_acc = 0;
+      for (int k = g.w0; k < g.w0 + g.cnt; k++) {
+        const BAWinDev& V = B->h_wins[k];
+        gx_lin = std::max(gx_lin, V.n_lin_blocks); gx_res = std::max(gx_res, V.n_res_blocks); gx_pt = std::max(gx_pt, V.n_pt_blocks); gx_acc = std::max(gx_acc, V.n_acc_blocks);
+      }
+      const BAWinDev* dw = B->d_wins + g.w0;
+      const int F = g.F, n_gather = B->h_wins[g.w0].n_gather_blocks;
+      hipLaunchKernelGGL(k_ba_marg_linearize_b, dim3(gx_lin, g.cnt), dim3(LIN_THREADS), 0, s, dw, fs);
+      hipLaunchKernelGGL(k_ba_marg_apply_fix_b, dim3(gx_res, g.cnt), dim3(256), 0, s, dw);
+      hipLaunchKernelGGL(k_ba_marg_point_sums_b, dim3(gx_pt, g.cnt), dim3(256), 0, s, dw);
+      hipLaunchKernelGGL(k_ba_accumulate_bm, dim3(gx_acc, g.cnt), dim3(256), 0, s, dw);
+      hipLaunchKernelGGL(k_ba_stitch_b, dim3(F + F * F, g.cnt), dim3(64 * F), sizeof(StitchWave) * F, s, dw, (int)BA_GATE_ALWAYS, (int)BA_PASS_M);
+      BA_BY_MAXF(F, M, hipLaunchKernelGGL((k_ba_stitch_gather_b<M>), dim3(n_gather, g.cnt), dim3(256), 0, s, dw, (int)BA_GATE_ALWAYS, (int)BA_PASS_M));
+      work[0] += 6;
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(B->h_marg + inBytes, B->d_marg + inBytes, outBytes, hipMemcpyDeviceToHost, s));
+    work[2] = 1;
+    if (B->profile) HIPCHK(hipEventRecord(B->ev[7], s));
+    HIPCHK(hipStreamSynchronize(s));
+    work[3] = 1;
+    B->marg_ms = 0;
+    if (B->profile) HIPCHK(hipEventElapsedTime(&B->marg_ms, B->ev[6], B->ev[7]));
+    return 0;
+  }
+
+  // ---- behind the wait: the host tail of the single call (the increment 0.25 (M - Msc) of HM / bM, the prior, the residual count; ef->resInA stays what it was)
+  int finishWindow(const int k) {
+    dmvio_hip_ba_marg_window& q = win[order[k]];
+    BAHost& H = q.ba->H;
+    const int n = H.n(), N = H.N;
+    const BatchLayout L(n, H.F);
+    const double* M = reinterpret_cast<const double*>(B->h_marg + outOff[k]);
+    const double* Mb = M + (size_t)n * n; const double* Msc = Mb + n; const double* Mbsc = Msc + (size_t)n * n;
+    if (H.HM.size() != (size_t)n * n) { H.HM.assign((size_t)n * n, 0.0); H.bM.assign(n, 0.0); }
+    for (size_t i = 0; i < (size_t)n * n; i++) { const double v = BA_MARG_WEIGHT_FAC * (M[i] - Msc[i]); if (q.Hadd) q.Hadd[i] = v; if (q.update_prior) H.HM[i] += v; }
+    for (int i = 0; i < n; i++) { const double v = BA_MARG_WEIGHT_FAC * (Mb[i] - Mbsc[i]); if (q.badd) q.badd[i] = v; if (q.update_prior) H.bM[i] += v; }
+    q.resInM = (int)M[L.outResInA()];
+    memcpy(q.decision, B->h_marg + outOff[k] + L.margOutDecision(), (size_t)N);
+    return 0;
+  }
+};
+
 extern "C" {
+int dmvio_hip_ba_marginalize_points_batch(dmvio_hip_ba_batch* B, int W, dmvio_hip_ba_marg_window* win) {
+  if (!B) return failmsg("ba_marginalize_points_batch: null batch");
+  if (W < 0) return failmsg("ba_marginalize_points_batch: W < 0");
+  if (W > B->cap) return failmsg("ba_marginalize_points_batch: more windows than the batch was created for");
+  std::lock_guard<std::mutex> lkB(B->mu);
+  for (int i = 0; i < 4; i++) B->marg_work[i] = 0;
+  if (W == 0) return 0;
+  if (!win) return failmsg("ba_marginalize_points_batch: null window list");
+  std::vector<dmvio_hip_ba*> order(W);
+  for (int i = 0; i < W; i++) {
+    if (!win[i].ba) return failmsg("ba_marginalize_points_batch: null window");
+    if (!win[i].candidates || !win[i].decision) return failmsg("ba_marginalize_points_batch: null candidates / decision");
+    if (win[i].ba->ctx != B->ctx) return failmsg("ba_marginalize_points_batch: a window belongs to another context");
+    order[i] = win[i].ba;
+  }
+  // the handles' locks, in address order (as dmvio_hip_ba_optimize_batch)
+  std::sort(order.begin(), order.end());
+  for (int i = 1; i < W; i++) if (order[i] == order[i - 1]) return failmsg("ba_marginalize_points_batch: a window appears twice");
+  std::vector<std::unique_lock<std::recursive_mutex>> locks;
+  for (dmvio_hip_ba* b : order) locks.emplace_back(b->mu);
+  for (int i = 0; i < W; i++) {
+    if (!win[i].ba->graph_ready) return failmsg("ba_marginalize_points_batch: window / graph not set");
+    if (sharded(win[i].ba)) return failmsg("ba_marginalize_points_batch: a window sharded over ranks cannot join a batch");
+  }
+  HIPCHK(hipSetDevice(B->ctx->device));
+  MargBatchCall c(B, W, win);
+  if (int r = c.plan()) return r;
+  if (int r = B->workers.parallelFor(W, [&c](const int k) { return c.prepareWindow(k); })) return r;
+  if (int r = c.enqueue()) return r;
+  return B->workers.parallelFor(W, [&c](const int k) { return c.finishWindow(k); });
+}
+int dmvio_hip_ba_batch_last_marg_ms(dmvio_hip_ba_batch* B, float* ms) {
+  if (!B || !ms) return failmsg("ba_batch_last_marg_ms: null argument");
+  std::lock_guard<std::mutex> lkB(B->mu);
+  *ms = B->marg_ms;
+  return 0;
+}
+int dmvio_hip_ba_batch_last_marg_work(dmvio_hip_ba_batch* B, int* launches, int* uploads, int* downloads, int* waits) {
+  if (!B) return failmsg("ba_batch_last_marg_work: null batch");
+  std::lock_guard<std::mutex> lkB(B->mu);
+  if (launches) *launches = B->marg_work[0];
+  if (uploads) *uploads = B->marg_work[1];
+  if (downloads) *downloads = B->marg_work[2];
+  if (waits) *waits = B->marg_work[3];
+  return 0;
+}
 // windows[W]: handles of the batch's context, each with its window set (set_window + set_graph), all distinct.  rmse / finalEnergy / iterations: W entries each (may be
 // NULL); trace: W x 64 x 4 doubles or NULL ([E_A, E_L, E_M, accepted] per iteration, row 0 = the initial state).  Windows with different keyframe counts run as separate
 // groups, one after the other.  Every window's result is what a batch of that window alone gives, bit for bit (no arithmetic crosses windows).

@@ -71,6 +71,15 @@ struct BAWinDev {
   float adHTdelta[2][BA_MAXF_CAP * BA_MAXF_CAP * 8];
   float cDeltaF[2][4];
   BASolveDev S;
+  // point marginalisation (dmvio_hip_ba_marginalize_points_batch; behind everything the Gauss-Newton loop reads: its kernels address the record as before; adHTdelta[0] / cDeltaF[0]: setDeltaF of the state the window stands at): the candidate flags and the
+  // decisions in the batch's buffers, the handle's Jacobians (rewritten for the candidates' residuals), its isLinearized flags (NULL: none; cleared for those residuals,
+  // FullSystem.cpp:840-843), the records addPoint<2> consumes with their activity and per-point sums, and where the stitched [H | b | Hsc | bsc | resInA] goes
+  const unsigned char* margCand; unsigned char* margDecision;
+  float* margFullJ; unsigned char* margLinClear;
+  float* margRec; unsigned char* margActive;
+  float *mHdiF, *mbdSumF, *mHcd;
+  double* margSys;
+  int n_pt_blocks, pad_marg;
 };
 
 // ---- the record's pointers as GLOBAL pointers.  A pointer that arrives as a kernel argument is known to point into global memory; one that a kernel loads from a
@@ -207,7 +216,10 @@ __global__ void __launch_bounds__(256) k_ba_point_sums_b(const BAWinDev* __restr
 // pass: 0 = the one accumulation of a graph without residuals kept linearised; 1 / 2 / 3 = the L / A / Schur pass of the three-pass accumulation (accumulateLin in
 // capi_ba.hip: addPoint<1> over the linearised residuals' records, addPoint<0> over the others, the Schur side over every active one).  A window WITHOUT such residuals in a
 // launch of pass 1 or 3 has nothing to do; in pass 2 it runs its one ordinary accumulation.
-enum { BA_PASS_ALL = 0, BA_PASS_L = 1, BA_PASS_A = 2, BA_PASS_S = 3 };
+// 4 = the marginalisation view (marginalizePointsF, EnergyFunctional.cpp:678-742: addPoint<2> + the Schur side over the points to marginalise): the records margRec with
+// their activity, the per-point sums mHdiF / mbdSumF / mHcd, the system into the window's output slab — every window of such a launch takes part.  The stitch and the
+// gather take it as a pass value; the accumulation over that view is k_ba_accumulate_bm
+enum { BA_PASS_ALL = 0, BA_PASS_L = 1, BA_PASS_A = 2, BA_PASS_S = 3, BA_PASS_M = 4 };
 __device__ __forceinline__ bool baPassIdle(const BAWinDev& V, const int pass) { return V.n_lin == 0 && (pass == BA_PASS_L || pass == BA_PASS_S); }
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) k_ba_accumulate_b(const BAWinDev* __restrict__ wins, const int gate, const int pass) {
   const BAWinDev& V = wins[blockIdx.y];
@@ -218,6 +230,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))
   if (pass == BA_PASS_L) { Rv.rec[0] = Rv.rec[1] = gl(V.linRec); Rv.active = gl(V.linActive); Rv.lin = nullptr; }
   else Rv.active = gl(V.topActive);
   baAccumulateBody(A, Rv, P, ctl, gate);
+}
+// BA_PASS_M of the accumulation: the same body over the marginalisation view, whole members replaced like BA_PASS_L's (no indexed member: baRec()).  A kernel of its own:
+// as one more pass value of k_ba_accumulate_b the view cost that kernel — the Gauss-Newton loop's, tuned to its 80-register budget — a third spilled value.
+__global__ void __launch_bounds__(256) k_ba_accumulate_bm(const BAWinDev* __restrict__ wins) {
+  const BAWinDev& V = wins[blockIdx.y];
+  if ((int)blockIdx.x >= V.n_acc_blocks) return;
+  const AccumArgs A = blAccum(V.A);
+  BAPoints P = blPoints(V.P);
+  BARes Rv = blRes(V.Rs);
+  Rv.rec[0] = Rv.rec[1] = gl(V.margRec); Rv.active = gl(V.margActive);
+  P.HdiF = gl(V.mHdiF); P.bdSumF = gl(V.mbdSumF); P.Hcd = gl(V.mHcd);
+  baAccumulateBody(A, Rv, P, gl(V.ctl), BA_GATE_ALWAYS);
 }
 // every window of a batch has the same F (the host groups them): blockDim = 64 F
 __global__ void __launch_bounds__(64 * BA_MAXF_CAP) k_ba_stitch_b(const BAWinDev* __restrict__ wins, const int gate, const int pass) {
@@ -233,9 +257,48 @@ __global__ void __launch_bounds__(256) k_ba_stitch_gather_b(const BAWinDev* __re
   const int F = V.A.F;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const AccumArgs A = blAccum(V.A); const StitchBufs SB = blStitch(V.SB);
-  if (V.n_lin == 0 || pass == BA_PASS_ALL) gatherElement<MF>(F, A.nsC, A.accC, SB, A.numTop, F * F * A.nsTop, gl(V.sys), t, false, 3, true);
+  if (pass == BA_PASS_M || V.n_lin == 0 || pass == BA_PASS_ALL) gatherElement<MF>(F, A.nsC, A.accC, SB, A.numTop, F * F * A.nsTop, pass == BA_PASS_M ? gl(V.margSys) : gl(V.sys), t, false, 3, true);
   else if (pass == BA_PASS_L) gatherElement<MF>(F, A.nsC, A.accC, SB, A.numTop, F * F * A.nsTop, gl(V.sysL), t, false, 1, false);
   else gatherElement<MF>(F, A.nsC, A.accC, SB, A.numTop, F * F * A.nsTop, gl(V.sys), t, false, pass == BA_PASS_A ? 1 : 2, true);
+}
+// ---- point marginalisation of W windows (dmvio_hip_ba_marginalize_points_batch): the device work of dmvio_hip_ba_marginalize_points in blockIdx.y form.  Per group of
+// equal keyframe count six launches: the masked relinearisation, applyRes + fixLinearizationF, the per-point sums + decisions, then k_ba_accumulate_bm and the stitch /
+// gather kernels above with pass = BA_PASS_M.  k_ba_marg_decide has no launch of its own: its consumers evaluate baMargDecision where they need it.
+// FullSystem::flagPointsForRemoval's relinearisation (FullSystem.cpp:836-849): resetOOB + linearize of the candidates' residuals, the Jacobians kept; no decision pass
+// (BADecide::mode = -1 in the record).  The pair table is the uploaded one (use_dyn = 0), as in the single call.
+__global__ void __launch_bounds__(LIN_THREADS) k_ba_marg_linearize_b(const BAWinDev* __restrict__ wins, const FrameStore fs) {
+  const BAWinDev& V = wins[blockIdx.y];
+  if ((int)blockIdx.x >= V.n_lin_blocks) return;
+  const BADecide D = blDecide(V.D);
+  baLinearizeBody(V.W, blPoints(V.P), blRes(V.Rs), gl(V.pre), fs, gl(V.margFullJ), gl(V.margCand), D, BA_GATE_ALWAYS, 0, V.T.v, 0, V.X.xc, V.X.xAd, 0, V.n_lin_blocks);
+}
+// applyRes of the candidates' residuals (k_ba_apply with the mask), their isLinearized flags cleared, then EFResidual::fixLinearizationF and the addPoint<2> record
+// (k_ba_fix_linearization) — a residual's own thread applies it and then reads its activity: the two kernels of the single call in one launch, the same values
+__global__ void __launch_bounds__(256) k_ba_marg_apply_fix_b(const BAWinDev* __restrict__ wins) {
+  const BAWinDev& V = wins[blockIdx.y];
+  if ((int)blockIdx.x >= V.n_res_blocks) return;
+  const int ri = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ri >= V.W.R) return;
+  const BARes Rs = blRes(V.Rs); const BAPoints P = blPoints(V.P);
+  const unsigned char* const cand = gl(V.margCand);
+  baApplyBody(V.W.R, Rs, cand, 0);
+  const int pi = Rs.point[ri];
+  const unsigned char c = cand[pi];
+  unsigned char* const lin = gl(V.margLinClear);
+  if (lin && c) lin[ri] = 0;
+  baFixLinearizationBody(V.W, P, Rs, ri, pi, baMargDecision(c, P.idepth_hessian[pi], BA_MARG_MIN_IDEPTH_H), gl(V.margFullJ), V.adHTdelta[0],
+                         make_float4(V.cDeltaF[0][0], V.cDeltaF[0][1], V.cDeltaF[0][2], V.cDeltaF[0][3]), gl(V.margRec), gl(V.margActive), nullptr);
+}
+// addPoint<2>'s per-point sums and the Schur side's head (k_ba_marg_point_sums), and the decisions the caller receives (k_ba_marg_decide)
+__global__ void __launch_bounds__(256) k_ba_marg_point_sums_b(const BAWinDev* __restrict__ wins) {
+  const BAWinDev& V = wins[blockIdx.y];
+  if ((int)blockIdx.x >= V.n_pt_blocks) return;
+  const int pi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pi >= V.W.N) return;
+  const BAPoints P = blPoints(V.P);
+  const int dec = baMargDecision(gl(V.margCand)[pi], P.idepth_hessian[pi], BA_MARG_MIN_IDEPTH_H);
+  gl(V.margDecision)[pi] = (unsigned char)dec;
+  baMargPointSumsBody(P, pi, dec, gl(V.margRec), gl(V.margActive), BA_MARG_IDEPTH_FIX_PRIOR_FAC, gl(V.mHdiF), gl(V.mbdSumF), gl(V.mHcd));
 }
 // the records addPoint<1> consumes and the linearised residuals' per-point sums, at the deltas of the state the window stands at (k_ba_lin_records / k_ba_lin_point_sums)
 __global__ void __launch_bounds__(256) k_ba_lin_records_b(const BAWinDev* __restrict__ wins, const int gate) {

@@ -972,6 +972,20 @@ __device__ __forceinline__ void baPointSumsBody(const BAWindow& W, const BAPoint
 // record AccumulatedTopHessianSSE::addPoint<2> consumes: identical to the applied record except that the inner products with the
 // residual use res_toZeroF (AccumulatedTopHessian.cpp:70-71,103-113,131).  fullJ: the 74-float RawResidualJacobian of the applied
 // linearisation ([0,8) resF, [8,20) Jpdxi, [20,28) Jpdc, 28-29 Jpdd, [30,46) JIdx, [46,62) JabF).
+// The settings of the point marginalisation (settings.cpp: setting_minIdepthH_marg, setting_idepthFixPriorMargFac, setting_margWeightFac), for the single call
+// (capi_ba.hip) and the batched one (ba_batch_kernels.hpp / ba_batch_host.hpp)
+constexpr float BA_MARG_MIN_IDEPTH_H = 50;
+constexpr float BA_MARG_IDEPTH_FIX_PRIOR_FAC = 600 * 600;
+constexpr double BA_MARG_WEIGHT_FAC = 0.5 * 0.5;
+// decision of flagPointsForRemoval for a candidate (FullSystem.cpp:846): marginalise (1) if idepth_hessian > setting_minIdepthH_marg, else drop (2); 0: no candidate.
+// A pure function of the candidate flag and the point's idepth_hessian (which no kernel of the marginalisation writes): the batched kernels evaluate it where they need it.
+__device__ __forceinline__ int baMargDecision(const unsigned char cand, const float idepth_hessian, const float minIdepthH_marg) {
+  return cand ? (idepth_hessian > minIdepthH_marg ? 1 : 2) : 0;
+}
+// dec: the decision of the residual's point (read from the decision array by the single call, evaluated by the batched kernel)
+__device__ __forceinline__ void baFixLinearizationBody(const BAWindow& W, const BAPoints& P, const BARes& Rs, const int ri, const int pi, const int dec,
+                                                       const float* __restrict__ fullJ, const float* __restrict__ adHTdeltaF /* F*F x 8, h + F*t */, const float4 cDeltaF,
+                                                       float* __restrict__ margRec, unsigned char* __restrict__ margActive, float* __restrict__ res_toZeroF /* R x 8 or NULL */);
 __global__ void __launch_bounds__(256) k_ba_fix_linearization(const BAWindow W, const BAPoints P, const BARes Rs, const float* __restrict__ fullJ,
                                                                const unsigned char* __restrict__ decision, const float* __restrict__ adHTdeltaF /* F*F x 8, h + F*t */,
                                                                const float4 cDeltaF, float* __restrict__ margRec, unsigned char* __restrict__ margActive,
@@ -979,7 +993,12 @@ __global__ void __launch_bounds__(256) k_ba_fix_linearization(const BAWindow W, 
   const int ri = blockIdx.x * blockDim.x + threadIdx.x;
   if (ri >= W.R) return;
   const int pi = Rs.point[ri];
-  const bool on = decision[pi] == 1 && Rs.active[ri] != 0;
+  baFixLinearizationBody(W, P, Rs, ri, pi, decision[pi], fullJ, adHTdeltaF, cDeltaF, margRec, margActive, res_toZeroF);
+}
+__device__ __forceinline__ void baFixLinearizationBody(const BAWindow& W, const BAPoints& P, const BARes& Rs, const int ri, const int pi, const int dec,
+                                                       const float* __restrict__ fullJ, const float* __restrict__ adHTdeltaF, const float4 cDeltaF,
+                                                       float* __restrict__ margRec, unsigned char* __restrict__ margActive, float* __restrict__ res_toZeroF) {
+  const bool on = dec == 1 && Rs.active[ri] != 0;
   margActive[ri] = on ? 1 : 0;
   if (!on) return;
   const float* __restrict__ J = fullJ + (size_t)ri * 74;
@@ -1011,18 +1030,24 @@ __global__ void __launch_bounds__(256) k_ba_fix_linearization(const BAWindow W, 
 __global__ void __launch_bounds__(256) k_ba_marg_decide(const int N, const unsigned char* __restrict__ cand, const float* __restrict__ idepth_hessian,
                                                          const float minIdepthH_marg, unsigned char* __restrict__ decision) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pi < N) decision[pi] = cand[pi] ? (idepth_hessian[pi] > minIdepthH_marg ? 1 : 2) : 0;
+  if (pi < N) decision[pi] = (unsigned char)baMargDecision(cand[pi], idepth_hessian[pi], minIdepthH_marg);
 }
 // addPoint<2>'s per-point sums (Hdd_accLF, bd_accLF, Hcd_accLF; accAF = 0) and the head of AccumulatedSCHessianSSE::addPoint(p, false)
 // with priorF * setting_idepthFixPriorMargFac; points that are not marginalised get HdiF = 0 (skipped by every accumulator)
+__device__ __forceinline__ void baMargPointSumsBody(const BAPoints& P, const int pi, const int dec, const float* __restrict__ margRec, const unsigned char* __restrict__ margActive,
+                                                    const float priorMargFac, float* __restrict__ HdiF, float* __restrict__ bdSumF, float* __restrict__ Hcd4);
 __global__ void __launch_bounds__(256) k_ba_marg_point_sums(const BAWindow W, const BAPoints P, const BARes Rs, const float* __restrict__ margRec,
                                                              const unsigned char* __restrict__ margActive, const unsigned char* __restrict__ decision,
                                                              const float priorMargFac, float* __restrict__ HdiF, float* __restrict__ bdSumF, float* __restrict__ Hcd4) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= W.N) return;
+  baMargPointSumsBody(P, pi, decision[pi], margRec, margActive, priorMargFac, HdiF, bdSumF, Hcd4);
+}
+__device__ __forceinline__ void baMargPointSumsBody(const BAPoints& P, const int pi, const int dec, const float* __restrict__ margRec, const unsigned char* __restrict__ margActive,
+                                                    const float priorMargFac, float* __restrict__ HdiF, float* __restrict__ bdSumF, float* __restrict__ Hcd4) {
   float Hdd = 0, bd = 0, Hcd[4] = {0, 0, 0, 0};
   int ngood = 0;
-  if (decision[pi] == 1)
+  if (dec == 1)
     for (int ri = P.res_begin[pi]; ri < P.res_begin[pi + 1]; ri++) {
       if (!margActive[ri]) continue;
       const float* __restrict__ rec = margRec + (size_t)ri * REC_FLOATS;

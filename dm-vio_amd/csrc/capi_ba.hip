@@ -747,8 +747,8 @@ int dmvio_hip_ba_marginalize_points(dmvio_hip_ba* b, const unsigned char* candid
   BAHost& H = b->H;
   const int N = H.N, R = H.R, n = H.n();
   hipStream_t s = b->stream;
-  const float setting_minIdepthH_marg = 50, setting_idepthFixPriorMargFac = 600 * 600;
-  const double setting_margWeightFac = 0.5 * 0.5;
+  const float setting_minIdepthH_marg = BA_MARG_MIN_IDEPTH_H, setting_idepthFixPriorMargFac = BA_MARG_IDEPTH_FIX_PRIOR_FAC;
+  const double setting_margWeightFac = BA_MARG_WEIGHT_FAC;
   // deltas at the current state (EnergyFunctional::setDeltaF, EnergyFunctional.cpp:175-198)
   std::vector<float> adHT;
   H.adHTdeltaF(adHT);

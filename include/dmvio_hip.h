@@ -616,6 +616,30 @@ typedef struct dmvio_hip_ba_batch dmvio_hip_ba_batch;
 dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows);
 void dmvio_hip_ba_batch_destroy(dmvio_hip_ba_batch* batch);
 int dmvio_hip_ba_optimize_batch(dmvio_hip_ba_batch* batch, int W, dmvio_hip_ba* const* windows, int mnumOptIts, float* rmse, double* finalEnergy, int* iterations, double* trace);
+/* Point marginalisation of W windows per call: dmvio_hip_ba_marginalize_points (FullSystem::flagPointsForRemoval's relinearisation FullSystem.cpp:829-859,
+ * EFResidual::fixLinearizationF EnergyFunctionalStructs.cpp:76-106, EnergyFunctional::marginalizePointsF EnergyFunctional.cpp:678-742) for every window of win[W], the
+ * stage that follows dmvio_hip_ba_optimize_batch in a keyframe's cycle.  Every window ends exactly where its own single call with the same arguments would have left it,
+ * bit for bit: decision / Hadd / badd / resInM, the handle's marginalisation prior (update_prior), the residual records, states and Jacobians on the device, and the
+ * isLinearized flags of the candidates' residuals (dmvio_hip_ba_fix_linearization) — in both accumulation orders, so single and batched calls may be mixed on a handle.
+ * Runs on the batch's stream under the rules of dmvio_hip_ba_optimize_batch (the handles locked in address order; work pending on a handle's own stream is in front of the
+ * call, the call is complete on return).  The windows' inputs travel in packed uploads, the results in one download behind one wait: the number of copies and of kernel
+ * launches does not depend on W, only on the number of distinct keyframe counts in the call (six launches per count).
+ * Refused as a whole, with a message and before any window is touched: W < 0 or W > max_windows, win / a handle / candidates / decision NULL, a handle twice, a handle of
+ * another context, without a graph, or sharded over ranks (dmvio_hip_ba_set_comm).  W == 0 returns 0 and does nothing. */
+typedef struct dmvio_hip_ba_marg_window {
+  dmvio_hip_ba* ba;
+  const unsigned char* candidates;   /* N bytes, as dmvio_hip_ba_marginalize_points */
+  unsigned char* decision;           /* N bytes out: 0 untouched, 1 marginalised, 2 dropped */
+  double* Hadd; double* badd;        /* n*n, n; either may be NULL */
+  int resInM;                        /* out */
+  int update_prior;
+} dmvio_hip_ba_marg_window;
+int dmvio_hip_ba_marginalize_points_batch(dmvio_hip_ba_batch* batch, int W, dmvio_hip_ba_marg_window* win);
+/* what the last such call enqueued (all 0 after W == 0; any pointer may be NULL) */
+int dmvio_hip_ba_batch_last_marg_work(dmvio_hip_ba_batch* batch, int* launches, int* uploads, int* downloads, int* waits);
+/* measurement (tools/bench_marg_batch.py): with dmvio_hip_ba_batch_set_profile(1), HIP-event time in ms of the last such call's device work on the batch's stream,
+ * from the first upload to the download; 0 otherwise */
+int dmvio_hip_ba_batch_last_marg_ms(dmvio_hip_ba_batch* batch, float* ms);
 int dmvio_hip_ba_batch_set_exact_backsub(dmvio_hip_ba_batch* batch, int on);
 /* HIP-event times of the last dmvio_hip_ba_optimize_batch call on the batch's stream (ms): [0] initial chain + all iterations, [1] the final fix-linearisation,
  * [2] with dmvio_hip_ba_batch_set_profile(1): the stepped linearisation of the second iteration (k_ba_linearize_b over ALL windows of the call: a profiled call runs as one
