@@ -940,6 +940,12 @@ int dmvio_hip_debug_lm_ticks(double out8[8], int reset) {
   if (reset) { double z[8] = {0}; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lm_ticks), z, sizeof(z))); }
   return 0;
 }
+int dmvio_hip_debug_lm_epilogue(double out4[4], int reset) {
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_lm_epi), sizeof(double) * 4));
+  if (reset) { double z[4] = {0}; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_lm_epi), z, sizeof(z))); }
+  return 0;
+}
 #endif
 int dmvio_hip_tracker_last_ticks(dmvio_hip_tracker* t, long long* ticks_step, long long* ticks_eval) {
   if (!t) return failmsg("null tracker");

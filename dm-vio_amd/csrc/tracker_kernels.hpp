@@ -33,6 +33,7 @@
 namespace dmv {
 
 #ifdef DMV_LM_TICKS
+__device__ double g_lm_epi[4];     // experiment only (profiles/lm_loop_scratch.md): between the two barriers that end an evaluation, on thread 0 — full evaluations: ticks, count; residual-only: ticks, count
 __device__ double g_lm_ticks[8];   // experiment only (profiles/r02_lm_control_step.md): LM control step — solve, lane-0 part 1, lane-0 part 2, whole step (100 MHz ticks), solves, steps; evaluation server — [6] seen -> evaluated, [7] evaluated -> stored
 #endif
 
@@ -234,6 +235,20 @@ __device__ __forceinline__ float waveReduceStats(const EvalStats& st, const int 
   return t;  // total of slot (lane & 7)
 }
 
+// The slot of s_tot a thread of the reducing wavefront sums in the epilogue of an evaluation.  The slot and everything derived from it (the row / column of the upper
+// triangle, the LDS addresses of the waves' partials) is the same in every evaluation a kernel runs; left visible, the compiler computes those once at kernel entry, finds no
+// register for them across the evaluation loops and reloads each from scratch memory between the two barriers of every epilogue, one dependent round trip after the other
+// while the other wavefronts wait (profiles/lm_loop_scratch.md).  The empty asm statement hides the value's origin: the dozen integer instructions run where they are used.
+__device__ __forceinline__ int epilogueSlot() {
+  int k = threadIdx.x;
+  asm volatile("" : "+v"(k));
+  return k;
+}
+// row r of slot k < 45 in the row-major upper triangle of a 9x9 matrix (row r starts at slot 9r - r(r-1)/2: 0, 9, 17, 24, 30, 35, 39, 42, 44)
+__device__ __forceinline__ int triRow9(const int k) {
+  return (int)(k >= 9) + (int)(k >= 17) + (int)(k >= 24) + (int)(k >= 30) + (int)(k >= 35) + (int)(k >= 39) + (int)(k >= 42) + (int)(k >= 44);
+}
+
 // Workgroup-wide evaluation over the template points first, first+stride, ... < n (first = this THREAD's first index;
 // stride = threads taking part).  The weighted 9x9 outer products  sum_p w_p J_p J_p^T  are accumulated on the matrix
 // cores: per wave, 64 rows are staged component-major in LDS and consumed by 16 v_mfma_f32_16x16x4_f32 (A = J,
@@ -248,7 +263,10 @@ __device__ __forceinline__ void blockEval(const EvalP& e, const LevelGeom& g, co
                                           const unsigned long long* __restrict__ flow_mask, const int first, const int stride,
                                           const float* __restrict__ img, const float huberTH, float* s_stage, float* s_partH,
                                           float (*s_partS)[8], float* s_tot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // what follows from the thread's index alone (its staging addresses, its MFMA operand offsets) is formed at the head of every evaluation, not once per kernel and kept
+  // across the control step (epilogueSlot())
+  const int tid = epilogueSlot();
+  const int lane = tid & 63, wave = tid >> 6;
   float* __restrict__ wJ = s_stage + wave * SJ_WAVE_FLOATS;
   float* __restrict__ wW = wJ + SJ_ROWS * SJ_STRIDE;
   // four independent accumulator chains: a 16x16x4 f32 MFMA has a 40-cycle dependent latency but a 32-cycle issue slot
@@ -324,22 +342,28 @@ __device__ __forceinline__ void blockEval(const EvalP& e, const LevelGeom& g, co
   const float stot = waveReduceStats(st, lane);
   if (lane < 8) s_partS[wave][lane] = stot;
   __syncthreads();
+#ifdef DMV_LM_TICKS
+  const long long qe0 = wall_clock64();
+#endif
   if (threadIdx.x < ACC_PAD) {
     // slot -> (r, c) of the upper triangle, or a statistic
     float s = 0.0f;
-    const int k = threadIdx.x;
+    const int k = epilogueSlot();
     if (k < 45) {
-      int r = 0, off = 0;
-      while (k >= off + (9 - r)) { off += 9 - r; r++; }
-      const int c = r + (k - off);
+      const int r = triRow9(k), c = r + (k - (9 * r - ((r * (r - 1)) >> 1)));
+      const float* __restrict__ p = s_partH + (r * 16 + c);   // one address per thread; the wave index is an immediate offset of the read
 #pragma unroll
-      for (int wv = 0; wv < T / 64; wv++) s += s_partH[wv * 256 + r * 16 + c];
+      for (int wv = 0; wv < T / 64; wv++) s += p[wv * 256];
     } else if (k < ACC_N) {
+      const float* __restrict__ p = &s_partS[0][0] + (k - 45);
 #pragma unroll
-      for (int wv = 0; wv < T / 64; wv++) s += s_partS[wv][k - 45];
+      for (int wv = 0; wv < T / 64; wv++) s += p[wv * 8];
     }
     s_tot[k] = s;
   }
+#ifdef DMV_LM_TICKS
+  if (threadIdx.x == 0) { atomicAdd(&g_lm_epi[0], (double)(wall_clock64() - qe0)); atomicAdd(&g_lm_epi[1], 1.0); }
+#endif
   __syncthreads();
 }
 
@@ -350,7 +374,8 @@ __device__ __forceinline__ void blockEval(const EvalP& e, const LevelGeom& g, co
 template <int T, bool GUARD = true>
 __device__ __forceinline__ void blockEvalRes(const EvalP& e, const LevelGeom& g, const float4* __restrict__ pc, const int n, const int first, const int stride,
                                              const float* __restrict__ img, const float huberTH, float (*s_partS)[8], float* s_tot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tid = epilogueSlot();   // as in blockEval
+  const int lane = tid & 63, wave = tid >> 6;
   EvalStats st = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const EvalU eu = makeEvalU(e, g, huberTH);
   const int base0 = first - lane;   // wave-uniform trip count, as in blockEval
@@ -381,15 +406,22 @@ __device__ __forceinline__ void blockEvalRes(const EvalP& e, const LevelGeom& g,
   const float stot = waveReduceStats(st, lane);
   if (lane < 8) s_partS[wave][lane] = stot;
   __syncthreads();
+#ifdef DMV_LM_TICKS
+  const long long qe0 = wall_clock64();
+#endif
   if (threadIdx.x < ACC_PAD) {
     float s = 0.0f;
-    const int k = threadIdx.x;
+    const int k = epilogueSlot();
     if (k >= 45 && k < ACC_N) {
+      const float* __restrict__ p = &s_partS[0][0] + (k - 45);
 #pragma unroll
-      for (int wv = 0; wv < T / 64; wv++) s += s_partS[wv][k - 45];
+      for (int wv = 0; wv < T / 64; wv++) s += p[wv * 8];
     }
     s_tot[k] = s;
   }
+#ifdef DMV_LM_TICKS
+  if (threadIdx.x == 0) { atomicAdd(&g_lm_epi[2], (double)(wall_clock64() - qe0)); atomicAdd(&g_lm_epi[3], 1.0); }
+#endif
   __syncthreads();
 }
 
@@ -684,7 +716,12 @@ DMV_HD void makeEvalP(const TrackerDev& trk, int lvl, const Pose& T, double affA
   e.aff0 = (float)aff[0]; e.aff1 = (float)aff[1];
   e.b0 = (float)trk.ref_aff_b;
   e.cutoff = cutoffTH;
-  e.maxEnergy = 2 * trk.huberTH * cutoffTH - trk.huberTH * trk.huberTH;
+  float huberTH = trk.huberTH;
+#ifdef __HIP_DEVICE_COMPILE__
+  // the two products of huberTH alone are the same in every control step of a kernel: computed once at kernel entry they are reloaded from scratch memory in each (epilogueSlot())
+  asm volatile("" : "+v"(huberTH));
+#endif
+  e.maxEnergy = 2 * huberTH * cutoffTH - huberTH * huberTH;
   e.lvl = lvl;
   e.res_only = 0;
 }
@@ -848,7 +885,10 @@ __device__ __noinline__ double waveLdltSolve8(double m, double dv, const int lan
 // its 45 sums — refills them first (LM_REFILL_EVAL; not counted as work of the LM loop).
 template <bool RES_ONLY = false>
 __device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, const LMProblemIn& in, LMProblemOut& out, const float* s_tot, double* s_H, double* s_b,
-                                           double* s_x, int* s_trk, EvalP& s_e, const int lane, const bool res_only_on = false) {
+                                           double* s_x, int* s_trk, EvalP& s_e, const int lane_in, const bool res_only_on = false) {
+  // the lane's row / column and the LDS addresses that follow from them are formed in every step, not once per kernel and reloaded from scratch memory (epilogueSlot())
+  int lane = lane_in;
+  asm volatile("" : "+v"(lane));
   const int maxIterations[5] = {10, 20, 50, 50, 50};
   const float lambdaExtrapolationLimit = 0.001f;
   int takeH = 0, action = ACT_DONE;
@@ -860,6 +900,7 @@ __device__ __forceinline__ bool lmWaveStep(LMState& S, const TrackerDev& trk, co
     if (S.st == LM_INIT_EVAL) {
       res6FromSums(s_tot, S.resOld);
       if (S.resOld[5] > 0.6 && (S.cutoffRepeat < 50 || S.resOld[5] > 0.99)) {
+        asm volatile("" ::: "memory");   // S.cutoffRepeat is read again from LDS: the value of the test above, kept across the branch, was a spill / reload pair
         S.cutoffRepeat *= 2;
         action = ACT_EVAL_CUR;  // same pose, doubled cutoff; stay in LM_INIT_EVAL
       } else {
@@ -1052,9 +1093,12 @@ struct ClusterArgs { int C; float* part; /* B x 2 x C x ACC_PAD */ unsigned int*
                      EvalP* log; /* diagnostics (dmvio_hip_tracker_debug_record_replay): B x LM_LOG_EVALS evaluation parameters, or NULL */ int* log_n; /* B */
                      int res_only; /* dmvio_hip_tracker_set_residual_only_evals: evaluations whose sums nothing reads run as blockEvalRes */ };
 
-__device__ __forceinline__ void clusterExchange(float* s_tot, const ClusterArgs& cl, const int prob, const int rank, const unsigned int phase) {
+__device__ __forceinline__ void clusterExchange(float* s_tot, const ClusterArgs& cl, const int prob_in, const int rank, const unsigned int phase) {
+  const int tid = epilogueSlot();   // the per-thread addresses below, and the problem's offset into cl.part, are formed here, in every exchange
+  int prob = prob_in;               // (wave-uniform at every caller)
+  asm volatile("" : "+s"(prob));
   float* __restrict__ mine = cl.part + (((size_t)prob * 2 + (phase & 1u)) * cl.C + rank) * ACC_PAD;
-  if (threadIdx.x < ACC_PAD) __hip_atomic_store(mine + threadIdx.x, s_tot[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid < ACC_PAD) __hip_atomic_store(mine + tid, s_tot[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   if (threadIdx.x == 0) {
     __hip_atomic_fetch_add(cl.cnt + prob, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -1062,9 +1106,9 @@ __device__ __forceinline__ void clusterExchange(float* s_tot, const ClusterArgs&
     while (__hip_atomic_load(cl.cnt + prob, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(2);
   }
   __syncthreads();
-  if (threadIdx.x < ACC_PAD) {
+  if (tid < ACC_PAD) {
     const float* __restrict__ all = cl.part + ((size_t)prob * 2 + (phase & 1u)) * cl.C * ACC_PAD;
-    s_tot[threadIdx.x] = sumPartialsInOrder(all + threadIdx.x, cl.C);
+    s_tot[tid] = sumPartialsInOrder(all + tid, cl.C);
   }
   __syncthreads();
 }

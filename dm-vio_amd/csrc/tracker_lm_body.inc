@@ -12,7 +12,9 @@
   __shared__ double s_H[64], s_b[8], s_x[8];
   __shared__ int s_go, s_trk[8];
   __shared__ LMState S;  // written by lane 0 of wave 0 only
-  const int prob = blockIdx.x / cl.C, rank = blockIdx.x % cl.C;
+  // the division by the cluster size runs on the vector unit: back to scalar registers, so that what is indexed by the problem or the rank (out, cl.part, cl.log) is addressed
+  // from scalar registers and not from per-lane copies that would be spilled across the evaluation loops
+  const int prob = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / cl.C)), rank = __builtin_amdgcn_readfirstlane((int)(blockIdx.x % cl.C));
   // `in` is pinned host memory: one read of the 120-byte record per workgroup, kept in LDS
   __shared__ LMProblemIn s_in;
   static_assert(sizeof(LMProblemIn) % 4 == 0 && sizeof(LMProblemIn) <= 256, "LMProblemIn is copied as dwords by one wavefront");
@@ -33,7 +35,7 @@
   }
   if (threadIdx.x < 64) { s_H[threadIdx.x] = 0; if (threadIdx.x < 8) { s_b[threadIdx.x] = 0; s_x[threadIdx.x] = 0; } }
   initStage<T>(s_stage);
-  const int slot = pin.new_slot;
+  const int slot = __builtin_amdgcn_readfirstlane(pin.new_slot);   // read from LDS, so a vector register to the compiler: what is addressed by the slot (its planes, its stamps) stays scalar
   // every pixel of the new frame finite (stamped by its pyramid build): the evaluation loop without the isfinite guards gives the same values
   const bool clean = __builtin_amdgcn_readfirstlane((int)(fs.bad_gen[slot] != fs.build_gen[slot])) != 0;
   const bool tiled0 = TL && __builtin_amdgcn_readfirstlane((int)fs.tiled0[slot]) != 0;
@@ -54,29 +56,32 @@
     tStep += t1 - t0;
     if (cl.log && rank == 0 && threadIdx.x == 0) {   // diagnostics: the schedule of evaluations this problem runs (k_track_replay runs it again without the control steps)
       const int k = (int)phase_log;
-      if (s_go && k < LM_LOG_EVALS) cl.log[(size_t)prob * LM_LOG_EVALS + k] = s_e;
-      if (!s_go) cl.log_n[prob] = k < LM_LOG_EVALS ? k : LM_LOG_EVALS;
+      int lp = prob;
+      asm volatile("" : "+s"(lp));   // the two addresses are formed here (epilogueSlot())
+      if (s_go && k < LM_LOG_EVALS) cl.log[(size_t)lp * LM_LOG_EVALS + k] = s_e;
+      if (!s_go) cl.log_n[lp] = k < LM_LOG_EVALS ? k : LM_LOG_EVALS;
     }
     phase_log++;
     if (!s_go) break;
     const int lvl = s_e.lvl;
     // the plane's address is wave-uniform (level 0 comes out of the pointer table): keep it in scalar registers
     const float* img = dmvUniformGlobal(fs.level(slot, lvl));
+    const int first = rank * T + epilogueSlot();   // this thread's first template record; formed in every round (epilogueSlot())
     if (__builtin_amdgcn_readfirstlane(s_e.res_only)) {   // workgroup-uniform; above level 0 only (lmWaveStep)
-      if (clean) blockEvalRes<T, false>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_partS, s_tot);
-      else blockEvalRes<T, true>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_partS, s_tot);
+      if (clean) blockEvalRes<T, false>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), first, cl.C * T, img, trk.huberTH, s_partS, s_tot);
+      else blockEvalRes<T, true>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), first, cl.C * T, img, trk.huberTH, s_partS, s_tot);
     } else if (TL && tiled0 && lvl == 0) {   // workgroup-uniform
       if (clean)
-        blockEval<T, false, TL>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
+        blockEval<T, false, TL>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), first, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
                                 s_tot);
       else
-        blockEval<T, true, TL>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
+        blockEval<T, true, TL>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), first, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
                                s_tot);
     } else if (clean)
-      blockEval<T, false>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
+      blockEval<T, false>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), first, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
                           s_tot);
     else
-      blockEval<T, true>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), rank * T + threadIdx.x, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
+      blockEval<T, true>(s_e, trk.g[lvl], refPtr<TABLE>(trk.pc[lvl]), refInt<TABLE>(trk.pc_n[lvl]), refPtr<TABLE>(trk.flow_mask), first, cl.C * T, img, trk.huberTH, s_stage, s_partH, s_partS,
                          s_tot);
     if (cl.C > 1) { clusterExchange(s_tot, cl, prob, rank, phase); phase++; }
     tEval += wall_clock64() - t1;
