@@ -8,7 +8,7 @@
 // 30-40 us per window each) is dealt out over a few persistent worker threads — at 64 windows it was 4.3 ms of a 12 ms call
 //
 // The host side only, and part of capi_ba.hip's translation unit: included there, once, behind the handle's helpers it uses (fillWindow, dynFromHost, makeDecide, resolveTh,
-// uploadAdjoints, calcLEnergy, BA_BY_MAXF).  The BA device code stays in that one unit in its include order — a second unit that instantiated the batched kernels compiled
+// uploadAdjoints, BA_BY_MAXF; calcLEnergy of ba_loop_host.hpp; accumArgs / accBlocks of the handle).  The BA device code stays in that one unit in its include order — a second unit that instantiated the batched kernels compiled
 // three of them differently.
 #pragma once
 #include <thread>
@@ -315,7 +315,7 @@ struct BatchCall {
   Grp grp[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
   int groupOf(const int w) const { int g = 0; while (g + 1 < G && w >= grp[g + 1].w0) g++; return g; }
   const BAWinDev* dwins(const Grp& q) const { return B->d_wins + q.w0; }
-  // a group that holds a window with residuals kept linearised runs EnergyFunctional's three accumulations (L / A / Schur pass: accumulateLin in capi_ba.hip) for those
+  // a group that holds a window with residuals kept linearised runs EnergyFunctional's three accumulations (L / A / Schur pass: accumulateLin in ba_loop_host.hpp) for those
   // windows; its other windows take their one ordinary accumulation in the A pass
   bool grpLin[dmvio_hip_ba_batch::BA_BATCH_STREAMS];
   // grid extents: the largest window's
@@ -364,8 +364,7 @@ struct BatchCall {
       dmvio_hip_ba* b = hs[w];
       const hipStream_t gs = grp[groupOf(w)].st;
       if (b->stream != gs) { HIPCHK(hipStreamSynchronize(b->stream)); swap.saved.emplace_back(b, b->stream); b->stream = gs; }
-      const int nacc = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
-      gx_lin = std::max(gx_lin, b->n_lin_blocks); gx_pt8 = std::max(gx_pt8, b->n_pt8_blocks); gx_acc = std::max(gx_acc, nacc); gx_res = std::max(gx_res, (b->H.R + 255) / 256); gx_pts = std::max(gx_pts, b->H.N);
+      gx_lin = std::max(gx_lin, b->n_lin_blocks); gx_pt8 = std::max(gx_pt8, b->n_pt8_blocks); gx_acc = std::max(gx_acc, b->accBlocks()); gx_res = std::max(gx_res, (b->H.R + 255) / 256); gx_pts = std::max(gx_pts, b->H.N);
     }
     gx_lin1 = (gx_res * 256 + LIN_THREADS - 1) / LIN_THREADS;
     stamp(0);
@@ -394,16 +393,10 @@ struct BatchCall {
     V.D.frameTH = B->d_wins[w].frameTH;   // (an address: the record's own copy on the device)
     dynFromHost(H, V.T); V.Tb = V.T;
     b->dyn_cur = V.T;
-    {
-      AccumArgs& A = V.A;
-      A.F = F; A.N = H.N; A.nsTop = b->nsTop; A.nsD = b->nsD; A.nsC = b->nsC;
-      A.top_begin = b->d_top_begin; A.top_members = b->d_top_members; A.scd_begin = b->d_scd_begin; A.scd_members = b->d_scd_members;
-      A.accTop = b->d_accTop; A.accD = b->d_accD; A.accE = b->d_accE; A.accC = b->d_accC; A.numTop = b->d_numTop; A.numD = b->d_numD;
-      A.ticks = nullptr;
-    }
+    V.A = b->accumArgs();
     V.SB = b->SB; V.adHost = b->d_adHost; V.adTarget = b->d_adTarget;
     V.ctl = b->d_ctl;
-    V.n_lin_blocks = b->n_lin_blocks; V.n_pt8_blocks = b->n_pt8_blocks; V.n_acc_blocks = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
+    V.n_lin_blocks = b->n_lin_blocks; V.n_pt8_blocks = b->n_pt8_blocks; V.n_acc_blocks = b->accBlocks();
     V.n_res_blocks = (H.R + 255) / 256; V.n_gather_blocks = n_gather; V.n_stitch_blocks = n_stitch; V.n_lin1_blocks = (H.R + LIN_THREADS - 1) / LIN_THREADS;
     BASolveDev& S = V.S;
     S.F = F; S.n = n; S.stepped = 0; S.iterations_done = 0; S.n_accepted = 0; S.exact_backsub = B->exact_backsub;
@@ -740,15 +733,9 @@ struct MargBatchCall {
       if (b->n_lin == 0) { b->Rs.lin = nullptr; b->P.lHdd = b->P.lbd = b->P.lHcd = nullptr; b->P.HcdAF = nullptr; b->H.HLraw.clear(); b->H.bLraw.clear(); }
     }
     V.P = b->P; V.Rs = b->Rs;
-    {
-      AccumArgs& A = V.A;
-      A.F = F; A.N = N; A.nsTop = b->nsTop; A.nsD = b->nsD; A.nsC = b->nsC;
-      A.top_begin = b->d_top_begin; A.top_members = b->d_top_members; A.scd_begin = b->d_scd_begin; A.scd_members = b->d_scd_members;
-      A.accTop = b->d_accTop; A.accD = b->d_accD; A.accE = b->d_accE; A.accC = b->d_accC; A.numTop = b->d_numTop; A.numD = b->d_numD;
-      A.ticks = nullptr;
-    }
+    V.A = b->accumArgs();
     V.SB = b->SB; V.ctl = b->d_ctl;
-    V.n_lin_blocks = b->n_lin_blocks; V.n_pt8_blocks = b->n_pt8_blocks; V.n_pt_blocks = b->n_pt_blocks; V.n_acc_blocks = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
+    V.n_lin_blocks = b->n_lin_blocks; V.n_pt8_blocks = b->n_pt8_blocks; V.n_pt_blocks = b->n_pt_blocks; V.n_acc_blocks = b->accBlocks();
     V.n_res_blocks = (R + 255) / 256; V.n_gather_blocks = (int)((L.margSysDoubles() + 255) / 256); V.n_stitch_blocks = F + F2; V.n_lin1_blocks = (R + LIN_THREADS - 1) / LIN_THREADS;
     // deltas at the current state (EnergyFunctional::setDeltaF, EnergyFunctional.cpp:175-198)
     std::vector<float> adHT;

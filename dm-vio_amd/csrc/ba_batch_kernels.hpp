@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) k_ba_lin_point_sums_b(const BAWinDev* __r
 }
 // calcLEnergyPt's term of the residuals kept linearised (EnergyFunctional.cpp:349-409), at the deltas of the STEPPED state k_ba_solve just left in the record: every residual's
 // eight products (2 res_toZeroF + J delta) . (J delta) in parallel, then — last workgroup of the window — the reference's summation: an Accumulator11 (four fp32 lanes) per run of
-// 50 points, two 4-lane updates per residual in point / residual order, the runs' totals added in double (capi_ba.hip: linEnergy).  The sum goes on top of the frame / calibration
+// 50 points, two 4-lane updates per residual in point / residual order, the runs' totals added in double (ba_loop_host.hpp: linEnergy).  The sum goes on top of the frame / calibration
 // prior energy the solve stored (BADecide::newL, BASolveDev::newL): the stepped linearisation's accept test, next in the stream, reads it there.
 __global__ void __launch_bounds__(256) k_ba_lin_energy_b(BAWinDev* __restrict__ wins) {
   BAWinDev& V = wins[blockIdx.y];

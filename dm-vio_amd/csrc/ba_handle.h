@@ -1,6 +1,7 @@
 // The window optimiser's handle (include/dmvio_hip.h, "sliding-window BA"): struct dmvio_hip_ba, its lock and ready checks, and the transitions of the caches that the
-// host-driven loop (capi_ba.hip: gnIteration) and the device-resident loop (ba_batch_host.hpp) leave to each other.  A declaration file of capi_ba.hip's translation unit:
-// included there behind ba_kernels.hpp / ba_host.hpp (the types the handle holds) and rccl_api.h.
+// host-driven loop (ba_loop_host.hpp: GnIteration) and the device-resident loop (ba_batch_host.hpp) leave to each other.  A declaration file of capi_ba.hip's translation
+// unit: included there behind ba_kernels.hpp / ba_host.hpp (the types the handle holds) and rccl_api.h, in front of the unit's other host pieces — ba_shard_host.hpp (the
+// exchanges of a sharded window), ba_loop_host.hpp (the host loop), ba_graph_host.hpp (the graph build) and ba_batch_host.hpp.
 #pragma once
 #include <chrono>
 // optional host-side time split of the GN iteration (DMVIO_HIP_BA_TIMING=1 prints it when the handle is destroyed)
@@ -22,15 +23,12 @@ struct dmvio_hip_ba {
   // host copies of the graph
   std::vector<int> h_host, h_point, h_target, h_res_begin;
   std::vector<int> h_newest;   // residuals that target the newest keyframe (inputs of setNewFrameEnergyTH), ascending
-  std::vector<unsigned char> h_prior_flag;
   // device storage.  The window is rebuilt for every keyframe (dmvio_hip_ba_set_graph): its ~75 device arrays are carved out of a few large chunks that stay with the
   // handle and are cleared with one memset each — not allocated, cleared and freed one by one (that cost milliseconds per keyframe, more than optimize(6) itself)
   std::vector<void*> allocs;
   struct Arena { std::vector<std::pair<char*, size_t>> chunks; std::vector<size_t> used; size_t cur = 0, off = 0; bool on = false; } arena;   // used[k]: bytes of chunk k handed out since it was last cleared
   size_t cap_spart = 0, cap_idepth_backup = 0;   // capacities of the grow-only pinned host buffers
-  BAPrecalc* d_pre = nullptr;        // the precalc table the kernels read: one of the two halves of d_pre2
-  BAPrecalc* d_pre2 = nullptr;       // [2][F*F]: the table of the backed-up state stays resident, a rejected step switches back to it
-  int pre_half = 0;
+  BAPrecalc* d_pre = nullptr;        // [F*F]: the precalc table the kernels read (a rejected step relinearises from the backed-up pair terms it gets as a kernel argument)
   double *d_adHost = nullptr, *d_adTarget = nullptr;
   int *d_top_begin = nullptr, *d_top_members = nullptr, *d_scd_begin = nullptr, *d_scd_members = nullptr;
   float *d_accTop = nullptr, *d_accD = nullptr, *d_accE = nullptr, *d_accC = nullptr;
@@ -38,7 +36,8 @@ struct dmvio_hip_ba {
   StitchBufs SB{};
   double *h_sys = nullptr;     // [H_A | b_A | H_sc | b_sc | resInA]: pinned host memory, written by k_ba_stitch_gather
   float *d_spart = nullptr, *h_spart = nullptr;  // point-step partial sums
-  // pinned staging for the per-linearisation precalc upload (no pageable copy, no sync before the kernel that consumes it)
+  // pinned staging for the per-linearisation precalc upload (no pageable copy, no sync before the kernel that consumes it); two, used in turn: an upload may still be
+  // in flight behind a linearisation the host did not wait for
   BAPrecalc* h_pre[2] = {nullptr, nullptr};
   int pre_toggle = 0;
   float* d_fullJ = nullptr;
@@ -65,7 +64,6 @@ struct dmvio_hip_ba {
   bool sys_ready = false;      // h_sys holds the stitched system of the CURRENT state (left behind by the previous GN iteration's chain)
   int n_lin_blocks = 0, n_pt_blocks = 0, n_pt8_blocks = 0, n_epart = 0;   // n_pt8: kernels with eight lanes per point
   bool keep_fullJ = false;   // the 74-float RawResidualJacobian is only materialised on request (dmvio_hip_ba_keep_jacobians) and for marginalisation
-  // partial accumulators per bucket: 1 (default) replays the single-threaded reference order bit for bit; DMVIO_HIP_BA_SPLIT=k uses k
   // partial accumulators per bucket: k > 1 = the structure of the reference's multi-threaded accumulation (per-worker fp32 accumulators summed
   // in double, AccumulatedTopHessian.h:91-139) with a FIXED assignment of members to partials; 1 = the reference's single-threaded order, bit for bit
   int nsTop = 4, nsD = 4, nsC = 16;
@@ -77,9 +75,6 @@ struct dmvio_hip_ba {
   BATimes tm;
   bool timing = false;
   double tm_graph[6] = {0, 0, 0, 0, 0, 0}; long tm_graph_n = 0;   // dmvio_hip_ba_set_graph: drain + arena memset, host lists, allocation, uploads, pinned buffers + slot table, adjoints + final wait
-  // true only between a REJECTED step of gnIteration and the next gnIteration: the state was restored to the one the per-point sums (and the
-  // point backup) were computed at, so k_ba_point_sums would reproduce what is already there.  Every other entry point clears it.
-  bool sums_fresh = false;
   // point marginalisation scratch (dmvio_hip_ba_marginalize_points)
   unsigned char *d_cand = nullptr, *d_decision = nullptr, *d_margActive = nullptr;
   float *d_mHdiF = nullptr, *d_mbdSumF = nullptr, *d_mHcd = nullptr, *d_margRec = nullptr, *d_adHTdelta = nullptr;
@@ -127,10 +122,20 @@ struct dmvio_hip_ba {
   bool fullJ_applied = false;   // d_fullJ holds the Jacobians of the APPLIED linearisation (the last linearisation was followed by its applyRes)
   bool adj_dirty = false;   // the host's adjoint tables (H.adHost / adTarget) are newer than the device copy: uploaded by the next consumer (accumulateViews, a batch call)
 
-  // ---- transitions of the caches above.  Outside of these only the state machine itself (gnIteration, settleReject, accumulate*, optimizeImpl) writes sums_fresh,
-  // sys_ready, pending_reject, pending_trace and pre_static_valid.
-  // the state or the graph changed: the stitched system in h_sys and the per-point sums in hand are stale
-  void stateChanged() { sums_fresh = false; sys_ready = false; }
+  // ---- what the accumulation launches of the host loop and of the batched drivers share: the kernel's view of the buckets and its grid (one workgroup per calibration
+  // partial and per top partial, four Schur partials per workgroup)
+  AccumArgs accumArgs() const {
+    AccumArgs A{};
+    A.F = H.F; A.N = H.N; A.nsTop = nsTop; A.nsD = nsD; A.nsC = nsC;
+    A.top_begin = d_top_begin; A.top_members = d_top_members; A.scd_begin = d_scd_begin; A.scd_members = d_scd_members;
+    A.accTop = d_accTop; A.accD = d_accD; A.accE = d_accE; A.accC = d_accC; A.numTop = d_numTop; A.numD = d_numD;
+    return A;   // (ticks: null)
+  }
+  int accBlocks() const { const int F2 = H.F * H.F; return nsC + F2 * nsTop + (F2 * H.F * nsD + 3) / 4; }
+  // ---- transitions of the caches above.  Outside of these only the state machine itself (GnIteration, settleReject, optimizeImpl) writes sys_ready, pending_reject,
+  // pending_trace and pre_static_valid.
+  // the state or the graph changed: the stitched system in h_sys is stale
+  void stateChanged() { sys_ready = false; }
   // an evaluation point changed (state_zero, a new graph's window): the device table's R0 / t0 / b0 are stale; evalPointUploaded: uploadWindowTables has refreshed them
   void evalPointChanged() { pre_static_valid = false; }
   void evalPointUploaded() { pre_static_valid = true; }

@@ -21,16 +21,8 @@ using namespace dmv;
 #include "rccl_api.h"    // the sharded iteration's collectives (loader and communicator entry points: capi_comm.hip)
 #include "ba_handle.h"   // struct dmvio_hip_ba, its lock / ready checks and the transitions of the loops' caches
 
-// The kernels whose ARGUMENTS are sized by the window (ba_kernels.hpp: BAPreDynT / ResubArgsT, the stitch workgroup of 64 F threads): windows of up to BA_MAXF keyframes
-// take the compact instantiation (the host's wide structs cut down to their prefix), larger ones (up to BA_MAXF_CAP) the wide one.
-#define BA_LAUNCH_LINEARIZE(b, W_, fullJ_, mask_, D_, gate_, use_backup_, T_, use_dyn_, X_, do_resub_) do { \
-    (b)->fullJ_applied = false; \
-    if ((b)->H.F <= BA_MAXF) hipLaunchKernelGGL((k_ba_linearize<BA_MAXF>), dim3((b)->n_lin_blocks), dim3(LIN_THREADS), 0, (b)->stream, W_, (b)->P, (b)->Rs, (const BAPrecalc*)(b)->d_pre, \
-        (b)->ctx->fs, fullJ_, mask_, D_, (int)(gate_), (int)(use_backup_), baNarrow<BAPreDynT<BA_MAXF>>(T_), (int)(use_dyn_), baNarrow<ResubArgsT<BA_MAXF>>(X_), (int)(do_resub_)); \
-    else hipLaunchKernelGGL((k_ba_linearize<BA_MAXF_CAP>), dim3((b)->n_lin_blocks), dim3(LIN_THREADS), 0, (b)->stream, W_, (b)->P, (b)->Rs, (const BAPrecalc*)(b)->d_pre, \
-        (b)->ctx->fs, fullJ_, mask_, D_, (int)(gate_), (int)(use_backup_), T_, (int)(use_dyn_), X_, (int)(do_resub_)); \
-  } while (0)
-// the other launch pairs of that kind: `...` (a launch that names M_ as its template argument) once with M_ = BA_MAXF, once with M_ = BA_MAXF_CAP, the window's F picks
+// The kernels whose ARGUMENTS are sized by the window (ba_kernels.hpp: BAPreDynT / ResubArgsT, the stitch workgroup of 64 F threads) take the compact instantiation up to
+// BA_MAXF keyframes, the wide one up to BA_MAXF_CAP: `...` (a launch that names M_ as its template argument) once with M_ = BA_MAXF, once with BA_MAXF_CAP, the window's F picks
 #define BA_BY_MAXF(F_, M_, ...) do { \
     if ((F_) <= BA_MAXF) { constexpr int M_ = BA_MAXF; __VA_ARGS__; } \
     else { constexpr int M_ = BA_MAXF_CAP; __VA_ARGS__; } \
@@ -78,16 +70,12 @@ static void freeAll(dmvio_hip_ba* b) {
   for (auto& ch : b->arena.chunks) hipFree(ch.first);
   b->arena.chunks.clear(); b->arena.used.clear(); b->arena.cur = b->arena.off = 0;
   b->bounce.release();
-  if (b->h_sys) { hipHostFree(b->h_sys); b->h_sys = nullptr; }
-  if (b->h_spart) { hipHostFree(b->h_spart); b->h_spart = nullptr; }
-  if (b->h_res) { hipHostFree(b->h_res); b->h_res = nullptr; }
-  if (b->h_frameTH) { hipHostFree(b->h_frameTH); b->h_frameTH = nullptr; }
-  if (b->h_idepth_backup) { hipHostFree(b->h_idepth_backup); b->h_idepth_backup = nullptr; }
-  for (int k = 0; k < 2; k++) if (b->h_pre[k]) { hipHostFree(b->h_pre[k]); b->h_pre[k] = nullptr; }
+  auto freeHost = [](auto*& p) { if (p) { hipHostFree(p); p = nullptr; } };
+  freeHost(b->h_sys); freeHost(b->h_spart); freeHost(b->h_res); freeHost(b->h_frameTH); freeHost(b->h_idepth_backup); freeHost(b->h_pre[0]); freeHost(b->h_pre[1]);
   b->cap_spart = b->cap_idepth_backup = 0;
 }
 
-// switch_back: the state was restored to the one whose table is still in the other half (loadSateBackup after a rejected step)
+// the kernels' view of the window (calibration, frame slots, thresholds) from the host's
 static void fillWindow(dmvio_hip_ba* b) {
   BAHost& H = b->H;
   BAWindow& W = b->W;
@@ -108,20 +96,12 @@ static void dynFromHost(const BAHost& H, BAPreDyn& T) {
       v[9] = pc.Kt[0]; v[10] = pc.Kt[1]; v[11] = pc.Kt[2]; v[12] = pc.aff0; v[13] = pc.aff1;
     }
 }
-static int uploadWindowTables(dmvio_hip_ba* b, bool new_state = false, bool switch_back = false) {
+// ... and the precalc table of the current state into the device table
+static int uploadWindowTables(dmvio_hip_ba* b) {
   BAHost& H = b->H;
-  BAWindow& W = b->W;
   b->evalPointUploaded();
-  W.F = H.F; W.w = H.w; W.h = H.h; W.N = H.N; W.R = H.R;
-  W.fx = H.c_f[0]; W.fy = H.c_f[1]; W.cx = H.c_f[2]; W.cy = H.c_f[3];
-  W.fxi = H.c_i[0]; W.fyi = H.c_i[1]; W.cxi = H.c_i[2]; W.cyi = H.c_i[3];
-  W.wM3 = H.w - 3; W.hM3 = H.h - 3;
-  W.huberTH = H.S.huberTH; W.outlierTHSum = H.S.outlierTHSumComponent; W.modeA = H.S.affineOptModeA; W.modeB = H.S.affineOptModeB;
-  for (int f = 0; f < H.F; f++) { W.slot[f] = H.fr[f].slot; W.frameEnergyTH[f] = H.fr[f].frameEnergyTH; }
-  // two pinned staging copies: at most one earlier upload can still be in flight (every linearize ends with a stream sync)
-  if (switch_back) { b->pre_half ^= 1; b->d_pre = b->d_pre2 + (size_t)b->pre_half * H.F * H.F; return 0; }
-  if (new_state) b->pre_half ^= 1;   // keep the previous state's table in the other half
-  b->d_pre = b->d_pre2 + (size_t)b->pre_half * H.F * H.F;
+  fillWindow(b);
+  // two pinned staging copies: the previous upload may still be in flight behind a linearisation the host did not wait for (a deferred one), the one before it cannot be
   BAPrecalc* stage = b->h_pre[b->pre_toggle ^= 1];
   memcpy(stage, H.pre.data(), sizeof(BAPrecalc) * H.F * H.F);
   HIPCHK(hipMemcpyAsync(b->d_pre, stage, sizeof(BAPrecalc) * H.F * H.F, hipMemcpyHostToDevice, b->stream));
@@ -137,34 +117,30 @@ static int uploadAdjoints(dmvio_hip_ba* b) {
 
 // Completion of a chain of kernels: its last kernel stores the chain's ticket into host-coherent memory behind its results; the host spins
 // on that word instead of paying a stream synchronisation (wake-up latency) per Gauss-Newton iteration.
-static int waitTicket(dmvio_hip_ba* b, const unsigned int ticket) {
-  volatile unsigned int* flag = &b->h_res->ticket;
+template <class Published>
+static int spinUntil(dmvio_hip_ba* b, Published published, const char* what, const char* unpublished) {
   unsigned long long spins = 0;
-  while (*flag != ticket) {
+  while (!published()) {
     __builtin_ia32_pause();
     if ((++spins & 0xFFFFF) == 0) {
       const hipError_t q = hipStreamQuery(b->stream);
-      if (q != hipSuccess && q != hipErrorNotReady) return fail("BA kernel chain", __FILE__, __LINE__, q);
-      if (q == hipSuccess && *flag != ticket) return failmsg("BA kernel chain finished without publishing its ticket");
+      if (q != hipSuccess && q != hipErrorNotReady) return fail(what, __FILE__, __LINE__, q);
+      if (q == hipSuccess && !published()) return failmsg(unpublished);
     }
   }
   std::atomic_thread_fence(std::memory_order_acquire);
   return 0;
 }
+static int waitTicket(dmvio_hip_ba* b, const unsigned int ticket) {
+  volatile unsigned int* flag = &b->h_res->ticket;
+  return spinUntil(b, [=] { return *flag == ticket; }, "BA kernel chain", "BA kernel chain finished without publishing its ticket");
+}
 // the host's mirror of the newest keyframe's threshold after an accepted step: the decision pass publishes its decision first and the threshold behind it
 static int resolveTh(dmvio_hip_ba* b) {
   if (!b->th_pending) return 0;
   volatile unsigned int* flag = &b->h_res->th_ticket;
-  unsigned long long spins = 0;
-  while ((int)(*flag - b->th_pending_ticket) < 0) {
-    __builtin_ia32_pause();
-    if ((++spins & 0xFFFFF) == 0) {
-      const hipError_t q = hipStreamQuery(b->stream);
-      if (q != hipSuccess && q != hipErrorNotReady) return fail("BA decision pass", __FILE__, __LINE__, q);
-      if (q == hipSuccess && (int)(*flag - b->th_pending_ticket) < 0) return failmsg("BA decision pass finished without publishing its threshold");
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
+  const unsigned int ticket = b->th_pending_ticket;
+  if (int r = spinUntil(b, [=] { return (int)(*flag - ticket) >= 0; }, "BA decision pass", "BA decision pass finished without publishing its threshold")) return r;
   b->H.fr[b->H.F - 1].frameEnergyTH = b->h_res->th[0];
   b->th_pending = false;
   return 0;
@@ -191,324 +167,9 @@ static BADecide makeDecide(dmvio_hip_ba* b, int mode, bool update_th, bool publi
   if (publish) D.ticket = ++b->ticket;
   return D;
 }
-
-// ---- exchange steps of the sharded iteration.  With an RCCL communicator they are enqueued on the handle's stream between the kernels that produce
-// and consume the buffers (no host hop); the callback transport stages them through host memory.
-static bool sharded(const dmvio_hip_ba* b) { return b->world > 0; }
-static bool linAny(const dmvio_hip_ba* b) { return sharded(b) ? b->n_lin_global > 0 : b->n_lin > 0; }   // any rank holds a residual kept linearised
-static hipEvent_t* commEvents(dmvio_hip_ba* b, const int kind) {
-  b->comm_total[kind]++;
-  if (!b->comm_timing || b->comm_n[kind] >= dmvio_hip_ba::COMM_EVS) return nullptr;
-  hipEvent_t* e = b->comm_ev[kind][b->comm_n[kind]];
-  if (!e[0] && (hipEventCreate(&e[0]) != hipSuccess || hipEventCreate(&e[1]) != hipSuccess)) return nullptr;
-  b->comm_n[kind]++;
-  return e;
-}
-static int commAllReduceSum(dmvio_hip_ba* b, double* d_buf, size_t count) {
-  if (b->nccl) {
-    hipEvent_t* e = commEvents(b, 0);
-    if (e) HIPCHK(hipEventRecord(e[0], b->stream));
-    NCCLCHK(rccl().allReduce(d_buf, d_buf, count, ncclDouble, ncclSum, b->nccl, b->stream));
-    if (e) HIPCHK(hipEventRecord(e[1], b->stream));
-    return 0;
-  }
-  b->h_stage.resize(count);
-  HIPCHK(hipMemcpyAsync(b->h_stage.data(), d_buf, sizeof(double) * count, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  if (b->comm_cb.allreduce_sum_f64(b->comm_cb.user, b->h_stage.data(), count) != 0) return failmsg("comm callback allreduce_sum_f64 failed");
-  HIPCHK(hipMemcpyAsync(d_buf, b->h_stage.data(), sizeof(double) * count, hipMemcpyHostToDevice, b->stream));
-  return 0;
-}
-static int commAllGather(dmvio_hip_ba* b, const float* d_in, float* d_out, size_t count_per_rank) {
-  if (b->nccl) {
-    hipEvent_t* e = commEvents(b, 1);
-    if (e) HIPCHK(hipEventRecord(e[0], b->stream));
-    NCCLCHK(rccl().allGather(d_in, d_out, count_per_rank, ncclFloat, b->nccl, b->stream));
-    if (e) HIPCHK(hipEventRecord(e[1], b->stream));
-    return 0;
-  }
-  const size_t bytes = sizeof(float) * count_per_rank;
-  b->h_stage.resize((bytes * (b->world + 1) + 7) / 8);
-  char* in = (char*)b->h_stage.data(); char* out = in + bytes;
-  HIPCHK(hipMemcpyAsync(in, d_in, bytes, hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  if (b->comm_cb.allgather(b->comm_cb.user, in, out, bytes) != 0) return failmsg("comm callback allgather failed");
-  HIPCHK(hipMemcpyAsync(d_out, out, bytes * b->world, hipMemcpyHostToDevice, b->stream));
-  return 0;
-}
-// record width of the decision exchange: agreed on once per graph (the largest per-rank number of residuals that target the newest keyframe)
-static int ensureExchange(dmvio_hip_ba* b) {
-  if (b->xchg_width) return 0;
-  int mine = (int)b->h_newest.size(), widest = mine;
-  if (b->world > 1) {
-    float* d_tmp = nullptr;
-    if (dalloc(b, &d_tmp, (size_t)b->world + 1)) return -1;
-    const float v = (float)mine;   // exact below 2^24 residuals
-    HIPCHK(hipMemcpyAsync(d_tmp, &v, sizeof(float), hipMemcpyHostToDevice, b->stream));
-    if (int r = commAllGather(b, d_tmp, d_tmp + 1, 1)) return r;
-    std::vector<float> all(b->world);
-    HIPCHK(hipMemcpyAsync(all.data(), d_tmp + 1, sizeof(float) * b->world, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (float a : all) widest = std::max(widest, (int)a);
-  }
-  b->xchg_width = BA_XCHG_HEADER + ((widest + 1) & ~1);   // even: the fp64 energy of every record stays 8-byte aligned
-  if (dalloc(b, &b->d_xchg_local, (size_t)b->xchg_width) || dalloc(b, &b->d_xchg_all, (size_t)b->xchg_width * b->world)) return -1;
-  return 0;
-}
-// tail of a sharded linearisation: the linearisation's last workgroup packed this rank's record (mode 3); gather the records of all ranks and take
-// the decisions of `D` over their union
-static int decideGlobal(dmvio_hip_ba* b, BADecide D) {
-  if (int r = commAllGather(b, b->d_xchg_local, b->d_xchg_all, (size_t)b->xchg_width)) return r;
-  D.xchg_all = b->d_xchg_all; D.xchg_width = b->xchg_width; D.world = b->world;
-  hipLaunchKernelGGL(k_ba_decide_global, dim3(1), dim3(256), 0, b->stream, D);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-// the linearisation kernel's view of a decision block when the points are sharded: pack only
-static BADecide packOnly(dmvio_hip_ba* b, const BADecide& D) {
-  BADecide Dp = D;
-  Dp.mode = 3; Dp.publish = 0; Dp.xchg_local = b->d_xchg_local; Dp.xchg_width = b->xchg_width;
-  return Dp;
-}
-
-// FullSystem::linearizeAll (FullSystemOptimize.cpp:150-218) — returns the energy sum; updates the newest frame's energy threshold
-// (setNewFrameEnergyTH, on the device by the kernel's last workgroup) unless keep_threshold.
-// defer: enqueue only — the caller waits for a LATER ticket of the same stream (kernels it enqueues behind this one) and then picks the results up with linearizePickUp
-static void linearizePickUp(dmvio_hip_ba* b, double* energy, bool keep_threshold) {
-  *energy = b->h_res->E[0];
-  if (!keep_threshold) { b->H.fr[b->H.F - 1].frameEnergyTH = b->h_res->th[0]; b->th_pending = false; }
-}
-static int linearizeAll(dmvio_hip_ba* b, bool fix, double* energy, int table_mode = 0 /* 0 re-upload in place, 1 new state, 2 switch back */, bool keep_threshold = false,
-                        bool defer = false) {
-  BAHost& H = b->H;
-  if (int r = uploadWindowTables(b, table_mode == 1, table_mode == 2)) return r;  // precalc of the current state
-  if (int r = uploadThresholds(b)) return r;
-  const bool shard = sharded(b);
-  if (shard) { if (int r = ensureExchange(b)) return r; }
-  // the decision pass (last workgroup of the linearisation) publishes the ticket the host polls; the applyRes kernel of a fix-linearisation runs behind it on the
-  // same stream and nothing it writes is read by the host, so no stream synchronisation is needed for it either
-  const BADecide D = makeDecide(b, 0, !keep_threshold, true);
-  BA_PROF(b, 0);
-  BA_LAUNCH_LINEARIZE(b, b->W, b->keep_fullJ ? b->d_fullJ : (float*)nullptr, (const unsigned char*)nullptr, shard ? packOnly(b, D) : D, BA_GATE_ALWAYS, 0, b->dyn_cur, 0, b->x_none, 0);
-  BA_PROF(b, 1);
-  if (fix) { hipLaunchKernelGGL(k_ba_apply, dim3((H.R + 255) / 256), dim3(256), 0, b->stream, H.R, b->Rs, (const unsigned char*)nullptr, 1); b->fullJ_applied = b->keep_fullJ; }   // + linearizeAll(true)'s removal of inactive residuals
-  HIPCHK(hipGetLastError());
-  if (shard) { if (int r = decideGlobal(b, D)) return r; }
-  if (defer) return 0;
-  if (int r = waitTicket(b, D.ticket)) return r;
-  linearizePickUp(b, energy, keep_threshold);
-  return 0;
-}
-static int applyRes(dmvio_hip_ba* b) {
-  hipLaunchKernelGGL(k_ba_apply, dim3((b->H.R + 255) / 256), dim3(256), 0, b->stream, b->H.R, b->Rs, (const unsigned char*)nullptr, 0);
-  HIPCHK(hipGetLastError());
-  b->fullJ_applied = b->keep_fullJ;
-  return 0;
-}
-// accumulateAF + accumulateSCF + adjoint stitching on the device; result in h_sys
-static int accumulateViews(dmvio_hip_ba* b, const BARes& Rs, const BAPoints& P, bool wait = true, int gate = BA_GATE_ALWAYS);
-static int accumulateWait(dmvio_hip_ba* b);
-// apply_first: applyRes_Reductor(true) fused into the per-point sums; gate: the whole chain only runs when the last accept test says so
-static int accumulateLin(dmvio_hip_ba* b, bool backup_points, bool apply_first);
-static int accumulate(dmvio_hip_ba* b, bool backup_points = false, bool wait = true, bool sums_fresh = false, bool apply_first = false, int gate = BA_GATE_ALWAYS) {
-  if (linAny(b)) {
-    if (!wait || gate != BA_GATE_ALWAYS) return failmsg("ba: a graph with residuals kept linearised is accumulated synchronously");
-    return accumulateLin(b, backup_points, apply_first);
-  }
-  // (the flag describes the DEVICE's state: a gated chain may not run its applyRes, and a chain without one leaves the buffer as the last linearisation wrote it)
-  if (apply_first) b->fullJ_applied = gate == BA_GATE_ALWAYS ? b->keep_fullJ : false;
-  if (!sums_fresh) hipLaunchKernelGGL(k_ba_point_sums, dim3(b->n_pt8_blocks), dim3(256), 0, b->stream, b->W, b->P, b->Rs, backup_points ? 1 : 0, apply_first ? 1 : 0,
-                                      (const BACtl*)b->d_ctl, gate, (backup_points && b->vio) ? b->h_idepth_backup : (float*)nullptr);
-  BA_PROF(b, 2);
-  return accumulateViews(b, b->Rs, b->P, wait, gate);
-}
-// the accumulation + stitching launches over an arbitrary (records, activity, per-point sums) view of the graph
-static int accumulateViews(dmvio_hip_ba* b, const BARes& RsV, const BAPoints& PV, bool wait, int gate) {
-  BAHost& H = b->H;
-  if (b->adj_dirty) { if (int r = uploadAdjoints(b)) return r; }
-  const int F = H.F, F2 = F * F, n = H.n();
-  hipStream_t s = b->stream;
-  {
-    AccumArgs A;
-    A.F = F; A.N = H.N; A.nsTop = b->nsTop; A.nsD = b->nsD; A.nsC = b->nsC;
-    A.top_begin = b->d_top_begin; A.top_members = b->d_top_members; A.scd_begin = b->d_scd_begin; A.scd_members = b->d_scd_members;
-    A.accTop = b->d_accTop; A.accD = b->d_accD; A.accE = b->d_accE; A.accC = b->d_accC; A.numTop = b->d_numTop; A.numD = b->d_numD;
-    const int nblk = b->nsC + F2 * b->nsTop + (F2 * F * b->nsD + 3) / 4;
-    A.ticks = nullptr;
-    if (b->timing) {
-      if (b->accTicksBlocks != nblk) { if (b->d_accTicks) hipFree(b->d_accTicks); HIPCHK(hipMalloc((void**)&b->d_accTicks, sizeof(long long) * 2 * nblk)); b->accTicksBlocks = nblk; }
-      A.ticks = b->d_accTicks;
-    }
-    hipLaunchKernelGGL(k_ba_accumulate, dim3(nblk), dim3(256), 0, s, A, RsV, PV, (const BACtl*)b->d_ctl, gate);
-  }
-  BA_PROF(b, 3);
-  if (F <= BA_MAXF) hipLaunchKernelGGL((k_ba_stitch<BA_MAXF>), dim3(F + F2), dim3(64 * F), sizeof(StitchWave) * F, s, F, b->nsTop, b->nsD, b->d_accTop, b->d_numTop, b->d_accD, b->d_numD,
-                                       b->d_accE, b->d_adHost, b->d_adTarget, b->SB, (const BACtl*)b->d_ctl, gate);
-  else hipLaunchKernelGGL((k_ba_stitch<BA_MAXF_CAP>), dim3(F + F2), dim3(64 * F), sizeof(StitchWave) * F, s, F, b->nsTop, b->nsD, b->d_accTop, b->d_numTop, b->d_accD, b->d_numD,
-                          b->d_accE, b->d_adHost, b->d_adTarget, b->SB, (const BACtl*)b->d_ctl, gate);
-  BA_PROF(b, 4);
-  const int tot = 2 * (n * n + n);
-  if (!sharded(b)) {
-    b->acc_ticket = ++b->ticket;
-    if (F <= BA_MAXF) hipLaunchKernelGGL((k_ba_stitch_gather<BA_MAXF>), dim3((tot + 256) / 256), dim3(256), 0, s, F, b->nsC, b->d_accC, b->SB, b->d_numTop, F2 * b->nsTop, b->h_sys,
-                                         b->d_ctl, gate, b->h_res, b->acc_ticket);
-    else hipLaunchKernelGGL((k_ba_stitch_gather<BA_MAXF_CAP>), dim3((tot + 256) / 256), dim3(256), 0, s, F, b->nsC, b->d_accC, b->SB, b->d_numTop, F2 * b->nsTop, b->h_sys,
-                            b->d_ctl, gate, b->h_res, b->acc_ticket);
-  } else {
-    // this rank's part of the system stays in HBM, is summed over the ranks in place and only then published to the host
-    if (gate != BA_GATE_ALWAYS) return failmsg("sharded accumulation cannot be gated: every rank must enter the collective");
-    if (F <= BA_MAXF) hipLaunchKernelGGL((k_ba_stitch_gather<BA_MAXF>), dim3((tot + 256) / 256), dim3(256), 0, s, F, b->nsC, b->d_accC, b->SB, b->d_numTop, F2 * b->nsTop, b->d_sys,
-                                         b->d_ctl, gate, (BAHostRes*)nullptr, 0u);
-    else hipLaunchKernelGGL((k_ba_stitch_gather<BA_MAXF_CAP>), dim3((tot + 256) / 256), dim3(256), 0, s, F, b->nsC, b->d_accC, b->SB, b->d_numTop, F2 * b->nsTop, b->d_sys,
-                            b->d_ctl, gate, (BAHostRes*)nullptr, 0u);
-    HIPCHK(hipGetLastError());
-    if (int r = commAllReduceSum(b, b->d_sys, (size_t)tot + 1)) return r;
-    b->acc_ticket = ++b->ticket;
-    hipLaunchKernelGGL(k_ba_publish_sys, dim3(1), dim3(1024), 0, s, (const double*)b->d_sys, b->h_sys, tot + 1, b->h_res, b->acc_ticket);
-  }
-  HIPCHK(hipGetLastError());
-  BA_PROF(b, 5);
-  return wait ? accumulateWait(b) : 0;
-}
-// solveSystemF's three accumulations for a graph with residuals kept linearised (EnergyFunctional.cpp:846-852: accumulateAF_MT, accumulateLF_MT, accumulateSCF_MT).  One
-// accumulation kernel serves a (host,target) bucket's top block and its Schur terms from ONE activity flag; here the three reference passes see different sets — addPoint<0>
-// the active residuals that are not linearised, addPoint<1> those that are (with the res_toZeroF + J delta record), the Schur side every active one — so the kernel chain
-// runs three times over three views and each pass contributes its part: [HL | bL] -> BAHost::HLraw / bLraw, [HA | bA | resInA] and [Hsc | bsc] -> h_sys as always.
-static int accumulateLin(dmvio_hip_ba* b, bool backup_points, bool apply_first) {
-  BAHost& H = b->H;
-  hipStream_t s = b->stream;
-  const int R = H.R, N = H.N, n = H.n(), tot = 2 * (n * n + n);
-  if (apply_first) { if (int r = applyRes(b)) return r; }
-  std::vector<float> adHT;
-  H.adHTdeltaF(adHT);   // EnergyFunctional::setDeltaF at the current state
-  HIPCHK(b->bounce.h2d(b->d_adHTdelta, adHT.data(), sizeof(float) * adHT.size(), s));
-  const float4 cd = make_float4(H.cDeltaF[0], H.cDeltaF[1], H.cDeltaF[2], H.cDeltaF[3]);
-  hipLaunchKernelGGL(k_ba_lin_records, dim3((R + 255) / 256), dim3(256), 0, s, b->W, b->P, b->Rs, (const float*)b->d_fullJ, (const unsigned char*)b->d_lin, (const float*)b->d_rtz,
-                     (const float*)b->d_adHTdelta, cd, b->d_linRec, b->d_linActive, b->d_topActive);
-  hipLaunchKernelGGL(k_ba_lin_point_sums, dim3((N + 255) / 256), dim3(256), 0, s, b->W, b->P, (const float*)b->d_linRec, (const unsigned char*)b->d_linActive, b->d_lHdd, b->d_lbd, b->d_lHcd);
-  hipLaunchKernelGGL(k_ba_point_sums, dim3(b->n_pt8_blocks), dim3(256), 0, s, b->W, b->P, b->Rs, backup_points ? 1 : 0, 0, (const BACtl*)b->d_ctl, (int)BA_GATE_ALWAYS,
-                     (backup_points && b->vio) ? b->h_idepth_backup : (float*)nullptr);
-  HIPCHK(hipGetLastError());
-  // L pass
-  BARes RsL = b->Rs; RsL.rec[0] = RsL.rec[1] = b->d_linRec; RsL.active = b->d_linActive; RsL.lin = nullptr;
-  if (int r = accumulateViews(b, RsL, b->P, true)) return r;
-  H.HLraw.assign(b->h_sys, b->h_sys + (size_t)n * n); H.bLraw.assign(b->h_sys + (size_t)n * n, b->h_sys + (size_t)n * n + n);
-  // A pass
-  BARes RsA = b->Rs; RsA.active = b->d_topActive;
-  if (int r = accumulateViews(b, RsA, b->P, true)) return r;
-  std::vector<double> top(b->h_sys, b->h_sys + (size_t)n * n + n);
-  const int resInA = H.resInA;
-  // Schur pass
-  if (int r = accumulateViews(b, b->Rs, b->P, true)) return r;
-  memcpy(b->h_sys, top.data(), sizeof(double) * top.size());
-  b->h_sys[tot] = (double)resInA; H.resInA = resInA;
-  return 0;
-}
-// calcLEnergyPt (EnergyFunctional.cpp:349-409) for the residuals kept linearised: (2 res_toZeroF + J delta) . (J delta), summed the way the reference does — an Accumulator11
-// (four fp32 lanes; its 1k / 1M levels never fill within a run) per run of 50 points (IndexThreadReduce::reduce with step 50, EnergyFunctional.cpp:427-428), two 4-lane
-// updates per residual in point / residual order, the runs' fp32 totals added in double.  The points' own prior term deltaF^2 priorF is zero: idepth_zero follows idepth.
-static double linEnergy(dmvio_hip_ba* b) {
-  const BAHost& H = b->H;
-  std::vector<float> adHT;
-  H.adHTdeltaF(adHT);
-  double A = 0;
-  for (int p0 = 0; p0 < H.N; p0 += 50) {
-    float d1[4] = {0, 0, 0, 0};
-    for (int pi = p0; pi < std::min(H.N, p0 + 50); pi++)
-      for (int ri = b->h_res_begin[pi]; ri < b->h_res_begin[pi + 1]; ri++) {
-        if (!b->h_lin[ri] || !b->h_linAct[ri]) continue;
-        const float* J = &b->h_linJ[(size_t)ri * 74];
-        const float* rtz = &b->h_rtz[(size_t)ri * 8];
-        const float* dp = &adHT[(size_t)(b->h_host[pi] + H.F * b->h_target[ri]) * 8];
-        const float dd = 0.0f;
-        float sx = 0, sy = 0, cx = 0, cy = 0;
-        for (int i = 0; i < 6; i++) { sx += J[8 + i] * dp[i]; sy += J[14 + i] * dp[i]; }
-        for (int i = 0; i < 4; i++) { cx += J[20 + i] * H.cDeltaF[i]; cy += J[24 + i] * H.cDeltaF[i]; }
-        const float Jp_delta_x = sx + cx + J[28] * dd, Jp_delta_y = sy + cy + J[29] * dd;
-        for (int i = 0; i < 8; i += 4)
-          for (int k = 0; k < 4; k++) {
-            float Jdelta = J[30 + i + k] * Jp_delta_x;
-            Jdelta = Jdelta + J[38 + i + k] * Jp_delta_y;
-            Jdelta = Jdelta + J[46 + i + k] * dp[6];
-            Jdelta = Jdelta + J[54 + i + k] * dp[7];
-            float r0 = rtz[i + k];
-            r0 = r0 + r0;
-            r0 = r0 + Jdelta;
-            d1[k] = d1[k] + Jdelta * r0;
-          }
-      }
-    A += (double)(d1[0] + d1[1] + d1[2] + d1[3]);
-  }
-  return A;
-}
-// EnergyFunctional::calcLEnergyF_MT (EnergyFunctional.cpp:414-431)
-static double calcLEnergy(dmvio_hip_ba* b) { return b->n_lin > 0 ? b->H.calcLEnergyFrames() + linEnergy(b) : b->H.calcLEnergyFrames(); }
-// ... of a window whose points are sharded over ranks: the frame / calibration part is the same on every rank, the linearised residuals' term is this rank's points' share —
-// summed over the ranks by one more (one-double) all-reduce, which every rank enters (n_lin_global decides, not the rank's own count)
-static int calcLEnergyR(dmvio_hip_ba* b, double* out) {
-  if (!sharded(b) || b->n_lin_global == 0) { *out = calcLEnergy(b); return 0; }
-  double l = b->n_lin > 0 ? linEnergy(b) : 0.0;
-  if (!b->d_red1) { if (dalloc(b, &b->d_red1, 1)) return -1; }
-  HIPCHK(b->bounce.h2d(b->d_red1, &l, sizeof(double), b->stream));
-  if (int r = commAllReduceSum(b, b->d_red1, 1)) return r;
-  HIPCHK(b->bounce.d2h(&l, b->d_red1, sizeof(double), b->stream));
-  HIPCHK(b->bounce.finish(b->stream));
-  *out = b->H.calcLEnergyFrames() + l;
-  return 0;
-}
-// the gather kernel publishes per workgroup (BAHostRes::gticket): wait until every slot shows the chain's ticket
-static int waitGather(dmvio_hip_ba* b, const unsigned int ticket, const int nblk) {
-  volatile unsigned int* slots = b->h_res->gticket;
-  unsigned long long spins = 0;
-  for (;;) {
-    bool all = true;
-    for (int k = nblk - 1; k >= 0; k--) if (slots[k] != ticket) { all = false; break; }
-    if (all) break;
-    __builtin_ia32_pause();
-    if ((++spins & 0xFFFFF) == 0) {
-      const hipError_t q = hipStreamQuery(b->stream);
-      if (q != hipSuccess && q != hipErrorNotReady) return fail("BA kernel chain", __FILE__, __LINE__, q);
-      if (q == hipSuccess) {
-        for (int k = 0; k < nblk; k++) if (slots[k] != ticket) return failmsg("BA accumulation chain finished without publishing its system");
-      }
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
-}
-static int accumulateWait(dmvio_hip_ba* b) {
-  const int n = b->H.n(), tot = 2 * (n * n + n);
-  if (!sharded(b)) { if (int r = waitGather(b, b->acc_ticket, (tot + 256) / 256)) return r; }
-  else if (int r = waitTicket(b, b->acc_ticket)) return r;   // h_sys = [H_A | b_A | H_sc | b_sc | resInA]
-  b->H.resInA = (int)b->h_sys[tot];
-  return 0;
-}
-static int resubstitute(dmvio_hip_ba* b, const std::vector<double>& x, bool apply_step = false) {
-  float xc[4];
-  std::vector<float> xAd;
-  b->H.prepareResubstitute(x, xc, xAd);
-  ResubArgs X;
-  memcpy(X.xc, xc, sizeof(xc));
-  memset(X.xAd, 0, sizeof(X.xAd));
-  memcpy(X.xAd, xAd.data(), sizeof(float) * xAd.size());
-  if (b->H.F <= BA_MAXF) hipLaunchKernelGGL((k_ba_resubstitute<BA_MAXF>), dim3(b->n_pt8_blocks), dim3(256), 0, b->stream, b->W, b->P, b->Rs, baNarrow<ResubArgsT<BA_MAXF>>(X), apply_step ? 1 : 0);
-  else hipLaunchKernelGGL((k_ba_resubstitute<BA_MAXF_CAP>), dim3(b->n_pt8_blocks), dim3(256), 0, b->stream, b->W, b->P, b->Rs, X, apply_step ? 1 : 0);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-// mode 0 backup, 1 step from backup, 2 restore; the step-norm sums (mode 1) are only fetched when the caller asks for them
-static int pointStep(dmvio_hip_ba* b, int mode, float fac, float* sumID, float* sumNID) {
-  hipLaunchKernelGGL(k_ba_point_step, dim3(b->n_pt_blocks), dim3(256), 0, b->stream, b->H.N, b->P, mode, fac, (mode == 1 && sumID && sumNID) ? b->d_spart : (float*)nullptr);
-  HIPCHK(hipGetLastError());
-  if (mode == 1 && sumID && sumNID) {
-    HIPCHK(hipMemcpyAsync(b->h_spart, b->d_spart, sizeof(float) * 2 * b->n_pt_blocks, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    float a = 0, d = 0;
-    for (int i = 0; i < b->n_pt_blocks; i++) { a += b->h_spart[2 * i]; d += b->h_spart[2 * i + 1]; }
-    *sumID = a / b->H.N; *sumNID = d / b->H.N;
-  }
-  return 0;
-}
+#include "ba_shard_host.hpp"   // the exchange steps of a window sharded over ranks
+#include "ba_loop_host.hpp"    // the host-driven Gauss-Newton loop: linearise, accumulate, the stages of one iteration, optimizeImpl
+#include "ba_graph_host.hpp"   // setGraphImpl / setGraphFrom, the buffers of residuals kept linearised
 
 extern "C" {
 
@@ -544,7 +205,6 @@ dmvio_hip_ba* dmvio_hip_ba_create(dmvio_hip_ctx* ctx) {
   if (const char* e = getenv("DMVIO_HIP_BA_TIMING")) b->timing = atoi(e) != 0;
   return b;
 }
-void dmvio_hip_ba_batch_destroy(struct dmvio_hip_ba_batch* B);
 void dmvio_hip_ba_destroy(dmvio_hip_ba* b) {
   if (!b) return;
   hipSetDevice(b->ctx->device);
@@ -760,7 +420,9 @@ int dmvio_hip_ba_marginalize_points(dmvio_hip_ba* b, const unsigned char* candid
   {
     const bool fullJ_applied = b->fullJ_applied;
     const BADecide D = makeDecide(b, -1, false, false);   // masked relinearisation: no energy / threshold / accept pass
-    BA_LAUNCH_LINEARIZE(b, b->W, b->d_fullJ, (const unsigned char*)b->d_cand, D, BA_GATE_ALWAYS, 0, b->dyn_cur, 0, b->x_none, 0);
+    LinearizeArgs A = linearizeArgs(b, D);
+    A.fullJ = b->d_fullJ; A.mask = b->d_cand;
+    launchLinearize(b, A);
     b->fullJ_applied = fullJ_applied;   // the candidates' rows are rewritten and applied right below, the others untouched
   }
   hipLaunchKernelGGL(k_ba_apply, dim3((R + 255) / 256), dim3(256), 0, s, R, b->Rs, (const unsigned char*)b->d_cand, 0);
@@ -793,305 +455,16 @@ int dmvio_hip_ba_marginalize_points(dmvio_hip_ba* b, const unsigned char* candid
   return 0;
 }
 
-static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u, const float* v, const float* idepth, const float* color8,
-                        const float* weights8, const unsigned char* hasDepthPrior, int R, const int* res_point, const int* res_target, bool wait);
 // synchronous on return, like every entry point that takes caller arrays; dmvio_hip_ba_set_graph_from is the stream-ordered form
 int dmvio_hip_ba_set_graph(dmvio_hip_ba* b, int N, const int* host, const float* u, const float* v, const float* idepth, const float* color8,
                            const float* weights8, const unsigned char* hasDepthPrior, int R, const int* res_point, const int* res_target) {
   return setGraphImpl(b, N, host, u, v, idepth, color8, weights8, hasDepthPrior, R, res_point, res_target, true);
 }
-static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u, const float* v, const float* idepth, const float* color8,
-                        const float* weights8, const unsigned char* hasDepthPrior, int R, const int* res_point, const int* res_target, bool wait) {
-  if (!b || !host || !u || !v || !idepth || !color8 || !weights8 || !res_point || !res_target) return failmsg("ba_set_graph: null argument");
-  BA_LOCK(b);
-  b->stateChanged();
-  BAHost& H = b->H;
-  if (H.F < 1) return failmsg("ba_set_graph: set_window first");
-  if (N < 1 || R < 1) return failmsg("ba_set_graph: empty graph");
-  dmvio_hip_ctx* c = b->ctx;
-  HIPCHK(hipSetDevice(c->device));
-  double tg0 = b->timing ? nowUs() : 0, tg1;
-#define SG_PH(i) do { if (b->timing) { tg1 = nowUs(); b->tm_graph[i] += tg1 - tg0; tg0 = tg1; } } while (0)
-  HIPCHK(hipStreamSynchronize(b->stream));
-  b->th_pending = false;   // the stream is drained and h_res is cleared below (th_ticket restarts at 0 while b->ticket keeps counting): nothing of the old graph may be awaited
-  freeDevice(b);
-  // residuals kept linearised belong to the graph they were linearised in
-  b->n_lin = 0; b->n_lin_global = 0; b->Rs.lin = nullptr; b->P.lHdd = b->P.lbd = b->P.lHcd = nullptr; b->P.HcdAF = nullptr; b->d_lin = nullptr; b->d_red1 = nullptr; b->H.HLraw.clear(); b->H.bLraw.clear();
-  b->h_lin.clear(); b->h_linAct.clear(); b->h_linJ.clear(); b->h_rtz.clear(); b->fullJ_applied = false;
-  // the arena of the previous graph, cleared for this one on the handle's stream; the uploads and kernels below follow on the same stream: no wait
-  for (size_t k = 0; k < b->arena.chunks.size(); k++) if (b->arena.used[k]) { HIPCHK(hipMemsetAsync(b->arena.chunks[k].first, 0, b->arena.used[k], b->stream)); b->arena.used[k] = 0; }   // what the previous graph used, not the whole chunk
-  SG_PH(0);
-  b->arena.cur = 0; b->arena.off = 0;
-  struct ArenaScope { dmvio_hip_ba* b; ~ArenaScope() { b->arena.on = false; } } arenaScope{b};
-  b->arena.on = true;
-  const int F = H.F, F2 = F * F;
-  H.N = N; H.R = R;
-  b->h_host.assign(host, host + N); b->h_point.assign(res_point, res_point + R); b->h_target.assign(res_target, res_target + R);
-  b->h_newest.clear();
-  for (int ri = 0; ri < R; ri++) if (res_target[ri] == H.F - 1) b->h_newest.push_back(ri);
-  // residuals must be grouped by point, points in window order
-  b->h_res_begin.assign(N + 1, 0);
-  for (int ri = 0; ri < R; ri++) {
-    const int p = res_point[ri];
-    if (p < 0 || p >= N || res_target[ri] < 0 || res_target[ri] >= F) return failmsg("ba_set_graph: residual index out of range");
-    if (ri > 0 && p < res_point[ri - 1]) return failmsg("ba_set_graph: residuals must be sorted by point");
-    if (host[p] < 0 || host[p] >= F || host[p] == res_target[ri]) return failmsg("ba_set_graph: bad host / target");
-    b->h_res_begin[p + 1]++;
-  }
-  for (int p = 0; p < N; p++) b->h_res_begin[p + 1] += b->h_res_begin[p];
-  // bucket member lists in the reference's traversal order (points, then residuals of the point)
-  std::vector<int> top_begin(F2 + 1, 0), top_members(R), scd_begin(F2 * F + 1, 0);
-  for (int ri = 0; ri < R; ri++) top_begin[host[res_point[ri]] + F * res_target[ri] + 1]++;
-  for (int k = 0; k < F2; k++) top_begin[k + 1] += top_begin[k];
-  { std::vector<int> cur(top_begin.begin(), top_begin.end() - 1); for (int ri = 0; ri < R; ri++) top_members[cur[host[res_point[ri]] + F * res_target[ri]]++] = ri; }
-  size_t npairs = 0;
-  for (int p = 0; p < N; p++) { const size_t k = b->h_res_begin[p + 1] - b->h_res_begin[p]; npairs += k * k; }
-  // The Schur buckets' member lists are built on the device (k_ba_scd_*: ba_kernels.hpp) when no point observes a keyframe twice — always, in the reference's graphs (one
-  // PointFrameResidual per point and target, FullSystem.cpp:1248-1262); a graph that does is served by the host loops below, as every graph was before.
-  std::vector<int> pt_first(F, N), pt_last(F, -1);
-  bool scd_on_device = true;
-  for (int p = 0; p < N && scd_on_device; p++) {
-    pt_first[host[p]] = std::min(pt_first[host[p]], p); pt_last[host[p]] = std::max(pt_last[host[p]], p);
-    unsigned int seen = 0;
-    for (int ri = b->h_res_begin[p]; ri < b->h_res_begin[p + 1]; ri++) { const unsigned int bit = 1u << res_target[ri]; if (seen & bit) scd_on_device = false; seen |= bit; }
-  }
-  std::vector<int> scd_members;
-  if (!scd_on_device) {
-    scd_members.resize(3 * npairs);
-    for (int p = 0; p < N; p++)
-      for (int r1 = b->h_res_begin[p]; r1 < b->h_res_begin[p + 1]; r1++)
-        for (int r2 = b->h_res_begin[p]; r2 < b->h_res_begin[p + 1]; r2++) scd_begin[(host[p] + F * res_target[r1]) + res_target[r2] * F2 + 1]++;
-    for (int k = 0; k < F2 * F; k++) scd_begin[k + 1] += scd_begin[k];
-    std::vector<int> cur(scd_begin.begin(), scd_begin.end() - 1);
-    for (int p = 0; p < N; p++)
-      for (int r1 = b->h_res_begin[p]; r1 < b->h_res_begin[p + 1]; r1++)
-        for (int r2 = b->h_res_begin[p]; r2 < b->h_res_begin[p + 1]; r2++) {
-          const int k = (host[p] + F * res_target[r1]) + res_target[r2] * F2;
-          const int o = cur[k]++;
-          scd_members[3 * o] = r1; scd_members[3 * o + 1] = r2; scd_members[3 * o + 2] = p;
-        }
-  }
-  SG_PH(1);
-  // ---- device arrays
-  int *d_host, *d_res_begin, *d_point, *d_target;
-  float *d_u, *d_v, *d_color, *d_weights, *d_prior;
-  if (dalloc(b, &d_host, N) || dalloc(b, &d_res_begin, N + 1) || dalloc(b, &d_point, R) || dalloc(b, &d_target, R) || dalloc(b, &d_u, N) || dalloc(b, &d_v, N) ||
-      dalloc(b, &d_color, (size_t)N * 8) || dalloc(b, &d_weights, (size_t)N * 8) || dalloc(b, &d_prior, N)) return -1;
-  BAPoints& P = b->P; BARes& Rs = b->Rs;
-  if (dalloc(b, &P.idepth, N) || dalloc(b, &P.idepth_zero, N) || dalloc(b, &P.idepth_backup, N) || dalloc(b, &P.step, N) || dalloc(b, &P.Hdd, N) || dalloc(b, &P.bd, N) ||
-      dalloc(b, &P.Hcd, (size_t)N * 4) || dalloc(b, &P.HdiF, N) || dalloc(b, &P.bdSumF, N) || dalloc(b, &P.idepth_hessian, N) ||
-      dalloc(b, &b->d_cand, N) || dalloc(b, &b->d_decision, N) || dalloc(b, &b->d_mHdiF, N) || dalloc(b, &b->d_mbdSumF, N) || dalloc(b, &b->d_mHcd, (size_t)N * 4) ||
-      dalloc(b, &b->d_margRec, (size_t)R * REC_FLOATS) || dalloc(b, &b->d_margActive, R) || dalloc(b, &b->d_adHTdelta, (size_t)F2 * 8)) return -1;
-  if (dalloc(b, &Rs.removed, R) || dalloc(b, &Rs.state, R) || dalloc(b, &Rs.newState, R) || dalloc(b, &Rs.active, R) || dalloc(b, &Rs.which, R) || dalloc(b, &Rs.energy, R) || dalloc(b, &Rs.newEnergy, R) ||
-      dalloc(b, &Rs.center, (size_t)R * 3) || dalloc(b, &Rs.rec[0], (size_t)R * REC_FLOATS) || dalloc(b, &Rs.rec[1], (size_t)R * REC_FLOATS)) return -1;
-  P.host = d_host; P.u = d_u; P.v = d_v; P.color = d_color; P.weights = d_weights; P.priorF = d_prior; P.res_begin = d_res_begin;
-  Rs.point = d_point; Rs.target = d_target;
-  std::vector<float> prior(N, 0.0f);
-  if (hasDepthPrior) for (int p = 0; p < N; p++) prior[p] = hasDepthPrior[p] ? H.S.idepthFixPrior : 0.0f;   // EFPoint::takeData
-  hipStream_t s = b->stream;
-  SG_PH(2);
-  // the uploads of this call are staged and leave merged (DmvBounce::begin_group): the nine point / residual tables and the two copies of idepth are one copy, ...
-  struct GroupScope { DmvBounce& bn; ~GroupScope() { bn.grouping = false; bn.group.clear(); } } groupScope{b->bounce};   // an error return drops what was only staged
-  b->bounce.begin_group();
-  HIPCHK(b->bounce.h2d(d_host, host, sizeof(int) * N, s));
-  HIPCHK(b->bounce.h2d(d_res_begin, b->h_res_begin.data(), sizeof(int) * (N + 1), s));
-  HIPCHK(b->bounce.h2d(d_point, res_point, sizeof(int) * R, s));
-  HIPCHK(b->bounce.h2d(d_target, res_target, sizeof(int) * R, s));
-  HIPCHK(b->bounce.h2d(d_u, u, sizeof(float) * N, s));
-  HIPCHK(b->bounce.h2d(d_v, v, sizeof(float) * N, s));
-  HIPCHK(b->bounce.h2d(d_color, color8, sizeof(float) * N * 8, s));
-  HIPCHK(b->bounce.h2d(d_weights, weights8, sizeof(float) * N * 8, s));
-  HIPCHK(b->bounce.h2d(d_prior, prior.data(), sizeof(float) * N, s));
-  HIPCHK(b->bounce.h2d(P.idepth, idepth, sizeof(float) * N, s));
-  HIPCHK(b->bounce.h2d(P.idepth_zero, idepth, sizeof(float) * N, s));
-  b->pre_half = 0;
-  if (dalloc(b, &b->d_pre2, 2 * (size_t)F2) || dalloc(b, &b->d_adHost, (size_t)F2 * 64) || dalloc(b, &b->d_adTarget, (size_t)F2 * 64) || dalloc(b, &b->d_top_begin, F2 + 1) ||
-      dalloc(b, &b->d_top_members, R) || dalloc(b, &b->d_scd_begin, F2 * F + 1) || dalloc(b, &b->d_scd_members, 3 * npairs) || dalloc(b, &b->d_accTop, (size_t)F2 * 96 * b->nsTop) ||
-      dalloc(b, &b->d_accD, (size_t)F2 * F * 64 * b->nsD) || dalloc(b, &b->d_accE, (size_t)F2 * 40 * b->nsTop) || dalloc(b, &b->d_accC, 20 * b->nsC) || dalloc(b, &b->d_numTop, F2 * b->nsTop) || dalloc(b, &b->d_numD, F2 * F * b->nsD)) return -1;
-  HIPCHK(b->bounce.h2d(b->d_top_begin, top_begin.data(), sizeof(int) * (F2 + 1), s));
-  HIPCHK(b->bounce.h2d(b->d_top_members, top_members.data(), sizeof(int) * R, s));
-  if (!scd_on_device) {
-    HIPCHK(b->bounce.h2d(b->d_scd_begin, scd_begin.data(), sizeof(int) * (F2 * F + 1), s));
-    HIPCHK(b->bounce.h2d(b->d_scd_members, scd_members.data(), sizeof(int) * 3 * npairs, s));
-    HIPCHK(b->bounce.end_group(s));
-  } else {
-    // behind the uploads of host / point / target on the same stream: residual table, counts, scan, members
-    int *d_ridx, *d_cnt, *d_first, *d_last;
-    if (dalloc(b, &d_ridx, (size_t)N * F) || dalloc(b, &d_cnt, (size_t)F2 * F) || dalloc(b, &d_first, F) || dalloc(b, &d_last, F)) return -1;
-    HIPCHK(b->bounce.h2d(d_first, pt_first.data(), sizeof(int) * F, s));
-    HIPCHK(b->bounce.h2d(d_last, pt_last.data(), sizeof(int) * F, s));
-    HIPCHK(b->bounce.end_group(s));   // the kernels below read what was staged so far
-    HIPCHK(hipMemsetAsync(d_ridx, 0xff, sizeof(int) * (size_t)N * F, s));
-    hipLaunchKernelGGL(k_ba_scd_ridx, dim3((R + 255) / 256), dim3(256), 0, s, R, F, (const int*)d_point, (const int*)d_target, d_ridx);
-    hipLaunchKernelGGL(k_ba_scd_lists, dim3((F2 + 3) / 4, F), dim3(256), 0, s, F, (const int*)d_first, (const int*)d_last, (const int*)d_host, (const int*)d_ridx, 0, d_cnt, (const int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_ba_scd_scan, dim3(1), dim3(1024), 0, s, F2 * F, (const int*)d_cnt, b->d_scd_begin);
-    hipLaunchKernelGGL(k_ba_scd_lists, dim3((F2 + 3) / 4, F), dim3(256), 0, s, F, (const int*)d_first, (const int*)d_last, (const int*)d_host, (const int*)d_ridx, 1, d_cnt, (const int*)b->d_scd_begin, b->d_scd_members);
-    HIPCHK(hipGetLastError());
-  }
-  SG_PH(3);
-  b->bounce.begin_group();   // ... the slot table and the adjoint tables another
-  StitchBufs& SB = b->SB;
-  if (dalloc(b, &SB.topHH, (size_t)F * 64) || dalloc(b, &SB.topTT, (size_t)F2 * 64) || dalloc(b, &SB.topHT, (size_t)F2 * 64) || dalloc(b, &SB.topHC, (size_t)F * 32) ||
-      dalloc(b, &SB.topTC, (size_t)F2 * 32) || dalloc(b, &SB.topBH, (size_t)F * 8) || dalloc(b, &SB.topBT, (size_t)F2 * 8) || dalloc(b, &SB.topCC, (size_t)F * 20) ||
-      dalloc(b, &SB.scHH, (size_t)F2 * 64) || dalloc(b, &SB.scTT, (size_t)F2 * F * 64) || dalloc(b, &SB.scTH, (size_t)F2 * 64) || dalloc(b, &SB.scHT, (size_t)F2 * F * 64) ||
-      dalloc(b, &SB.scHC, (size_t)F2 * 32) ||
-      dalloc(b, &SB.scTC, (size_t)F2 * 32) || dalloc(b, &SB.scBH, (size_t)F2 * 8) || dalloc(b, &SB.scBT, (size_t)F2 * 8)) return -1;
-  const int n = H.n(), tot = 2 * (n * n + n);
-  b->n_lin_blocks = (R + LIN_RES_PER_BLOCK - 1) / LIN_RES_PER_BLOCK; b->n_pt_blocks = (N + 255) / 256; b->n_pt8_blocks = (N + PT_GROUPS_PER_BLOCK - 1) / PT_GROUPS_PER_BLOCK;
-  // energy partials (doubles) and the per-residual energies with outliers (floats) share one pinned allocation the kernel stores into
-  b->n_epart = std::max(b->n_lin_blocks, F2 * 8);
-  if (dalloc(b, &b->d_spart, 2 * b->n_pt_blocks) || dalloc(b, &b->d_fullJ, (size_t)R * 74)) return -1;
-  // what the host reads back every iteration (the stitched system, the energy partials, the per-residual energies) is written by the
-  // kernels straight into pinned host memory: no copy engine between the last kernel and the host's wait
-  constexpr int NMAXF = 4 + 8 * BA_MAXF_CAP;
-  if (!b->h_sys) HIPCHK(hipHostMalloc((void**)&b->h_sys, sizeof(double) * (2 * (NMAXF * NMAXF + NMAXF) + 1), hipHostMallocCoherent | hipHostMallocMapped));   // polled: host-coherent; sized for BA_MAXF_CAP keyframes once
-  if (dalloc(b, &b->d_sys, (size_t)tot + 1)) return -1;
-  b->xchg_width = 0; b->d_xchg_local = b->d_xchg_all = nullptr;
-  b->graphReplaced();
-  if (!b->h_res) HIPCHK(hipHostMalloc((void**)&b->h_res, sizeof(BAHostRes), hipHostMallocCoherent | hipHostMallocMapped));
-  memset(b->h_res, 0, sizeof(BAHostRes));
-  if (!b->h_frameTH) HIPCHK(hipHostMalloc((void**)&b->h_frameTH, sizeof(float) * BA_MAXF_CAP, hipHostMallocDefault));
-  if ((size_t)N > b->cap_idepth_backup) {
-    if (b->h_idepth_backup) HIPCHK(hipHostFree(b->h_idepth_backup));
-    b->cap_idepth_backup = (size_t)N + (size_t)N / 2 + 256;
-    HIPCHK(hipHostMalloc((void**)&b->h_idepth_backup, sizeof(float) * b->cap_idepth_backup, hipHostMallocCoherent | hipHostMallocMapped));
-  }
-  if (dalloc(b, &b->d_ctl, 1) || dalloc(b, &b->d_frameTH, BA_MAXF_CAP) || dalloc(b, &b->d_epart, (size_t)b->n_epart) || dalloc(b, &b->d_newestSlot, (size_t)R) || dalloc(b, &b->d_newestE, b->h_newest.size()) ||
-      dalloc(b, &b->d_newEnergyWO, (size_t)R)) return -1;
-  {
-    std::vector<int> slot(R, -1);
-    for (size_t k = 0; k < b->h_newest.size(); k++) slot[b->h_newest[k]] = (int)k;
-    if (R) HIPCHK(b->bounce.h2d(b->d_newestSlot, slot.data(), sizeof(int) * R, s));   // staged (the vector may go): asynchronous like the other uploads
-    Rs.newestSlot = b->d_newestSlot; Rs.newestE = b->d_newestE;
-  }
-  for (int k = 0; k < 2; k++) if (!b->h_pre[k]) HIPCHK(hipHostMalloc((void**)&b->h_pre[k], sizeof(BAPrecalc) * BA_MAXF_CAP * BA_MAXF_CAP, hipHostMallocDefault));
-  Rs.newEnergyWO = b->d_newEnergyWO;
-  if ((size_t)2 * b->n_pt_blocks > b->cap_spart) {
-    if (b->h_spart) HIPCHK(hipHostFree(b->h_spart));
-    b->cap_spart = (size_t)2 * b->n_pt_blocks + 64;
-    HIPCHK(hipHostMalloc((void**)&b->h_spart, sizeof(float) * b->cap_spart, hipHostMallocDefault));
-  }
-  SG_PH(4);
-  if (int r = uploadAdjoints(b)) return r;
-  HIPCHK(b->bounce.end_group(s));
-  // everything above is staged in pinned memory and enqueued on the handle's stream, and so is whatever uses it: dmvio_hip_ba_set_graph_from does not wait (the 0.1 ms the
-  // uploads take overlap the caller's next calls — frame states, prior, the first host-side steps of optimize)
-  HIPCHK(hipGetLastError());
-  if (wait) HIPCHK(hipStreamSynchronize(s));
-  SG_PH(5);
-#undef SG_PH
-  b->tm_graph_n++;
-  b->graph_ready = true;
-  return 0;
-}
 
-// dmvio_hip_ba_set_graph from a resident graph (capi_graph.hip): the mirror flattened in makeIDX order — compact records, a few tens of microseconds — instead of arrays
-// the caller rebuilt from its pointer graph.  The window (dmvio_hip_ba_set_window) must have as many keyframes as the graph.  The scratch arrays stay with the handle.
-static int linImport(dmvio_hip_ba* b, const unsigned char* flags, const float* J74, const float* rtz, int* n_linearized);
 int dmvio_hip_ba_set_graph_from(dmvio_hip_ba* b, dmvio_hip_graph* g) {
   if (!b || !g) return failmsg("ba_set_graph_from: null argument");
   BA_LOCK(b);
-  int N = 0, R = 0;
-  unsigned long long flat_version = 0;
-  {
-    std::lock_guard<std::mutex> lg(g->mu);
-    if ((int)g->frames.size() != b->H.F) return failmsg("ba_set_graph_from: the graph has " + std::to_string(g->frames.size()) + " keyframes, the window " + std::to_string(b->H.F));
-    if (g->nDangling) return failmsg("ba_set_graph_from: " + std::to_string(g->nDangling) + " residuals still target a removed keyframe (their dropResidual has not been forwarded)");
-    N = g->nPoints; R = g->nRes;
-    if (N < 1 || R < 1) return failmsg("ba_set_graph: empty graph");
-    flat_version = g->version;
-    auto& S = b->gscratch;
-    S.host.resize(N); S.u.resize(N); S.v.resize(N); S.idepth.resize(N); S.color.resize(8 * (size_t)N); S.weights.resize(8 * (size_t)N); S.prior.resize(N);
-    S.res_point.resize(R); S.res_target.resize(R);
-    const bool anyLin = g->nLin > 0;   // residuals that arrive linearised: their flags / Jacobians / res_toZeroF in flat order (only then)
-    if (anyLin) { S.lin.assign(R, 0); S.linJ.resize((size_t)R * 74); S.linRtz.resize((size_t)R * 8); } else S.lin.clear();
-    int pi = 0, ri = 0;
-    for (int f = 0; f < (int)g->frames.size(); f++)
-      for (const DmvGraphPoint& P : g->frames[f]) {
-        S.host[pi] = f; S.u[pi] = P.u; S.v[pi] = P.v; S.idepth[pi] = P.idepth; S.prior[pi] = P.prior;
-        memcpy(&S.color[8 * (size_t)pi], P.color, sizeof(P.color)); memcpy(&S.weights[8 * (size_t)pi], P.weights, sizeof(P.weights));
-        for (int k = 0; k < P.nres; k++, ri++) {
-          S.res_point[ri] = pi; S.res_target[ri] = P.target[k];
-          if (anyLin && P.lin[k] >= 0) {
-            S.lin[ri] = 1;
-            memcpy(&S.linJ[(size_t)ri * 74], g->linPool[P.lin[k]].J, sizeof(float) * 74); memcpy(&S.linRtz[(size_t)ri * 8], g->linPool[P.lin[k]].res_toZeroF, sizeof(float) * 8);
-          }
-        }
-        pi++;
-      }
-  }
-  const auto& S = b->gscratch;
-  if (int r = setGraphImpl(b, N, S.host.data(), S.u.data(), S.v.data(), S.idepth.data(), S.color.data(), S.weights.data(), S.prior.data(), R, S.res_point.data(), S.res_target.data(), false)) return r;
-  if (!S.lin.empty()) { if (int r = linImport(b, S.lin.data(), S.linJ.data(), S.linRtz.data(), nullptr)) { b->graph_ready = false; return r; } }
-  // only a window that WAS built makes its flat order the one dmvio_hip_graph_set_idepths accepts values in (until the structure changes).  The uploads are stream-ordered:
-  // an asynchronous copy error of this call is reported by the next BA call that synchronises
-  std::lock_guard<std::mutex> lg(g->mu);
-  g->flat_version = flat_version;
-  return 0;
-}
-
-
-// buffers of the residuals kept linearised (first use on a graph)
-static int linAlloc(dmvio_hip_ba* b) {
-  const int R = b->H.R, N = b->H.N;
-  if (b->d_lin) return 0;
-  if (dalloc(b, &b->d_lin, R) || dalloc(b, &b->d_linMask, R) || dalloc(b, &b->d_linActive, R) || dalloc(b, &b->d_topActive, R) || dalloc(b, &b->d_rtz, (size_t)R * 8) ||
-      dalloc(b, &b->d_linRec, (size_t)R * REC_FLOATS) || dalloc(b, &b->d_lHdd, N) || dalloc(b, &b->d_lbd, N) || dalloc(b, &b->d_lHcd, (size_t)N * 4) ||
-      dalloc(b, &b->d_HcdAF, (size_t)N * 4) || dalloc(b, &b->d_linE, (size_t)R * 8)) return -1;
-  b->h_lin.assign(R, 0);
-  HIPCHK(hipMemsetAsync(b->d_lin, 0, R, b->stream));   // (the arena hands out zeroed memory after set_graph; a second graph's first use must not depend on it)
-  return 0;
-}
-// after the device flags changed: the host copies calcLEnergyPt reads (the energy terms are host arithmetic in this library), the counts, the kernels' views
-static int linFinish(dmvio_hip_ba* b, int* n_linearized) {
-  const int R = b->H.R;
-  hipStream_t s = b->stream;
-  b->h_linAct.resize(R); b->h_linJ.resize((size_t)R * 74); b->h_rtz.resize((size_t)R * 8);
-  HIPCHK(b->bounce.d2h(b->h_lin.data(), b->d_lin, R, s));
-  HIPCHK(b->bounce.d2h(b->h_linAct.data(), b->Rs.active, R, s));
-  HIPCHK(b->bounce.d2h(b->h_linJ.data(), b->d_fullJ, sizeof(float) * 74 * R, s));
-  HIPCHK(b->bounce.d2h(b->h_rtz.data(), b->d_rtz, sizeof(float) * 8 * R, s));
-  HIPCHK(b->bounce.finish(s));
-  b->n_lin = 0;
-  for (int ri = 0; ri < R; ri++) if (b->h_lin[ri]) b->n_lin++;
-  b->n_lin_global = b->n_lin;
-  if (sharded(b)) {   // collective: every rank of the window calls this (with the flags of its own residuals); the ranks' counts are summed
-    double cnt = (double)b->n_lin;
-    if (!b->d_red1) { if (dalloc(b, &b->d_red1, 1)) return -1; }
-    HIPCHK(b->bounce.h2d(b->d_red1, &cnt, sizeof(double), s));
-    if (int r = commAllReduceSum(b, b->d_red1, 1)) return r;
-    HIPCHK(b->bounce.d2h(&cnt, b->d_red1, sizeof(double), s));
-    HIPCHK(b->bounce.finish(s));
-    b->n_lin_global = (long long)(cnt + 0.5);
-  }
-  if (linAny(b)) { b->Rs.lin = b->d_lin; b->P.lHdd = b->d_lHdd; b->P.lbd = b->d_lbd; b->P.lHcd = b->d_lHcd; b->P.HcdAF = b->d_HcdAF; }
-  if (n_linearized) *n_linearized = b->n_lin;
-  return 0;
-}
-// residuals that arrive linearised: flags (R), J74 (R x 74) and res_toZeroF (R x 8) indexed by residual; only the flagged rows travel
-static int linImport(dmvio_hip_ba* b, const unsigned char* flags, const float* J74, const float* rtz, int* n_linearized) {
-  const int R = b->H.R;
-  hipStream_t s = b->stream;
-  std::vector<int> idx;
-  for (int ri = 0; ri < R; ri++) if (flags[ri]) idx.push_back(ri);
-  if (idx.empty() && !sharded(b)) { if (n_linearized) *n_linearized = b->n_lin; return 0; }
-  if (int r = linAlloc(b)) return r;
-  const int n = (int)idx.size();
-  if (n > 0) {
-    std::vector<float> packed((size_t)n * 82);
-    for (int k = 0; k < n; k++) {
-      memcpy(&packed[(size_t)k * 82], J74 + (size_t)idx[k] * 74, sizeof(float) * 74);
-      memcpy(&packed[(size_t)k * 82 + 74], rtz + (size_t)idx[k] * 8, sizeof(float) * 8);
-    }
-    int* d_idx = nullptr; float* d_packed = nullptr;
-    if (dalloc(b, &d_idx, n) || dalloc(b, &d_packed, (size_t)n * 82)) return -1;
-    HIPCHK(b->bounce.h2d(d_idx, idx.data(), sizeof(int) * n, s));
-    HIPCHK(b->bounce.h2d(d_packed, packed.data(), sizeof(float) * packed.size(), s));
-    hipLaunchKernelGGL(k_ba_lin_import, dim3((n + 255) / 256), dim3(256), 0, s, n, (const int*)d_idx, (const float*)d_packed, b->Rs, b->d_fullJ, b->d_rtz, b->d_linRec, b->d_lin);
-    HIPCHK(hipGetLastError());
-  }
-  b->stateChanged();
-  return linFinish(b, n_linearized);
+  return setGraphFrom(b, g);
 }
 
 int dmvio_hip_ba_set_residual_flags(dmvio_hip_ba* b, int R, const unsigned char* isLinearized) {
@@ -1188,7 +561,7 @@ int dmvio_hip_ba_activate_all(dmvio_hip_ba* b) {
 int dmvio_hip_ba_linearize(dmvio_hip_ba* b, int fix, double* energy) {
   BA_READY(b);
   double e = 0;
-  if (int r = linearizeAll(b, fix != 0, &e)) return r;
+  if (int r = linearizeAll(b, fix != 0, TH_UPDATE, &e)) return r;
   if (energy) *energy = e;
   return 0;
 }
@@ -1386,219 +759,12 @@ int dmvio_hip_ba_get_calib(dmvio_hip_ba* b, double fxfycxcy[4]) {
   return 0;
 }
 
-// One Gauss-Newton iteration = the loop body of FullSystem::optimize (FullSystemOptimize.cpp:485-586).
-//
-// The host solves the 68x68 system (the hand-off point of the reference's GTSAM branch, EnergyFunctional.cpp:958-969) and steps the
-// frames; everything else is ONE chain of kernels enqueued without waiting in between:
-//   resubstitute + point step  ->  linearise the stepped state, its last workgroup sums the energy, sets the newest keyframe's threshold
-//   and takes the accept / reject decision  ->  [rejected only] restore the points and relinearise the backed-up state  ->  [accepted only]
-//   applyRes + per-point sums + point backup -> accumulation -> adjoint stitching -> the stitched system of the NEW state in host memory.
-// The host waits once per iteration, by polling the ticket the chain's last kernel stores behind its results.  After a rejected step the
-// system in host memory is still the one of the (restored) state, so the next iteration goes straight to its solve with the larger lambda.
-// the energy / threshold of a relinearisation the host did not wait for, once a later ticket of the same stream has been seen (or after waiting for its own)
-static int settleReject(dmvio_hip_ba* b, double lastE[3], bool wait) {
-  if (!b->pending_reject) return 0;
-  if (wait) { if (int r = waitTicket(b, b->pending_ticket)) return r; }
-  lastE[0] = b->h_res->E[1];
-  b->H.fr[b->H.F - 1].frameEnergyTH = b->h_res->th[1]; b->th_pending = false;
-  if (b->pending_trace >= 0 && b->pending_trace < 64) b->trace[b->pending_trace][0] = lastE[0];
-  b->pending_reject = false; b->pending_trace = -1;
-  return 0;
-}
-// ---- the reference's default solver branch (setting_useGTSAMIntegration): views of the window for the hooks, calcMEnergyF with the GTSAM term
-static void fillFrameViews(dmvio_hip_ba* b) {
-  const BAHost& H = b->H;
-  b->vio_frames.resize(H.F);
-  for (int f = 0; f < H.F; f++) {
-    dmvio_hip_ba_frame_view& v = b->vio_frames[f];
-    const BAFrameHost& fr = H.fr[f];
-    v.frameID = fr.frameID; v.index = f;
-    poseTo7(fr.w2c, v.PRE_worldToCam7); poseTo7(fr.evalPT, v.worldToCam_evalPT7);
-    memcpy(v.state10, fr.state, sizeof(v.state10)); memcpy(v.state_zero10, fr.state_zero, sizeof(v.state_zero10));
-  }
-}
-// EnergyFunctional::calcMEnergyF (EnergyFunctional.cpp:322-345): without hooks delta.dot(2 bM + HM delta); with them updateBAValues(frames) when the current values are
-// asked for, then getBAEnergy(useNewValues) + delta.dot(2 bMForGTSAM + HMForGTSAM delta)
-static double calcMEnergy(dmvio_hip_ba* b, bool useNewValues) {
-  if (!b->vio) return b->H.calcMEnergy();
-  if (!useNewValues && b->vio->updateBAValues) { fillFrameViews(b); b->vio->updateBAValues(b->vio->user, b->H.F, b->vio_frames.data(), b->H.c_value); }
-  const double g = b->vio->getBAEnergy ? b->vio->getBAEnergy(b->vio->user, useNewValues ? 1 : 0) : 0.0;
-  return g + b->H.calcMEnergy();
-}
-static double vioDynamicWeight(dmvio_hip_ba* b, double E0, int resInA) {
-  if (!b->vio || !b->vio->updateDynamicWeight) return 1.0;
-  const float rmse = sqrtf((float)(E0 / (8 * resInA)));   // patternNum * ef->resInA (FullSystemOptimize.cpp:495-498)
-  return b->vio->updateDynamicWeight(b->vio->user, E0, (double)rmse, b->vio_opt ? b->vio_opt->coarseTrackingWasGood : 1);
-}
-// defer: after a rejected step return without waiting for the relinearisation of the restored state (its energy stays on the device for the next accept
-// test, BACtl::lastE0); lastE[0] is then filled in by the next call's wait or by settleReject.
-// last: the caller will not iterate again — an accepted step is applied, but the system of the new state (which only the next solve would read) is not
-// accumulated: the per-point sums (HdiF, idepth_hessian) and resInA then stay those of the last solveSystemF, as in the reference.
-// canbreak_out: doStepFromBackup's return value && baIntegration->canBreak() (FullSystemOptimize.cpp:520-523); only evaluated with hooks (false otherwise).
-static int gnIteration(dmvio_hip_ba* b, int iteration, double& lambda, double lastE[3], bool& accepted, bool defer = false, int trace_slot = -1, bool last = false,
-                       bool* canbreak_out = nullptr) {
-  BAHost& H = b->H;
-  const int n = H.n(), tot = 2 * (n * n + n);
-  const bool shard = sharded(b);
-  const dmvio_hip_ba_callbacks* vio = b->vio;
-  const bool dynDuring = vio && b->vio_opt && b->vio_opt->updateDynamicWeightDuringOptimization;
-  if (shard) { if (int r = ensureExchange(b)) return r; }
-  // backupState (the point part rode in the per-point sums that produced the system at hand)
-  double tq0 = b->timing ? nowUs() : 0, tq1;
-#define BA_PH(i) do { if (b->timing) { tq1 = nowUs(); b->tm.t[i] += tq1 - tq0; tq0 = tq1; } } while (0)
-  H.backupFrames();
-  H.prepareSolve();   // nullspaces, orthogonalisation basis, prior right-hand side
-  if (!b->sys_ready) {
-    const bool sums_fresh = b->sums_fresh;
-    b->sums_fresh = false;
-    if (int r = accumulate(b, true, true, sums_fresh)) return r;
-  }
-  b->sys_ready = false;
-  if (vio && (dynDuring || iteration == 0)) {
-    // the weight of the photometric energy against the GTSAM factors, updated before solving (FullSystemOptimize.cpp:491-503); ef->resInA is the count the LAST
-    // solveSystemF left behind — before the first solve of this call the caller's (vio_options::resInA_at_entry) or, without one, the current system's
-    if (b->pending_reject) { if (int r = settleReject(b, lastE, true)) return r; }
-    const int resInA_ref = iteration == 0 ? ((b->vio_opt && b->vio_opt->resInA_at_entry >= 0) ? b->vio_opt->resInA_at_entry : (int)b->h_sys[tot]) : b->resInA_solve;
-    b->dynW = vioDynamicWeight(b, lastE[0], resInA_ref);
-  }
-  BA_PH(0);
-  // solveSystem
-  const double* p = b->h_sys;
-  b->resInA_solve = (int)p[tot];
-  std::vector<double> x;
-  if (!vio) H.solveSystem(iteration, lambda, p, p + n * n, p + n * n + n, p + 2 * n * n + n, x);
-  else {
-    // hand-over of EnergyFunctional.cpp:958-969: the damped Schur system, its right-hand side and the undamped system go to the caller's solver
-    std::vector<double> HP((size_t)n * n), bP(n), HN((size_t)n * n);
-    H.buildGtsamSystem(lambda, p, p + n * n, p + n * n + n, p + 2 * n * n + n, HP.data(), bP.data(), HN.data());
-    fillFrameViews(b);
-    x.assign(n, 0.0);
-    if (!vio->computeBAUpdate) return failmsg("ba_optimize_vio: computeBAUpdate hook missing");
-    if (vio->computeBAUpdate(vio->user, n, HP.data(), bP.data(), lambda, HN.data(), H.F, b->vio_frames.data(), H.c_value, x.data()) != 0)
-      return failmsg("ba_optimize_vio: computeBAUpdate hook reported an error");
-    H.finishExternalSolve(iteration, x);
-  }
-  BA_PH(1);
-  // resubstituteF_MT + the point part of doStepFromBackup (stepfac 1) ride in front of the linearisation of the stepped state
-  ResubArgs X;
-  {
-    float xc[4];
-    std::vector<float> xAd;
-    H.prepareResubstitute(x, xc, xAd);
-    memcpy(X.xc, xc, sizeof(xc));
-    memset(X.xAd, 0, sizeof(X.xAd));
-    memcpy(X.xAd, xAd.data(), sizeof(float) * xAd.size());
-  }
-  // doStepFromBackup, frames and calibration; the step norms only feed canbreak, which stays false without the GTSAM hooks (FullSystemOptimize.cpp:387,523,583)
-  if (!b->pre_static_valid) { if (int r = uploadWindowTables(b)) return r; }   // evaluation-point members of the table (R0, t0, b0): once per window
-  fillWindow(b);
-  dynFromHost(H, b->dyn_cur);         // backed-up state: calibration (W) and step-dependent precalc members, for a relinearisation after a rejected step
-  const BAWindow W_backup = b->W;
-  const BAPreDyn dyn_backup = b->dyn_cur;
-  float fs[4];
-  H.stepFrames(1.0f, fs);
-  H.setPrecalcValues();
-  bool canbreak = false;
-  if (vio) {
-    // FullSystemOptimize.cpp:269-313: sumNID = mean |idepth_backup| over the points in window order (the per-point sums mirrored idepth_backup into host memory)
-    float sumNID = 0, numID = 0;
-    for (int pi = 0; pi < H.N; pi++) { sumNID += fabsf(b->h_idepth_backup[pi]); numID++; }
-    sumNID /= numID;
-    const float thOpt = H.S.thOptIterations;
-    canbreak = sqrtf(fs[0]) < 0.0005 * thOpt && sqrtf(fs[1]) < 0.00005 * thOpt && sqrtf(fs[3]) < 0.00005 * thOpt && sqrtf(fs[2]) * sumNID < 0.00005 * thOpt;
-    canbreak = canbreak && vio->canBreak && vio->canBreak(vio->user) != 0;
-  }
-  if (canbreak_out) *canbreak_out = canbreak;
-  const int minOpt = (b->vio_opt && b->vio_opt->minOptIterations >= 0) ? b->vio_opt->minOptIterations : H.S.minOptIterations;
-  if (canbreak && iteration >= minOpt) last = true;
-  double newL = 0;
-  if (int r = calcLEnergyR(b, &newL)) return r;
-  const double newM = calcMEnergy(b, true);
-  if (dynDuring) b->dynW = vioDynamicWeight(b, lastE[0], b->resInA_solve);   // before deciding whether to accept the step (FullSystemOptimize.cpp:534-538)
-  // linearise the stepped state; the kernel's last workgroup sums the energy, sets the newest keyframe's threshold and decides
-  fillWindow(b);
-  dynFromHost(H, b->dyn_cur);
-  if (int r = uploadThresholds(b)) return r;
-  unsigned int D_ticket = 0;
-  {
-    BA_PH(2);
-    BADecide D = makeDecide(b, 1, true, true);
-    D_ticket = D.ticket;
-    // newEnergy[0] + newEnergy[1] + newEnergyL + newEnergyM / dynamicGTSAMWeight (FullSystemOptimize.cpp:553-554): the quotients are formed here (x / 1.0 == x without hooks)
-    D.lastE0 = lastE[0]; D.lastL = lastE[1]; D.lastM = lastE[2] / b->dynW; D.newL = newL; D.newM = newM / b->dynW;
-    D.lastE0_from_ctl = b->pending_reject ? 1 : 0;   // the host has not seen the restored state's energy yet: the device has
-    BA_LAUNCH_LINEARIZE(b, b->W, b->keep_fullJ ? b->d_fullJ : (float*)nullptr, (const unsigned char*)nullptr, shard ? packOnly(b, D) : D, BA_GATE_ALWAYS, 0, b->dyn_cur, 1, X, 1);
-    HIPCHK(hipGetLastError());
-    if (shard) { if (int r = decideGlobal(b, D)) return r; }
-    BA_PH(3);
-    if (int r = waitTicket(b, D.ticket)) return r;   // energy and the accept / reject decision are in host memory (the threshold follows: resolveTh)
-    if (int r = settleReject(b, lastE, false)) return r;   // ... and so are those of an earlier relinearisation on the same stream
-    BA_PH(4);
-  }
-  accepted = b->h_res->accept != 0;
-  if (accepted) {
-    // applyRes + per-point sums + point backup -> accumulation -> stitching: the system of the new state, for the next iteration's solve.
-    // (Enqueuing this branch speculatively behind the linearisation, gated on the device-side decision, was measured: no gain — the four
-    // launches, not the host round trip, set its length.)
-    if (!last) { if (int r = accumulate(b, true, true, false, true, BA_GATE_ALWAYS)) return r; }
-    else { if (int r = applyRes(b)) return r; }
-    lastE[0] = b->h_res->E[0]; lastE[1] = newL; lastE[2] = newM;
-    b->th_pending = true; b->th_pending_ticket = D_ticket;   // the threshold follows its decision by a few microseconds: picked up by resolveTh before anything reads it
-    lambda = std::max(lambda * 0.25, 1e-5);
-    if (vio && vio->acceptBAUpdate) vio->acceptBAUpdate(vio->user, lastE[0]);   // FullSystemOptimize.cpp:569-572
-  } else {
-    // loadSateBackup + linearizeAll (FullSystemOptimize.cpp:575-581): the points are restored by the relinearisation kernel itself; the
-    // system in host memory is still the one of the restored state
-    const BADecide D2 = makeDecide(b, 2, true, true);
-    BA_LAUNCH_LINEARIZE(b, W_backup, b->keep_fullJ ? b->d_fullJ : (float*)nullptr, (const unsigned char*)nullptr, shard ? packOnly(b, D2) : D2, BA_GATE_ALWAYS, 1, dyn_backup, 1, b->x_none, 0);
-    HIPCHK(hipGetLastError());
-    if (shard) { if (int r = decideGlobal(b, D2)) return r; }
-    H.restoreFrames();
-    H.setPrecalcValues();
-    fillWindow(b);
-    b->dyn_cur = dyn_backup;
-    double oldL = 0;
-    if (int r = calcLEnergyR(b, &oldL)) return r;
-    const double oldM = calcMEnergy(b, false);
-    lastE[1] = oldL; lastE[2] = oldM;
-    b->pending_reject = true; b->pending_ticket = D2.ticket; b->pending_trace = trace_slot;
-    if (!defer) { if (int r = settleReject(b, lastE, true)) return r; }
-    lambda *= 1e2;
-  }
-  BA_PH(5);
-#undef BA_PH
-  b->sys_ready = !(accepted && last);   // accepted: the chain left the system of the new state behind; rejected: the one at hand still is the restored state's
-  b->tm.n++;
-  return 0;
-}
-
-// Measurement: the kernel chain of an ACCEPTED Gauss-Newton iteration on the current state — linearise (+ energy / threshold decision pass) -> applyRes + per-point sums
-// -> accumulate -> adjoint stitch -> gather — `reps` times, with HIP events recorded on the handle's stream between the launches; us5 = mean microseconds of the five
-// kernels (each figure includes the gap to the next launch: what the chain costs on the stream).  The window state is left as a linearise + applyRes + accumulate leaves it.
+// Measurement: mean microseconds of the five kernels of an ACCEPTED Gauss-Newton iteration's chain on the current state (ba_loop_host.hpp: profileChain)
 int dmvio_hip_ba_profile_chain(dmvio_hip_ba* b, int reps, float us5[5]) {
   BA_READY(b);
   if (!us5 || reps < 1) return failmsg("ba_profile_chain: bad argument");
   if (sharded(b)) return failmsg("ba_profile_chain: single-device windows only");
-  struct Events {   // destroyed on every way out
-    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (int k = 0; k < 6; k++) if (e[k]) hipEventDestroy(e[k]); }
-  } evs;
-  hipEvent_t* ev = evs.e;
-  for (int k = 0; k < 6; k++) HIPCHK(hipEventCreate(&ev[k]));
-  struct ProfScope { dmvio_hip_ba* b; ~ProfScope() { b->prof = nullptr; } } profScope{b};
-  double acc[5] = {0, 0, 0, 0, 0};
-  int rc = 0;
-  for (int r = 0; r < reps && rc == 0; r++) {
-    double e = 0;
-    b->prof = ev;
-    rc = linearizeAll(b, false, &e, 0, false, true);   // enqueue only
-    if (rc == 0) rc = accumulate(b, true, true, false, true);
-    b->prof = nullptr;
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int k = 0; k < 5; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); acc[k] += 1e3 * ms; }
-  }
-  for (int k = 0; k < 5; k++) us5[k] = (float)(acc[k] / reps);
-  return rc;
+  return profileChain(b, reps, us5);
 }
 
 // diagnostics: in-kernel timeline of the last decision pass, 100 MHz ticks since its workgroup started (begin, energy, keys, selected)
@@ -1613,11 +779,11 @@ int dmvio_hip_ba_gn_iteration(dmvio_hip_ba* b, int iteration, double* lambda_io,
   if (!b) return failmsg("ba: null handle");
   BA_LOCK(b);
   BA_CHECK_LOCKED(b);
-  bool acc = false;
   double lam = *lambda_io;
-  if (int r = gnIteration(b, iteration, lam, lastE, acc)) return r;
+  const GnResult g = gnIteration(b, iteration, lam, lastE, GnOpts{});
+  if (g.rc) return g.rc;
   *lambda_io = lam;
-  if (accepted) *accepted = acc ? 1 : 0;
+  if (accepted) *accepted = g.accepted ? 1 : 0;
   return 0;
 }
 
@@ -1626,8 +792,7 @@ int dmvio_hip_ba_gn_iteration(dmvio_hip_ba* b, int iteration, double* lambda_io,
 int dmvio_hip_ba_backup(dmvio_hip_ba* b) {
   BA_READY(b);
   b->H.backupFrames();
-  float d0, d1;
-  return pointStep(b, 0, 0.f, &d0, &d1);
+  return pointStep(b, 0, 0.f);
 }
 int dmvio_hip_ba_solve_system(dmvio_hip_ba* b, int iteration, double lambda, const double* HA, const double* bA, const double* Hsc, const double* bsc, double* x_out) {
   BA_READY(b);
@@ -1649,8 +814,7 @@ int dmvio_hip_ba_step(dmvio_hip_ba* b, float stepfac, float sums6[6]) {
 int dmvio_hip_ba_restore(dmvio_hip_ba* b) {
   BA_READY(b);
   b->H.restoreFrames();
-  float d0, d1;
-  if (int r = pointStep(b, 2, 0.f, &d0, &d1)) return r;
+  if (int r = pointStep(b, 2, 0.f)) return r;
   b->H.setPrecalcValues();
   return 0;
 }
@@ -1660,7 +824,7 @@ int dmvio_hip_ba_restore(dmvio_hip_ba* b) {
 int dmvio_hip_ba_linearize_local(dmvio_hip_ba* b, int fix, double* energy, float* new_frame_energies, int* n_new_frame_energies) {
   BA_READY(b);
   double e = 0;
-  if (int r = linearizeAll(b, fix != 0, &e, 0, true)) return r;   // the threshold is set by the caller from the energies gathered over all shards
+  if (int r = linearizeAll(b, fix != 0, TH_KEEP, &e)) return r;   // the threshold is set by the caller from the energies gathered over all shards
   if (energy) *energy = e;
   std::vector<float> wo(b->H.R);
   if (b->H.R) HIPCHK(b->bounce.d2h(wo.data(), b->d_newEnergyWO, sizeof(float) * b->H.R, b->stream));
@@ -1687,65 +851,6 @@ int dmvio_hip_ba_energy_terms(dmvio_hip_ba* b, double* EL, double* EM) {
   return 0;
 }
 
-// FullSystem::optimize (FullSystemOptimize.cpp:417-647).  vio == NULL: the library's own damped LDLT (the reference's solver with setting_useGTSAMIntegration off);
-// otherwise every solve, the M-energy term, the dynamic weight and the early exit go through the caller's hooks, in the order the reference calls BAGTSAMIntegration.
-static int optimizeImpl(dmvio_hip_ba* b, int mnumOptIts, const dmvio_hip_ba_callbacks* vio, const dmvio_hip_ba_vio_options* opt, float* rmse, double* finalEnergy, int* iterations,
-                        double* trace /* 64x4 or NULL */) {
-  BAHost& H = b->H;
-  if (H.F < 2) { if (rmse) *rmse = 0; return 0; }
-  mnumOptIts = BAHost::optIterations(H.F, mnumOptIts);
-  struct VioScope {   // the hooks are those of this call only
-    dmvio_hip_ba* b;
-    ~VioScope() { b->vio = nullptr; b->vio_opt = nullptr; b->H.gtsam = false; b->dynW = 1.0; }
-  } scope{b};
-  b->vio = vio; b->vio_opt = vio ? opt : nullptr; b->dynW = 1.0;
-  const int n = H.n();
-  if (vio) {
-    H.gtsam = true;
-    if (opt && opt->HMForGTSAM && opt->bMForGTSAM) { H.HMG.assign(opt->HMForGTSAM, opt->HMForGTSAM + (size_t)n * n); H.bMG.assign(opt->bMForGTSAM, opt->bMForGTSAM + n); }
-    else { H.HMG.assign((size_t)n * n, 0.0); H.bMG.assign(n, 0.0); }
-  }
-  if (int r = dmvio_hip_ba_activate_all(b)) return r;
-  double lastE[3];
-  // initial linearisation, applyRes and the first system (per-point sums → accumulation → stitching) go out as ONE chain: nothing in it waits for the host, which
-  // picks the energy and the threshold up behind the chain's last ticket
-  if (int r = linearizeAll(b, false, &lastE[0], 0, false, true)) return r;
-  if (int r = applyRes(b)) return r;
-  if (int r = accumulate(b, true, true, false)) return r;   // backupState of the points rides in the per-point sums; the frames are backed up by the first iteration
-  linearizePickUp(b, &lastE[0], false);
-  b->sys_ready = true;
-  if (int r = calcLEnergyR(b, &lastE[1])) return r;
-  lastE[2] = calcMEnergy(b, false);
-  double lambda = 1e-5;
-  int done = 0;
-  b->trace[0][0] = lastE[0]; b->trace[0][1] = lastE[1]; b->trace[0][2] = lastE[2]; b->trace[0][3] = 1;
-  for (int iteration = 0; iteration < mnumOptIts; iteration++) {
-    bool acc = false, canbreak = false;
-    if (int r = gnIteration(b, iteration, lambda, lastE, acc, true, done + 1, iteration == mnumOptIts - 1, &canbreak)) return r;
-    done++;
-    if (done < 64) { b->trace[done][0] = lastE[0]; b->trace[done][1] = lastE[1]; b->trace[done][2] = lastE[2]; b->trace[done][3] = acc ? 1 : 0; }
-    // canbreak && iteration >= setting_minOptIterations (FullSystemOptimize.cpp:586): baIntegration->canBreak() stays false without the GTSAM hooks
-    const int minOpt = (opt && vio && opt->minOptIterations >= 0) ? opt->minOptIterations : H.S.minOptIterations;
-    if (canbreak && iteration >= minOpt) break;
-  }
-  if (int r = settleReject(b, lastE, true)) return r;
-  if (vio) b->dynW = vioDynamicWeight(b, lastE[0], b->resInA_solve);   // "Update again!" (FullSystemOptimize.cpp:594)
-  // fix the newest frame's linearisation point, re-linearise with applyRes (FullSystemOptimize.cpp:596-609)
-  H.reanchorNewest();
-  if (int r = uploadAdjoints(b)) return r;   // (nothing is enqueued between the two: the upload stands in the stream where it stood inside the sequence)
-  double fe = 0;
-  if (int r = linearizeAll(b, true, &fe)) return r;
-  b->final_energy = fe; b->iterations_done = done;
-  if (rmse) *rmse = sqrtf((float)(fe / (8 * H.resInA)));
-  if (finalEnergy) *finalEnergy = fe;
-  if (iterations) *iterations = done;
-  if (trace) memcpy(trace, b->trace, sizeof(b->trace));
-  if (vio && vio->postOptimization) { fillFrameViews(b); vio->postOptimization(vio->user, H.F, b->vio_frames.data(), H.c_value); }   // FullSystemOptimize.cpp:641
-  return 0;
-}
-int dmvio_hip_ba_optimize_batch(struct dmvio_hip_ba_batch* B, int W, dmvio_hip_ba* const* windows, int mnumOptIts, float* rmse, double* finalEnergy, int* iterations, double* trace);
-struct dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows);
-void dmvio_hip_ba_batch_destroy(struct dmvio_hip_ba_batch* B);
 int dmvio_hip_ba_optimize(dmvio_hip_ba* b, int mnumOptIts, float* rmse, double* finalEnergy, int* iterations, double* trace /* 64x4 or NULL */) {
   BA_READY(b);
   if (b->device_loop && !sharded(b)) {

@@ -272,8 +272,8 @@ def test_sharded_driver_world1_equals_gn_iteration(pkg, oracle, synth, gpu_requi
 
 
 def test_gn_iterations_through_rejected_steps_match_oracle(pkg, oracle, synth, gpu_required):
-    """Thirty GN iterations on one window: once converged, steps are rejected (restore + re-linearise; the library then skips the per-point
-    sums of the next iteration because nothing they depend on has changed).  Accept sequence, damping and energies follow the oracle throughout,
+    """Thirty GN iterations on one window: once converged, steps are rejected (restore + re-linearise; the next iteration then reuses the system at
+    hand: the one in host memory still is the restored state's).  Accept sequence, damping and energies follow the oracle throughout,
     and calls in between (a query, a re-linearisation) do not disturb the sequence."""
     case = synth.ba_case(512, 512, n_frames=8, n_points=1000, seed=13)
     ctx, ba, W = _window(pkg, oracle, case)
