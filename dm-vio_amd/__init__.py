@@ -102,6 +102,11 @@ class BAMargWindow(C.Structure):
                 ("update_prior", C.c_int)]
 
 
+class BAMargFrameWindow(C.Structure):
+    """dmvio_hip_ba_marg_frame_window: one window of dmvio_hip_ba_marginalize_frame_batch."""
+    _fields_ = [("ba", C.c_void_p), ("frame", C.c_int), ("HM_new", C.c_void_p), ("bM_new", C.c_void_p)]
+
+
 class ActivationOptimize(C.Structure):
     """dmvio_hip_activation_optimize: one window of dmvio_hip_immature_optimize_selected_batch."""
     _fields_ = [("imm", C.c_void_p), ("F", C.c_int), ("frame_slots", c_i), ("w2c7", c_d), ("aff2", c_d), ("exposure", c_f), ("minObs", C.c_int), ("result", c_i),
@@ -1577,6 +1582,36 @@ class BundleAdjusterBatch:
         v = [C.c_int(0) for _ in range(4)]
         fn = self.L.dmvio_hip_ba_batch_last_marg_work; fn.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4; fn.restype = C.c_int
         _chk(self.L, fn(self.p, *[C.byref(x) for x in v]), "ba_batch_last_marg_work")
+        return dict(launches=v[0].value, uploads=v[1].value, downloads=v[2].value, waits=v[3].value)
+
+    def marginalize_frames(self, windows, frames):
+        """dmvio_hip_ba_marginalize_frame_batch: BundleAdjusterHip.marginalize_frame(frames[k]) of every window in one call.  Returns [(HM_new, bM_new)] per window; the
+        handles keep their priors."""
+        W = len(windows)
+        assert len(frames) == W, (len(frames), W)
+        fn = self.L.dmvio_hip_ba_marginalize_frame_batch; fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(BAMargFrameWindow)]; fn.restype = C.c_int
+        arr = (BAMargFrameWindow * max(W, 1))()
+        out = []
+        for k, w in enumerate(windows):
+            n = w.n - 8
+            H = np.zeros((n, n)); b = np.zeros(n)
+            out.append((H, b))
+            arr[k].ba = w.p.value if isinstance(w.p, C.c_void_p) else w.p; arr[k].frame = int(frames[k]); arr[k].HM_new = H.ctypes.data; arr[k].bM_new = b.ctypes.data
+        _chk(self.L, fn(self.p, W, arr), "ba_marginalize_frame_batch")
+        return out
+
+    def last_marg_frame_ms(self):
+        """with set_profile(True): HIP-event time (ms) of the last marginalize_frames call's device work, the upload to the download"""
+        ms = C.c_float(0)
+        fn = self.L.dmvio_hip_ba_batch_last_marg_frame_ms; fn.argtypes = [C.c_void_p, C.POINTER(C.c_float)]; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, C.byref(ms)), "ba_batch_last_marg_frame_ms")
+        return float(ms.value)
+
+    def last_marg_frame_work(self):
+        """what the last marginalize_frames call enqueued: dict(launches, uploads, downloads, waits)"""
+        v = [C.c_int(0) for _ in range(4)]
+        fn = self.L.dmvio_hip_ba_batch_last_marg_frame_work; fn.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, *[C.byref(x) for x in v]), "ba_batch_last_marg_frame_work")
         return dict(launches=v[0].value, uploads=v[1].value, downloads=v[2].value, waits=v[3].value)
 
     def last_ms(self):

@@ -170,6 +170,11 @@ struct dmvio_hip_ba_batch {
   hipEvent_t marg_ev = nullptr;
   int marg_work[4] = {0, 0, 0, 0};   // launches, uploads, downloads, waits
   float marg_ms = 0;                 // with `profile`: HIP events around the last call's device work (first upload .. the download)
+  // dmvio_hip_ba_marginalize_frame_batch: in the same buffers (a call owns them under the batch's lock); the most dynamic LDS a launch may ask for on this device
+  // (0: not asked yet — k_ba_marg_frame_b's attribute is set with the first call)
+  int margf_work[4] = {0, 0, 0, 0};
+  float margf_ms = 0;
+  size_t margf_lds_limit = 0;
 };
 extern "C" {
 dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
@@ -822,6 +827,8 @@ struct MargBatchCall {
     return 0;
   }
 };
+
+#include "ba_marg_frame_host.hpp"   // dmvio_hip_ba_marginalize_frame_batch and its two accessors
 
 extern "C" {
 int dmvio_hip_ba_marginalize_points_batch(dmvio_hip_ba_batch* B, int W, dmvio_hip_ba_marg_window* win) {

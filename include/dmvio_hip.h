@@ -640,6 +640,31 @@ int dmvio_hip_ba_batch_last_marg_work(dmvio_hip_ba_batch* batch, int* launches, 
 /* measurement (tools/bench_marg_batch.py): with dmvio_hip_ba_batch_set_profile(1), HIP-event time in ms of the last such call's device work on the batch's stream,
  * from the first upload to the download; 0 otherwise */
 int dmvio_hip_ba_batch_last_marg_ms(dmvio_hip_ba_batch* batch, float* ms);
+/* Frame marginalisation of W windows per call: dmvio_hip_ba_marginalize_frame (EnergyFunctional::marginalizeFrame, visual-only branch EnergyFunctional.cpp:570-640: the
+ * keyframe's block moved last, its prior added, diagonal pre-scaling, the 8x8 block's inverse, the Schur complement, un-scaling and symmetrisation) for every window of
+ * win[W], the stage that follows dmvio_hip_ba_marginalize_points_batch in a keyframe's cycle.  One workgroup per window does on the device what the single call does on
+ * the host, operation for operation: every window receives exactly the bytes its own dmvio_hip_ba_marginalize_frame(ba, frame, ...) returns.  (A window whose scaled 8x8
+ * block is singular gets non-finite values in the same entries as from the single call; NaN payloads are not specified.)  Like the single call it leaves the handle's
+ * prior, window and graph as they were — the caller installs the result with dmvio_hip_ba_set_marg_prior after dmvio_hip_ba_set_window — and a handle whose prior was
+ * never set counts as a zero prior.  Windows of any keyframe counts from 1 to dmvio_hip_ba_max_frames() may share a call.
+ * Runs on the batch's stream under the rules of dmvio_hip_ba_marginalize_points_batch (the handles locked in address order; work pending on a handle's own stream is in
+ * front of the call, the call is complete on return).  Per call: ONE packed upload (per window HM, bM, the frame's prior and delta_prior, F and frame), one launch per
+ * distinct keyframe count, ONE download behind ONE wait.  The kernel keeps a window's system in LDS (88 KB at 12 keyframes); a device that allows less per workgroup
+ * refuses the windows that do not fit, with a message that names both sizes.
+ * Refused as a whole, with a message and before anything is enqueued or written: W < 0 or W > max_windows, win / a handle / HM_new / bM_new NULL, a handle twice, a
+ * handle of another context, without a window, or sharded over ranks, frame out of range.  W == 0 returns 0 and does nothing. */
+typedef struct dmvio_hip_ba_marg_frame_window {
+  dmvio_hip_ba* ba;
+  int frame;          /* keyframe to remove, 0 <= frame < F of that handle */
+  double* HM_new;     /* out: (n-8) x (n-8) row-major, n = 4 + 8F */
+  double* bM_new;     /* out: n-8 */
+} dmvio_hip_ba_marg_frame_window;
+int dmvio_hip_ba_marginalize_frame_batch(dmvio_hip_ba_batch* batch, int W, dmvio_hip_ba_marg_frame_window* win);
+/* what the last such call enqueued (all 0 after W == 0; unchanged by a refused call; any pointer may be NULL) */
+int dmvio_hip_ba_batch_last_marg_frame_work(dmvio_hip_ba_batch* batch, int* launches, int* uploads, int* downloads, int* waits);
+/* measurement (tools/bench_marg_frame_batch.py): with dmvio_hip_ba_batch_set_profile(1), HIP-event time in ms of the last such call's device work on the batch's stream,
+ * from the upload to the download; 0 otherwise */
+int dmvio_hip_ba_batch_last_marg_frame_ms(dmvio_hip_ba_batch* batch, float* ms);
 int dmvio_hip_ba_batch_set_exact_backsub(dmvio_hip_ba_batch* batch, int on);
 /* HIP-event times of the last dmvio_hip_ba_optimize_batch call on the batch's stream (ms): [0] initial chain + all iterations, [1] the final fix-linearisation,
  * [2] with dmvio_hip_ba_batch_set_profile(1): the stepped linearisation of the second iteration (k_ba_linearize_b over ALL windows of the call: a profiled call runs as one
