@@ -107,6 +107,11 @@ class BAMargFrameWindow(C.Structure):
     _fields_ = [("ba", C.c_void_p), ("frame", C.c_int), ("HM_new", C.c_void_p), ("bM_new", C.c_void_p)]
 
 
+class BAGraphWindow(C.Structure):
+    """dmvio_hip_ba_graph_window: one window of dmvio_hip_ba_set_graph_from_batch."""
+    _fields_ = [("ba", C.c_void_p), ("graph", C.c_void_p)]
+
+
 class ActivationOptimize(C.Structure):
     """dmvio_hip_activation_optimize: one window of dmvio_hip_immature_optimize_selected_batch."""
     _fields_ = [("imm", C.c_void_p), ("F", C.c_int), ("frame_slots", c_i), ("w2c7", c_d), ("aff2", c_d), ("exposure", c_f), ("minObs", C.c_int), ("result", c_i),
@@ -296,6 +301,9 @@ def _sig(L):
     L.dmvio_hip_immature_select_for_activation_batch.argtypes = [vp, C.c_int, C.POINTER(ActivationWindow)]
     L.dmvio_hip_immature_optimize_selected_batch.argtypes = [vp, C.c_int, C.POINTER(ActivationOptimize), c_d]
     L.dmvio_hip_immature_remove_marked_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), c_i]
+    L.dmvio_hip_ba_set_graph_from_batch.argtypes = [vp, C.c_int, C.POINTER(BAGraphWindow)]
+    L.dmvio_hip_ba_batch_last_graph_work.argtypes = [vp, c_i, c_i, c_i, c_i]
+    L.dmvio_hip_ba_batch_last_graph_ms.argtypes = [vp, C.POINTER(C.c_float)]
 
 
 def load_library():
@@ -1614,6 +1622,32 @@ class BundleAdjusterBatch:
         _chk(self.L, fn(self.p, *[C.byref(x) for x in v]), "ba_batch_last_marg_frame_work")
         return dict(launches=v[0].value, uploads=v[1].value, downloads=v[2].value, waits=v[3].value)
 
+    def set_graph_from(self, windows, graphs):
+        """dmvio_hip_ba_set_graph_from_batch: BundleAdjusterHip.set_graph_from(graphs[k]) of every window in one call (windows[k].N / .R follow, as after the single call).
+        An entry of either list may be None (the call then refuses)."""
+        W = len(windows)
+        assert len(graphs) == W, (len(graphs), W)
+        arr = (BAGraphWindow * max(W, 1))()
+        for k, (w, g) in enumerate(zip(windows, graphs)):
+            arr[k].ba = None if w is None else (w.p.value if isinstance(w.p, C.c_void_p) else w.p)
+            arr[k].graph = None if g is None else (g.p.value if isinstance(g.p, C.c_void_p) else g.p)
+        _chk(self.L, self.L.dmvio_hip_ba_set_graph_from_batch(self.p, W, arr), "ba_set_graph_from_batch")
+        for w, g in zip(windows, graphs):
+            _F, w.N, w.R = g.counts()
+            w._n_newest = g   # (counted on first use: the graph's export would stamp its flat order a second time)
+
+    def last_graph_work(self):
+        """what the last set_graph_from call enqueued: dict(launches, uploads, downloads, waits)"""
+        v = [C.c_int(0) for _ in range(4)]
+        _chk(self.L, self.L.dmvio_hip_ba_batch_last_graph_work(self.p, *[C.byref(x) for x in v]), "ba_batch_last_graph_work")
+        return dict(launches=v[0].value, uploads=v[1].value, downloads=v[2].value, waits=v[3].value)
+
+    def last_graph_ms(self):
+        """with set_profile(True): HIP-event time (ms) of the last set_graph_from call's device work, the upload to the last kernel"""
+        ms = C.c_float(0)
+        _chk(self.L, self.L.dmvio_hip_ba_batch_last_graph_ms(self.p, C.byref(ms)), "ba_batch_last_graph_ms")
+        return float(ms.value)
+
     def last_ms(self):
         ms = np.zeros(3, np.float32)
         _chk(self.L, self.L.dmvio_hip_ba_batch_last_ms(self.p, ms.ctypes.data), "ba_batch_last_ms")
@@ -2019,6 +2053,8 @@ class BundleAdjusterHip:
 
     def count_newest_residuals(self):
         """Residuals of this graph that target the newest keyframe (the inputs of setNewFrameEnergyTH)."""
+        if not isinstance(self._n_newest, int):   # handed over by BundleAdjusterBatch.set_graph_from: the graph itself
+            self._n_newest = int((self._n_newest.export()["res_target"] == self.F - 1).sum())
         return self._n_newest
 
     def linearize_local(self, fix=False):

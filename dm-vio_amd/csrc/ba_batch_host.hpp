@@ -175,6 +175,13 @@ struct dmvio_hip_ba_batch {
   int margf_work[4] = {0, 0, 0, 0};
   float margf_ms = 0;
   size_t margf_lds_limit = 0;
+  // dmvio_hip_ba_set_graph_from_batch (ba_graph_batch_host.hpp): the call's records, range / piece tables and flattened graphs, pinned and on the device, grown on demand
+  // and kept like the marginalisation buffer; what the last call enqueued
+  char* d_graph = nullptr;
+  char* h_graph = nullptr;
+  size_t graph_cap = 0;
+  int graph_work[4] = {0, 0, 0, 0};   // launches, uploads, downloads, waits
+  float graph_ms = 0;                 // with `profile`: HIP events from the upload to the last kernel
 };
 extern "C" {
 dmvio_hip_ba_batch* dmvio_hip_ba_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
@@ -213,6 +220,8 @@ void dmvio_hip_ba_batch_destroy(dmvio_hip_ba_batch* B) {
   if (B->h_trace) hipHostFree(B->h_trace);
   if (B->d_marg) hipFree(B->d_marg);
   if (B->h_marg) hipHostFree(B->h_marg);
+  if (B->d_graph) hipFree(B->d_graph);
+  if (B->h_graph) hipHostFree(B->h_graph);
   if (B->marg_ev) hipEventDestroy(B->marg_ev);
   for (int k = 0; k < 8; k++) if (B->ev[k]) hipEventDestroy(B->ev[k]);
   for (int g = 1; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS; g++) if (B->gstream[g]) { hipStreamSynchronize(B->gstream[g]); hipStreamDestroy(B->gstream[g]); }

@@ -1,7 +1,144 @@
 // Building the window's device graph: dmvio_hip_ba_set_graph (flat arrays) and dmvio_hip_ba_set_graph_from (the resident mirror, capi_graph.hip), and the buffers of residuals
-// kept linearised (first use, hand-over, the host copies the energy term reads).  A declaration file of capi_ba.hip's translation unit: included there, once, behind dalloc /
+// kept linearised (first use, hand-over, the host copies the energy term reads).  The build is three parts — the host preparation (graphHostPrepare), the arena layout
+// (graphLayout) and the enqueue — of which the batched hand-over (ba_graph_batch_host.hpp) shares the first two.  A declaration file of capi_ba.hip's translation unit: included there, once, behind dalloc /
 // freeDevice / uploadAdjoints and ba_shard_host.hpp.
 #pragma once
+// ---- part one: the host preparation.  Validation and every table the host derives from the flat arrays, written where the caller wants them (the single call: vectors of
+// its own; the batched hand-over, ba_graph_batch_host.hpp: the window's section of the pinned slab).  Touches no handle.
+struct GraphLists {   // destinations: res_begin N + 1, top_begin F*F + 1, top_members R, pt_first / pt_last F, slot R
+  int *res_begin, *top_begin, *top_members, *pt_first, *pt_last, *slot;
+};
+struct GraphPrep {
+  int F = 0, N = 0, R = 0;
+  size_t npairs = 0;
+  bool scd_on_device = true;                 // no point observes a keyframe twice: the Schur buckets' member lists are built on the device
+  std::vector<int> newest;                   // residuals that target the newest keyframe, ascending
+  std::vector<int> scd_begin, scd_members;   // the host-built lists (!scd_on_device)
+};
+static int graphHostPrepare(const int F, const int N, const int* host, const int R, const int* res_point, const int* res_target, const GraphLists& L, GraphPrep& G) {
+  const int F2 = F * F;
+  G.F = F; G.N = N; G.R = R;
+  G.newest.clear();
+  for (int ri = 0; ri < R; ri++) if (res_target[ri] == F - 1) G.newest.push_back(ri);
+  // residuals must be grouped by point, points in window order
+  int* const res_begin = L.res_begin;
+  std::fill(res_begin, res_begin + N + 1, 0);
+  for (int ri = 0; ri < R; ri++) {
+    const int p = res_point[ri];
+    if (p < 0 || p >= N || res_target[ri] < 0 || res_target[ri] >= F) return failmsg("ba_set_graph: residual index out of range");
+    if (ri > 0 && p < res_point[ri - 1]) return failmsg("ba_set_graph: residuals must be sorted by point");
+    if (host[p] < 0 || host[p] >= F || host[p] == res_target[ri]) return failmsg("ba_set_graph: bad host / target");
+    res_begin[p + 1]++;
+  }
+  for (int p = 0; p < N; p++) res_begin[p + 1] += res_begin[p];
+  // bucket member lists in the reference's traversal order (points, then residuals of the point)
+  int* const top_begin = L.top_begin;
+  std::fill(top_begin, top_begin + F2 + 1, 0);
+  for (int ri = 0; ri < R; ri++) top_begin[host[res_point[ri]] + F * res_target[ri] + 1]++;
+  for (int k = 0; k < F2; k++) top_begin[k + 1] += top_begin[k];
+  { std::vector<int> cur(top_begin, top_begin + F2); for (int ri = 0; ri < R; ri++) L.top_members[cur[host[res_point[ri]] + F * res_target[ri]]++] = ri; }
+  G.npairs = 0;
+  for (int p = 0; p < N; p++) { const size_t k = res_begin[p + 1] - res_begin[p]; G.npairs += k * k; }
+  // The Schur buckets' member lists are built on the device (k_ba_scd_*: ba_kernels.hpp) when no point observes a keyframe twice — always, in the reference's graphs (one
+  // PointFrameResidual per point and target, FullSystem.cpp:1248-1262); a graph that does is served by the host loops below, as every graph was before.
+  std::fill(L.pt_first, L.pt_first + F, N); std::fill(L.pt_last, L.pt_last + F, -1);
+  G.scd_on_device = true;
+  for (int p = 0; p < N && G.scd_on_device; p++) {
+    L.pt_first[host[p]] = std::min(L.pt_first[host[p]], p); L.pt_last[host[p]] = std::max(L.pt_last[host[p]], p);
+    unsigned int seen = 0;
+    for (int ri = res_begin[p]; ri < res_begin[p + 1]; ri++) { const unsigned int bit = 1u << res_target[ri]; if (seen & bit) G.scd_on_device = false; seen |= bit; }
+  }
+  G.scd_begin.clear(); G.scd_members.clear();
+  if (!G.scd_on_device) {
+    G.scd_begin.assign(F2 * F + 1, 0); G.scd_members.resize(3 * G.npairs);
+    for (int p = 0; p < N; p++)
+      for (int r1 = res_begin[p]; r1 < res_begin[p + 1]; r1++)
+        for (int r2 = res_begin[p]; r2 < res_begin[p + 1]; r2++) G.scd_begin[(host[p] + F * res_target[r1]) + res_target[r2] * F2 + 1]++;
+    for (int k = 0; k < F2 * F; k++) G.scd_begin[k + 1] += G.scd_begin[k];
+    std::vector<int> cur(G.scd_begin.begin(), G.scd_begin.end() - 1);
+    for (int p = 0; p < N; p++)
+      for (int r1 = res_begin[p]; r1 < res_begin[p + 1]; r1++)
+        for (int r2 = res_begin[p]; r2 < res_begin[p + 1]; r2++) {
+          const int k = (host[p] + F * res_target[r1]) + res_target[r2] * F2;
+          const int o = cur[k]++;
+          G.scd_members[3 * o] = r1; G.scd_members[3 * o + 1] = r2; G.scd_members[3 * o + 2] = p;
+        }
+  }
+  // per residual: its position among the residuals that target the newest keyframe, or -1
+  std::fill(L.slot, L.slot + R, -1);
+  for (size_t k = 0; k < G.newest.size(); k++) L.slot[G.newest[k]] = (int)k;
+  return 0;
+}
+// what a new graph does to the handle before anything of it exists: the arrays outside the arena go, and so does everything the old graph's linearised residuals left
+// behind (residuals kept linearised belong to the graph they were linearised in)
+static void graphDropOld(dmvio_hip_ba* b) {
+  b->th_pending = false;   // the stream is drained and h_res is cleared (th_ticket restarts at 0 while b->ticket keeps counting): nothing of the old graph may be awaited
+  freeDevice(b);
+  b->n_lin = 0; b->n_lin_global = 0; b->Rs.lin = nullptr; b->P.lHdd = b->P.lbd = b->P.lHcd = nullptr; b->P.HcdAF = nullptr; b->d_lin = nullptr; b->d_red1 = nullptr; b->H.HLraw.clear(); b->H.bLraw.clear();
+  b->h_lin.clear(); b->h_linAct.clear(); b->h_linJ.clear(); b->h_rtz.clear(); b->fullJ_applied = false;
+}
+// ---- part two: the arena layout — the dalloc sequence of a graph of N points / R residuals in a window of F keyframes, from the start of the (cleared) arena; with it the
+// handle's kernel views, grid sizes and grow-only pinned buffers (the host mirrors are in place by now: h_newest sizes d_newestE).  The arrays that receive uploads come
+// back in GraphDev.
+struct GraphDev {
+  int *host, *res_begin, *point, *target;
+  float *u, *v, *color, *weights, *prior;
+  int *ridx, *cnt, *first, *last;   // scd_on_device only
+};
+static int graphLayout(dmvio_hip_ba* b, const GraphPrep& G, GraphDev& D) {
+  const int N = G.N, R = G.R, F = G.F, F2 = F * F;
+  b->arena.cur = 0; b->arena.off = 0;
+  struct ArenaScope { dmvio_hip_ba* b; ~ArenaScope() { b->arena.on = false; } } arenaScope{b};
+  b->arena.on = true;
+  b->H.N = N; b->H.R = R;
+  if (dalloc(b, &D.host, N) || dalloc(b, &D.res_begin, N + 1) || dalloc(b, &D.point, R) || dalloc(b, &D.target, R) || dalloc(b, &D.u, N) || dalloc(b, &D.v, N) ||
+      dalloc(b, &D.color, (size_t)N * 8) || dalloc(b, &D.weights, (size_t)N * 8) || dalloc(b, &D.prior, N)) return -1;
+  BAPoints& P = b->P; BARes& Rs = b->Rs;
+  if (dalloc(b, &P.idepth, N) || dalloc(b, &P.idepth_zero, N) || dalloc(b, &P.idepth_backup, N) || dalloc(b, &P.step, N) || dalloc(b, &P.Hdd, N) || dalloc(b, &P.bd, N) ||
+      dalloc(b, &P.Hcd, (size_t)N * 4) || dalloc(b, &P.HdiF, N) || dalloc(b, &P.bdSumF, N) || dalloc(b, &P.idepth_hessian, N) ||
+      dalloc(b, &b->d_cand, N) || dalloc(b, &b->d_decision, N) || dalloc(b, &b->d_mHdiF, N) || dalloc(b, &b->d_mbdSumF, N) || dalloc(b, &b->d_mHcd, (size_t)N * 4) ||
+      dalloc(b, &b->d_margRec, (size_t)R * REC_FLOATS) || dalloc(b, &b->d_margActive, R) || dalloc(b, &b->d_adHTdelta, (size_t)F2 * 8)) return -1;
+  if (dalloc(b, &Rs.removed, R) || dalloc(b, &Rs.state, R) || dalloc(b, &Rs.newState, R) || dalloc(b, &Rs.active, R) || dalloc(b, &Rs.which, R) || dalloc(b, &Rs.energy, R) || dalloc(b, &Rs.newEnergy, R) ||
+      dalloc(b, &Rs.center, (size_t)R * 3) || dalloc(b, &Rs.rec[0], (size_t)R * REC_FLOATS) || dalloc(b, &Rs.rec[1], (size_t)R * REC_FLOATS)) return -1;
+  P.host = D.host; P.u = D.u; P.v = D.v; P.color = D.color; P.weights = D.weights; P.priorF = D.prior; P.res_begin = D.res_begin;
+  Rs.point = D.point; Rs.target = D.target;
+  if (dalloc(b, &b->d_pre, (size_t)F2) || dalloc(b, &b->d_adHost, (size_t)F2 * 64) || dalloc(b, &b->d_adTarget, (size_t)F2 * 64) || dalloc(b, &b->d_top_begin, F2 + 1) ||
+      dalloc(b, &b->d_top_members, R) || dalloc(b, &b->d_scd_begin, F2 * F + 1) || dalloc(b, &b->d_scd_members, 3 * G.npairs) || dalloc(b, &b->d_accTop, (size_t)F2 * 96 * b->nsTop) ||
+      dalloc(b, &b->d_accD, (size_t)F2 * F * 64 * b->nsD) || dalloc(b, &b->d_accE, (size_t)F2 * 40 * b->nsTop) || dalloc(b, &b->d_accC, 20 * b->nsC) || dalloc(b, &b->d_numTop, F2 * b->nsTop) || dalloc(b, &b->d_numD, F2 * F * b->nsD)) return -1;
+  D.ridx = D.cnt = D.first = D.last = nullptr;
+  if (G.scd_on_device) { if (dalloc(b, &D.ridx, (size_t)N * F) || dalloc(b, &D.cnt, (size_t)F2 * F) || dalloc(b, &D.first, F) || dalloc(b, &D.last, F)) return -1; }
+  StitchBufs& SB = b->SB;
+  if (dalloc(b, &SB.topHH, (size_t)F * 64) || dalloc(b, &SB.topTT, (size_t)F2 * 64) || dalloc(b, &SB.topHT, (size_t)F2 * 64) || dalloc(b, &SB.topHC, (size_t)F * 32) ||
+      dalloc(b, &SB.topTC, (size_t)F2 * 32) || dalloc(b, &SB.topBH, (size_t)F * 8) || dalloc(b, &SB.topBT, (size_t)F2 * 8) || dalloc(b, &SB.topCC, (size_t)F * 20) ||
+      dalloc(b, &SB.scHH, (size_t)F2 * 64) || dalloc(b, &SB.scTT, (size_t)F2 * F * 64) || dalloc(b, &SB.scTH, (size_t)F2 * 64) || dalloc(b, &SB.scHT, (size_t)F2 * F * 64) ||
+      dalloc(b, &SB.scHC, (size_t)F2 * 32) ||
+      dalloc(b, &SB.scTC, (size_t)F2 * 32) || dalloc(b, &SB.scBH, (size_t)F2 * 8) || dalloc(b, &SB.scBT, (size_t)F2 * 8)) return -1;
+  const int n = b->H.n(), tot = 2 * (n * n + n);
+  b->n_lin_blocks = (R + LIN_RES_PER_BLOCK - 1) / LIN_RES_PER_BLOCK; b->n_pt_blocks = (N + 255) / 256; b->n_pt8_blocks = (N + PT_GROUPS_PER_BLOCK - 1) / PT_GROUPS_PER_BLOCK;
+  // energy partials (doubles) and the per-residual energies with outliers (floats) share one pinned allocation the kernel stores into
+  b->n_epart = std::max(b->n_lin_blocks, F2 * 8);
+  if (dalloc(b, &b->d_spart, 2 * b->n_pt_blocks) || dalloc(b, &b->d_fullJ, (size_t)R * 74)) return -1;
+  // what the host reads back every iteration (the stitched system, the energy partials, the per-residual energies) is written by the
+  // kernels straight into pinned host memory (h_sys, h_res: allocated with the handle, sized for BA_MAXF_CAP keyframes): no copy engine between the last kernel and the host's wait
+  if (dalloc(b, &b->d_sys, (size_t)tot + 1)) return -1;
+  b->xchg_width = 0; b->d_xchg_local = b->d_xchg_all = nullptr;
+  if ((size_t)N > b->cap_idepth_backup) {
+    if (b->h_idepth_backup) HIPCHK(hipHostFree(b->h_idepth_backup));
+    b->cap_idepth_backup = (size_t)N + (size_t)N / 2 + 256;
+    HIPCHK(hipHostMalloc((void**)&b->h_idepth_backup, sizeof(float) * b->cap_idepth_backup, hipHostMallocCoherent | hipHostMallocMapped));
+  }
+  if (dalloc(b, &b->d_ctl, 1) || dalloc(b, &b->d_frameTH, BA_MAXF_CAP) || dalloc(b, &b->d_epart, (size_t)b->n_epart) || dalloc(b, &b->d_newestSlot, (size_t)R) || dalloc(b, &b->d_newestE, b->h_newest.size()) ||
+      dalloc(b, &b->d_newEnergyWO, (size_t)R)) return -1;
+  Rs.newestSlot = b->d_newestSlot; Rs.newestE = b->d_newestE;
+  Rs.newEnergyWO = b->d_newEnergyWO;
+  if ((size_t)2 * b->n_pt_blocks > b->cap_spart) {
+    if (b->h_spart) HIPCHK(hipHostFree(b->h_spart));
+    b->cap_spart = (size_t)2 * b->n_pt_blocks + 64;
+    HIPCHK(hipHostMalloc((void**)&b->h_spart, sizeof(float) * b->cap_spart, hipHostMallocDefault));
+  }
+  return 0;
+}
+// ---- the single call: parts one and two, then part three, the enqueue on the handle's own stream
 static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u, const float* v, const float* idepth, const float* color8,
                         const float* weights8, const unsigned char* hasDepthPrior, int R, const int* res_point, const int* res_target, bool wait) {
   if (!b || !host || !u || !v || !idepth || !color8 || !weights8 || !res_point || !res_target) return failmsg("ba_set_graph: null argument");
@@ -15,79 +152,23 @@ static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u,
   double tg0 = b->timing ? nowUs() : 0, tg1;
 #define SG_PH(i) do { if (b->timing) { tg1 = nowUs(); b->tm_graph[i] += tg1 - tg0; tg0 = tg1; } } while (0)
   HIPCHK(hipStreamSynchronize(b->stream));
-  b->th_pending = false;   // the stream is drained and h_res is cleared below (th_ticket restarts at 0 while b->ticket keeps counting): nothing of the old graph may be awaited
-  freeDevice(b);
-  // residuals kept linearised belong to the graph they were linearised in
-  b->n_lin = 0; b->n_lin_global = 0; b->Rs.lin = nullptr; b->P.lHdd = b->P.lbd = b->P.lHcd = nullptr; b->P.HcdAF = nullptr; b->d_lin = nullptr; b->d_red1 = nullptr; b->H.HLraw.clear(); b->H.bLraw.clear();
-  b->h_lin.clear(); b->h_linAct.clear(); b->h_linJ.clear(); b->h_rtz.clear(); b->fullJ_applied = false;
+  graphDropOld(b);
   // the arena of the previous graph, cleared for this one on the handle's stream; the uploads and kernels below follow on the same stream: no wait
   for (size_t k = 0; k < b->arena.chunks.size(); k++) if (b->arena.used[k]) { HIPCHK(hipMemsetAsync(b->arena.chunks[k].first, 0, b->arena.used[k], b->stream)); b->arena.used[k] = 0; }   // what the previous graph used, not the whole chunk
   SG_PH(0);
-  b->arena.cur = 0; b->arena.off = 0;
-  struct ArenaScope { dmvio_hip_ba* b; ~ArenaScope() { b->arena.on = false; } } arenaScope{b};
-  b->arena.on = true;
   const int F = H.F, F2 = F * F;
   H.N = N; H.R = R;
+  std::vector<int> res_begin(N + 1), top_begin(F2 + 1), top_members(R), pt_first(F), pt_last(F), slot(R);
+  GraphPrep G;
+  if (int r = graphHostPrepare(F, N, host, R, res_point, res_target, GraphLists{res_begin.data(), top_begin.data(), top_members.data(), pt_first.data(), pt_last.data(), slot.data()}, G)) return r;
   b->h_host.assign(host, host + N); b->h_point.assign(res_point, res_point + R); b->h_target.assign(res_target, res_target + R);
-  b->h_newest.clear();
-  for (int ri = 0; ri < R; ri++) if (res_target[ri] == H.F - 1) b->h_newest.push_back(ri);
-  // residuals must be grouped by point, points in window order
-  b->h_res_begin.assign(N + 1, 0);
-  for (int ri = 0; ri < R; ri++) {
-    const int p = res_point[ri];
-    if (p < 0 || p >= N || res_target[ri] < 0 || res_target[ri] >= F) return failmsg("ba_set_graph: residual index out of range");
-    if (ri > 0 && p < res_point[ri - 1]) return failmsg("ba_set_graph: residuals must be sorted by point");
-    if (host[p] < 0 || host[p] >= F || host[p] == res_target[ri]) return failmsg("ba_set_graph: bad host / target");
-    b->h_res_begin[p + 1]++;
-  }
-  for (int p = 0; p < N; p++) b->h_res_begin[p + 1] += b->h_res_begin[p];
-  // bucket member lists in the reference's traversal order (points, then residuals of the point)
-  std::vector<int> top_begin(F2 + 1, 0), top_members(R), scd_begin(F2 * F + 1, 0);
-  for (int ri = 0; ri < R; ri++) top_begin[host[res_point[ri]] + F * res_target[ri] + 1]++;
-  for (int k = 0; k < F2; k++) top_begin[k + 1] += top_begin[k];
-  { std::vector<int> cur(top_begin.begin(), top_begin.end() - 1); for (int ri = 0; ri < R; ri++) top_members[cur[host[res_point[ri]] + F * res_target[ri]]++] = ri; }
-  size_t npairs = 0;
-  for (int p = 0; p < N; p++) { const size_t k = b->h_res_begin[p + 1] - b->h_res_begin[p]; npairs += k * k; }
-  // The Schur buckets' member lists are built on the device (k_ba_scd_*: ba_kernels.hpp) when no point observes a keyframe twice — always, in the reference's graphs (one
-  // PointFrameResidual per point and target, FullSystem.cpp:1248-1262); a graph that does is served by the host loops below, as every graph was before.
-  std::vector<int> pt_first(F, N), pt_last(F, -1);
-  bool scd_on_device = true;
-  for (int p = 0; p < N && scd_on_device; p++) {
-    pt_first[host[p]] = std::min(pt_first[host[p]], p); pt_last[host[p]] = std::max(pt_last[host[p]], p);
-    unsigned int seen = 0;
-    for (int ri = b->h_res_begin[p]; ri < b->h_res_begin[p + 1]; ri++) { const unsigned int bit = 1u << res_target[ri]; if (seen & bit) scd_on_device = false; seen |= bit; }
-  }
-  std::vector<int> scd_members;
-  if (!scd_on_device) {
-    scd_members.resize(3 * npairs);
-    for (int p = 0; p < N; p++)
-      for (int r1 = b->h_res_begin[p]; r1 < b->h_res_begin[p + 1]; r1++)
-        for (int r2 = b->h_res_begin[p]; r2 < b->h_res_begin[p + 1]; r2++) scd_begin[(host[p] + F * res_target[r1]) + res_target[r2] * F2 + 1]++;
-    for (int k = 0; k < F2 * F; k++) scd_begin[k + 1] += scd_begin[k];
-    std::vector<int> cur(scd_begin.begin(), scd_begin.end() - 1);
-    for (int p = 0; p < N; p++)
-      for (int r1 = b->h_res_begin[p]; r1 < b->h_res_begin[p + 1]; r1++)
-        for (int r2 = b->h_res_begin[p]; r2 < b->h_res_begin[p + 1]; r2++) {
-          const int k = (host[p] + F * res_target[r1]) + res_target[r2] * F2;
-          const int o = cur[k]++;
-          scd_members[3 * o] = r1; scd_members[3 * o + 1] = r2; scd_members[3 * o + 2] = p;
-        }
-  }
+  b->h_newest.swap(G.newest);
+  b->h_res_begin.swap(res_begin);
   SG_PH(1);
   // ---- device arrays
-  int *d_host, *d_res_begin, *d_point, *d_target;
-  float *d_u, *d_v, *d_color, *d_weights, *d_prior;
-  if (dalloc(b, &d_host, N) || dalloc(b, &d_res_begin, N + 1) || dalloc(b, &d_point, R) || dalloc(b, &d_target, R) || dalloc(b, &d_u, N) || dalloc(b, &d_v, N) ||
-      dalloc(b, &d_color, (size_t)N * 8) || dalloc(b, &d_weights, (size_t)N * 8) || dalloc(b, &d_prior, N)) return -1;
-  BAPoints& P = b->P; BARes& Rs = b->Rs;
-  if (dalloc(b, &P.idepth, N) || dalloc(b, &P.idepth_zero, N) || dalloc(b, &P.idepth_backup, N) || dalloc(b, &P.step, N) || dalloc(b, &P.Hdd, N) || dalloc(b, &P.bd, N) ||
-      dalloc(b, &P.Hcd, (size_t)N * 4) || dalloc(b, &P.HdiF, N) || dalloc(b, &P.bdSumF, N) || dalloc(b, &P.idepth_hessian, N) ||
-      dalloc(b, &b->d_cand, N) || dalloc(b, &b->d_decision, N) || dalloc(b, &b->d_mHdiF, N) || dalloc(b, &b->d_mbdSumF, N) || dalloc(b, &b->d_mHcd, (size_t)N * 4) ||
-      dalloc(b, &b->d_margRec, (size_t)R * REC_FLOATS) || dalloc(b, &b->d_margActive, R) || dalloc(b, &b->d_adHTdelta, (size_t)F2 * 8)) return -1;
-  if (dalloc(b, &Rs.removed, R) || dalloc(b, &Rs.state, R) || dalloc(b, &Rs.newState, R) || dalloc(b, &Rs.active, R) || dalloc(b, &Rs.which, R) || dalloc(b, &Rs.energy, R) || dalloc(b, &Rs.newEnergy, R) ||
-      dalloc(b, &Rs.center, (size_t)R * 3) || dalloc(b, &Rs.rec[0], (size_t)R * REC_FLOATS) || dalloc(b, &Rs.rec[1], (size_t)R * REC_FLOATS)) return -1;
-  P.host = d_host; P.u = d_u; P.v = d_v; P.color = d_color; P.weights = d_weights; P.priorF = d_prior; P.res_begin = d_res_begin;
-  Rs.point = d_point; Rs.target = d_target;
+  GraphDev D;
+  if (int r = graphLayout(b, G, D)) return r;
+  BAPoints& P = b->P;
   std::vector<float> prior(N, 0.0f);
   if (hasDepthPrior) for (int p = 0; p < N; p++) prior[p] = hasDepthPrior[p] ? H.S.idepthFixPrior : 0.0f;   // EFPoint::takeData
   hipStream_t s = b->stream;
@@ -95,78 +176,40 @@ static int setGraphImpl(dmvio_hip_ba* b, int N, const int* host, const float* u,
   // the uploads of this call are staged and leave merged (DmvBounce::begin_group): the nine point / residual tables and the two copies of idepth are one copy, ...
   struct GroupScope { DmvBounce& bn; ~GroupScope() { bn.grouping = false; bn.group.clear(); } } groupScope{b->bounce};   // an error return drops what was only staged
   b->bounce.begin_group();
-  HIPCHK(b->bounce.h2d(d_host, host, sizeof(int) * N, s));
-  HIPCHK(b->bounce.h2d(d_res_begin, b->h_res_begin.data(), sizeof(int) * (N + 1), s));
-  HIPCHK(b->bounce.h2d(d_point, res_point, sizeof(int) * R, s));
-  HIPCHK(b->bounce.h2d(d_target, res_target, sizeof(int) * R, s));
-  HIPCHK(b->bounce.h2d(d_u, u, sizeof(float) * N, s));
-  HIPCHK(b->bounce.h2d(d_v, v, sizeof(float) * N, s));
-  HIPCHK(b->bounce.h2d(d_color, color8, sizeof(float) * N * 8, s));
-  HIPCHK(b->bounce.h2d(d_weights, weights8, sizeof(float) * N * 8, s));
-  HIPCHK(b->bounce.h2d(d_prior, prior.data(), sizeof(float) * N, s));
+  HIPCHK(b->bounce.h2d(D.host, host, sizeof(int) * N, s));
+  HIPCHK(b->bounce.h2d(D.res_begin, b->h_res_begin.data(), sizeof(int) * (N + 1), s));
+  HIPCHK(b->bounce.h2d(D.point, res_point, sizeof(int) * R, s));
+  HIPCHK(b->bounce.h2d(D.target, res_target, sizeof(int) * R, s));
+  HIPCHK(b->bounce.h2d(D.u, u, sizeof(float) * N, s));
+  HIPCHK(b->bounce.h2d(D.v, v, sizeof(float) * N, s));
+  HIPCHK(b->bounce.h2d(D.color, color8, sizeof(float) * N * 8, s));
+  HIPCHK(b->bounce.h2d(D.weights, weights8, sizeof(float) * N * 8, s));
+  HIPCHK(b->bounce.h2d(D.prior, prior.data(), sizeof(float) * N, s));
   HIPCHK(b->bounce.h2d(P.idepth, idepth, sizeof(float) * N, s));
   HIPCHK(b->bounce.h2d(P.idepth_zero, idepth, sizeof(float) * N, s));
-  if (dalloc(b, &b->d_pre, (size_t)F2) || dalloc(b, &b->d_adHost, (size_t)F2 * 64) || dalloc(b, &b->d_adTarget, (size_t)F2 * 64) || dalloc(b, &b->d_top_begin, F2 + 1) ||
-      dalloc(b, &b->d_top_members, R) || dalloc(b, &b->d_scd_begin, F2 * F + 1) || dalloc(b, &b->d_scd_members, 3 * npairs) || dalloc(b, &b->d_accTop, (size_t)F2 * 96 * b->nsTop) ||
-      dalloc(b, &b->d_accD, (size_t)F2 * F * 64 * b->nsD) || dalloc(b, &b->d_accE, (size_t)F2 * 40 * b->nsTop) || dalloc(b, &b->d_accC, 20 * b->nsC) || dalloc(b, &b->d_numTop, F2 * b->nsTop) || dalloc(b, &b->d_numD, F2 * F * b->nsD)) return -1;
   HIPCHK(b->bounce.h2d(b->d_top_begin, top_begin.data(), sizeof(int) * (F2 + 1), s));
   HIPCHK(b->bounce.h2d(b->d_top_members, top_members.data(), sizeof(int) * R, s));
-  if (!scd_on_device) {
-    HIPCHK(b->bounce.h2d(b->d_scd_begin, scd_begin.data(), sizeof(int) * (F2 * F + 1), s));
-    HIPCHK(b->bounce.h2d(b->d_scd_members, scd_members.data(), sizeof(int) * 3 * npairs, s));
+  if (!G.scd_on_device) {
+    HIPCHK(b->bounce.h2d(b->d_scd_begin, G.scd_begin.data(), sizeof(int) * (F2 * F + 1), s));
+    HIPCHK(b->bounce.h2d(b->d_scd_members, G.scd_members.data(), sizeof(int) * 3 * G.npairs, s));
     HIPCHK(b->bounce.end_group(s));
   } else {
     // behind the uploads of host / point / target on the same stream: residual table, counts, scan, members
-    int *d_ridx, *d_cnt, *d_first, *d_last;
-    if (dalloc(b, &d_ridx, (size_t)N * F) || dalloc(b, &d_cnt, (size_t)F2 * F) || dalloc(b, &d_first, F) || dalloc(b, &d_last, F)) return -1;
-    HIPCHK(b->bounce.h2d(d_first, pt_first.data(), sizeof(int) * F, s));
-    HIPCHK(b->bounce.h2d(d_last, pt_last.data(), sizeof(int) * F, s));
+    HIPCHK(b->bounce.h2d(D.first, pt_first.data(), sizeof(int) * F, s));
+    HIPCHK(b->bounce.h2d(D.last, pt_last.data(), sizeof(int) * F, s));
     HIPCHK(b->bounce.end_group(s));   // the kernels below read what was staged so far
-    HIPCHK(hipMemsetAsync(d_ridx, 0xff, sizeof(int) * (size_t)N * F, s));
-    hipLaunchKernelGGL(k_ba_scd_ridx, dim3((R + 255) / 256), dim3(256), 0, s, R, F, (const int*)d_point, (const int*)d_target, d_ridx);
-    hipLaunchKernelGGL(k_ba_scd_lists, dim3((F2 + 3) / 4, F), dim3(256), 0, s, F, (const int*)d_first, (const int*)d_last, (const int*)d_host, (const int*)d_ridx, 0, d_cnt, (const int*)nullptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_ba_scd_scan, dim3(1), dim3(1024), 0, s, F2 * F, (const int*)d_cnt, b->d_scd_begin);
-    hipLaunchKernelGGL(k_ba_scd_lists, dim3((F2 + 3) / 4, F), dim3(256), 0, s, F, (const int*)d_first, (const int*)d_last, (const int*)d_host, (const int*)d_ridx, 1, d_cnt, (const int*)b->d_scd_begin, b->d_scd_members);
+    HIPCHK(hipMemsetAsync(D.ridx, 0xff, sizeof(int) * (size_t)N * F, s));
+    hipLaunchKernelGGL(k_ba_scd_ridx, dim3((R + 255) / 256), dim3(256), 0, s, R, F, (const int*)D.point, (const int*)D.target, D.ridx);
+    hipLaunchKernelGGL(k_ba_scd_lists, dim3((F2 + 3) / 4, F), dim3(256), 0, s, F, (const int*)D.first, (const int*)D.last, (const int*)D.host, (const int*)D.ridx, 0, D.cnt, (const int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_ba_scd_scan, dim3(1), dim3(1024), 0, s, F2 * F, (const int*)D.cnt, b->d_scd_begin);
+    hipLaunchKernelGGL(k_ba_scd_lists, dim3((F2 + 3) / 4, F), dim3(256), 0, s, F, (const int*)D.first, (const int*)D.last, (const int*)D.host, (const int*)D.ridx, 1, D.cnt, (const int*)b->d_scd_begin, b->d_scd_members);
     HIPCHK(hipGetLastError());
   }
   SG_PH(3);
   b->bounce.begin_group();   // ... the slot table and the adjoint tables another
-  StitchBufs& SB = b->SB;
-  if (dalloc(b, &SB.topHH, (size_t)F * 64) || dalloc(b, &SB.topTT, (size_t)F2 * 64) || dalloc(b, &SB.topHT, (size_t)F2 * 64) || dalloc(b, &SB.topHC, (size_t)F * 32) ||
-      dalloc(b, &SB.topTC, (size_t)F2 * 32) || dalloc(b, &SB.topBH, (size_t)F * 8) || dalloc(b, &SB.topBT, (size_t)F2 * 8) || dalloc(b, &SB.topCC, (size_t)F * 20) ||
-      dalloc(b, &SB.scHH, (size_t)F2 * 64) || dalloc(b, &SB.scTT, (size_t)F2 * F * 64) || dalloc(b, &SB.scTH, (size_t)F2 * 64) || dalloc(b, &SB.scHT, (size_t)F2 * F * 64) ||
-      dalloc(b, &SB.scHC, (size_t)F2 * 32) ||
-      dalloc(b, &SB.scTC, (size_t)F2 * 32) || dalloc(b, &SB.scBH, (size_t)F2 * 8) || dalloc(b, &SB.scBT, (size_t)F2 * 8)) return -1;
-  const int n = H.n(), tot = 2 * (n * n + n);
-  b->n_lin_blocks = (R + LIN_RES_PER_BLOCK - 1) / LIN_RES_PER_BLOCK; b->n_pt_blocks = (N + 255) / 256; b->n_pt8_blocks = (N + PT_GROUPS_PER_BLOCK - 1) / PT_GROUPS_PER_BLOCK;
-  // energy partials (doubles) and the per-residual energies with outliers (floats) share one pinned allocation the kernel stores into
-  b->n_epart = std::max(b->n_lin_blocks, F2 * 8);
-  if (dalloc(b, &b->d_spart, 2 * b->n_pt_blocks) || dalloc(b, &b->d_fullJ, (size_t)R * 74)) return -1;
-  // what the host reads back every iteration (the stitched system, the energy partials, the per-residual energies) is written by the
-  // kernels straight into pinned host memory (h_sys, h_res: allocated with the handle, sized for BA_MAXF_CAP keyframes): no copy engine between the last kernel and the host's wait
-  if (dalloc(b, &b->d_sys, (size_t)tot + 1)) return -1;
-  b->xchg_width = 0; b->d_xchg_local = b->d_xchg_all = nullptr;
   b->graphReplaced();
   memset(b->h_res, 0, sizeof(BAHostRes));
-  if ((size_t)N > b->cap_idepth_backup) {
-    if (b->h_idepth_backup) HIPCHK(hipHostFree(b->h_idepth_backup));
-    b->cap_idepth_backup = (size_t)N + (size_t)N / 2 + 256;
-    HIPCHK(hipHostMalloc((void**)&b->h_idepth_backup, sizeof(float) * b->cap_idepth_backup, hipHostMallocCoherent | hipHostMallocMapped));
-  }
-  if (dalloc(b, &b->d_ctl, 1) || dalloc(b, &b->d_frameTH, BA_MAXF_CAP) || dalloc(b, &b->d_epart, (size_t)b->n_epart) || dalloc(b, &b->d_newestSlot, (size_t)R) || dalloc(b, &b->d_newestE, b->h_newest.size()) ||
-      dalloc(b, &b->d_newEnergyWO, (size_t)R)) return -1;
-  {
-    std::vector<int> slot(R, -1);
-    for (size_t k = 0; k < b->h_newest.size(); k++) slot[b->h_newest[k]] = (int)k;
-    if (R) HIPCHK(b->bounce.h2d(b->d_newestSlot, slot.data(), sizeof(int) * R, s));   // staged (the vector may go): asynchronous like the other uploads
-    Rs.newestSlot = b->d_newestSlot; Rs.newestE = b->d_newestE;
-  }
-  Rs.newEnergyWO = b->d_newEnergyWO;
-  if ((size_t)2 * b->n_pt_blocks > b->cap_spart) {
-    if (b->h_spart) HIPCHK(hipHostFree(b->h_spart));
-    b->cap_spart = (size_t)2 * b->n_pt_blocks + 64;
-    HIPCHK(hipHostMalloc((void**)&b->h_spart, sizeof(float) * b->cap_spart, hipHostMallocDefault));
-  }
+  HIPCHK(b->bounce.h2d(b->d_newestSlot, slot.data(), sizeof(int) * R, s));   // staged (the vector may go): asynchronous like the other uploads
   SG_PH(4);
   if (int r = uploadAdjoints(b)) return r;
   HIPCHK(b->bounce.end_group(s));

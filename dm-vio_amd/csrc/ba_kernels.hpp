@@ -1603,18 +1603,21 @@ __device__ __forceinline__ void baAccumulateBody(const AccumArgs& A, const BARes
 // per target keyframe, so a bucket (h, t1, t2) receives at most ONE member per point, and the traversal order inside a bucket is simply "points ascending".  That makes the
 // lists cheap to build where they are used (the host built and uploaded 86k triples = 1 MB per keyframe before): ridx[p][t] = the residual of point p that targets t,
 // one thread per bucket scans the points of its host keyframe in order — first to count, then, behind a scan over the F^3 counts, to write.
-__global__ void __launch_bounds__(256) k_ba_scd_ridx(const int R, const int F, const int* __restrict__ point, const int* __restrict__ target, int* __restrict__ ridx) {
-  const int ri = blockIdx.x * 256 + threadIdx.x;
+// (the bodies are __device__ functions: the batched forms of ba_graph_batch_kernels.hpp run the same code for the window of blockIdx.y)
+__device__ __forceinline__ void baScdRidxBody(const int ri, const int R, const int F, const int* __restrict__ point, const int* __restrict__ target, int* __restrict__ ridx) {
   if (ri < R) ridx[point[ri] * F + target[ri]] = ri;
+}
+__global__ void __launch_bounds__(256) k_ba_scd_ridx(const int R, const int F, const int* __restrict__ point, const int* __restrict__ target, int* __restrict__ ridx) {
+  baScdRidxBody(blockIdx.x * 256 + threadIdx.x, R, F, point, target, ridx);
 }
 // mode 0: counts[k] = members of bucket k = h + F*t1 + F*F*t2;  mode 1: members written at begin[k]...   One WAVEFRONT per bucket (grid: F*F / 4 blocks of four waves x F
 // host keyframes): the lanes take 64 consecutive points of the host keyframe at a time, a ballot ranks the ones that observe both targets — points ascending, as the
-// reference's traversal leaves them.
-__global__ void __launch_bounds__(256) k_ba_scd_lists(const int F, const int* __restrict__ pt_first, const int* __restrict__ pt_last, const int* __restrict__ host,
-                                                        const int* __restrict__ ridx, const int mode, int* __restrict__ counts, const int* __restrict__ begin,
-                                                        int* __restrict__ members) {
-  const int h = blockIdx.y, F2 = F * F, lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+// reference's traversal leaves them.  (h: the host keyframe, blk: the workgroup's index among the F*F / 4 of that keyframe)
+__device__ __forceinline__ void baScdListsBody(const int h, const int blk, const int F, const int* __restrict__ pt_first, const int* __restrict__ pt_last,
+                                               const int* __restrict__ host, const int* __restrict__ ridx, const int mode, int* __restrict__ counts,
+                                               const int* __restrict__ begin, int* __restrict__ members) {
+  const int F2 = F * F, lane = threadIdx.x & 63;
+  const int b = blk * 4 + (threadIdx.x >> 6);
   if (b >= F2) return;
   const int t1 = b % F, t2 = b / F;
   const int k = h + F * t1 + F2 * t2;
@@ -1635,9 +1638,13 @@ __global__ void __launch_bounds__(256) k_ba_scd_lists(const int F, const int* __
     }
   if (!mode && lane == 0) counts[k] = n;
 }
+__global__ void __launch_bounds__(256) k_ba_scd_lists(const int F, const int* __restrict__ pt_first, const int* __restrict__ pt_last, const int* __restrict__ host,
+                                                        const int* __restrict__ ridx, const int mode, int* __restrict__ counts, const int* __restrict__ begin,
+                                                        int* __restrict__ members) {
+  baScdListsBody(blockIdx.y, blockIdx.x, F, pt_first, pt_last, host, ridx, mode, counts, begin, members);
+}
 // begin[0 .. n] = exclusive prefix sums of counts[0 .. n)   (n = F^3 <= 1728: one workgroup, 1024 threads x 2 entries, Hillis-Steele in LDS)
-__global__ void __launch_bounds__(1024) k_ba_scd_scan(const int n, const int* __restrict__ counts, int* __restrict__ begin) {
-  __shared__ int s[2048];
+__device__ __forceinline__ void baScdScanBody(int* __restrict__ s /* LDS, 2048 */, const int n, const int* __restrict__ counts, int* __restrict__ begin) {
   for (int i = threadIdx.x; i < 2048; i += 1024) s[i] = i < n ? counts[i] : 0;
   __syncthreads();
   for (int d = 1; d < 2048; d <<= 1) {
@@ -1648,6 +1655,10 @@ __global__ void __launch_bounds__(1024) k_ba_scd_scan(const int n, const int* __
     __syncthreads();
   }
   for (int i = threadIdx.x; i <= n; i += 1024) begin[i] = i == 0 ? 0 : s[i - 1];
+}
+__global__ void __launch_bounds__(1024) k_ba_scd_scan(const int n, const int* __restrict__ counts, int* __restrict__ begin) {
+  __shared__ int s[2048];
+  baScdScanBody(s, n, counts, begin);
 }
 
 // ------------------------------------------------------------------------------------------------ fp64 stitching

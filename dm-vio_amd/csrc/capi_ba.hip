@@ -892,6 +892,7 @@ int dmvio_hip_ba_solve_ldlt(int n, const double* HPassed, const double* b_in, do
 }  // extern "C"
 
 #include "ba_batch_host.hpp"
+#include "ba_graph_batch_host.hpp"   // dmvio_hip_ba_set_graph_from_batch: the hand-over of W windows per call, on the batch object above
 
 extern "C" {
 // dmvio_hip_ba_optimize of this handle through the device-resident loop (a batch of one window, created on first use): no PCIe poll per iteration.  The host-driven loop

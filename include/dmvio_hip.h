@@ -665,6 +665,33 @@ int dmvio_hip_ba_batch_last_marg_frame_work(dmvio_hip_ba_batch* batch, int* laun
 /* measurement (tools/bench_marg_frame_batch.py): with dmvio_hip_ba_batch_set_profile(1), HIP-event time in ms of the last such call's device work on the batch's stream,
  * from the upload to the download; 0 otherwise */
 int dmvio_hip_ba_batch_last_marg_frame_ms(dmvio_hip_ba_batch* batch, float* ms);
+/* Window hand-over of W windows per call: dmvio_hip_ba_set_graph_from(win[i].ba, win[i].graph) for every window of win[W], the stage that re-creates the windows of a
+ * keyframe's cycle in front of dmvio_hip_ba_optimize_batch.  After the call every handle is in the state its own single call would have left it in: the device tables
+ * (point and residual tables, idepth / idepth_zero, the top and Schur bucket lists, the newest-keyframe slot table, adjoints, cleared accumulators, all in the handle's
+ * own arena at the single call's addresses), the host mirrors and bookkeeping (no residual kept linearised, thresholds and pair tables due for upload), and the graph's
+ * flat order is the one dmvio_hip_graph_set_idepths accepts.  Nothing is computed: every later entry point gives the bits it gives after the single call, in both
+ * accumulation orders, and single and batched hand-overs may be mixed freely on a handle.  Windows of any keyframe counts from 1 to dmvio_hip_ba_max_frames() and of any
+ * sizes may share a call; the handles must be distinct, a graph may stand for more than one handle.
+ * Runs on the batch's stream under the rules of dmvio_hip_ba_marginalize_points_batch (the handles locked in address order; work pending on a handle's own stream is in
+ * front of the call, the call is complete on return — where the single call is stream-ordered and returns before its uploads have landed).  The graphs are flattened
+ * straight into one pinned slab the batch owns (grown on demand and kept) beside the windows' records.  Per call, whatever W, the sizes and the keyframe counts:
+ * ONE upload (records and slab together), SIX kernel launches (arena ranges of the previous graphs cleared and the residual tables set to -1; the slab's pieces copied
+ * into the handles' arenas; residual table, bucket counts, scan, bucket members), no download, ONE wait.
+ * Measured on 8-keyframe / 2000-point windows (tools/bench_set_graph_batch.py, profiles/set_graph_batch.md; microseconds per window by the wall clock, ranges of three
+ * runs, against W single calls of the previous library): 26.3-27.4 against 136.8-139.1 at W = 64, 32.2-33.9 against 136.6-139.0 at W = 16, 86.8-88.0 against 140.4-142.8
+ * at W = 4, 140.9-147.2 against 159.8-169.1 at W = 1; with dmvio_hip_ba_optimize_batch(6) behind it the ranges overlap at W = 1 (1007-1049 against 1044-1084): a caller
+ * with one window gains nothing measurable and may keep the single call, which does not wait.
+ * Refused as a whole, with a message that names the window, before anything is enqueued and before any handle or graph is touched: batch / win / a handle / a graph
+ * NULL, W < 0 or W > max_windows, a handle twice, a handle of another context, without dmvio_hip_ba_set_window, or sharded over ranks, a graph whose keyframe count
+ * differs from its window's, with a dangling residual, empty (N < 1 or R < 1), carrying linearised residuals, or in which a point observes one keyframe twice — the single
+ * call serves the last two (through its import of linearised residuals and its host-built Schur lists), the reference's own graphs contain neither.  W == 0 returns 0. */
+typedef struct dmvio_hip_ba_graph_window { dmvio_hip_ba* ba; dmvio_hip_graph* graph; } dmvio_hip_ba_graph_window;
+int dmvio_hip_ba_set_graph_from_batch(dmvio_hip_ba_batch* batch, int W, const dmvio_hip_ba_graph_window* win);
+/* what the last such call enqueued (all 0 after W == 0; unchanged by a refused call; any pointer may be NULL) */
+int dmvio_hip_ba_batch_last_graph_work(dmvio_hip_ba_batch* batch, int* launches, int* uploads, int* downloads, int* waits);
+/* measurement (tools/bench_set_graph_batch.py): with dmvio_hip_ba_batch_set_profile(1), HIP-event time in ms of the last such call's device work on the batch's stream,
+ * from the upload to the last kernel; 0 otherwise */
+int dmvio_hip_ba_batch_last_graph_ms(dmvio_hip_ba_batch* batch, float* ms);
 int dmvio_hip_ba_batch_set_exact_backsub(dmvio_hip_ba_batch* batch, int on);
 /* HIP-event times of the last dmvio_hip_ba_optimize_batch call on the batch's stream (ms): [0] initial chain + all iterations, [1] the final fix-linearisation,
  * [2] with dmvio_hip_ba_batch_set_profile(1): the stepped linearisation of the second iteration (k_ba_linearize_b over ALL windows of the call: a profiled call runs as one
