@@ -441,6 +441,12 @@ class Context:
                                                       qs.ctypes.data_as(C.c_void_p), qi.ctypes.data_as(C.c_void_p)), "selftest_divide")
         return qs, qi
 
+    def set_deferred_attach(self, on):
+        """dmvio_hip_set_deferred_attach: 1 (default) = frames_attach_device_batch leaves the coarser levels to the tracking kernel that first reads a slot (or to the first
+        other reader), 0 = the attach builds them itself."""
+        fn = self.L.dmvio_hip_set_deferred_attach; fn.argtypes = [C.c_void_p, C.c_int]; fn.restype = C.c_int
+        _chk(self.L, fn(self.p, 1 if on else 0), "set_deferred_attach")
+
     def set_build_stream(self, stream_ptr):
         """dmvio_hip_set_build_stream: the batched pyramid builds on a stream of their own (0 / None: the context's stream); the caller orders the streams with events."""
         fn = self.L.dmvio_hip_set_build_stream; fn.argtypes = [C.c_void_p, C.c_void_p]; fn.restype = C.c_int
@@ -706,6 +712,11 @@ class CoarseTrackerHip:
         a = C.c_longlong(0); b = C.c_longlong(0)
         _chk(self.L, self.L.dmvio_hip_tracker_last_work(self.p, C.byref(a), C.byref(b)), "last_work")
         return a.value, b.value
+
+    def last_fused_builds(self):
+        """problems of the last batch launch whose frame's pyramid the tracking kernel built itself (a deferred attach)"""
+        fn = self.L.dmvio_hip_tracker_last_fused_builds; fn.argtypes = [C.c_void_p]; fn.restype = C.c_int
+        return _chk(self.L, fn(self.p), "last_fused_builds")
 
     def last_residual_only_work(self):
         """(evaluations, point evaluations) of the last batch launch that ran residual-only; both are part of last_work()'s counts"""

@@ -53,23 +53,25 @@ static int ctxInit(dmvio_hip_ctx* c) {
   size_t off = 0;
   for (int l = 0; l < c->levels; l++) {
     c->wl[l] = w >> l; c->hl[l] = h >> l;
-    c->fs.level_off[l] = off;
+    c->fs_.level_off[l] = off;
     off += (size_t)c->wl[l] * c->hl[l];
   }
-  c->fs.levels = c->levels;
-  c->fs.slot_stride = (off + 63) & ~(size_t)63;
+  c->fs_.levels = c->levels;
+  c->fs_.slot_stride = (off + 63) & ~(size_t)63;
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(hipMalloc((void**)&c->fs.base, sizeof(float) * c->fs.slot_stride * n_frame_slots));
-  HIPCHK(hipMemsetAsync(c->fs.base, 0, sizeof(float) * c->fs.slot_stride * n_frame_slots, c->stream));
-  HIPCHK(hipMalloc((void**)&c->fs.build_gen, sizeof(unsigned int) * 2 * n_frame_slots));   // build_gen | bad_gen: equal (0) = not known to be clean
-  HIPCHK(hipMemsetAsync(c->fs.build_gen, 0, sizeof(unsigned int) * 2 * n_frame_slots, c->stream));
-  c->fs.bad_gen = c->fs.build_gen + n_frame_slots;
-  HIPCHK(hipMalloc((void**)&c->fs.lvl0, sizeof(const float*) * n_frame_slots));
+  HIPCHK(hipMalloc((void**)&c->fs_.base, sizeof(float) * c->fs_.slot_stride * n_frame_slots));
+  HIPCHK(hipMemsetAsync(c->fs_.base, 0, sizeof(float) * c->fs_.slot_stride * n_frame_slots, c->stream));
+  HIPCHK(hipMalloc((void**)&c->fs_.build_gen, sizeof(unsigned int) * 3 * n_frame_slots));   // build_gen | bad_gen: equal (0) = not known to be clean | pend_gen: 0 = built
+  HIPCHK(hipMemsetAsync(c->fs_.build_gen, 0, sizeof(unsigned int) * 3 * n_frame_slots, c->stream));
+  c->fs_.bad_gen = c->fs_.build_gen + n_frame_slots;
+  c->h_pending.assign(n_frame_slots, 0);
+  c->slot_stamp.assign(n_frame_slots, 0u);
+  HIPCHK(hipMalloc((void**)&c->fs_.lvl0, sizeof(const float*) * n_frame_slots));
   c->h_lvl0.resize(n_frame_slots);
-  for (int s = 0; s < n_frame_slots; s++) c->h_lvl0[s] = c->fs.own_level(s, 0);
-  HIPCHK(hipMemcpyAsync(c->fs.lvl0, c->h_lvl0.data(), sizeof(const float*) * n_frame_slots, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMalloc((void**)&c->fs.tiled0, n_frame_slots));
-  HIPCHK(hipMemsetAsync(c->fs.tiled0, 0, n_frame_slots, c->stream));
+  for (int s = 0; s < n_frame_slots; s++) c->h_lvl0[s] = c->fs_.own_level(s, 0);
+  HIPCHK(hipMemcpyAsync(c->fs_.lvl0, c->h_lvl0.data(), sizeof(const float*) * n_frame_slots, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMalloc((void**)&c->fs_.tiled0, n_frame_slots));
+  HIPCHK(hipMemsetAsync(c->fs_.tiled0, 0, n_frame_slots, c->stream));
   c->h_tiled.assign(n_frame_slots, 0);
   HIPCHK(hipMalloc((void**)&c->d_upload, sizeof(float) * w * h));
   c->pg.levels = c->levels;
@@ -108,11 +110,12 @@ int dmvio_hip_set_pyramid_tile_log2(dmvio_hip_ctx* c, int tw_log2) {
 void dmvio_hip_destroy(dmvio_hip_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
+  // (slots that still wait for a deferred build are not built: nothing can read them any more, and their images need not outlive the context)
   if (c->stream) hipStreamSynchronize(c->stream);   // (null only in a handle whose creation failed)
-  hipFree(c->fs.base);
-  hipFree(c->fs.build_gen);
-  hipFree(c->fs.lvl0);
-  hipFree(c->fs.tiled0);
+  hipFree(c->fs_.base);
+  hipFree(c->fs_.build_gen);
+  hipFree(c->fs_.lvl0);
+  hipFree(c->fs_.tiled0);
   hipFree(c->d_upload);
   c->bounce.release();
   hipFree(c->d_f3);
@@ -127,6 +130,7 @@ int dmvio_hip_set_stream(dmvio_hip_ctx* c, void* s) {
   if (!c) return failmsg("null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
+  if (int r = dmv_flush_pending(c, 0)) return r;   // a deferred attach is finished on the stream it was made on
   HIPCHK(hipStreamSynchronize(c->stream));
   if (s) {
     if (c->own_stream) { HIPCHK(hipStreamDestroy(c->stream)); }
@@ -145,6 +149,7 @@ int dmvio_hip_set_build_stream(dmvio_hip_ctx* c, void* s) {
   if (!c) return failmsg("null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
+  if (int r = dmv_flush_pending(c, 0)) return r;   // with a build stream nothing is deferred: what waits is built now, on the context's stream
   HIPCHK(hipStreamSynchronize(buildStream(c)));
   c->build_stream = (hipStream_t)s;
   return 0;
@@ -153,6 +158,7 @@ int dmvio_hip_set_build_stream(dmvio_hip_ctx* c, void* s) {
 int dmvio_hip_synchronize(dmvio_hip_ctx* c) {
   if (!c) return failmsg("null ctx");
   HIPCHK(hipSetDevice(c->device));
+  if (int r = dmv_flush_pending(c, 0)) return r;   // after a synchronize every slot is built: the caller may read the store from any stream
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->build_stream) HIPCHK(hipStreamSynchronize(c->build_stream));
   return 0;
@@ -163,10 +169,48 @@ int dmvio_hip_synchronize(dmvio_hip_ctx* c) {
 // multiples of 8; everything else (and dmvio_hip_set_raw_batch_kernel(ctx, 0)) goes to the LDS-tile builds
 static bool regBuild(const dmvio_hip_ctx* c) { return c->raw_batch_kernel && c->levels <= 4 && (c->w % 8) == 0 && (c->h % 8) == 0; }
 static dim3 regGrid(const dmvio_hip_ctx* c, int B) { return dim3(((c->w / 4) * (c->h / 8) + 255) / 256, B); }
+
+// ---- deferred attach: see dmvio_hip_ctx (internal.h) and DESIGN.md section 4.  *Held: the caller holds c->pend_mu.
+// The ordinary build of the slots that still wait, from the recorded source: one launch per run of consecutive entries of the staged list (the kernel finds frame f of its
+// launch at base + f * stride and its slot at slots[f], so a run is the same launch shifted), stamped with the generation the attach set aside for it, then their marks cleared.
+static int flushPendingHeld(dmvio_hip_ctx* c, bool wait) {
+  if (!c->n_pending.load(std::memory_order_relaxed)) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  const dmvio_hip_ctx::PendingAttach& P = c->pend;
+  for (int i = 0; i < P.B;) {
+    if (c->h_pending[P.slots[i]] != i + 1) { i++; continue; }
+    int j = i;
+    while (j < P.B && c->h_pending[P.slots[j]] == j + 1) { c->h_pending[P.slots[j]] = 0; j++; }
+    hipLaunchKernelGGL((k_build_pyramids_reg<true>), regGrid(c, j - i), dim3(256), 0, c->stream, P.base + (size_t)i * P.stride, P.stride, c->pg, c->fs_, P.d_slots + i, 0, P.flush_gen);
+    hipLaunchKernelGGL(k_clear_pending, dim3((j - i + 255) / 256), dim3(256), 0, c->stream, c->fs_, P.d_slots + i, j - i);
+    i = j;
+  }
+  c->n_pending.store(0, std::memory_order_release);
+  HIPCHK(hipGetLastError());
+  if (wait) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int dmv_flush_pending_held(dmvio_hip_ctx* c) { return flushPendingHeld(c, false); }
+int dmv_flush_pending(dmvio_hip_ctx* c, int wait) {
+  std::lock_guard<std::mutex> pl(c->pend_mu);
+  return flushPendingHeld(c, wait != 0);
+}
+// the host marks of slots another build is about to rewrite (the device marks follow: a memset for one slot, k_clear_pending for a staged list); returns how many waited
+static int dropPendingHeld(dmvio_hip_ctx* c, int B, const int* slots) {
+  if (!c->n_pending.load(std::memory_order_relaxed)) return 0;
+  int n = 0;
+  for (int i = 0; i < B; i++) if (c->h_pending[slots[i]]) { c->h_pending[slots[i]] = 0; n++; }
+  c->n_pending.fetch_sub(n, std::memory_order_release);
+  return n;
+}
 static int buildPyramid(dmvio_hip_ctx* c, int slot, const float* d_color) {
-  hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, 1), dim3(256), 0, c->stream, d_color, (size_t)0, c->pg, c->fs,
+  {
+    std::lock_guard<std::mutex> pl(c->pend_mu);
+    if (dropPendingHeld(c, 1, &slot)) HIPCHK(hipMemsetAsync(c->fs_.pend_gen() + slot, 0, sizeof(unsigned int), c->stream));
+  }
+  hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, 1), dim3(256), 0, c->stream, d_color, (size_t)0, c->pg, c->fs_,
                      (const int*)nullptr, slot, ++c->build_gen, 0);
-  c->h_lvl0[slot] = c->fs.own_level(slot, 0); c->h_tiled[slot] = 0;
+  c->h_lvl0[slot] = c->fs_.own_level(slot, 0); c->h_tiled[slot] = 0;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -176,11 +220,11 @@ int dmv_ensure_row_major_locked(dmvio_hip_ctx* c, int slot) {
   if (slot < 0 || slot >= c->n_slots || !c->h_tiled[slot]) return 0;
   HIPCHK(hipSetDevice(c->device));
   const int n = c->w * c->h;
-  float* own = c->fs.own_level(slot, 0);
+  float* own = c->fs_.own_level(slot, 0);
   hipLaunchKernelGGL(k_untile_level0, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float*)own, c->w, c->h, c->d_upload);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(own, c->d_upload, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->fs.tiled0 + slot, 0, 1, c->stream));
+  HIPCHK(hipMemsetAsync(c->fs_.tiled0 + slot, 0, 1, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));   // consumers on other streams (a window optimiser's) read the plane next
   c->h_tiled[slot] = 0;
   return 0;
@@ -206,6 +250,16 @@ int dmvio_hip_set_raw_batch_kernel(dmvio_hip_ctx* c, int variant) {
   if (variant != 0 && variant != 1) return failmsg("set_raw_batch_kernel: variant must be 0 or 1");
   std::lock_guard<std::mutex> lk(c->mu);
   c->raw_batch_kernel = variant;
+  return 0;
+}
+// 1 (default): dmvio_hip_frames_attach_device_batch only records the attach (one small kernel) where the register build would run on the context's stream; the coarser
+// levels of a slot are formed by the batched tracking kernel that first reads it (k_track_lm_build) or, for every other reader, right before that reader.  0: the attach
+// launches the build itself.  Same planes, same stamps' meaning, same results either way (tests/test_track_fused_build_gpu.py).
+int dmvio_hip_set_deferred_attach(dmvio_hip_ctx* c, int on) {
+  if (!c) return failmsg("null ctx");
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (int r = dmv_flush_pending(c, 0)) return r;
+  c->deferred_attach = on ? 1 : 0;
   return 0;
 }
 int dmvio_hip_frame_level0_is_tiled(dmvio_hip_ctx* c, int slot) {
@@ -307,7 +361,7 @@ int dmvio_hip_frame_from_device(dmvio_hip_ctx* c, int slot, const float* dev) {
   return buildPyramid(c, slot, dev);  // asynchronous on the ctx stream
 }
 
-// slot list of a batched build -> device (kept while the same list comes again); caller holds c->mu
+// slot list of a batched build -> device (kept while the same list comes again); caller holds c->mu and c->pend_mu
 static int stageSlots(dmvio_hip_ctx* c, int B, const int* slots) {
   for (int i = 0; i < B; i++) if (slots[i] < 0 || slots[i] >= c->n_slots) return failmsg("frame batch: slot out of range");
   dmvio_hip_ctx::SlotList* hit = nullptr;
@@ -318,6 +372,7 @@ static int stageSlots(dmvio_hip_ctx* c, int B, const int* slots) {
   }
   if (!hit) {
     hit = lru;
+    if (hit->d && hit->d == c->pend.d_slots) { if (int r = flushPendingHeld(c, false)) return r; }   // slots that still wait are listed in the entry about to be rewritten
     // the pinned copy may still be the source of an in-flight upload, the device copy the argument of a running build: drain before rewriting
     HIPCHK(hipStreamSynchronize(buildStream(c)));
     if (c->build_stream) HIPCHK(hipStreamSynchronize(c->stream));
@@ -341,14 +396,36 @@ static int framesFromDeviceBatch(dmvio_hip_ctx* c, int B, const int* slots, cons
   if (B <= 0 || stride_bytes % sizeof(float)) return failmsg("frames_from_device_batch: bad B / stride");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < B; i++) if (slots[i] < 0 || slots[i] >= c->n_slots) return failmsg("frame batch: slot out of range");
+  std::lock_guard<std::mutex> pl(c->pend_mu);
+  // slots of this call that still wait for a deferred build are superseded: their old image is never read
+  const int dropped = dropPendingHeld(c, B, slots);
   if (int r = stageSlots(c, B, slots)) return r;
+  if (attach && regBuild(c) && !c->build_stream && c->deferred_attach) {
+    // deferred: only the table kernel now; the levels 1.. are formed by the tracking kernel that first reads a slot, or by a flush.  One deferred attach is kept: what an
+    // older one left is built first.  Three generations: "not known clean" until built, the stamp of a build inside the tracking kernel, the stamp of a flush.
+    if (int r = flushPendingHeld(c, false)) return r;
+    const unsigned int gen = c->build_gen + 1u;
+    c->build_gen += 3u;
+    hipLaunchKernelGGL(k_attach_deferred, dim3((B + 255) / 256), dim3(256), 0, c->stream, dev_base, stride_bytes / sizeof(float), c->fs_, (const int*)c->d_slots, B, gen);
+    dmvio_hip_ctx::PendingAttach& P = c->pend;
+    P.base = dev_base; P.stride = stride_bytes / sizeof(float); P.d_slots = c->d_slots; P.B = B; P.flush_gen = gen + 2u;
+    P.slots.assign(slots, slots + B);
+    int n = 0;
+    for (int i = 0; i < B; i++) { if (!c->h_pending[slots[i]]) n++; c->h_pending[slots[i]] = i + 1; }
+    c->n_pending.store(n, std::memory_order_release);
+    for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = dev_base + (size_t)i * P.stride; c->h_tiled[slots[i]] = 0; }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  if (dropped) hipLaunchKernelGGL(k_clear_pending, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->fs_, (const int*)c->d_slots, B);
   // attached in place: the register build (read-dominated: 5 % ahead); level 0 copied: the LDS-tile build (4 % ahead there) — both measured, tools/time_pyramids.py
   if (regBuild(c) && attach)
-    hipLaunchKernelGGL((k_build_pyramids_reg<true>), regGrid(c, B), dim3(256), 0, buildStream(c), dev_base, stride_bytes / sizeof(float), c->pg, c->fs, (const int*)c->d_slots, 0, ++c->build_gen);
+    hipLaunchKernelGGL((k_build_pyramids_reg<true>), regGrid(c, B), dim3(256), 0, buildStream(c), dev_base, stride_bytes / sizeof(float), c->pg, c->fs_, (const int*)c->d_slots, 0, ++c->build_gen);
   else
     hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, B), dim3(256), 0, buildStream(c), dev_base, stride_bytes / sizeof(float),
-                       c->pg, c->fs, (const int*)c->d_slots, 0, ++c->build_gen, attach ? 1 : 0);
-  for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = attach ? dev_base + (size_t)i * (stride_bytes / sizeof(float)) : c->fs.own_level(slots[i], 0); c->h_tiled[slots[i]] = 0; }
+                       c->pg, c->fs_, (const int*)c->d_slots, 0, ++c->build_gen, attach ? 1 : 0);
+  for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = attach ? dev_base + (size_t)i * (stride_bytes / sizeof(float)) : c->fs_.own_level(slots[i], 0); c->h_tiled[slots[i]] = 0; }
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -357,7 +434,7 @@ static int framesFromDeviceBatch(dmvio_hip_ctx* c, int B, const int* slots, cons
 // the eight instantiations of the raw-image builds: pixel type (the caller), then register / LDS-tile build x tiled / row-major level 0
 template <typename T>
 static void launchRawBuild(dmvio_hip_ctx* c, bool reg, bool tiled, dim3 grid, const void* raw, size_t stride, const UndistortDev& U) {
-  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, buildStream(c), (const T*)raw, stride, U, c->pg, c->fs, (const int*)c->d_slots, ++c->build_gen); };
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, buildStream(c), (const T*)raw, stride, U, c->pg, c->fs_, (const int*)c->d_slots, ++c->build_gen); };
   if (reg) { if (tiled) go(k_build_pyramids_raw_reg<T, true>); else go(k_build_pyramids_raw_reg<T, false>); }
   else { if (tiled) go(k_build_pyramids_raw<T, true>); else go(k_build_pyramids_raw<T, false>); }
 }
@@ -372,7 +449,11 @@ int dmvio_hip_frames_from_raw_device_batch(dmvio_hip_ctx* c, dmvio_hip_undistort
     return failmsg("frames_from_raw_device_batch: bad B / stride / alignment");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < B; i++) if (slots[i] < 0 || slots[i] >= c->n_slots) return failmsg("frame batch: slot out of range");
+  std::lock_guard<std::mutex> pl(c->pend_mu);
+  const int dropped = dropPendingHeld(c, B, slots);   // rewritten here: a deferred build of these slots is void
   if (int r = stageSlots(c, B, slots)) return r;
+  if (dropped) hipLaunchKernelGGL(k_clear_pending, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->fs_, (const int*)c->d_slots, B);
   UndistortDev U = u->U;
   U.factor = factor;
   // level 0 in 8x4 tiles on request (dmvio_hip_set_raw_batch_layout)
@@ -382,7 +463,7 @@ int dmvio_hip_frames_from_raw_device_batch(dmvio_hip_ctx* c, dmvio_hip_undistort
   const dim3 grid = reg ? regGrid(c, B) : dim3(c->pg.tiles_x * c->pg.tiles_y, B);
   if (u->bytes_per_px == 1) launchRawBuild<unsigned char>(c, reg, tiled, grid, raw_dev_base, stride_bytes, U);
   else launchRawBuild<unsigned short>(c, reg, tiled, grid, raw_dev_base, stride_bytes / 2, U);
-  for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = c->fs.own_level(slots[i], 0); c->h_tiled[slots[i]] = tiled ? 1 : 0; }
+  for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = c->fs_.own_level(slots[i], 0); c->h_tiled[slots[i]] = tiled ? 1 : 0; }
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -401,7 +482,8 @@ int dmvio_hip_frame_mark_unclean(dmvio_hip_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= c->n_slots) return failmsg("frame_mark_unclean: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(c->fs.bad_gen + slot, c->fs.build_gen + slot, sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+  if (int r = dmv_flush_pending(c, 0)) return r;
+  HIPCHK(hipMemcpyAsync(c->fs_.bad_gen + slot, c->fs_.build_gen + slot, sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -410,9 +492,10 @@ int dmvio_hip_frame_is_clean(dmvio_hip_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= c->n_slots) return failmsg("frame_is_clean: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
+  if (int r = dmv_flush_pending(c, 0)) return r;   // the verdict of a slot that still waits is formed with its levels
   unsigned int g[2] = {0, 0};
-  HIPCHK(c->bounce.d2h(&g[0], c->fs.build_gen + slot, sizeof(unsigned int), c->stream));
-  HIPCHK(c->bounce.d2h(&g[1], c->fs.bad_gen + slot, sizeof(unsigned int), c->stream));
+  HIPCHK(c->bounce.d2h(&g[0], c->fs_.build_gen + slot, sizeof(unsigned int), c->stream));
+  HIPCHK(c->bounce.d2h(&g[1], c->fs_.bad_gen + slot, sizeof(unsigned int), c->stream));
   HIPCHK(c->bounce.finish(c->stream));
   return g[0] != g[1] ? 1 : 0;
 }

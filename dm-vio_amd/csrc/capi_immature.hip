@@ -469,7 +469,7 @@ int dmv_immature_optimize_launch_locked(dmvio_hip_immature* m, int F, const int*
   T.fxl = (float)fxfycxcy[0]; T.fyl = (float)fxfycxcy[1]; T.cxl = (float)fxfycxcy[2]; T.cyl = (float)fxfycxcy[3];
   T.fxli = 1.0f / T.fxl; T.fyli = 1.0f / T.fyl;   // CalibHessian::setValueScaled (HessianBlocks.h:373-387)
   m->P.n = m->n;
-  hipLaunchKernelGGL(k_immature_optimize, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->fs, c->w, c->h, m->P, T, d_mask, minObs,
+  hipLaunchKernelGGL(k_immature_optimize, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->store(), c->w, c->h, m->P, T, d_mask, minObs,
                      100.0f /* setting_minIdepthH_act */, 3 /* setting_GNItsOnPointActivation */, m->S.huberTH, m->d_result, m->d_idepth, m->d_res_state);
   HIPCHK(hipGetLastError());
   return 0;

@@ -27,6 +27,11 @@ struct FrameStore {
   // (k_build_pyramids).  bad_gen[slot] != build_gen[slot]  <=>  every pixel of every level is finite and so is every central difference:
   // consumers may then skip the reference's isfinite guards (HessianBlocks.cpp:172-181, CoarseTracker.cpp:455) — they cannot fire.
   unsigned int *build_gen, *bad_gen;
+  // per slot: 0 = the coarser levels are built; g != 0 = a deferred attach left only level 0 (lvl0[slot]) and the levels 1.. are formed from it by the first kernel that
+  // reads the slot (k_track_lm_build), which then stamps the slot with generation g (k_attach_deferred, image_kernels.hpp).  The three per-slot arrays are one allocation,
+  // build_gen | bad_gen | pend_gen; the third is reached from the first two and not through a member of its own, so that the kernel-argument layout of every kernel that
+  // takes a FrameStore (and with it those kernels' code) stays what it was.
+  __host__ __device__ unsigned int* pend_gen() const { return bad_gen + (bad_gen - build_gen); }
   // level 0 of a slot is reached through a pointer table: it is either the slot's own plane or — frames attached in place
   // (dmvio_hip_frames_attach_device_batch) — the caller's resident image itself: the intensity plane IS the input image, so nothing is copied.
   // The table lives in device memory (written by k_build_pyramids); host code uses dmvio_hip_ctx::levelPtr.

@@ -12,10 +12,10 @@
 #pragma once
 #include "common.h"
 #include "interp.hpp"
+#include "pyr_reg_block.hpp"
 
 namespace dmv {
 
-typedef float pyr_f4 __attribute__((ext_vector_type(4)));
 // level-0 tile of a workgroup: PYR_TILE_PX pixels, 2^tw_log2 wide (PyrGeom::tw_log2, chosen per context: as wide as the image allows — a 512-pixel-wide tile of a
 // 512-pixel-wide image is 8 rows x 2 KB = 16 KB of CONTIGUOUS level-0 memory per workgroup, where a 128 x 32 tile wrote 32 separate 512-byte pieces — and as high as the
 // 2x2 reductions of the coarser levels need: 2^(levels-1) rows)
@@ -216,37 +216,6 @@ __global__ void __launch_bounds__(256) k_build_pyramids_raw(const T* __restrict_
   pyrReduceLevels(s_a, s_b, G, fs, slot, x0, y0, pitch);
 }
 
-// Levels 1..3 of a thread's 4 x 8 pixel block (k_build_pyramids_raw_reg, k_build_pyramids_reg): 2 x 4 values of level 1 and two of level 2 in registers, level 3 by the even
-// lane of a lane pair.  0.25f * (((a + b) + c) + d) per level, the reference's operand order (HessianBlocks.cpp:150-166).
-__device__ __forceinline__ void pyrRegCoarse(const float (&v)[8][4], const PyrGeom& G, const FrameStore& fs, const int slot, const int tx, const int ty, const bool live, const int lane) {
-  if (G.levels < 2) return;
-  float l1[4][2];
-#pragma unroll
-  for (int r = 0; r < 4; r++)
-#pragma unroll
-    for (int c = 0; c < 2; c++) l1[r][c] = 0.25f * (v[2 * r][2 * c] + v[2 * r][2 * c + 1] + v[2 * r + 1][2 * c] + v[2 * r + 1][2 * c + 1]);
-  if (live) {
-    float* __restrict__ d1 = fs.own_level(slot, 1);
-    const int w1 = G.w[1];
-#pragma unroll
-    for (int r = 0; r < 4; r++) { const float2 q = make_float2(l1[r][0], l1[r][1]); __builtin_memcpy(d1 + (size_t)(4 * ty + r) * w1 + 2 * tx, &q, 8); }
-  }
-  if (G.levels < 3) return;
-  float l2[2];
-#pragma unroll
-  for (int r = 0; r < 2; r++) l2[r] = 0.25f * (l1[2 * r][0] + l1[2 * r][1] + l1[2 * r + 1][0] + l1[2 * r + 1][1]);
-  if (live) {
-    float* __restrict__ d2 = fs.own_level(slot, 2);
-    const int w2 = G.w[2];
-    d2[(size_t)(2 * ty) * w2 + tx] = l2[0];
-    d2[(size_t)(2 * ty + 1) * w2 + tx] = l2[1];
-  }
-  if (G.levels < 4) return;
-  // level 3: the 2 x 2 block of level 2 = this lane's two values and those of the lane to its right (w0 % 8 == 0: a lane pair never straddles a block row)
-  const float nb0 = __shfl_down(l2[0], 1, 64), nb1 = __shfl_down(l2[1], 1, 64);
-  if (live && !(lane & 1)) fs.own_level(slot, 3)[(size_t)ty * G.w[3] + (tx >> 1)] = 0.25f * (l2[0] + nb0 + l2[1] + nb1);
-}
-
 // The same build without workgroup coupling — the default of dmvio_hip_frames_from_raw_device_batch for pyramids of at most four levels on images whose sides are
 // multiples of 8 (512x512, 640x480, 800x400 ...).  A thread owns a 4 x 8 pixel block: its eight level-0 rows, the 2 x 4 values of level 1 and the two of level 2 they
 // reduce to never leave registers, level 3 is formed by the even lane of a lane pair (one cross-lane read).  No barrier and — row-major level 0 — no LDS: a wavefront
@@ -364,40 +333,32 @@ __global__ void __launch_bounds__(256) k_build_pyramids_reg(const float* __restr
   const int f = blockIdx.y;
   const int slot = slots ? slots[f] : single_slot;
   const float* __restrict__ src = in_base + (size_t)f * in_stride;
-  const int w0 = G.w[0], h0 = G.h[0];
-  const int tpr4 = w0 >> 2, nthr = tpr4 * (h0 >> 3);
   const int t = blockIdx.x * 256 + threadIdx.x;
-  const bool live = t < nthr;
-  const int tx = live ? t % tpr4 : 0, ty = live ? t / tpr4 : 0;
-  const int x = 4 * tx, y = 8 * ty;
   const int lane = threadIdx.x & 63;
-  float v[8][4];
-  const float* __restrict__ p0 = src + (size_t)y * w0 + x;
-  if (((uintptr_t)src & 15) == 0) {   // x % 4 == 0, w0 % 8 == 0: the frame's base decides for every row
-#pragma unroll
-    for (int r = 0; r < 8; r++) { const pyr_f4 q = __builtin_nontemporal_load(reinterpret_cast<const pyr_f4*>(p0 + (size_t)r * w0)); v[r][0] = q[0]; v[r][1] = q[1]; v[r][2] = q[2]; v[r][3] = q[3]; }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 8; r++) __builtin_memcpy(v[r], p0 + (size_t)r * w0, 16);
-  }
-  bool bad = false;
-#pragma unroll
-  for (int r = 0; r < 8; r++)
-#pragma unroll
-    for (int k = 0; k < 4; k++) bad |= !(fabsf(v[r][k]) <= 1e30f);
-  if (__any(bad && live) && lane == 0) fs.bad_gen[slot] = gen;
-  if (t == 0) { fs.build_gen[slot] = gen; fs.lvl0[slot] = ATTACH ? src : fs.own_level(slot, 0); fs.tiled0[slot] = 0; }
-  if (!ATTACH && live) {
-    float* __restrict__ dst0 = fs.own_level(slot, 0);
-    if (((uintptr_t)dst0 & 15) == 0) {
-#pragma unroll
-      for (int r = 0; r < 8; r++) { const pyr_f4 q = {v[r][0], v[r][1], v[r][2], v[r][3]}; __builtin_nontemporal_store(q, reinterpret_cast<pyr_f4*>(dst0 + (size_t)(y + r) * w0 + x)); }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 8; r++) __builtin_memcpy(dst0 + (size_t)(y + r) * w0 + x, v[r], 16);
-    }
-  }
-  pyrRegCoarse(v, G, fs, slot, tx, ty, live, lane);
+  pyrRegBlock<ATTACH>(src, G, fs, slot, t, lane, [&](const bool bad, const bool live) {
+    if (__any(bad && live) && lane == 0) fs.bad_gen[slot] = gen;
+    if (t == 0) { fs.build_gen[slot] = gen; fs.lvl0[slot] = ATTACH ? src : fs.own_level(slot, 0); fs.tiled0[slot] = 0; }
+  });
+}
+
+// Deferred attach (dmvio_hip_set_deferred_attach, the default): what an attach of B frames leaves on the device when the coarser levels are formed later, by the tracking
+// kernel that first reads the slot (k_track_lm_build) or by k_build_pyramids_reg<true> when another reader comes first.  One thread per entry of the staged slot list: the
+// level-0 pointer, the layout flag, build_gen = bad_gen = gen ("not known clean": a reader that slipped through takes the guarded path) and pend_gen = gen + 1, the
+// generation the slot is stamped with once it is built.
+__global__ void __launch_bounds__(256) k_attach_deferred(const float* __restrict__ in_base, const size_t in_stride, const FrameStore fs, const int* __restrict__ slots, const int B,
+                                                          const unsigned int gen) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= B) return;
+  const int slot = slots[f];
+  fs.lvl0[slot] = in_base + (size_t)f * in_stride;
+  fs.tiled0[slot] = 0;
+  fs.build_gen[slot] = gen; fs.bad_gen[slot] = gen;
+  fs.pend_gen()[slot] = gen + 1u;
+}
+// the pending marks of n listed slots withdrawn (their pyramids were built by a kernel that does not know the marks, or the slots were rewritten)
+__global__ void __launch_bounds__(256) k_clear_pending(const FrameStore fs, const int* __restrict__ slots, const int n) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f < n) fs.pend_gen()[slots[f]] = 0u;
 }
 
 // level 0 of a slot out of the 8x4-tile layout into a row-major plane (consumers other than the coarse tracker's batch kernel: dmv_ensure_row_major)

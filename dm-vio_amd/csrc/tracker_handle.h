@@ -147,6 +147,7 @@ struct dmvio_hip_tracker {
   BatchPipeline pipe;
   LastRun last;
   int batch_kernel = 0;          // dmvio_hip_tracker_set_batch_kernel: 1 = full batches on k_track_lm_pp (control steps beside the evaluations)
+  int last_fused_builds = 0;     // dmvio_hip_tracker_last_fused_builds: problems of the last batch launch whose frame's pyramid the tracking kernel built itself (k_track_lm_build)
   int res_only_evals = 1;        // dmvio_hip_tracker_set_residual_only_evals: k_track_lm runs the evaluations whose 9x9 sums nothing reads as residual-only ones
   unsigned int* d_pp_next = nullptr;
   int lm_threads_override = 0, lm_cluster_override = 0;   // dmvio_hip_tracker_set_launch_shape

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "lie_dev.h"
 #include "interp.hpp"
+#include "pyr_reg_block.hpp"
 
 namespace dmv {
 
@@ -1132,6 +1133,38 @@ template <int T, int W, bool TL = false>
 __global__ void __launch_bounds__(T, W) k_track_lm(const TrackerDev trk, const FrameStore fs, const LMProblemIn* __restrict__ in,
                                                  LMProblemOut* __restrict__ out, const int coarsestLvl, const ClusterArgs cl) {
   constexpr bool TABLE = false;
+  constexpr int BUILT_CLEAN = -1;   // the slot's stamps decide (tracker_lm_body.inc)
+#include "tracker_lm_body.inc"
+}
+
+// k_track_lm<T, W, false> for one workgroup per problem, whose workgroups first form the pyramid of their problem's frame where a deferred attach left only level 0
+// (FrameStore::pend_gen, dmvio_hip_frames_attach_device_batch): the build streams through HBM beside the gathers and the arithmetic of the other workgroups of the CU,
+// where k_build_pyramids_reg ahead of the launch had the device to itself for a quarter of the step.  The launch names no waiting slot twice (checked on the host), so a
+// slot's levels are written and read by one workgroup: the barrier behind the build orders them (one CU, one vector L1).  Nothing the prologue writes is read back by
+// this kernel along a path the scalar cache can serve — neighbouring workgroups share that cache and a line holds sixteen slots' stamps —: `clean` is the prologue's own
+// verdict where it ran (BUILT_CLEAN), pend_gen[slot] is read before the barrier that precedes its reset.  A kernel of its own name and not a fourth parameter of
+// k_track_lm: that would rename every existing instantiation's symbol.
+template <int T, int W>
+__global__ void __launch_bounds__(T, W) k_track_lm_build(const TrackerDev trk, const FrameStore fs, const LMProblemIn* __restrict__ in,
+                                                       LMProblemOut* __restrict__ out, const int coarsestLvl, const ClusterArgs cl, const PyrGeom G) {
+  constexpr bool TABLE = false, TL = false;
+  int BUILT_CLEAN = -1;
+  {
+    const int bslot = __builtin_amdgcn_readfirstlane(in[blockIdx.x].new_slot);   // (launched with one workgroup per problem)
+    const unsigned int pend = (unsigned int)__builtin_amdgcn_readfirstlane((int)fs.pend_gen()[bslot]);
+    if (pend) {   // workgroup-uniform
+      const float* src = dmvUniformGlobal(fs.level(bslot, 0));
+      const int nblk = (G.w[0] >> 2) * (G.h[0] >> 3);
+      const int lane = threadIdx.x & 63;
+      bool bad = false;
+      // 4 x 8 blocks t = k * T + thread: a wave-uniform trip count, consecutive blocks on consecutive lanes (the lane pair of level 3)
+      for (int t0 = 0; t0 < nblk; t0 += T) pyrRegBlock<true>(src, G, fs, bslot, t0 + (int)threadIdx.x, lane, [&](const bool b, const bool live) { bad |= b && live; });
+      const int anyBad = __builtin_amdgcn_readfirstlane(__syncthreads_or(bad ? 1 : 0));   // every thread has read pend_gen[slot] by now
+      if (threadIdx.x == 0) { fs.build_gen[bslot] = pend; if (anyBad) fs.bad_gen[bslot] = pend; fs.pend_gen()[bslot] = 0u; }
+      BUILT_CLEAN = anyBad ? 0 : 1;
+      __syncthreads();   // the levels are read next, by every wavefront of this workgroup
+    }
+  }
 #include "tracker_lm_body.inc"
 }
 
@@ -1148,6 +1181,7 @@ __global__ void __launch_bounds__(T, W) k_track_lm_w(const TrackerDev* __restric
   __syncthreads();
   const TrackerDev& trk = s_ref;
   constexpr bool TABLE = true;
+  constexpr int BUILT_CLEAN = -1;
 #include "tracker_lm_body.inc"
 }
 

@@ -1,5 +1,6 @@
 // The device-resident LM of one alignment problem: the body of k_track_lm and of k_track_lm_w (tracker_kernels.hpp), which include this text.  In scope at the point of
-// inclusion: T, TL, TABLE (compile-time), trk (the reference: the kernel argument itself, or k_track_lm_w's copy in LDS), fs, in, out, coarsestLvl, cl.
+// inclusion: T, TL, TABLE (compile-time), BUILT_CLEAN (-1, compile-time: the slot's stamps say whether the frame is clean; 0 / 1: the verdict of the including kernel's own
+// pyramid build, k_track_lm_build), trk (the reference: the kernel argument itself, or k_track_lm_w's copy in LDS), fs, in, out, coarsestLvl, cl.
 // Included rather than called: behind a function boundary (forced inline, by reference or by value) the compiler no longer hoists the loads of the kernel-argument reference
 // the way it does inside the kernel, and every k_track_lm instantiation comes out with another schedule and register allocation (tools/isa_diff.py: all five differ by
 // 20-80 instructions).  Included, four of the five are the same instruction for instruction as before the body was shared; k_track_lm<256, 4, true> differs in two address
@@ -37,7 +38,7 @@
   initStage<T>(s_stage);
   const int slot = __builtin_amdgcn_readfirstlane(pin.new_slot);   // read from LDS, so a vector register to the compiler: what is addressed by the slot (its planes, its stamps) stays scalar
   // every pixel of the new frame finite (stamped by its pyramid build): the evaluation loop without the isfinite guards gives the same values
-  const bool clean = __builtin_amdgcn_readfirstlane((int)(fs.bad_gen[slot] != fs.build_gen[slot])) != 0;
+  const bool clean = BUILT_CLEAN >= 0 ? BUILT_CLEAN != 0 : __builtin_amdgcn_readfirstlane((int)(fs.bad_gen[slot] != fs.build_gen[slot])) != 0;
   const bool tiled0 = TL && __builtin_amdgcn_readfirstlane((int)fs.tiled0[slot]) != 0;
   long long tStep = 0, tEval = 0;
   unsigned int phase_log = 0;

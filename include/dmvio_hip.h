@@ -79,8 +79,15 @@ int dmvio_hip_frames_from_device_batch(dmvio_hip_ctx* ctx, int B, const int* slo
 /* Zero-copy form of the call above for images that stay resident: this library keeps the intensity plane only (the gradient channels of
  * dIp are rebuilt at the taps), so level 0 of FrameHessian::makeImages IS the input image — the slots reference the caller's images in
  * place and only the coarser levels are built (1.33 B written per input byte less).  The images (row-major, w floats per row) must stay
- * valid and unchanged until their slots are rebuilt or the context is destroyed. */
+ * valid and unchanged until their slots are rebuilt or the context is destroyed.  The coarser levels may be formed as late as the first use of a slot
+ * (dmvio_hip_set_deferred_attach): the images are read then, not necessarily by this call. */
 int dmvio_hip_frames_attach_device_batch(dmvio_hip_ctx* ctx, int B, const int* slots, const float* dev_base, size_t stride_bytes);
+/* When dmvio_hip_frames_attach_device_batch forms the coarser levels.  on != 0 (default): the call only records the attach (one small kernel) and the levels of a slot
+ * are built by the batched tracking kernel that first reads it (dmvio_hip_tracker_track_batch on full batches: the build then streams beside the tracking of the other
+ * frames instead of in front of it), or in front of any other reader — another tracking path, setCoarseTrackingRef, the window optimiser, a download,
+ * dmvio_hip_synchronize.  on == 0: the call launches the build itself.  Applies where the register build would run on the context's stream (dmvio_hip_set_raw_batch_kernel,
+ * no dmvio_hip_set_build_stream); everything else builds at once either way.  Same planes, same results, bit for bit.  Switching builds what still waits. */
+int dmvio_hip_set_deferred_attach(dmvio_hip_ctx* ctx, int on);
 /* Raw-image form of the batched build: B raw camera images (8- or 16-bit as the undistorter was created, wOrg x hOrg each, frame i at
  * raw_dev_base + i * stride_bytes) ALREADY IN DEVICE MEMORY -> PhotometricUndistorter::processFrame + Undistort::undistort (src/dso/util/Undistort.cpp:214-250,
  * 386-481) + FrameHessian::makeImages (src/dso/FullSystem/HessianBlocks.cpp:128-191) of slots[i], fused into one launch: a frame crosses PCIe and
@@ -300,6 +307,9 @@ int dmvio_hip_tracker_last_work(dmvio_hip_tracker* trk, long long* n_evals, long
 /* Of those counts, the share that ran as residual-only evaluations (dmvio_hip_tracker_set_residual_only_evals): dmvio_hip_tracker_last_work counts every evaluation in
  * full whichever way it ran. */
 int dmvio_hip_tracker_last_residual_only_work(dmvio_hip_tracker* trk, long long* n_evals, long long* n_point_evals);
+/* Problems of the last batch launch whose frame's pyramid the tracking kernel built itself (a slot left waiting by a deferred attach, dmvio_hip_set_deferred_attach);
+ * 0 when the launch found every slot built or had the waiting ones built in front of it.  < 0 on error. */
+int dmvio_hip_tracker_last_fused_builds(dmvio_hip_tracker* trk);
 /* In-kernel time split of the last batch launch, summed over problems, in 100 MHz wall_clock64 ticks:
  * LM control steps (solve, pose update, bookkeeping) vs evaluations (calcRes+calcGS). Diagnostics only. */
 int dmvio_hip_tracker_last_ticks(dmvio_hip_tracker* trk, long long* ticks_step, long long* ticks_eval);

@@ -8,6 +8,7 @@ w = h = 512; B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 dev = torch.device("cuda", 0)
 ctx = P.Context(w, h, n_slots=B)
 stream = torch.cuda.Stream(device=dev); ctx.set_stream(stream.cuda_stream)
+ctx.set_deferred_attach(False)   # the build kernel itself is timed: the attach launches it
 raw = torch.rand((B, h, w), device=dev) * 255
 raw8 = (torch.rand((B, h, w), device=dev) * 255).to(torch.uint8)
 slots = np.arange(B, dtype=np.int32)

@@ -24,6 +24,7 @@ for k in range(B):
     R, t = synth.se3_exp(xi)
     metas.append((R, t))
 ctx = pkg.Context(w, h, n_slots=B + 1)
+ctx.set_deferred_attach(False)   # the tracking launches are timed by themselves: the attach builds the pyramids
 stream = torch.cuda.Stream(device=dev)
 ctx.set_stream(stream.cuda_stream)
 trk = pkg.CoarseTrackerHip(ctx)
