@@ -358,7 +358,7 @@ struct BatchCall {
 
   BatchCall(dmvio_hip_ba_batch* B_, const int Wn_, dmvio_hip_ba* const* hs_, const int its, double* x_last_)
       : B(B_), Wn(Wn_), hs(hs_), mnumOptIts(its), x_last(x_last_), F(hs_[0]->H.F), n(hs_[0]->H.n()), F2(F * F), L(n, F), s(B_->stream),
-        n_gather((int)((L.outTrace() + 255) / 256)), n_stitch(F + F2), fs(B_->ctx->store()),
+        n_gather((int)((L.outTrace() + 255) / 256)), n_stitch(F + F2), fs(B_->ctx->frames.built_and_waited()),
         solveLds(sizeof(double) * baSolveLdsDoubles(n, F, F <= BA_MAXF ? BASolveDims<BA_MAXF>::ALIAS_HM : BASolveDims<BA_MAXF_CAP>::ALIAS_HM)),
         lin1(B_->lin_lanes == 1 && Wn_ >= 4), workerWait{B_->workers, false} {
     const int maxG = B->streams > 0 ? B->streams : 3;   // measured (tools/ba_batch_streams.py): three groups are best at W = 16 and 64; a fourth stream shares a hardware queue
@@ -792,7 +792,7 @@ struct MargBatchCall {
     HIPCHK(hipMemcpy2DAsync(B->dTab(0), B->slab.tabStride(), B->hTab(0), B->slab.tabStride(), tabWidth, W, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(B->d_marg, B->h_marg, inBytes, hipMemcpyHostToDevice, s));
     work[1] = 3;
-    const FrameStore fs = B->ctx->store();
+    const FrameStore fs = B->ctx->frames.built_and_waited();
     for (const Grp& g : grp) {
       int gx_lin = 0, gx_res = 0, gx_pt = 0, gx_acc = 0;
       for (int k = g.w0; k < g.w0 + g.cnt; k++) {

@@ -20,7 +20,7 @@ static LinearizeArgs linearizeArgs(dmvio_hip_ba* b, const BADecide& D) {
 static void launchLinearize(dmvio_hip_ba* b, const LinearizeArgs& A) {
   b->fullJ_applied = false;
   BA_BY_MAXF(b->H.F, M, hipLaunchKernelGGL((k_ba_linearize<M>), dim3(b->n_lin_blocks), dim3(LIN_THREADS), 0, b->stream, *A.window, b->P, b->Rs, (const BAPrecalc*)b->d_pre,
-                                           b->ctx->store(), A.fullJ, A.mask, A.decide, (int)BA_GATE_ALWAYS, A.use_backup ? 1 : 0, baNarrow<BAPreDynT<M>>(*A.dyn), A.use_dyn ? 1 : 0,
+                                           b->ctx->frames.built_and_waited(), A.fullJ, A.mask, A.decide, (int)BA_GATE_ALWAYS, A.use_backup ? 1 : 0, baNarrow<BAPreDynT<M>>(*A.dyn), A.use_dyn ? 1 : 0,
                                            baNarrow<ResubArgsT<M>>(*A.resub), A.do_resub ? 1 : 0));
 }
 // FullSystem::linearizeAll (FullSystemOptimize.cpp:150-218) — the energy sum; updates the newest frame's energy threshold (setNewFrameEnergyTH, on the device by the

@@ -150,7 +150,7 @@ static int evalFused(dmvio_hip_tracker* t, int lvl, int new_slot, const EvalP& e
   constexpr int T = 256;
   G = std::max(1, std::min(G, t->max_eval_blocks));
   const unsigned int ticket = ++t->eval_ticket;
-  hipLaunchKernelGGL(k_eval_fused<T>, dim3(G), dim3(T), 0, c->stream, t->dev, c->store_on_stream(), new_slot, e, t->d_partials, t->d_arrive, t->h_tot, ticket);
+  hipLaunchKernelGGL(k_eval_fused<T>, dim3(G), dim3(T), 0, c->stream, t->dev, c->frames.built_on_stream(), new_slot, e, t->d_partials, t->d_arrive, t->h_tot, ticket);
   HIPCHK(hipGetLastError());
   volatile unsigned int* flag = reinterpret_cast<volatile unsigned int*>(t->h_tot) + ACC_PAD;
   unsigned long long spins = 0;
@@ -175,7 +175,7 @@ static void mailTicket(dmvio_hip_tracker* t, unsigned int v) {
 }
 static int serverLaunch(dmvio_hip_tracker* t) {
   dmvio_hip_ctx* c = t->ctx;
-  hipLaunchKernelGGL(k_eval_server<256>, dim3(t->server_G), dim3(256), 0, c->stream, t->dev, c->store_on_stream(), t->server_slot, (const unsigned int*)t->h_mail, t->d_leave, t->eval_ticket,
+  hipLaunchKernelGGL(k_eval_server<256>, dim3(t->server_G), dim3(256), 0, c->stream, t->dev, c->frames.built_on_stream(), t->server_slot, (const unsigned int*)t->h_mail, t->d_leave, t->eval_ticket,
                      t->server_idle_ticks, t->h_rec, t->server_session);
   HIPCHK(hipGetLastError());
   return 0;
@@ -399,37 +399,17 @@ static int launchLocked(dmvio_hip_tracker* t) {
   // not flip a slot's layout between the choice of the instantiation and the launch that relies on it)
   const LMProblemIn* pin = pl.in(pl.staged_half);
   bool any_tiled = false;
-  for (int i = 0; i < B && !any_tiled; i++) any_tiled = c->h_tiled[pin[i].new_slot] != 0;
+  for (int i = 0; i < B && !any_tiled; i++) any_tiled = c->frames.is_tiled(pin[i].new_slot);
   const LaunchShape s = chooseLaunchShape(B, t->dev.pc_n[0], t->lm_threads_override, t->lm_cluster_override, t->batch_kernel == 1 && !t->debug_mode, any_tiled);
   if (s.refusal) return failmsg(s.refusal);
   const int C = s.C;
   ClusterArgs cl = clusterArgs(C, pl.d_discard, t->res_only_evals);
   // Slots a deferred attach left without their coarser levels (dmvio_hip_frames_attach_device_batch): full batches on the plain 256-thread kernel go to k_track_lm_build,
-  // whose workgroups build their own frame's pyramid first — unless the launch names a waiting slot twice (two workgroups would build and read the same planes).  Every
-  // other launch has them built by the ordinary kernel first, on this stream.  Slots that wait and are not named stay as they are.
-  int fused = 0;
+  // whose workgroups build their own frame's pyramid first, where the store lets the launch claim them (FrameSlots::claimWaiting_locked: the launch below is the next thing on
+  // the stream and this thread holds the context's lock until then).  Every other launch has them built by the ordinary kernel first, on this stream.
   t->last_fused_builds = 0;
-  if (c->n_pending.load(std::memory_order_acquire)) {
-    std::lock_guard<std::mutex> pk(c->pend_mu);
-    bool can = s.kernel == LM_256 && C == 1 && !t->debug_mode;
-    if (can) {
-      const unsigned int stamp = ++c->stamp_clock;
-      if (!stamp) { std::fill(c->slot_stamp.begin(), c->slot_stamp.end(), 0u); c->stamp_clock = 1; }
-      for (int i = 0; i < B && can; i++) {
-        const int sl = pin[i].new_slot;
-        if (!c->h_pending[sl]) continue;
-        if (c->slot_stamp[sl] == c->stamp_clock) can = false;
-        c->slot_stamp[sl] = c->stamp_clock;
-        fused++;
-      }
-    }
-    if (!can || !fused) { fused = 0; if (int r = dmv_flush_pending_held(c)) return r; }
-    else {
-      // the marks go now: the launch below is the next thing on the stream, and this thread holds the context's lock until then
-      for (int i = 0; i < B; i++) c->h_pending[pin[i].new_slot] = 0;
-      c->n_pending.fetch_sub(fused, std::memory_order_release);
-    }
-  }
+  const int fused = s.kernel == LM_256 && C == 1 && !t->debug_mode ? c->frames.claimWaiting_locked(B, [pin](int i) { return pin[i].new_slot; }) : c->frames.flush(false);
+  if (fused < 0) return fused;
   if (t->debug_mode) {
     // diagnostics: 1 = record the evaluations of this launch, 2 = run the recorded evaluations again without the control steps (dmvio_hip_tracker_debug_record_replay)
     if (C != 1 || s.T != 256) return failmsg("tracker record / replay: full batches only (one 256-thread workgroup per problem)");
@@ -442,7 +422,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
     if (t->debug_mode == 1) { cl.log = t->d_log; cl.log_n = t->d_log_n; t->log_B = B; }
     else {
       if (t->log_B != B) return failmsg("tracker replay: record a launch of the same batch first");
-      hipLaunchKernelGGL((k_track_replay<256, 4>), dim3(B), dim3(256), 0, c->stream, t->dev, c->store_deferred(), pin, (const EvalP*)t->d_log, (const int*)t->d_log_n, t->d_log_sink);
+      hipLaunchKernelGGL((k_track_replay<256, 4>), dim3(B), dim3(256), 0, c->stream, t->dev, c->frames.as_is(), pin, (const EvalP*)t->d_log, (const int*)t->d_log_n, t->d_log_sink);
       HIPCHK(hipGetLastError());
       return 0;   // nothing to fetch: the caller times the launch and synchronises the stream itself
     }
@@ -458,7 +438,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
   if (s.untile)
     for (int i = 0; i < B; i++) if (int r = dmv_ensure_row_major_locked(c, pin[i].new_slot)) return r;
   LMProblemOut* pout = pl.out(pl.staged_half);
-  auto lm = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B * C), dim3(s.T), 0, c->stream, t->dev, c->store_deferred(), pin, pout, pl.staged_coarsest, cl); };
+  auto lm = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B * C), dim3(s.T), 0, c->stream, t->dev, c->frames.as_is(), pin, pout, pl.staged_coarsest, cl); };
   switch (s.kernel) {
     case LM_256_TILED: lm(k_track_lm<256, 4, true>); break;
     case LM_512_TILED: lm(k_track_lm<512, 4, true>); break;
@@ -466,7 +446,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
     case LM_512: lm(k_track_lm<512, 4, false>); break;
     case LM_256:
       if (fused) {
-        hipLaunchKernelGGL((k_track_lm_build<256, 4>), dim3(B), dim3(256), 0, c->stream, t->dev, c->store_deferred(), pin, pout, pl.staged_coarsest, cl, c->pg);
+        hipLaunchKernelGGL((k_track_lm_build<256, 4>), dim3(B), dim3(256), 0, c->stream, t->dev, c->frames.as_is(), pin, pout, pl.staged_coarsest, cl, c->pg);
         t->last_fused_builds = fused;
       } else lm(k_track_lm<256, 4, false>);
       break;
@@ -474,7 +454,7 @@ static int launchLocked(dmvio_hip_tracker* t) {
       if (!t->d_pp_next) HIPCHK(hipMalloc((void**)&t->d_pp_next, sizeof(unsigned int)));
       HIPCHK(hipMemsetAsync(t->d_pp_next, 0, sizeof(unsigned int), c->stream));
       const int grid = std::min((B + 1) / 2, (int)LM_RESIDENT_WORKGROUPS);   // persistent: no more workgroups than are resident at 128 registers
-      hipLaunchKernelGGL(k_track_lm_pp, dim3(grid), dim3(256), 0, c->stream, t->dev, c->store_deferred(), pin, pout, pl.staged_coarsest, B, t->d_pp_next);
+      hipLaunchKernelGGL(k_track_lm_pp, dim3(grid), dim3(256), 0, c->stream, t->dev, c->frames.as_is(), pin, pout, pl.staged_coarsest, B, t->d_pp_next);
       break;
     }
     case LM_NONE: break;   // refused above
@@ -1132,7 +1112,7 @@ int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tra
     if (window_of[i] < 0 || window_of[i] >= W) return failmsg("track_multi: window_of entry out of range");
     if (new_slots[i] < 0 || new_slots[i] >= c->n_slots) return failmsg("track_multi: frame slot out of range");
     pc0 = std::max(pc0, trackers[window_of[i]]->dev.pc_n[0]);
-    any_tiled = any_tiled || c->h_tiled[new_slots[i]] != 0;
+    any_tiled = any_tiled || c->frames.is_tiled(new_slots[i]);
   }
   if (B == 0) return 0;
   const int C = m->lm_cluster > 0 ? m->lm_cluster : clusterSize(B, pc0);
@@ -1161,7 +1141,7 @@ int dmvio_hip_tracker_track_multi(dmvio_hip_track_multi* m, int W, dmvio_hip_tra
   const int* d_ref_of = reinterpret_cast<const int*>(m->d_table + sizeof(TrackerDev) * (size_t)W);
   LMProblemOut* pout = pl.out(half);
   pl.unlaunched = false;
-  auto lm = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B * C), dim3(256), 0, c->stream, d_refs, d_ref_of, c->store_on_stream(), (const LMProblemIn*)in, pout, coarsestLvl, cl); };
+  auto lm = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B * C), dim3(256), 0, c->stream, d_refs, d_ref_of, c->frames.built_on_stream(), (const LMProblemIn*)in, pout, coarsestLvl, cl); };
   if (any_tiled) lm(k_track_lm_w<256, 4, true>); else lm(k_track_lm_w<256, 4, false>);
   HIPCHK(hipGetLastError());
   m->last_cluster = C; m->last_threads = 256;

@@ -17,6 +17,7 @@
 
 using namespace dmv;
 
+#define DMV_FRAME_STORE_IMPL   // this unit compiles the frame store's function bodies (frame_store_host.hpp): they launch kernels of image_kernels.hpp
 #include "internal.h"
 
 std::string& dmv_err() { static thread_local std::string e; return e; }
@@ -50,32 +51,11 @@ static void setPyramidTile(dmvio_hip_ctx* c, int tw_log2) {
 static int ctxInit(dmvio_hip_ctx* c) {
   const int w = c->w, h = c->h, n_frame_slots = c->n_slots;
   c->levels = pyrLevels(w, h);
-  size_t off = 0;
-  for (int l = 0; l < c->levels; l++) {
-    c->wl[l] = w >> l; c->hl[l] = h >> l;
-    c->fs_.level_off[l] = off;
-    off += (size_t)c->wl[l] * c->hl[l];
-  }
-  c->fs_.levels = c->levels;
-  c->fs_.slot_stride = (off + 63) & ~(size_t)63;
-  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(hipMalloc((void**)&c->fs_.base, sizeof(float) * c->fs_.slot_stride * n_frame_slots));
-  HIPCHK(hipMemsetAsync(c->fs_.base, 0, sizeof(float) * c->fs_.slot_stride * n_frame_slots, c->stream));
-  HIPCHK(hipMalloc((void**)&c->fs_.build_gen, sizeof(unsigned int) * 3 * n_frame_slots));   // build_gen | bad_gen: equal (0) = not known to be clean | pend_gen: 0 = built
-  HIPCHK(hipMemsetAsync(c->fs_.build_gen, 0, sizeof(unsigned int) * 3 * n_frame_slots, c->stream));
-  c->fs_.bad_gen = c->fs_.build_gen + n_frame_slots;
-  c->h_pending.assign(n_frame_slots, 0);
-  c->slot_stamp.assign(n_frame_slots, 0u);
-  HIPCHK(hipMalloc((void**)&c->fs_.lvl0, sizeof(const float*) * n_frame_slots));
-  c->h_lvl0.resize(n_frame_slots);
-  for (int s = 0; s < n_frame_slots; s++) c->h_lvl0[s] = c->fs_.own_level(s, 0);
-  HIPCHK(hipMemcpyAsync(c->fs_.lvl0, c->h_lvl0.data(), sizeof(const float*) * n_frame_slots, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMalloc((void**)&c->fs_.tiled0, n_frame_slots));
-  HIPCHK(hipMemsetAsync(c->fs_.tiled0, 0, n_frame_slots, c->stream));
-  c->h_tiled.assign(n_frame_slots, 0);
-  HIPCHK(hipMalloc((void**)&c->d_upload, sizeof(float) * w * h));
   c->pg.levels = c->levels;
-  for (int l = 0; l < c->levels; l++) { c->pg.w[l] = c->wl[l]; c->pg.h[l] = c->hl[l]; }
+  for (int l = 0; l < c->levels; l++) { c->pg.w[l] = c->wl[l] = w >> l; c->pg.h[l] = c->hl[l] = h >> l; }
+  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  if (int r = c->frames.init(c->device, n_frame_slots)) return r;
+  HIPCHK(hipMalloc((void**)&c->d_upload, sizeof(float) * w * h));
   // tile shape of the pyramid build: as wide as the image (contiguous level-0 memory per workgroup), at least 2^(levels-1) rows for the 2x2 reductions
   int twl = 9;
   while (twl > 7 && ((1 << (twl - 1)) >= w || (PYR_TILE_PX >> twl) < (1 << (c->levels - 1)))) twl--;
@@ -110,16 +90,11 @@ int dmvio_hip_set_pyramid_tile_log2(dmvio_hip_ctx* c, int tw_log2) {
 void dmvio_hip_destroy(dmvio_hip_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
-  // (slots that still wait for a deferred build are not built: nothing can read them any more, and their images need not outlive the context)
   if (c->stream) hipStreamSynchronize(c->stream);   // (null only in a handle whose creation failed)
-  hipFree(c->fs_.base);
-  hipFree(c->fs_.build_gen);
-  hipFree(c->fs_.lvl0);
-  hipFree(c->fs_.tiled0);
+  c->frames.release();
   hipFree(c->d_upload);
   c->bounce.release();
   hipFree(c->d_f3);
-  for (auto& L : c->slot_lists) { if (L.d) hipFree(L.d); if (L.h) hipHostFree(L.h); }
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -130,7 +105,7 @@ int dmvio_hip_set_stream(dmvio_hip_ctx* c, void* s) {
   if (!c) return failmsg("null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  if (int r = dmv_flush_pending(c, 0)) return r;   // a deferred attach is finished on the stream it was made on
+  if (int r = c->frames.flush(false)) return r;   // a deferred attach is finished on the stream it was made on
   HIPCHK(hipStreamSynchronize(c->stream));
   if (s) {
     if (c->own_stream) { HIPCHK(hipStreamDestroy(c->stream)); }
@@ -141,7 +116,6 @@ int dmvio_hip_set_stream(dmvio_hip_ctx* c, void* s) {
   return 0;
 }
 
-static hipStream_t buildStream(const dmvio_hip_ctx* c) { return c->build_stream ? c->build_stream : c->stream; }
 // The stream the BATCHED pyramid builds (dmvio_hip_frames_from_device_batch / _attach_device_batch / _from_raw_device_batch) are enqueued on; NULL (default): the context's
 // stream.  With a stream of its own the build of batch k+1 overlaps the tracking of batch k — the build is bound by HBM, k_track_lm by its L1 miss path and VALU issue.  The
 // CALLER orders the two streams (events): a build must not start before the consumers of the slots it rewrites have finished, a consumer not before the build of its slots.
@@ -149,18 +123,18 @@ int dmvio_hip_set_build_stream(dmvio_hip_ctx* c, void* s) {
   if (!c) return failmsg("null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  if (int r = dmv_flush_pending(c, 0)) return r;   // with a build stream nothing is deferred: what waits is built now, on the context's stream
-  HIPCHK(hipStreamSynchronize(buildStream(c)));
-  c->build_stream = (hipStream_t)s;
+  if (int r = c->frames.flush(false)) return r;   // with a build stream nothing is deferred: what waits is built now, on the context's stream
+  HIPCHK(hipStreamSynchronize(c->frames.buildStream()));
+  c->frames.build_stream = (hipStream_t)s;
   return 0;
 }
 
 int dmvio_hip_synchronize(dmvio_hip_ctx* c) {
   if (!c) return failmsg("null ctx");
   HIPCHK(hipSetDevice(c->device));
-  if (int r = dmv_flush_pending(c, 0)) return r;   // after a synchronize every slot is built: the caller may read the store from any stream
+  if (int r = c->frames.flush(false)) return r;   // after a synchronize every slot is built: the caller may read the store from any stream
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->build_stream) HIPCHK(hipStreamSynchronize(c->build_stream));
+  if (c->frames.build_stream) HIPCHK(hipStreamSynchronize(c->frames.build_stream));
   return 0;
 }
 
@@ -168,66 +142,24 @@ int dmvio_hip_synchronize(dmvio_hip_ctx* c) {
 // the wave-autonomous builds (a 4 x 8 pixel block per thread, levels in registers: image_kernels.hpp) take pyramids of at most four levels on images whose sides are
 // multiples of 8; everything else (and dmvio_hip_set_raw_batch_kernel(ctx, 0)) goes to the LDS-tile builds
 static bool regBuild(const dmvio_hip_ctx* c) { return c->raw_batch_kernel && c->levels <= 4 && (c->w % 8) == 0 && (c->h % 8) == 0; }
-static dim3 regGrid(const dmvio_hip_ctx* c, int B) { return dim3(((c->w / 4) * (c->h / 8) + 255) / 256, B); }
-
-// ---- deferred attach: see dmvio_hip_ctx (internal.h) and DESIGN.md section 4.  *Held: the caller holds c->pend_mu.
-// The ordinary build of the slots that still wait, from the recorded source: one launch per run of consecutive entries of the staged list (the kernel finds frame f of its
-// launch at base + f * stride and its slot at slots[f], so a run is the same launch shifted), stamped with the generation the attach set aside for it, then their marks cleared.
-static int flushPendingHeld(dmvio_hip_ctx* c, bool wait) {
-  if (!c->n_pending.load(std::memory_order_relaxed)) return 0;
-  HIPCHK(hipSetDevice(c->device));
-  const dmvio_hip_ctx::PendingAttach& P = c->pend;
-  for (int i = 0; i < P.B;) {
-    if (c->h_pending[P.slots[i]] != i + 1) { i++; continue; }
-    int j = i;
-    while (j < P.B && c->h_pending[P.slots[j]] == j + 1) { c->h_pending[P.slots[j]] = 0; j++; }
-    hipLaunchKernelGGL((k_build_pyramids_reg<true>), regGrid(c, j - i), dim3(256), 0, c->stream, P.base + (size_t)i * P.stride, P.stride, c->pg, c->fs_, P.d_slots + i, 0, P.flush_gen);
-    hipLaunchKernelGGL(k_clear_pending, dim3((j - i + 255) / 256), dim3(256), 0, c->stream, c->fs_, P.d_slots + i, j - i);
-    i = j;
-  }
-  c->n_pending.store(0, std::memory_order_release);
-  HIPCHK(hipGetLastError());
-  if (wait) HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-int dmv_flush_pending_held(dmvio_hip_ctx* c) { return flushPendingHeld(c, false); }
-int dmv_flush_pending(dmvio_hip_ctx* c, int wait) {
-  std::lock_guard<std::mutex> pl(c->pend_mu);
-  return flushPendingHeld(c, wait != 0);
-}
-// the host marks of slots another build is about to rewrite (the device marks follow: a memset for one slot, k_clear_pending for a staged list); returns how many waited
-static int dropPendingHeld(dmvio_hip_ctx* c, int B, const int* slots) {
-  if (!c->n_pending.load(std::memory_order_relaxed)) return 0;
-  int n = 0;
-  for (int i = 0; i < B; i++) if (c->h_pending[slots[i]]) { c->h_pending[slots[i]] = 0; n++; }
-  c->n_pending.fetch_sub(n, std::memory_order_release);
-  return n;
-}
 static int buildPyramid(dmvio_hip_ctx* c, int slot, const float* d_color) {
-  {
-    std::lock_guard<std::mutex> pl(c->pend_mu);
-    if (dropPendingHeld(c, 1, &slot)) HIPCHK(hipMemsetAsync(c->fs_.pend_gen() + slot, 0, sizeof(unsigned int), c->stream));
-  }
-  hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, 1), dim3(256), 0, c->stream, d_color, (size_t)0, c->pg, c->fs_,
-                     (const int*)nullptr, slot, ++c->build_gen, 0);
-  c->h_lvl0[slot] = c->fs_.own_level(slot, 0); c->h_tiled[slot] = 0;
+  unsigned int gen;
+  if (int r = c->frames.begin_locked(1, &slot, nullptr, &gen)) return r;
+  hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, 1), dim3(256), 0, c->stream, d_color, (size_t)0, c->pg, c->frames.as_is(), (const int*)nullptr, slot, gen, 0);
+  c->frames.commit_locked(1, &slot, nullptr, 0, false);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 // see internal.h
 int dmv_ensure_row_major_locked(dmvio_hip_ctx* c, int slot) {
-  if (slot < 0 || slot >= c->n_slots || !c->h_tiled[slot]) return 0;
+  if (slot < 0 || slot >= c->n_slots || !c->frames.is_tiled(slot)) return 0;
   HIPCHK(hipSetDevice(c->device));
-  const int n = c->w * c->h;
-  float* own = c->fs_.own_level(slot, 0);
+  const int n = c->w * c->h; float* own = c->frames.as_is().own_level(slot, 0);
   hipLaunchKernelGGL(k_untile_level0, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float*)own, c->w, c->h, c->d_upload);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(own, c->d_upload, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->fs_.tiled0 + slot, 0, 1, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));   // consumers on other streams (a window optimiser's) read the plane next
-  c->h_tiled[slot] = 0;
-  return 0;
+  return c->frames.untiled_locked(slot);
 }
 int dmv_ensure_row_major(dmvio_hip_ctx* c, int slot) {
   if (!c) return failmsg("null ctx");
@@ -240,7 +172,7 @@ int dmv_ensure_row_major(dmvio_hip_ctx* c, int slot) {
 int dmvio_hip_set_raw_batch_layout(dmvio_hip_ctx* c, int tiled) {
   if (!c) return failmsg("null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
-  c->raw_batch_tiled = tiled ? 1 : 0;
+  c->raw_batch_layout = tiled ? 1 : 0;
   return 0;
 }
 // Which kernels build the pyramids of the raw-image batch and of frames attached in place: 1 (default) = the wave-autonomous register builds where the geometry allows it
@@ -258,14 +190,14 @@ int dmvio_hip_set_raw_batch_kernel(dmvio_hip_ctx* c, int variant) {
 int dmvio_hip_set_deferred_attach(dmvio_hip_ctx* c, int on) {
   if (!c) return failmsg("null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
-  if (int r = dmv_flush_pending(c, 0)) return r;
-  c->deferred_attach = on ? 1 : 0;
+  if (int r = c->frames.flush(false)) return r;
+  c->frames.deferred_attach = on ? 1 : 0;
   return 0;
 }
 int dmvio_hip_frame_level0_is_tiled(dmvio_hip_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= c->n_slots) return failmsg("frame_level0_is_tiled: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
-  return c->h_tiled[slot] ? 1 : 0;
+  return c->frames.is_tiled(slot) ? 1 : 0;
 }
 
 int dmvio_hip_frame_upload(dmvio_hip_ctx* c, int slot, const float* host) {
@@ -361,71 +293,23 @@ int dmvio_hip_frame_from_device(dmvio_hip_ctx* c, int slot, const float* dev) {
   return buildPyramid(c, slot, dev);  // asynchronous on the ctx stream
 }
 
-// slot list of a batched build -> device (kept while the same list comes again); caller holds c->mu and c->pend_mu
-static int stageSlots(dmvio_hip_ctx* c, int B, const int* slots) {
-  for (int i = 0; i < B; i++) if (slots[i] < 0 || slots[i] >= c->n_slots) return failmsg("frame batch: slot out of range");
-  dmvio_hip_ctx::SlotList* hit = nullptr;
-  dmvio_hip_ctx::SlotList* lru = &c->slot_lists[0];
-  for (auto& L : c->slot_lists) {
-    if (L.n == B && L.h && !memcmp(L.h, slots, sizeof(int) * B)) { hit = &L; break; }
-    if (L.used < lru->used) lru = &L;
-  }
-  if (!hit) {
-    hit = lru;
-    if (hit->d && hit->d == c->pend.d_slots) { if (int r = flushPendingHeld(c, false)) return r; }   // slots that still wait are listed in the entry about to be rewritten
-    // the pinned copy may still be the source of an in-flight upload, the device copy the argument of a running build: drain before rewriting
-    HIPCHK(hipStreamSynchronize(buildStream(c)));
-    if (c->build_stream) HIPCHK(hipStreamSynchronize(c->stream));
-    if (B > hit->cap) {
-      if (hit->d) { HIPCHK(hipFree(hit->d)); HIPCHK(hipHostFree(hit->h)); hit->d = nullptr; hit->h = nullptr; }
-      hit->cap = std::max(B, 64);
-      HIPCHK(hipMalloc((void**)&hit->d, sizeof(int) * hit->cap));
-      HIPCHK(hipHostMalloc((void**)&hit->h, sizeof(int) * hit->cap, hipHostMallocDefault));
-    }
-    memcpy(hit->h, slots, sizeof(int) * B);
-    hit->n = B;
-    HIPCHK(hipMemcpyAsync(hit->d, hit->h, sizeof(int) * B, hipMemcpyHostToDevice, buildStream(c)));
-  }
-  hit->used = ++c->slot_clock;
-  c->d_slots = hit->d;
-  return 0;
-}
-
 static int framesFromDeviceBatch(dmvio_hip_ctx* c, int B, const int* slots, const float* dev_base, size_t stride_bytes, const bool attach) {
   if (!c || !slots || !dev_base) return failmsg("frames_from_device_batch: null argument");
   if (B <= 0 || stride_bytes % sizeof(float)) return failmsg("frames_from_device_batch: bad B / stride");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < B; i++) if (slots[i] < 0 || slots[i] >= c->n_slots) return failmsg("frame batch: slot out of range");
-  std::lock_guard<std::mutex> pl(c->pend_mu);
-  // slots of this call that still wait for a deferred build are superseded: their old image is never read
-  const int dropped = dropPendingHeld(c, B, slots);
-  if (int r = stageSlots(c, B, slots)) return r;
-  if (attach && regBuild(c) && !c->build_stream && c->deferred_attach) {
-    // deferred: only the table kernel now; the levels 1.. are formed by the tracking kernel that first reads a slot, or by a flush.  One deferred attach is kept: what an
-    // older one left is built first.  Three generations: "not known clean" until built, the stamp of a build inside the tracking kernel, the stamp of a flush.
-    if (int r = flushPendingHeld(c, false)) return r;
-    const unsigned int gen = c->build_gen + 1u;
-    c->build_gen += 3u;
-    hipLaunchKernelGGL(k_attach_deferred, dim3((B + 255) / 256), dim3(256), 0, c->stream, dev_base, stride_bytes / sizeof(float), c->fs_, (const int*)c->d_slots, B, gen);
-    dmvio_hip_ctx::PendingAttach& P = c->pend;
-    P.base = dev_base; P.stride = stride_bytes / sizeof(float); P.d_slots = c->d_slots; P.B = B; P.flush_gen = gen + 2u;
-    P.slots.assign(slots, slots + B);
-    int n = 0;
-    for (int i = 0; i < B; i++) { if (!c->h_pending[slots[i]]) n++; c->h_pending[slots[i]] = i + 1; }
-    c->n_pending.store(n, std::memory_order_release);
-    for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = dev_base + (size_t)i * P.stride; c->h_tiled[slots[i]] = 0; }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (dropped) hipLaunchKernelGGL(k_clear_pending, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->fs_, (const int*)c->d_slots, B);
+  FrameSlots& F = c->frames;
+  const size_t stride = stride_bytes / sizeof(float);
+  // deferred: where the register build would run on the context's stream, and the switch is on
+  if (attach && regBuild(c) && !F.build_stream && F.deferred_attach) return F.defer_locked(B, slots, dev_base, stride);
+  const int* d_slots; unsigned int gen;
+  if (int r = F.begin_locked(B, slots, &d_slots, &gen)) return r;
   // attached in place: the register build (read-dominated: 5 % ahead); level 0 copied: the LDS-tile build (4 % ahead there) — both measured, tools/time_pyramids.py
   if (regBuild(c) && attach)
-    hipLaunchKernelGGL((k_build_pyramids_reg<true>), regGrid(c, B), dim3(256), 0, buildStream(c), dev_base, stride_bytes / sizeof(float), c->pg, c->fs_, (const int*)c->d_slots, 0, ++c->build_gen);
+    hipLaunchKernelGGL((k_build_pyramids_reg<true>), F.regGrid(B), dim3(256), 0, F.buildStream(), dev_base, stride, c->pg, F.as_is(), d_slots, 0, gen);
   else
-    hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, B), dim3(256), 0, buildStream(c), dev_base, stride_bytes / sizeof(float),
-                       c->pg, c->fs_, (const int*)c->d_slots, 0, ++c->build_gen, attach ? 1 : 0);
-  for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = attach ? dev_base + (size_t)i * (stride_bytes / sizeof(float)) : c->fs_.own_level(slots[i], 0); c->h_tiled[slots[i]] = 0; }
+    hipLaunchKernelGGL(k_build_pyramids, dim3(c->pg.tiles_x * c->pg.tiles_y, B), dim3(256), 0, F.buildStream(), dev_base, stride, c->pg, F.as_is(), d_slots, 0, gen, attach ? 1 : 0);
+  F.commit_locked(B, slots, attach ? dev_base : nullptr, stride, false);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -433,8 +317,8 @@ static int framesFromDeviceBatch(dmvio_hip_ctx* c, int B, const int* slots, cons
 }  // extern "C"
 // the eight instantiations of the raw-image builds: pixel type (the caller), then register / LDS-tile build x tiled / row-major level 0
 template <typename T>
-static void launchRawBuild(dmvio_hip_ctx* c, bool reg, bool tiled, dim3 grid, const void* raw, size_t stride, const UndistortDev& U) {
-  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, buildStream(c), (const T*)raw, stride, U, c->pg, c->fs_, (const int*)c->d_slots, ++c->build_gen); };
+static void launchRawBuild(dmvio_hip_ctx* c, bool reg, bool tiled, dim3 grid, const void* raw, size_t stride, const UndistortDev& U, const int* d_slots, unsigned int gen) {
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->frames.buildStream(), (const T*)raw, stride, U, c->pg, c->frames.as_is(), d_slots, gen); };
   if (reg) { if (tiled) go(k_build_pyramids_raw_reg<T, true>); else go(k_build_pyramids_raw_reg<T, false>); }
   else { if (tiled) go(k_build_pyramids_raw<T, true>); else go(k_build_pyramids_raw<T, false>); }
 }
@@ -449,21 +333,18 @@ int dmvio_hip_frames_from_raw_device_batch(dmvio_hip_ctx* c, dmvio_hip_undistort
     return failmsg("frames_from_raw_device_batch: bad B / stride / alignment");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < B; i++) if (slots[i] < 0 || slots[i] >= c->n_slots) return failmsg("frame batch: slot out of range");
-  std::lock_guard<std::mutex> pl(c->pend_mu);
-  const int dropped = dropPendingHeld(c, B, slots);   // rewritten here: a deferred build of these slots is void
-  if (int r = stageSlots(c, B, slots)) return r;
-  if (dropped) hipLaunchKernelGGL(k_clear_pending, dim3((B + 255) / 256), dim3(256), 0, c->stream, c->fs_, (const int*)c->d_slots, B);
+  const int* d_slots; unsigned int gen;
+  if (int r = c->frames.begin_locked(B, slots, &d_slots, &gen)) return r;
   UndistortDev U = u->U;
   U.factor = factor;
   // level 0 in 8x4 tiles on request (dmvio_hip_set_raw_batch_layout)
-  const bool tiled = c->raw_batch_tiled && (c->w % 8) == 0 && (c->h % 4) == 0;
+  const bool tiled = c->raw_batch_layout && (c->w % 8) == 0 && (c->h % 4) == 0;
   // the wave-autonomous build (a 4 x 8 pixel block per thread, levels in registers) where the pyramid allows it, the LDS-tile build otherwise
   const bool reg = regBuild(c);
-  const dim3 grid = reg ? regGrid(c, B) : dim3(c->pg.tiles_x * c->pg.tiles_y, B);
-  if (u->bytes_per_px == 1) launchRawBuild<unsigned char>(c, reg, tiled, grid, raw_dev_base, stride_bytes, U);
-  else launchRawBuild<unsigned short>(c, reg, tiled, grid, raw_dev_base, stride_bytes / 2, U);
-  for (int i = 0; i < B; i++) { c->h_lvl0[slots[i]] = c->fs_.own_level(slots[i], 0); c->h_tiled[slots[i]] = tiled ? 1 : 0; }
+  const dim3 grid = reg ? c->frames.regGrid(B) : dim3(c->pg.tiles_x * c->pg.tiles_y, B);
+  if (u->bytes_per_px == 1) launchRawBuild<unsigned char>(c, reg, tiled, grid, raw_dev_base, stride_bytes, U, d_slots, gen);
+  else launchRawBuild<unsigned short>(c, reg, tiled, grid, raw_dev_base, stride_bytes / 2, U, d_slots, gen);
+  c->frames.commit_locked(B, slots, nullptr, 0, tiled);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -482,8 +363,8 @@ int dmvio_hip_frame_mark_unclean(dmvio_hip_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= c->n_slots) return failmsg("frame_mark_unclean: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  if (int r = dmv_flush_pending(c, 0)) return r;
-  HIPCHK(hipMemcpyAsync(c->fs_.bad_gen + slot, c->fs_.build_gen + slot, sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+  if (int r = c->frames.flush(false)) return r;
+  HIPCHK(hipMemcpyAsync(c->frames.as_is().bad_gen + slot, c->frames.as_is().build_gen + slot, sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -492,10 +373,10 @@ int dmvio_hip_frame_is_clean(dmvio_hip_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= c->n_slots) return failmsg("frame_is_clean: bad argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(hipSetDevice(c->device));
-  if (int r = dmv_flush_pending(c, 0)) return r;   // the verdict of a slot that still waits is formed with its levels
+  if (int r = c->frames.flush(false)) return r;   // the verdict of a slot that still waits is formed with its levels
   unsigned int g[2] = {0, 0};
-  HIPCHK(c->bounce.d2h(&g[0], c->fs_.build_gen + slot, sizeof(unsigned int), c->stream));
-  HIPCHK(c->bounce.d2h(&g[1], c->fs_.bad_gen + slot, sizeof(unsigned int), c->stream));
+  HIPCHK(c->bounce.d2h(&g[0], c->frames.as_is().build_gen + slot, sizeof(unsigned int), c->stream));
+  HIPCHK(c->bounce.d2h(&g[1], c->frames.as_is().bad_gen + slot, sizeof(unsigned int), c->stream));
   HIPCHK(c->bounce.finish(c->stream));
   return g[0] != g[1] ? 1 : 0;
 }
@@ -507,7 +388,7 @@ int dmvio_hip_frame_download(dmvio_hip_ctx* c, int slot, int lvl, float* out) {
   HIPCHK(hipSetDevice(c->device));
   const int n = c->wl[lvl] * c->hl[lvl];
   if (lvl == 0) { if (int r = dmv_ensure_row_major_locked(c, slot)) return r; }
-  hipLaunchKernelGGL(k_level_to_f3, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->levelPtr(slot, lvl), c->wl[lvl], c->hl[lvl], c->d_f3);
+  hipLaunchKernelGGL(k_level_to_f3, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->frames.levelPtr(slot, lvl), c->wl[lvl], c->hl[lvl], c->d_f3);
   HIPCHK(hipGetLastError());
   HIPCHK(c->bounce.d2h(out, c->d_f3, sizeof(float) * 3 * n, c->stream));
   HIPCHK(c->bounce.finish(c->stream));
@@ -532,7 +413,7 @@ int dmvio_hip_frame_abs_squared_grad(dmvio_hip_ctx* c, int slot, int n_levels, c
   size_t off = 0;
   for (int l = 0; l < n_levels; l++) {
     const int n = c->wl[l] * c->hl[l];
-    hipLaunchKernelGGL(k_abs_squared_grad, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->levelPtr(slot, l), c->wl[l], c->hl[l], (const float*)d_lut, d_out + off);
+    hipLaunchKernelGGL(k_abs_squared_grad, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->frames.levelPtr(slot, l), c->wl[l], c->hl[l], (const float*)d_lut, d_out + off);
     if (out_host[l]) HIPCHK(c->bounce.d2h(out_host[l], d_out + off, sizeof(float) * n, c->stream));
     off += n;
   }

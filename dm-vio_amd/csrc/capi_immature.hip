@@ -63,7 +63,7 @@ static int traceBatchLocked(dmvio_hip_trace_batch* b, int W, const dmvio_hip_tra
     off += traceTableBytes(V.n_hosts);
     m->P.n = m->n;
     TraceWin r{};
-    r.I = c->levelPtr(V.new_slot, 0); r.P = m->P; r.S = m->S;
+    r.I = c->frames.levelPtr(V.new_slot, 0); r.P = m->P; r.S = m->S;
     r.KRKi = dt; r.Kt = dt + 9 * nh; r.aff = dt + 12 * nh;
     r.w = c->w; r.h = c->h;
     memcpy(H + sizeof(TraceWin) * (size_t)k, &r, sizeof(r));
@@ -143,7 +143,7 @@ int dmvio_hip_immature_add_points(dmvio_hip_immature* m, int host_tag, int host_
     HIPCHK(hipMemcpyAsync(m->P.v + first, vf, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
   }
   m->P.n = first + n;
-  hipLaunchKernelGGL(k_immature_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->levelPtr(host_slot, 0), c->w, first, n, m->P, host_tag, m->S);
+  hipLaunchKernelGGL(k_immature_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->frames.levelPtr(host_slot, 0), c->w, first, n, m->P, host_tag, m->S);
   HIPCHK(hipGetLastError());
   m->n = first + n;
   m->max_tag = std::max(m->max_tag, host_tag);
@@ -169,7 +169,7 @@ int dmvio_hip_immature_add_selected(dmvio_hip_immature* m, int host_tag, int hos
   HIPCHK(hipMemcpyAsync(m->P.u + first, d_u, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(m->P.v + first, d_v, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   m->P.n = first + n;
-  hipLaunchKernelGGL(k_immature_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->levelPtr(host_slot, 0), c->w, first, n, m->P, host_tag, m->S);
+  hipLaunchKernelGGL(k_immature_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->frames.levelPtr(host_slot, 0), c->w, first, n, m->P, host_tag, m->S);
   hipLaunchKernelGGL(k_immature_types_from_map, dim3((n + 255) / 256), dim3(256), 0, c->stream, dmv_selector_map(sel), c->w, first, n, m->P);
   HIPCHK(hipGetLastError());
   m->n = first + n;
@@ -215,7 +215,7 @@ int dmvio_hip_immature_add_selected_batch(dmvio_hip_pixel_selector_batch* batch,
     for (int k = 0; k < W; k++) {
       const dmvio_hip_new_traces_window& V = win[k];
       NewTracesWin r{};
-      r.I = c->levelPtr(V.host_slot, 0); r.wu = du[k]; r.wv = dv[k]; r.map = dmv_selector_map(V.sel);
+      r.I = c->frames.levelPtr(V.host_slot, 0); r.wu = du[k]; r.wv = dv[k]; r.map = dmv_selector_map(V.sel);
       r.P = V.imm->P; r.P.n = V.imm->n + nn[k];
       r.S = V.imm->S;
       r.w = c->w; r.first = V.imm->n; r.n = nn[k]; r.host_tag = V.host_tag;
@@ -296,7 +296,7 @@ int dmvio_hip_immature_trace(dmvio_hip_immature* m, int new_slot, int n_hosts, c
     memcpy(T.KRKi, KRKi9, sizeof(float) * 9 * n_hosts);
     memcpy(T.Kt, Kt3, sizeof(float) * 3 * n_hosts);
     memcpy(T.aff, aff2, sizeof(float) * 2 * n_hosts);
-    hipLaunchKernelGGL(k_immature_trace<TraceTablesArg>, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->levelPtr(new_slot, 0), c->w, c->h, m->P, T, m->S);
+    hipLaunchKernelGGL(k_immature_trace<TraceTablesArg>, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->frames.levelPtr(new_slot, 0), c->w, c->h, m->P, T, m->S);
   } else {
     HIPCHK(hipStreamSynchronize(c->stream));   // the pinned tables of a previous call may still be in flight
     float* t = m->h_tables;
@@ -306,7 +306,7 @@ int dmvio_hip_immature_trace(dmvio_hip_immature* m, int new_slot, int n_hosts, c
     HIPCHK(hipMemcpyAsync(m->d_tables, t, sizeof(float) * 14 * IMM_MAX_HOSTS, hipMemcpyHostToDevice, c->stream));
     TraceTables T;
     T.KRKi = m->d_tables; T.Kt = m->d_tables + 9 * IMM_MAX_HOSTS; T.aff = m->d_tables + 12 * IMM_MAX_HOSTS;
-    hipLaunchKernelGGL(k_immature_trace<TraceTables>, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->levelPtr(new_slot, 0), c->w, c->h, m->P, T, m->S);
+    hipLaunchKernelGGL(k_immature_trace<TraceTables>, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->frames.levelPtr(new_slot, 0), c->w, c->h, m->P, T, m->S);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -469,7 +469,7 @@ int dmv_immature_optimize_launch_locked(dmvio_hip_immature* m, int F, const int*
   T.fxl = (float)fxfycxcy[0]; T.fyl = (float)fxfycxcy[1]; T.cxl = (float)fxfycxcy[2]; T.cyl = (float)fxfycxcy[3];
   T.fxli = 1.0f / T.fxl; T.fyli = 1.0f / T.fyl;   // CalibHessian::setValueScaled (HessianBlocks.h:373-387)
   m->P.n = m->n;
-  hipLaunchKernelGGL(k_immature_optimize, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->store(), c->w, c->h, m->P, T, d_mask, minObs,
+  hipLaunchKernelGGL(k_immature_optimize, dim3((m->n + 3) / 4), dim3(256), 0, c->stream, c->frames.built_and_waited(), c->w, c->h, m->P, T, d_mask, minObs,
                      100.0f /* setting_minIdepthH_act */, 3 /* setting_GNItsOnPointActivation */, m->S.huberTH, m->d_result, m->d_idepth, m->d_res_state);
   HIPCHK(hipGetLastError());
   return 0;

@@ -144,7 +144,7 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   P.energy_new = m->d_res; P.maxstep = m->d_res + 2 * PN; P.lastHessian_new = m->d_res + 3 * PN; P.JbBuffer_new = m->d_res + 4 * PN;
   P.isGood_new = reinterpret_cast<unsigned char*>(m->d_res + 14 * PN);
   const int G = std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256));
-  hipLaunchKernelGGL(k_init_partial, dim3(G), dim3(256), 0, s, c->levelPtr(first_slot, lvl), c->levelPtr(new_slot, lvl), P, A, m->d_partials);
+  hipLaunchKernelGGL(k_init_partial, dim3(G), dim3(256), 0, s, c->frames.levelPtr(first_slot, lvl), c->frames.levelPtr(new_slot, lvl), P, A, m->d_partials);
   hipLaunchKernelGGL(k_init_final, dim3(1), dim3(128), 0, s, m->d_partials, G, m->d_out);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(m->h_out, m->d_out, sizeof(float) * IN_PART, hipMemcpyDeviceToHost, s));

@@ -65,9 +65,9 @@ int dmvio_hip_tracker_set_ref(dmvio_hip_tracker* t, int ref_slot, float ref_expo
   }
   hipLaunchKernelGGL(k_ref_dilate, dim3((unsigned)((R.total + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp, t->d_idp2, t->d_wsp2);
   HIPCHK(hipMemsetAsync(t->d_flow_mask, 0, sizeof(unsigned long long) * t->flow_words, s));
-  hipLaunchKernelGGL(k_ref_count, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->store(), ref_slot, t->d_tile_count, t->d_seg);
+  hipLaunchKernelGGL(k_ref_count, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->frames.built_and_waited(), ref_slot, t->d_tile_count, t->d_seg);
   hipLaunchKernelGGL(k_ref_scan, dim3(2 * R.levels), dim3(1024), 0, s, R, t->d_tile_count, t->d_tile_base, t->d_pc_n, t->d_seg);
-  hipLaunchKernelGGL(k_ref_write, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->store(), ref_slot, t->d_tile_base, t->d_seg, t->d_pc_ptrs,
+  hipLaunchKernelGGL(k_ref_write, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->frames.built_and_waited(), ref_slot, t->d_tile_base, t->d_seg, t->d_pc_ptrs,
                      t->d_dense, t->d_flow_mask);
   HIPCHK(hipGetLastError());
   int pcn[DMV_MAX_LEVELS] = {};
@@ -273,9 +273,9 @@ int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmv
     hipLaunchKernelGGL(k_ref_pool_w, dim3((unsigned)((npool + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
   }
   hipLaunchKernelGGL(k_ref_dilate_w, dim3((unsigned)((R.total + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
-  hipLaunchKernelGGL(k_ref_count_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->store()); launches++;
+  hipLaunchKernelGGL(k_ref_count_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->frames.built_and_waited()); launches++;
   hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
-  hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->store()); launches++;
+  hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->frames.built_and_waited()); launches++;
   HIPCHK(hipGetLastError());
   b->last_launches = launches;
   HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * R.levels, hipMemcpyDeviceToHost, s));

@@ -97,7 +97,7 @@ static int selectPass(dmvio_hip_pixel_selector* s, int slot, int pot, float thFa
   unsigned long long *d_key2 = L.d_key2, *d_key3 = L.d_key3, *d_key4 = L.d_key4;
   hipStream_t st = c->stream;
   HIPCHK(hipMemsetAsync(s->d_zero, 0, L.bytes, st));
-  const float* I0 = c->levelPtr(slot, 0);
+  const float* I0 = c->frames.levelPtr(slot, 0);
   const float *ag0 = s->d_ag, *ag1 = ag0 + wh, *ag2 = ag1 + c->wl[1] * c->hl[1];
   hipLaunchKernelGGL(k_sel_cellmask, dim3((wh + 255) / 256), dim3(256), 0, st, I0, ag0, (const float*)s->d_thsS, G, d_mask);
   SelScanArgs A;
@@ -222,7 +222,7 @@ int dmvio_hip_pixel_selector_make_maps(dmvio_hip_pixel_selector* s, int slot, co
   // FrameHessian::makeImages' absSquaredGrad and makeHists (the reference keeps the histogram per FrameHessian pointer, :200: same values)
   if (B_lut256) HIPCHK(c->bounce.h2d(s->d_lut, B_lut256, sizeof(float) * 256, st));
   const int nag = wh + c->wl[1] * c->hl[1] + c->wl[2] * c->hl[2];
-  hipLaunchKernelGGL(k_sel_absgrad, dim3((nag + 255) / 256), dim3(256), 0, st, c->levelPtr(slot, 0), c->levelPtr(slot, 1), c->levelPtr(slot, 2), w, h, c->wl[1], c->hl[1],
+  hipLaunchKernelGGL(k_sel_absgrad, dim3((nag + 255) / 256), dim3(256), 0, st, c->frames.levelPtr(slot, 0), c->frames.levelPtr(slot, 1), c->frames.levelPtr(slot, 2), w, h, c->wl[1], c->hl[1],
                      c->wl[2], c->hl[2], (const float*)(B_lut256 ? s->d_lut : nullptr), s->d_ag);
   hipLaunchKernelGGL(k_sel_hist, dim3(s->nbW * s->nbH), dim3(256), 0, st, (const float*)s->d_ag, w, h, s->nbW, s->S.minGradHistCut, s->S.minGradHistAdd, s->d_ths);
   hipLaunchKernelGGL(k_sel_smooth, dim3((s->nbW * s->nbH + 255) / 256), dim3(256), 0, st, (const float*)s->d_ths, s->nbW, s->nbH, s->d_thsS);
@@ -344,7 +344,7 @@ static int selRecord(dmvio_hip_pixel_selector_batch* b, SelWin& R, int k, const 
   dmvio_hip_pixel_selector* s = V.sel;
   dmvio_hip_ctx* c = b->ctx;
   memset(&R, 0, sizeof(R));
-  R.I0 = c->levelPtr(V.slot, 0); R.I1 = c->levelPtr(V.slot, 1); R.I2 = c->levelPtr(V.slot, 2);
+  R.I0 = c->frames.levelPtr(V.slot, 0); R.I1 = c->frames.levelPtr(V.slot, 1); R.I2 = c->frames.levelPtr(V.slot, 2);
   if (V.B_lut256) {
     memcpy(b->h_slab + b->b_off + (size_t)k * 1024, V.B_lut256, sizeof(float) * 256);
     R.B = reinterpret_cast<const float*>(b->d_slab + b->b_off + (size_t)k * 1024);

@@ -1,5 +1,5 @@
-// internals shared by the translation units of libdmvio_hip.so.  capi_frames.hip defines the error string, the context (dmvio_hip_ctx) with its frame store and
-// dmv_ensure_row_major*; capi.hip is the coarse tracker and capi_ref.hip its reference template (their handle: tracker_handle.h); every other unit is one handle type of its own.
+// internals shared by the translation units of libdmvio_hip.so.  capi_frames.hip defines the error string, the entry points of the context (dmvio_hip_ctx; its frame store is
+// a class of its own, frame_store_host.hpp, whose bodies that unit compiles) and dmv_ensure_row_major*; capi.hip is the coarse tracker and capi_ref.hip its reference template (their handle: tracker_handle.h); every other unit is one handle type of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -104,55 +104,22 @@ struct DmvBounce {
   void release() { if (h) hipHostFree(h); h = nullptr; cap = used = 0; outs.clear(); group.clear(); grouping = false; }
 };
 
-struct dmvio_hip_ctx;
-// Deferred attach (capi_frames.hip): the ordinary pyramid build of every slot whose coarser levels are still to be formed, on the context's stream; wait != 0: the stream is
-// waited for (readers that go on on another stream).  Takes dmvio_hip_ctx::pend_mu, needs no other lock.  0 or <0.
-extern "C" int dmv_flush_pending(dmvio_hip_ctx* c, int wait);
-extern "C" int dmv_flush_pending_held(dmvio_hip_ctx* c);   // the same for a caller that holds pend_mu (the tracker's batch launch); never waits
+#include "frame_store_host.hpp"
 
 struct dmvio_hip_ctx {
   int device = 0, w = 0, h = 0, levels = 0, n_slots = 0;
   hipStream_t stream = nullptr;
   bool own_stream = true;
-  // The frame store.  A deferred attach (dmvio_hip_frames_attach_device_batch with dmvio_hip_set_deferred_attach on) leaves slots whose levels 1.. are not built yet: every
-  // reader takes the store through store(), which builds them first (dmv_flush_pending, and waits: the reader may go on on a stream of its own); the tracker's launches, which go
-  // onto the context's stream, need no wait (store_on_stream()); only its batch launch, whose kernel builds the waiting slots it names itself, and the frame store's own
-  // entry points take the store as it is.
-  dmv::FrameStore fs_{};
-  const dmv::FrameStore& store() { if (n_pending.load(std::memory_order_acquire)) dmv_flush_pending(this, 1); return fs_; }
-  const dmv::FrameStore& store_on_stream() { if (n_pending.load(std::memory_order_acquire)) dmv_flush_pending(this, 0); return fs_; }   // for what is enqueued on the context's stream next (the tracker's other launches): no wait
-  const dmv::FrameStore& store_deferred() const { return fs_; }
-  // The one deferred attach that can be outstanding (a new one flushes what the older left): its source, its staged slot list and the generation its
-  // slots are stamped with once built.  h_pending[slot] = 1 + the slot's index in that list while the slot waits, 0 otherwise; n_pending counts them.  All under pend_mu, a
-  // leaf lock (taken after `mu` by those that hold it; the window optimisers' threads take it alone); n_pending is atomic so that store() costs one load when nothing waits.
-  struct PendingAttach { const float* base = nullptr; size_t stride = 0; const int* d_slots = nullptr; int B = 0; unsigned int flush_gen = 0; std::vector<int> slots; };
-  PendingAttach pend;
-  std::vector<int> h_pending;
-  std::atomic<int> n_pending{0};
-  std::mutex pend_mu;
-  int deferred_attach = 1;              // dmvio_hip_set_deferred_attach
-  std::vector<unsigned int> slot_stamp; // launchLocked: which slots the launch being prepared has named (stamp_clock)
-  unsigned int stamp_clock = 0;
   float* d_upload = nullptr;  // staging for host uploads (w*h)
   float* d_f3 = nullptr;      // download scratch (w*h*3)
   dmv::PyrGeom pg{};
   int wl[DMV_MAX_LEVELS] = {}, hl[DMV_MAX_LEVELS] = {};
-  // slot lists of the batched builds, staged on the device: the last few distinct lists stay (a double-buffered pipeline alternates between two)
-  struct SlotList { int *d = nullptr, *h = nullptr; int cap = 0, n = 0; unsigned long long used = 0; };
-  SlotList slot_lists[4];
-  unsigned long long slot_clock = 0;
-  int* d_slots = nullptr;               // the list the current batched build reads (one of slot_lists[].d)
-  hipStream_t build_stream = nullptr;   // dmvio_hip_set_build_stream: where the batched builds are enqueued (NULL: the context's stream)
-  std::vector<const float*> h_lvl0;   // host mirror of FrameStore::lvl0 (kept by the build entry points)
-  const float* levelPtr(int slot, int lvl) { return lvl == 0 ? (store(), h_lvl0[slot]) : store().own_level(slot, lvl); }
-  unsigned int build_gen = 0;   // generation counter of pyramid builds (FrameStore::build_gen / bad_gen stamps)
-  std::vector<unsigned char> h_tiled;   // host mirror of FrameStore::tiled0: level 0 of the slot is stored in 8x4 tiles (written so by the batched raw-image build)
+  FrameSlots frames{stream, pg};        // the frame store: the device arrays, the per-slot host state and every transition of it (frame_store_host.hpp, where its locking rule stands)
   int raw_batch_kernel = 1;             // dmvio_hip_set_raw_batch_kernel: 1 = the wave-autonomous register build where the geometry allows (<= 4 levels, sides % 8 == 0), 0 = the LDS-tile build
-  int raw_batch_tiled = 0;              // dmvio_hip_set_raw_batch_layout: what dmvio_hip_frames_from_raw_device_batch writes (1 = tiles where the image size allows)
+  int raw_batch_layout = 0;              // dmvio_hip_set_raw_batch_layout: what dmvio_hip_frames_from_raw_device_batch writes (1 = tiles where the image size allows)
   DmvBounce bounce;             // caller-owned arrays cross PCIe through here (used under `mu`)
   std::mutex mu;
 };
-
 
 // Level 0 of `slot` back into the row-major layout if the batched raw-image build stored it in 8x4 tiles (FrameStore::tiled0): called by every consumer of a level-0 plane
 // other than the coarse tracker's batch kernel (reference template, single-frame tracking, window optimiser, immature points, initializer, downloads) before it reads the

@@ -308,6 +308,119 @@ def test_nothing_is_deferred(pkg, synth, torch_mod, how):
     A.close(); B.close()
 
 
+def _level0(S, slot):
+    return S.ctx.frame_download(slot, 0)[..., 0]
+
+
+def test_waiting_slots_rewritten_by_the_other_build_entry_points(pkg, synth, torch_mod):
+    """frame_upload, frames_from_device_batch and the raw-image batch each supersede one waiting slot: the kernel builds the three that are left"""
+    w, h = 320, 256
+    case = _case(w, h)
+    nB = 6
+    A, B = _pair(pkg, case, nB + 1)
+    raw = _device_frames(torch_mod, [f["img"] for f in case["frames"][:nB]])
+    up = case["frames"][6]["img"].astype(np.float32)
+    other = _device_frames(torch_mod, [case["frames"][7]["img"]])
+    img8 = np.clip(np.rint(case["frames"][0]["img"]), 0, 255).astype(np.uint8)
+    dev8 = torch_mod.from_numpy(img8.reshape(1, -1)).to("cuda:0"); torch_mod.cuda.synchronize()
+    slots = list(range(1, nB + 1))
+    poses, affs = _hypotheses(case, synth, nB)
+    res = []
+    for S in (A, B):
+        und = pkg.UndistorterHip(S.ctx, w, h, 8)   # passthrough geometry, no photometric calibration: image = raw
+        S.attach(slots, raw)
+        S.ctx.frame_upload(3, up)
+        S.ctx.frames_from_device_batch([5], other.data_ptr(), other.stride(0) * 4)
+        und.from_raw_device_batch([2], dev8.data_ptr(), w * h)
+        res.append(S.trk.track_batch(slots, poses.copy(), affs.copy()))
+        und.close()
+    assert A.trk.last_fused_builds() == 0 and B.trk.last_fused_builds() == 3
+    _same_results(*res)
+    _same_store(A, B, slots)
+    for S in (A, B):
+        assert _level0(S, 3).tobytes() == up.tobytes() and _level0(S, 5).tobytes() == other[0].cpu().numpy().tobytes()
+        assert _level0(S, 2).tobytes() == img8.astype(np.float32).tobytes()
+        for s in (1, 4, 6):
+            assert _level0(S, s).tobytes() == raw[s - 1].cpu().numpy().tobytes(), s
+    A.close(); B.close()
+
+
+def test_partially_overlapping_reattach(pkg, synth, torch_mod):
+    """a second attach names two of six waiting slots: the other four are built from the OLD source, as the runs of the recorded list that start at its entries 0 and 3"""
+    w, h = 320, 256
+    case = _case(w, h)
+    nB = 6
+    A, B = _pair(pkg, case, nB + 1)
+    raw = _device_frames(torch_mod, [f["img"] for f in case["frames"][:nB]])
+    raw2 = _device_frames(torch_mod, [case["frames"][6]["img"], case["frames"][7]["img"]])
+    slots = list(range(1, nB + 1))
+    poses, affs = _hypotheses(case, synth, nB)
+    res = []
+    for S in (A, B):
+        S.attach(slots, raw)
+        S.attach([2, 3], raw2)
+        res.append(S.trk.track_batch(slots, poses.copy(), affs.copy()))
+    assert A.trk.last_fused_builds() == 0 and B.trk.last_fused_builds() == 2
+    _same_results(*res)
+    _same_store(A, B, slots)
+    for S in (A, B):
+        for s in (1, 4, 5, 6):
+            assert _level0(S, s).tobytes() == raw[s - 1].cpu().numpy().tobytes(), s
+        for s in (2, 3):
+            assert _level0(S, s).tobytes() == raw2[s - 2].cpu().numpy().tobytes(), s
+    A.close(); B.close()
+
+
+def test_the_staged_list_of_a_waiting_attach_is_recycled(pkg, synth, torch_mod):
+    """four slot lists stay staged: the fourth new list after the attach takes the entry the attach's record points into, which has the waiting slots built first"""
+    w, h = 320, 256
+    case = _case(w, h)
+    nB = 6
+    A, B = _pair(pkg, case, 11)
+    raw = _device_frames(torch_mod, [f["img"] for f in case["frames"][:nB]])
+    other = _device_frames(torch_mod, [case["frames"][6]["img"]])
+    slots = list(range(1, nB + 1))
+    poses, affs = _hypotheses(case, synth, nB)
+    res = []
+    for S in (A, B):
+        S.attach(slots, raw)
+        for s in (7, 8, 9, 10):
+            S.ctx.frames_from_device_batch([s], other.data_ptr(), other.stride(0) * 4)
+        res.append(S.trk.track_batch(slots, poses.copy(), affs.copy()))
+    assert A.trk.last_fused_builds() == 0 and B.trk.last_fused_builds() == 0
+    _same_results(*res)
+    _same_store(A, B, list(range(1, 11)))
+    for S in (A, B):
+        for s in slots:
+            assert _level0(S, s).tobytes() == raw[s - 1].cpu().numpy().tobytes(), s
+    A.close(); B.close()
+
+
+def test_the_same_list_attached_twice_with_nothing_read_in_between(pkg, synth, torch_mod):
+    """the second attach supersedes all six marks of the first: nothing of the first source is ever built"""
+    w, h = 320, 256
+    case = _case(w, h)
+    nB = 6
+    A, B = _pair(pkg, case, nB + 1)
+    raw = _device_frames(torch_mod, [f["img"] for f in case["frames"][:nB]])
+    raw2 = _device_frames(torch_mod, [case["frames"][(k + 3) % N_DISTINCT]["img"] for k in range(nB)])
+    slots = list(range(1, nB + 1))
+    poses, affs = _hypotheses(case, synth, nB)
+    res = []
+    for S in (A, B):
+        S.attach(slots, raw)
+        S.attach(slots, raw2)
+        res.append(S.trk.track_batch(slots, poses.copy(), affs.copy()))
+    assert A.trk.last_fused_builds() == 0 and B.trk.last_fused_builds() == nB
+    _same_results(*res)
+    _same_store(A, B, slots)
+    for S in (A, B):
+        for s in slots:
+            l0 = _level0(S, s).tobytes()
+            assert l0 == raw2[s - 1].cpu().numpy().tobytes() and l0 != raw[s - 1].cpu().numpy().tobytes(), s
+    A.close(); B.close()
+
+
 def test_single_frame_tracking_of_a_waiting_slot(pkg, synth, torch_mod):
     """one problem: the host-driven LM against the evaluation server, which is no batch launch — the slot is built in front of it"""
     w, h = 320, 256
