@@ -124,6 +124,12 @@ class SetRefWindow(C.Structure):
                 ("u", c_f), ("v", c_f), ("idepth", c_f), ("hdiF", c_f)]
 
 
+class SetRefBaWindow(C.Structure):
+    """dmvio_hip_set_ref_ba_window (include/dmvio_hip.h): one window of dmvio_hip_tracker_set_ref_from_ba_batch."""
+    _fields_ = [("trk", C.c_void_p), ("ba", C.c_void_p), ("ref_slot", C.c_int), ("ref_exposure", C.c_float), ("ref_aff_a", C.c_double), ("ref_aff_b", C.c_double),
+                ("n_selected", C.c_int)]
+
+
 def _sig(L):
     vp = C.c_void_p
     L.dmvio_hip_last_error.restype = C.c_char_p
@@ -166,6 +172,8 @@ def _sig(L):
     L.dmvio_hip_set_ref_batch_destroy.argtypes = [vp]; L.dmvio_hip_set_ref_batch_destroy.restype = None
     L.dmvio_hip_tracker_set_ref_batch.argtypes = [vp, C.c_int, C.POINTER(SetRefWindow)]
     L.dmvio_hip_set_ref_batch_last_work.argtypes = [vp, c_i, c_i, c_i, c_i]
+    L.dmvio_hip_tracker_set_ref_from_ba.argtypes = [vp, vp, C.c_int, C.c_float, C.c_double, C.c_double, c_i]
+    L.dmvio_hip_tracker_set_ref_from_ba_batch.argtypes = [vp, C.c_int, C.POINTER(SetRefBaWindow)]
     L.dmvio_hip_tracker_track_batch_stage.argtypes = [vp, C.c_int, c_i, c_f, c_d, c_d, C.c_int, c_d]
     L.dmvio_hip_tracker_track_batch_launch.argtypes = [vp]
     L.dmvio_hip_tracker_track_batch_fetch_begin.argtypes = [vp]
@@ -516,6 +524,13 @@ class CoarseTrackerHip:
         _chk(self.L, self.L.dmvio_hip_tracker_set_ref(self.p, ref_slot, ref_exposure, ref_aff[0], ref_aff[1], len(u),
                                                       _f(u), _f(v), _f(idepth), _f(hdiF)), "setCoarseTrackingRef")
 
+    def setCoarseTrackingRefFromBA(self, ba, ref_slot, ref_exposure=1.0, ref_aff=(0.0, 0.0)):
+        """setCoarseTrackingRef with the points read from the resident window of `ba` (a BundleAdjusterHip of the same context): the residuals to its newest keyframe
+        that are active and IN, in graph order (dmvio_hip_tracker_set_ref_from_ba).  Returns the number of selected residuals."""
+        n = C.c_int(0)
+        _chk(self.L, self.L.dmvio_hip_tracker_set_ref_from_ba(self.p, ba.p, int(ref_slot), ref_exposure, ref_aff[0], ref_aff[1], C.byref(n)), "setCoarseTrackingRefFromBA")
+        return n.value
+
     def pc_n(self, lvl):
         return _chk(self.L, self.L.dmvio_hip_tracker_pc_n(self.p, lvl), "pc_n")
 
@@ -825,6 +840,23 @@ class SetRefBatchHip:
         """one dmvio_hip_tracker_set_ref_batch call over `windows` (see pack())"""
         arr, keep = self.pack(windows)
         _chk(self.L, self.L.dmvio_hip_tracker_set_ref_batch(self.p, len(windows), arr), "set_ref_batch")
+
+    @staticmethod
+    def pack_from_ba(windows):
+        """windows: one dict per tracker with trk (a CoarseTrackerHip), ba (a BundleAdjusterHip), ref_slot and optionally ref_exposure (1.0) and ref_aff ((0, 0))
+        -> array of dmvio_hip_set_ref_ba_window"""
+        arr = (SetRefBaWindow * max(len(windows), 1))()
+        for x, d in zip(arr, windows):
+            aff = d.get("ref_aff", (0.0, 0.0))
+            x.trk = d["trk"].p; x.ba = d["ba"].p; x.ref_slot = int(d["ref_slot"]); x.ref_exposure = float(d.get("ref_exposure", 1.0))
+            x.ref_aff_a = float(aff[0]); x.ref_aff_b = float(aff[1]); x.n_selected = -1
+        return arr
+
+    def set_ref_from_ba(self, windows):
+        """one dmvio_hip_tracker_set_ref_from_ba_batch call over `windows` (see pack_from_ba()); returns the selected residuals per window"""
+        arr = self.pack_from_ba(windows)
+        _chk(self.L, self.L.dmvio_hip_tracker_set_ref_from_ba_batch(self.p, len(windows), arr), "set_ref_from_ba_batch")
+        return [arr[i].n_selected for i in range(len(windows))]
 
     def last_work(self):
         """(kernel launches, uploads, downloads, stream waits) of the last call"""

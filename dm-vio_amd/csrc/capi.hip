@@ -61,7 +61,7 @@ static int trackerInit(dmvio_hip_tracker* t) {
   HIPCHK(hipMalloc((void**)&t->d_dense, sizeof(float) * off));
   HIPCHK(hipMalloc((void**)&t->d_tile_count, sizeof(int) * tiles));
   HIPCHK(hipMalloc((void**)&t->d_tile_base, sizeof(int) * tiles));
-  HIPCHK(hipMalloc((void**)&t->d_pc_n, sizeof(int) * DMV_MAX_LEVELS));
+  HIPCHK(hipMalloc((void**)&t->d_pc_n, sizeof(int) * dmvio_hip_tracker::PC_N_INTS));   // pc_n, then the two counters of set_ref_from_ba (tracker_handle.h)
   for (int l = 0; l < c->levels; l++) HIPCHK(hipMalloc((void**)&t->d_pc[l], sizeof(float4) * R.w[l] * R.h[l]));
   HIPCHK(hipMalloc((void**)&t->d_pc_ptrs, sizeof(float4*) * DMV_MAX_LEVELS));
   HIPCHK(hipMemcpy(t->d_pc_ptrs, t->d_pc, sizeof(float4*) * DMV_MAX_LEVELS, hipMemcpyHostToDevice));
@@ -98,6 +98,9 @@ void dmvio_hip_tracker_destroy(dmvio_hip_tracker* t) {
   hipFree(t->d_idp); hipFree(t->d_wsp); hipFree(t->d_idp2); hipFree(t->d_wsp2); hipFree(t->d_dense);
   hipFree(t->d_tile_count); hipFree(t->d_tile_base); hipFree(t->d_pc_n); hipFree(t->d_seg); hipFree(t->d_flow_mask);
   if (t->d_pp_next) hipFree(t->d_pp_next);
+  if (t->d_ba_crowded) hipFree(t->d_ba_crowded);
+  if (t->ev_ba_ready) hipEventDestroy(t->ev_ba_ready);
+  if (t->ev_ba_read) hipEventDestroy(t->ev_ba_read);
   if (t->d_log) { hipFree(t->d_log); hipFree(t->d_log_n); hipFree(t->d_log_sink); }
   for (int l = 0; l < t->ctx->levels; l++) hipFree(t->d_pc[l]);
   hipFree(t->d_pc_ptrs); hipFree(t->d_pts); hipFree(t->d_partials); if (t->h_mail) hipHostFree(t->h_mail); if (t->h_rec) hipHostFree(t->h_rec);

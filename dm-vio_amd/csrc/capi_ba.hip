@@ -912,3 +912,14 @@ int dmvio_hip_ba_get_last_x(dmvio_hip_ba* b, double* x_out) {
   return 0;
 }
 }  // extern "C"
+// internal.h: what dmvio_hip_tracker_set_ref_from_ba borrows of this handle
+void dmv_ba_lock(dmvio_hip_ba* b) { b->mu.lock(); }
+void dmv_ba_unlock(dmvio_hip_ba* b) { b->mu.unlock(); }
+void dmv_ba_ref_source_locked(dmvio_hip_ba* b, DmvBaRefSource* out) {
+  out->ctx = b->ctx; out->stream = b->stream;
+  out->graph_ready = b->graph_ready; out->sharded = b->world != 0;
+  out->F = b->H.F; out->N = b->graph_ready ? b->H.N : 0; out->R = b->graph_ready ? b->H.R : 0;   // without a graph the counts are an older window's
+  out->res_point = b->Rs.point; out->res_target = b->Rs.target;
+  out->newState = b->Rs.newState; out->active = b->Rs.active;
+  out->center = b->Rs.center; out->HdiF = b->P.HdiF;
+}

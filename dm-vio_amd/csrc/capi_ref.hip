@@ -1,5 +1,5 @@
-// libdmvio_hip.so — C ABI implementation (include/dmvio_hip.h), the coarse tracker's reference template: setCoarseTrackingRef of one tracker and of W trackers per call, and
-// the queries of what it left.  gfx950 only.  The only unit that compiles ref_kernels.hpp and ref_batch_kernels.hpp.
+// libdmvio_hip.so — C ABI implementation (include/dmvio_hip.h), the coarse tracker's reference template: setCoarseTrackingRef of one tracker and of W trackers per call, from
+// host arrays or straight out of resident BA windows, and the queries of what it left.  gfx950 only.  The only unit that compiles ref_kernels.hpp and ref_batch_kernels.hpp.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <mutex>
@@ -20,6 +20,24 @@ static void refPublish(dmvio_hip_tracker* t, const int* pcn, float ref_exposure,
   for (int l = 0; l < t->R.levels; l++) { t->dev.pc_n[l] = pcn[l]; t->dev.pc[l] = t->d_pc[l]; }
   t->dev.ref_exposure = ref_exposure; t->dev.ref_aff_a = aff_a; t->dev.ref_aff_b = aff_b;
   t->haveRef = true;
+}
+
+// the stages behind the scatter of a single call, host arrays or BA window alike: pyramid sums, dilation, ordered compaction (enqueued on the context's stream)
+static int refStagesFromPool(dmvio_hip_tracker* t, int ref_slot, hipStream_t s) {
+  dmvio_hip_ctx* c = t->ctx;
+  const RefLevels& R = t->R;
+  if (R.levels > 1) {
+    const size_t npool = R.total - R.off[1];
+    hipLaunchKernelGGL(k_ref_pool, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp);
+  }
+  hipLaunchKernelGGL(k_ref_dilate, dim3((unsigned)((R.total + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp, t->d_idp2, t->d_wsp2);
+  HIPCHK(hipMemsetAsync(t->d_flow_mask, 0, sizeof(unsigned long long) * t->flow_words, s));
+  hipLaunchKernelGGL(k_ref_count, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->frames.built_and_waited(), ref_slot, t->d_tile_count, t->d_seg);
+  hipLaunchKernelGGL(k_ref_scan, dim3(2 * R.levels), dim3(1024), 0, s, R, t->d_tile_count, t->d_tile_base, t->d_pc_n, t->d_seg);
+  hipLaunchKernelGGL(k_ref_write, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->frames.built_and_waited(), ref_slot, t->d_tile_base, t->d_seg, t->d_pc_ptrs,
+                     t->d_dense, t->d_flow_mask);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 extern "C" {
@@ -59,17 +77,7 @@ int dmvio_hip_tracker_set_ref(dmvio_hip_tracker* t, int ref_slot, float ref_expo
       hipLaunchKernelGGL(k_ref_scatter, dim3((n + 255) / 256), dim3(256), 0, s, n, t->d_pts, t->d_pts + t->pts_cap, t->d_pts + 2 * (size_t)t->pts_cap,
                          t->d_pts + 3 * (size_t)t->pts_cap, t->d_idp, t->d_wsp, R.w[0], R.h[0], d_rank, r == 1 ? 0 : r, r);
   }
-  if (R.levels > 1) {
-    const size_t npool = R.total - R.off[1];
-    hipLaunchKernelGGL(k_ref_pool, dim3((unsigned)((npool + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp);
-  }
-  hipLaunchKernelGGL(k_ref_dilate, dim3((unsigned)((R.total + 255) / 256)), dim3(256), 0, s, R, t->d_idp, t->d_wsp, t->d_idp2, t->d_wsp2);
-  HIPCHK(hipMemsetAsync(t->d_flow_mask, 0, sizeof(unsigned long long) * t->flow_words, s));
-  hipLaunchKernelGGL(k_ref_count, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->frames.built_and_waited(), ref_slot, t->d_tile_count, t->d_seg);
-  hipLaunchKernelGGL(k_ref_scan, dim3(2 * R.levels), dim3(1024), 0, s, R, t->d_tile_count, t->d_tile_base, t->d_pc_n, t->d_seg);
-  hipLaunchKernelGGL(k_ref_write, dim3(t->n_tiles), dim3(256), 0, s, R, t->d_idp2, t->d_wsp2, c->frames.built_and_waited(), ref_slot, t->d_tile_base, t->d_seg, t->d_pc_ptrs,
-                     t->d_dense, t->d_flow_mask);
-  HIPCHK(hipGetLastError());
+  if (int r = refStagesFromPool(t, ref_slot, s)) return r;
   int pcn[DMV_MAX_LEVELS] = {};
   HIPCHK(c->bounce.d2h(pcn, t->d_pc_n, sizeof(int) * R.levels, s));
   HIPCHK(c->bounce.finish(s));
@@ -150,7 +158,7 @@ struct dmvio_hip_set_ref_batch {
   int max_windows = 0, max_points = 0;
   size_t slab_bytes = 0;
   char *h_slab = nullptr, *d_slab = nullptr;
-  int *h_pcn = nullptr, *d_pcn = nullptr;      // [max_windows][DMV_MAX_LEVELS]; a call uses [W][levels]
+  int *h_pcn = nullptr, *d_pcn = nullptr;      // [max_windows][DMV_MAX_LEVELS + 1]; a call uses [W][levels], a from-BA call W selected counts behind them
   RefRanker ranker;
   std::vector<const dmvio_hip_tracker*> seen;  // the duplicate test
   int last_launches = 0, last_uploads = 0, last_downloads = 0, last_waits = 0;
@@ -158,6 +166,18 @@ struct dmvio_hip_set_ref_batch {
 // the slab: records, then floats, then bytes; every part starts on a 16-byte boundary
 static size_t refSlabPointsOff(int W) { return (sizeof(RefWin) * (size_t)W + 15) & ~(size_t)15; }
 static size_t refSlabRanksOff(int W, size_t total_points) { return (refSlabPointsOff(W) + sizeof(float) * 4 * total_points + 15) & ~(size_t)15; }
+// a from-BA call: the W RefWin records, then W RefBaWin records where the points of a host-array call start
+static size_t refSlabBaBytes(int W) { return refSlabPointsOff(W) + sizeof(RefBaWin) * (size_t)W; }
+
+// a tracker's buffers as the W-window kernels find them; the points of the window (none here) are the caller's part
+static void refWinRecord(RefWin& V, dmvio_hip_tracker* t, int* pc_n_row, int ref_slot) {
+  V.idp = t->d_idp; V.wsp = t->d_wsp; V.idp2 = t->d_idp2; V.wsp2 = t->d_wsp2; V.dense = t->d_dense;
+  V.tile_count = t->d_tile_count; V.tile_base = t->d_tile_base; V.seg = t->d_seg; V.pc_n = t->d_pc_n;
+  V.pc = t->d_pc_ptrs; V.flow_mask = t->d_flow_mask;
+  V.pc_n_row = pc_n_row;
+  V.pts_off = 0; V.rank_off = 0;
+  V.ref_slot = ref_slot; V.n = 0; V.order = t->R.order; V.max_rank = 0;
+}
 
 dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* c, int max_windows, int max_points_per_window) {
   if (!c) { failmsg("set_ref_batch_create: null context"); return nullptr; }
@@ -166,12 +186,12 @@ dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* c, int ma
   dmvio_hip_set_ref_batch* b = new dmvio_hip_set_ref_batch();
   b->ctx = c; b->max_windows = max_windows; b->max_points = max_points_per_window;
   const size_t total = (size_t)max_windows * (size_t)max_points_per_window;
-  b->slab_bytes = refSlabRanksOff(max_windows, total) + total;
+  b->slab_bytes = std::max(refSlabRanksOff(max_windows, total) + total, refSlabBaBytes(max_windows));
   auto init = [&]() -> int {
     HIPCHK(hipMalloc((void**)&b->d_slab, b->slab_bytes));
     HIPCHK(hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&b->d_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows));
-    HIPCHK(hipHostMalloc((void**)&b->h_pcn, sizeof(int) * DMV_MAX_LEVELS * (size_t)max_windows, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&b->d_pcn, sizeof(int) * (DMV_MAX_LEVELS + 1) * (size_t)max_windows));
+    HIPCHK(hipHostMalloc((void**)&b->h_pcn, sizeof(int) * (DMV_MAX_LEVELS + 1) * (size_t)max_windows, hipHostMallocDefault));
     return 0;
   };
   if (init()) { dmvio_hip_set_ref_batch_destroy(b); return nullptr; }
@@ -241,12 +261,8 @@ int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmv
     const dmvio_hip_set_ref_window& x = win[w];
     dmvio_hip_tracker* t = x.trk;
     RefWin& V = h_wins[w];
-    V.idp = t->d_idp; V.wsp = t->d_wsp; V.idp2 = t->d_idp2; V.wsp2 = t->d_wsp2; V.dense = t->d_dense;
-    V.tile_count = t->d_tile_count; V.tile_base = t->d_tile_base; V.seg = t->d_seg; V.pc_n = t->d_pc_n;
-    V.pc = t->d_pc_ptrs; V.flow_mask = t->d_flow_mask;
-    V.pc_n_row = b->d_pcn + (size_t)w * R.levels;
-    V.pts_off = pts; V.rank_off = ranks;
-    V.ref_slot = x.ref_slot; V.n = x.n; V.order = t->R.order; V.max_rank = 0;
+    refWinRecord(V, t, b->d_pcn + (size_t)w * R.levels, x.ref_slot);
+    V.pts_off = pts; V.rank_off = ranks; V.n = x.n;
     if (x.n > 0) {
       float* hp = reinterpret_cast<float*>(b->h_slab) + pts;
       memcpy(hp, x.u, sizeof(float) * x.n); memcpy(hp + x.n, x.v, sizeof(float) * x.n);
@@ -283,6 +299,190 @@ int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmv
   HIPCHK(hipStreamSynchronize(s));
   b->last_waits = 1;
   for (int w = 0; w < W; w++) refPublish(win[w].trk, b->h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
+  return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ the template straight out of resident BA windows
+// dmvio_hip_tracker_set_ref_from_ba / _from_ba_batch: what setCoarseTrackingRef reads per point (CoarseTracker.cpp:138-161: centerProjectedTo of the residual to the newest
+// keyframe, efPoint->HdiF) is on the device when dmvio_hip_ba_optimize returns; the scatter reads it there (ref_kernels.hpp: refBaCountBody / ScatterBody / CrowdedBody) and
+// every later stage is the host-array call's.
+// Locks: the BA handles of the call first, in address order (as the BA batches take them), then the context's.  BA code never takes the context's lock, so the order
+// cannot deadlock with a mapping thread that holds a BA handle.
+// Streams: the arrays are written on the BA handle's stream, the template is built on the context's.  No host wait orders them: an event recorded on the handle's stream
+// is waited for by the context's stream in front of the first kernel that reads the handle, and an event recorded on the context's stream behind the last such kernel
+// (the crowded pass) is waited for by the handle's stream — a dmvio_hip_ba_set_graph that follows cannot overwrite what the scatter still reads.
+struct RefBaLocks {
+  std::vector<dmvio_hip_ba*> held;
+  void lock(std::vector<dmvio_hip_ba*> v) {
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    for (dmvio_hip_ba* b : v) { dmv_ba_lock(b); held.push_back(b); }
+  }
+  ~RefBaLocks() { for (size_t i = held.size(); i-- > 0;) dmv_ba_unlock(held[i]); }
+};
+// the refusals one window can earn (under the handle's lock and the context's)
+static int refBaCheck(const char* who, const dmvio_hip_ctx* c, const dmvio_hip_tracker* t, const DmvBaRefSource& S, int ref_slot) {
+  if (t->ctx != c) return failmsg(std::string(who) + ": a tracker belongs to another context");
+  if (S.ctx != c) return failmsg(std::string(who) + ": a BA handle belongs to another context");
+  // a window of ONE keyframe can hold no residual, so dmvio_hip_ba_set_graph takes no graph for it: it selects nothing and the template ends empty
+  if (!S.graph_ready && S.F != 1) return failmsg(std::string(who) + ": a BA handle has no graph (set_window + set_graph first)");
+  if (S.sharded) return failmsg(std::string(who) + ": a BA handle is sharded over ranks (it holds a part of the window's points)");
+  if (ref_slot < 0 || ref_slot >= c->n_slots) return failmsg(std::string(who) + ": slot out of range");
+  return 0;
+}
+// the tracker's crowded list holds every residual of the window; its two events exist
+static int refBaReserve(dmvio_hip_tracker* t, int R) {
+  if (R > t->ba_crowded_cap) {
+    if (t->d_ba_crowded) HIPCHK(hipFree(t->d_ba_crowded));
+    t->d_ba_crowded = nullptr; t->ba_crowded_cap = 0;
+    const int cap = std::max(R, 4096);
+    HIPCHK(hipMalloc((void**)&t->d_ba_crowded, sizeof(int2) * (size_t)cap));
+    t->ba_crowded_cap = cap;
+  }
+  if (!t->ev_ba_ready) HIPCHK(hipEventCreateWithFlags(&t->ev_ba_ready, hipEventDisableTiming));
+  if (!t->ev_ba_read) HIPCHK(hipEventCreateWithFlags(&t->ev_ba_read, hipEventDisableTiming));
+  return 0;
+}
+
+extern "C" {
+
+int dmvio_hip_tracker_set_ref_from_ba(dmvio_hip_tracker* t, dmvio_hip_ba* ba, int ref_slot, float ref_exposure, double aff_a, double aff_b, int* n_selected) {
+  if (!t) return failmsg("tracker_set_ref_from_ba: null tracker");
+  if (!ba) return failmsg("tracker_set_ref_from_ba: null BA handle");
+  dmvio_hip_ctx* c = t->ctx;
+  RefBaLocks bl;
+  bl.lock({ba});
+  std::lock_guard<std::mutex> lk(c->mu);
+  DmvBaRefSource S;
+  dmv_ba_ref_source_locked(ba, &S);
+  if (int r = refBaCheck("tracker_set_ref_from_ba", c, t, S, ref_slot)) return r;
+  HIPCHK(hipSetDevice(c->device));
+  if (int r = dmv_ensure_row_major_locked(c, ref_slot)) return r;
+  if (int r = refBaReserve(t, S.R)) return r;
+  hipStream_t s = c->stream;
+  const RefLevels& R = t->R;
+  const size_t n0 = (size_t)R.w[0] * R.h[0];
+  int* d_cnt = reinterpret_cast<int*>(t->d_idp2);   // selected points per level-0 pixel: k_ref_dilate overwrites the plane later
+  HIPCHK(hipMemsetAsync(t->d_idp, 0, sizeof(float) * n0, s));
+  HIPCHK(hipMemsetAsync(t->d_wsp, 0, sizeof(float) * n0, s));
+  HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int) * n0, s));
+  HIPCHK(hipMemsetAsync(t->d_pc_n + dmvio_hip_tracker::REF_BA_SELECTED, 0, sizeof(int) * 2, s));
+  if (S.R > 0) {
+    HIPCHK(hipEventRecord(t->ev_ba_ready, S.stream));
+    HIPCHK(hipStreamWaitEvent(s, t->ev_ba_ready, 0));
+    RefBaSrc src{S.res_point, S.res_target, S.newState, S.active, S.center, S.HdiF, S.R, S.F - 1};
+    const dim3 g((unsigned)((S.R + 255) / 256));
+    int* d_sel = t->d_pc_n + dmvio_hip_tracker::REF_BA_SELECTED;
+    int* d_ncr = t->d_pc_n + dmvio_hip_tracker::REF_BA_CROWDED;
+    hipLaunchKernelGGL(k_ref_ba_count, g, dim3(256), 0, s, src, R.w[0], R.h[0], d_cnt, d_sel);
+    hipLaunchKernelGGL(k_ref_ba_scatter, g, dim3(256), 0, s, src, t->d_idp, t->d_wsp, R.w[0], R.h[0], (const int*)d_cnt, d_ncr, t->d_ba_crowded, t->ba_crowded_cap);
+    hipLaunchKernelGGL(k_ref_ba_crowded, g, dim3(256), 0, s, src, t->d_idp, t->d_wsp, (const int*)d_ncr, (const int2*)t->d_ba_crowded, t->ba_crowded_cap);
+    HIPCHK(hipEventRecord(t->ev_ba_read, s));
+    HIPCHK(hipStreamWaitEvent(S.stream, t->ev_ba_read, 0));
+  }
+  if (int r = refStagesFromPool(t, ref_slot, s)) return r;
+  int out[DMV_MAX_LEVELS + 1] = {};   // pc_n and, behind it, the number of selected residuals: one download
+  HIPCHK(c->bounce.d2h(out, t->d_pc_n, sizeof(int) * (DMV_MAX_LEVELS + 1), s));
+  HIPCHK(c->bounce.finish(s));
+  refPublish(t, out, ref_exposure, aff_a, aff_b);
+  if (n_selected) *n_selected = out[dmvio_hip_tracker::REF_BA_SELECTED];
+  return 0;
+}
+
+int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, dmvio_hip_set_ref_ba_window* win) {
+  // every refusal stands before the first enqueue and before the first write to a tracker
+  if (!b) return failmsg("tracker_set_ref_from_ba_batch: null handle");
+  if (W < 0 || W > b->max_windows) return failmsg("tracker_set_ref_from_ba_batch: W outside 0 .. max_windows");
+  if (W > 0 && !win) return failmsg("tracker_set_ref_from_ba_batch: null window array");
+  dmvio_hip_ctx* c = b->ctx;
+  std::vector<dmvio_hip_ba*> bas;
+  for (int w = 0; w < W; w++) {
+    if (!win[w].trk) return failmsg("tracker_set_ref_from_ba_batch: null tracker");
+    if (!win[w].ba) return failmsg("tracker_set_ref_from_ba_batch: null BA handle");
+    bas.push_back(win[w].ba);
+  }
+  RefBaLocks bl;
+  bl.lock(bas);
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::vector<DmvBaRefSource> S(W);
+  b->seen.clear();
+  int max_R = 0;
+  for (int w = 0; w < W; w++) {
+    dmv_ba_ref_source_locked(win[w].ba, &S[w]);
+    if (int r = refBaCheck("tracker_set_ref_from_ba_batch", c, win[w].trk, S[w], win[w].ref_slot)) return r;
+    b->seen.push_back(win[w].trk);
+    max_R = std::max(max_R, S[w].R);
+  }
+  std::sort(b->seen.begin(), b->seen.end());
+  if (std::adjacent_find(b->seen.begin(), b->seen.end()) != b->seen.end())
+    return failmsg("tracker_set_ref_from_ba_batch: the same tracker is named twice (two windows would write one set of buffers)");
+  b->last_launches = b->last_uploads = b->last_downloads = b->last_waits = 0;
+  if (W == 0) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  for (int w = 0; w < W; w++) if (int r = dmv_ensure_row_major_locked(c, win[w].ref_slot)) return r;
+  for (int w = 0; w < W; w++) if (int r = refBaReserve(win[w].trk, S[w].R)) return r;
+  hipStream_t s = c->stream;
+  RefLevels R = win[0].trk->R;   // (as in dmvio_hip_tracker_set_ref_batch: the context's geometry, the order travels in the record)
+  R.order = 0;
+  const int n_tiles = win[0].trk->n_tiles, flow_words = (int)win[0].trk->flow_words;
+  const int n0 = R.w[0] * R.h[0];
+  // the slab: two records per window, nothing else — no point crosses PCIe
+  RefWin* h_wins = reinterpret_cast<RefWin*>(b->h_slab);
+  RefBaWin* h_bas = reinterpret_cast<RefBaWin*>(b->h_slab + refSlabPointsOff(W));
+  int* d_nsel = b->d_pcn + (size_t)W * R.levels;
+  for (int w = 0; w < W; w++) {
+    dmvio_hip_tracker* t = win[w].trk;
+    refWinRecord(h_wins[w], t, b->d_pcn + (size_t)w * R.levels, win[w].ref_slot);
+    RefBaWin& A = h_bas[w];
+    A.res_point = S[w].res_point; A.res_target = S[w].res_target; A.newState = S[w].newState; A.active = S[w].active; A.center = S[w].center; A.HdiF = S[w].HdiF;
+    A.n_selected = d_nsel + w; A.n_crowded = t->d_pc_n + dmvio_hip_tracker::REF_BA_CROWDED; A.crowded = t->d_ba_crowded;
+    A.R = S[w].R; A.newest = S[w].F - 1; A.cap = t->ba_crowded_cap; A.pad = 0;
+  }
+  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, refSlabBaBytes(W), hipMemcpyHostToDevice, s));
+  b->last_uploads = 1;
+  // the context's stream behind whatever the BA handles' streams still hold
+  for (dmvio_hip_ba* ba : bl.held)
+    for (int w = 0; w < W; w++)
+      if (win[w].ba == ba) {
+        HIPCHK(hipEventRecord(win[w].trk->ev_ba_ready, S[w].stream));
+        HIPCHK(hipStreamWaitEvent(s, win[w].trk->ev_ba_ready, 0));
+        break;
+      }
+  const RefWin* d_wins = reinterpret_cast<const RefWin*>(b->d_slab);
+  const RefBaWin* d_bas = reinterpret_cast<const RefBaWin*>(b->d_slab + refSlabPointsOff(W));
+  int launches = 0;
+  const unsigned gw = (unsigned)W;
+  const unsigned gr = (unsigned)std::max(1, (max_R + 255) / 256);
+  hipLaunchKernelGGL(k_ref_ba_clear_w, dim3((unsigned)(((n0 + 3) / 4 + 255) / 256), gw), dim3(256), 0, s, d_wins, d_bas, n0, flow_words); launches++;
+  hipLaunchKernelGGL(k_ref_ba_count_w, dim3(gr, gw), dim3(256), 0, s, d_wins, d_bas, R.w[0], R.h[0]); launches++;
+  hipLaunchKernelGGL(k_ref_ba_scatter_w, dim3(gr, gw), dim3(256), 0, s, d_wins, d_bas, R.w[0], R.h[0]); launches++;
+  hipLaunchKernelGGL(k_ref_ba_crowded_w, dim3(gr, gw), dim3(256), 0, s, d_wins, d_bas); launches++;
+  // the last read of a BA handle's arrays is behind us: their streams may go on once it has run
+  hipEvent_t read = win[0].trk->ev_ba_read;
+  HIPCHK(hipEventRecord(read, s));
+  for (dmvio_hip_ba* ba : bl.held)
+    for (int w = 0; w < W; w++)
+      if (win[w].ba == ba) { HIPCHK(hipStreamWaitEvent(S[w].stream, read, 0)); break; }
+  if (R.levels > 1) {
+    const size_t npool = R.total - R.off[1];
+    hipLaunchKernelGGL(k_ref_pool_w, dim3((unsigned)((npool + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
+  }
+  hipLaunchKernelGGL(k_ref_dilate_w, dim3((unsigned)((R.total + 255) / 256), gw), dim3(256), 0, s, d_wins, R); launches++;
+  hipLaunchKernelGGL(k_ref_count_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->frames.built_and_waited()); launches++;
+  hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
+  hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->frames.built_and_waited()); launches++;
+  HIPCHK(hipGetLastError());
+  b->last_launches = launches;
+  HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * (R.levels + 1), hipMemcpyDeviceToHost, s));   // [W][levels] pc_n, then the W selected counts
+  b->last_downloads = 1;
+  HIPCHK(hipStreamSynchronize(s));
+  b->last_waits = 1;
+  for (int w = 0; w < W; w++) {
+    refPublish(win[w].trk, b->h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
+    win[w].n_selected = b->h_pcn[(size_t)W * R.levels + w];
+  }
   return 0;
 }
 

@@ -150,6 +150,23 @@ struct dmvio_hip_graph {
                                                      // flat order (dmvio_hip_graph_set_idepths) are only accepted while the two agree
 };
 
+// What dmvio_hip_tracker_set_ref_from_ba (capi_ref.hip) borrows of a window optimiser (capi_ba.hip, whose handle type stays that unit's own): the handle's lock, and under it
+// the device arrays the getters dmvio_hip_ba_get_res_state / _get_point_acc read, with the handle's stream (work enqueued there is what the arrays wait for).  A pure read:
+// none of the loop's caches is touched.  Lock order of the library: BA handles (in address order), then the context; BA code never takes the context's lock.
+struct dmvio_hip_ba;
+struct DmvBaRefSource {
+  dmvio_hip_ctx* ctx;
+  hipStream_t stream;
+  bool graph_ready, sharded;                  // a graph is set; points sharded over ranks (dmvio_hip_ba_set_comm)
+  int F, N, R;
+  const int *res_point, *res_target;
+  const unsigned char *newState, *active;
+  const float *center, *HdiF;
+};
+void dmv_ba_lock(dmvio_hip_ba* b);
+void dmv_ba_unlock(dmvio_hip_ba* b);
+void dmv_ba_ref_source_locked(dmvio_hip_ba* b, DmvBaRefSource* out);
+
 // the device-resident list of the selector's last selection restricted to the window FullSystem::makeNewTraces walks (capi_select.hip; read by
 // dmvio_hip_immature_add_selected in capi_immature.hip): pixel positions as floats, raster order.  Returns the number of entries or <0.
 struct dmvio_hip_pixel_selector;

@@ -35,20 +35,23 @@ template <class T> __device__ __forceinline__ T* refGl(T* const& member) {
 
 // level 0 of idp / wsp and the flow mask of every window: one thread per four pixels (the planes start on an allocation boundary), the tail pixel by pixel; the mask has
 // one word per 64 pixels, so the first threads of the same grid clear it
-__global__ void __launch_bounds__(256) k_ref_clear_w(const RefWin* __restrict__ wins, const int n0, const int flow_words) {
-  const RefWin& V = wins[blockIdx.y];
-  float* idp = refGl(V.idp);
-  float* wsp = refGl(V.wsp);
-  unsigned long long* mask = refGl(V.flow_mask);
+// (`third`, NULL in the host-array call: one more level-0 plane — the per-pixel counts of the from-BA call)
+__device__ __forceinline__ void refClearBody(float* __restrict__ idp, float* __restrict__ wsp, float* __restrict__ third, unsigned long long* __restrict__ mask, const int n0,
+                                             const int flow_words) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int i = 4 * t;
   if (i + 3 < n0) {
     reinterpret_cast<float4*>(idp)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
     reinterpret_cast<float4*>(wsp)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (third) reinterpret_cast<float4*>(third)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
   } else {
-    for (int k = i; k < n0; k++) { idp[k] = 0.f; wsp[k] = 0.f; }
+    for (int k = i; k < n0; k++) { idp[k] = 0.f; wsp[k] = 0.f; if (third) third[k] = 0.f; }
   }
   if (t < flow_words) mask[t] = 0ull;
+}
+__global__ void __launch_bounds__(256) k_ref_clear_w(const RefWin* __restrict__ wins, const int n0, const int flow_words) {
+  const RefWin& V = wins[blockIdx.y];
+  refClearBody(refGl(V.idp), refGl(V.wsp), nullptr, refGl(V.flow_mask), n0, flow_words);
 }
 
 // rank_lo == 0: the first launch (ranks 0 and 1; a window without a pixel of more than two points has no rank bytes and scatters all its points).  rank_lo >= 2: the
@@ -90,6 +93,52 @@ __global__ void __launch_bounds__(256) k_ref_write_w(const RefWin* __restrict__ 
   const RefWin& V = wins[blockIdx.y];
   refWriteBody<true>(R, V.order, (const float*)refGl(V.idp2), (const float*)refGl(V.wsp2), fs, V.ref_slot, (const int*)refGl(V.tile_base), (const int*)refGl(V.seg),
                      refGl(V.pc), refGl(V.dense), refGl(V.flow_mask));
+}
+
+// ---- dmvio_hip_tracker_set_ref_from_ba_batch: the scatter of every window out of its own resident BA window (ref_kernels.hpp: refBaCountBody / refBaScatterBody /
+// refBaCrowdedBody).  A second record per window, behind the W RefWin records in the slab; the stages from k_ref_pool_w on run on the RefWin records unchanged.
+//   k_ref_ba_clear_w                                 <- k_ref_clear_w, plus the count plane (level 0 of idp2) and the window's two counters
+//   k_ref_ba_count_w, k_ref_ba_scatter_w, k_ref_ba_crowded_w <- the point loop (CoarseTracker.cpp:144-161) over the window's residuals; grid.x covers the largest window
+struct RefBaWin {
+  const int *res_point, *res_target;
+  const unsigned char *newState, *active;
+  const float *center, *HdiF;
+  int* n_selected;     // this window's entry of the batch's table (one download per call)
+  int* n_crowded;      // the tracker's own counter
+  int2* crowded;       // the tracker's crowded list, `cap` entries
+  int R, newest, cap, pad;
+};
+
+__global__ void __launch_bounds__(256) k_ref_ba_clear_w(const RefWin* __restrict__ wins, const RefBaWin* __restrict__ bas, const int n0, const int flow_words) {
+  const RefWin& V = wins[blockIdx.y];
+  const RefBaWin& S = bas[blockIdx.y];
+  refClearBody(refGl(V.idp), refGl(V.wsp), refGl(V.idp2), refGl(V.flow_mask), n0, flow_words);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { *refGl(S.n_selected) = 0; *refGl(S.n_crowded) = 0; }
+}
+
+__global__ void __launch_bounds__(256) k_ref_ba_count_w(const RefWin* __restrict__ wins, const RefBaWin* __restrict__ bas, const int w0, const int h0) {
+  const RefWin& V = wins[blockIdx.y];
+  const RefBaWin& S = bas[blockIdx.y];
+  const int R = S.R;
+  if ((int)(blockIdx.x * blockDim.x) >= R) return;
+  refBaCountBody(R, S.newest, refGl(S.res_target), refGl(S.active), refGl(S.newState), refGl(S.center), w0, h0, reinterpret_cast<int*>(refGl(V.idp2)),
+                 refGl(S.n_selected));
+}
+
+__global__ void __launch_bounds__(256) k_ref_ba_scatter_w(const RefWin* __restrict__ wins, const RefBaWin* __restrict__ bas, const int w0, const int h0) {
+  const RefWin& V = wins[blockIdx.y];
+  const RefBaWin& S = bas[blockIdx.y];
+  const int R = S.R;
+  if ((int)(blockIdx.x * blockDim.x) >= R) return;
+  refBaScatterBody(R, S.newest, refGl(S.res_point), refGl(S.res_target), refGl(S.active), refGl(S.newState), refGl(S.center), refGl(S.HdiF), refGl(V.idp), refGl(V.wsp),
+                   w0, h0, (const int*)reinterpret_cast<int*>(refGl(V.idp2)), refGl(S.n_crowded), refGl(S.crowded), S.cap);
+}
+
+__global__ void __launch_bounds__(256) k_ref_ba_crowded_w(const RefWin* __restrict__ wins, const RefBaWin* __restrict__ bas) {
+  const RefWin& V = wins[blockIdx.y];
+  const RefBaWin& S = bas[blockIdx.y];
+  if ((int)(blockIdx.x * blockDim.x) >= S.R) return;
+  refBaCrowdedBody(refGl(S.res_point), refGl(S.center), refGl(S.HdiF), refGl(V.idp), refGl(V.wsp), (const int*)refGl(S.n_crowded), (const int2*)refGl(S.crowded), S.cap);
 }
 
 }  // namespace dmv

@@ -19,6 +19,16 @@ namespace dmv {
 // launches ranks [0,1] together and every further rank as its own launch behind them: sequential order, no data race.
 // (every stage below is a __device__ body that its single-window kernel here and its W-window kernel in ref_batch_kernels.hpp both call: the arithmetic and its operand
 // order exist once)
+// the level-0 pixel a point lands on (CoarseTracker.cpp:147-148), or -1: the reference would write out of bounds there; and its weight (:149).  Each exists once: the
+// scatter of host arrays below and the scatter out of a resident BA window (refBa*Body) call them
+__device__ __forceinline__ int refPointPixel(const float u, const float v, const int w0, const int h0) {
+  const int ui = (int)(u + 0.5f);
+  const int vi = (int)(v + 0.5f);
+  if (ui < 0 || vi < 0 || ui >= w0 || vi >= h0) return -1;
+  return ui + w0 * vi;
+}
+__device__ __forceinline__ float refPointWeight(const float hdiF) { return sqrtf((float)(1e-3 / ((double)hdiF + 1e-12))); }
+
 __device__ __forceinline__ void refScatterBody(const int n, const float* __restrict__ u, const float* __restrict__ v,
                                                const float* __restrict__ idepth, const float* __restrict__ hdiF,
                                                float* __restrict__ id0, float* __restrict__ ws0, const int w0, const int h0,
@@ -26,18 +36,102 @@ __device__ __forceinline__ void refScatterBody(const int n, const float* __restr
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (rank) { const int r = rank[i]; if (r < rank_lo || r > rank_hi) return; }
-  const int ui = (int)(u[i] + 0.5f);
-  const int vi = (int)(v[i] + 0.5f);
-  if (ui < 0 || vi < 0 || ui >= w0 || vi >= h0) return;  // the reference would write out of bounds here
-  const float weight = sqrtf((float)(1e-3 / ((double)hdiF[i] + 1e-12)));
-  atomicAdd(&id0[ui + w0 * vi], idepth[i] * weight);
-  atomicAdd(&ws0[ui + w0 * vi], weight);
+  const int pix = refPointPixel(u[i], v[i], w0, h0);
+  if (pix < 0) return;
+  const float weight = refPointWeight(hdiF[i]);
+  atomicAdd(&id0[pix], idepth[i] * weight);
+  atomicAdd(&ws0[pix], weight);
 }
 __global__ void __launch_bounds__(256) k_ref_scatter(const int n, const float* __restrict__ u, const float* __restrict__ v,
                                                       const float* __restrict__ idepth, const float* __restrict__ hdiF,
                                                       float* __restrict__ id0, float* __restrict__ ws0, const int w0, const int h0,
                                                       const unsigned char* __restrict__ rank, const int rank_lo, const int rank_hi) {
   refScatterBody(n, u, v, idepth, hdiF, id0, ws0, w0, h0, rank, rank_lo, rank_hi);
+}
+
+// ---- the same scatter out of a resident BA window (dmvio_hip_tracker_set_ref_from_ba): the points are the residuals to the newest keyframe that are active and IN
+// (CoarseTracker.cpp:144-146: `r->efResidual->isActive() && r->target == lastRef`, state IN), read where the window optimiser left them — centerProjectedTo and the
+// point's HdiF — in the graph's residual order.  The host never sees them, so it cannot rank them; the index order per pixel is kept by three launches instead:
+//   (a) refBaCountBody    one thread per residual: the selected points per level-0 pixel, in an int plane (level 0 of the dilated idepth plane, which k_ref_dilate
+//                         overwrites later), and the number of selected residuals
+//   (b) refBaScatterBody  one thread per selected residual: a pixel of at most two points takes the two atomics (0 + a + b commutes); a point of a fuller pixel appends
+//                         (pixel, residual) to the window's crowded list instead (any order)
+//   (c) refBaCrowdedBody  one thread per list entry: the entry with the lowest residual index of its pixel (none lower in the list) adds that pixel's entries in
+//                         ascending index order with plain adds onto the untouched pixel — the sum the rank launches of the host-array call form
+// The list has room for every residual of the window (the caller sizes it), so it cannot overflow; a residual beyond `cap` would be dropped, never written.
+struct RefBaSrc {
+  const int *res_point, *res_target;          // BARes::point / target
+  const unsigned char *newState, *active;     // BARes::newState (0 = IN) / active
+  const float *center, *HdiF;                 // BARes::center (R x 3: u, v, idepth), BAPoints::HdiF
+  int R, newest;                              // residuals of the graph, index of the newest keyframe
+};
+__device__ __forceinline__ bool refBaSelected(const int r, const int R, const int newest, const int* __restrict__ res_target, const unsigned char* __restrict__ active,
+                                              const unsigned char* __restrict__ newState) {
+  return r < R && res_target[r] == newest && active[r] != 0 && newState[r] == 0;
+}
+__device__ __forceinline__ void refBaCountBody(const int R, const int newest, const int* __restrict__ res_target, const unsigned char* __restrict__ active,
+                                               const unsigned char* __restrict__ newState, const float* __restrict__ center, const int w0, const int h0,
+                                               int* __restrict__ cnt, int* __restrict__ n_selected) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool sel = refBaSelected(r, R, newest, res_target, active, newState);
+  if (sel) {
+    const int pix = refPointPixel(center[3 * (size_t)r], center[3 * (size_t)r + 1], w0, h0);
+    if (pix >= 0) atomicAdd(&cnt[pix], 1);
+  }
+  const unsigned long long m = __ballot(sel);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_selected, __popcll(m));
+}
+__device__ __forceinline__ void refBaScatterBody(const int R, const int newest, const int* __restrict__ res_point, const int* __restrict__ res_target,
+                                                 const unsigned char* __restrict__ active, const unsigned char* __restrict__ newState,
+                                                 const float* __restrict__ center, const float* __restrict__ HdiF, float* __restrict__ id0, float* __restrict__ ws0,
+                                                 const int w0, const int h0, const int* __restrict__ cnt, int* __restrict__ n_crowded, int2* __restrict__ crowded,
+                                                 const int cap) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (!refBaSelected(r, R, newest, res_target, active, newState)) return;
+  const float* c3 = center + 3 * (size_t)r;
+  const int pix = refPointPixel(c3[0], c3[1], w0, h0);
+  if (pix < 0) return;
+  if (cnt[pix] <= 2) {
+    const float weight = refPointWeight(HdiF[res_point[r]]);
+    atomicAdd(&id0[pix], c3[2] * weight);
+    atomicAdd(&ws0[pix], weight);
+  } else {
+    const int k = atomicAdd(n_crowded, 1);
+    if (k < cap) crowded[k] = make_int2(pix, r);
+  }
+}
+__device__ __forceinline__ void refBaCrowdedBody(const int* __restrict__ res_point, const float* __restrict__ center, const float* __restrict__ HdiF,
+                                                 float* __restrict__ id0, float* __restrict__ ws0, const int* __restrict__ n_crowded,
+                                                 const int2* __restrict__ crowded, const int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int L = min(*n_crowded, cap);
+  if (i >= L) return;
+  const int2 e = crowded[i];
+  for (int j = 0; j < L; j++) { const int2 o = crowded[j]; if (o.x == e.x && o.y < e.y) return; }   // a lower index of this pixel owns it
+  float a = id0[e.x], b = ws0[e.x];   // zero: (b) left a crowded pixel alone
+  int last = -1;
+  for (;;) {
+    int r = 0x7fffffff;
+    for (int j = 0; j < L; j++) { const int2 o = crowded[j]; if (o.x == e.x && o.y > last && o.y < r) r = o.y; }
+    if (r == 0x7fffffff) break;
+    const float weight = refPointWeight(HdiF[res_point[r]]);
+    a += center[3 * (size_t)r + 2] * weight;
+    b += weight;
+    last = r;
+  }
+  id0[e.x] = a;
+  ws0[e.x] = b;
+}
+__global__ void __launch_bounds__(256) k_ref_ba_count(const RefBaSrc S, const int w0, const int h0, int* __restrict__ cnt, int* __restrict__ n_selected) {
+  refBaCountBody(S.R, S.newest, S.res_target, S.active, S.newState, S.center, w0, h0, cnt, n_selected);
+}
+__global__ void __launch_bounds__(256) k_ref_ba_scatter(const RefBaSrc S, float* __restrict__ id0, float* __restrict__ ws0, const int w0, const int h0,
+                                                         const int* __restrict__ cnt, int* __restrict__ n_crowded, int2* __restrict__ crowded, const int cap) {
+  refBaScatterBody(S.R, S.newest, S.res_point, S.res_target, S.active, S.newState, S.center, S.HdiF, id0, ws0, w0, h0, cnt, n_crowded, crowded, cap);
+}
+__global__ void __launch_bounds__(256) k_ref_ba_crowded(const RefBaSrc S, float* __restrict__ id0, float* __restrict__ ws0, const int* __restrict__ n_crowded,
+                                                         const int2* __restrict__ crowded, const int cap) {
+  refBaCrowdedBody(S.res_point, S.center, S.HdiF, id0, ws0, n_crowded, crowded, cap);
 }
 
 // nested 2x2 sums in the reference's operand order: ((a + b) + c) + d, level by level

@@ -122,6 +122,13 @@ struct dmvio_hip_tracker {
   int pts_cap = 0;
   RefRanker ranker;                            // set_ref: host-side ranking of the points that share a pixel
   std::vector<unsigned char> h_rank;
+  // set_ref_from_ba (capi_ref.hip): the crowded list ((pixel, residual) pairs, room for every residual of the window: grow-only) — its length and the number of
+  // selected residuals stand behind pc_n, d_pc_n[REF_BA_CROWDED] / [REF_BA_SELECTED]; the event the context's stream waits for before it reads a BA handle's arrays, and
+  // the one that handle's stream waits for behind the last read
+  enum { REF_BA_SELECTED = DMV_MAX_LEVELS, REF_BA_CROWDED = DMV_MAX_LEVELS + 1, PC_N_INTS = DMV_MAX_LEVELS + 2 };
+  int2* d_ba_crowded = nullptr;
+  int ba_crowded_cap = 0;
+  hipEvent_t ev_ba_ready = nullptr, ev_ba_read = nullptr;
   // fused evaluation (k_eval_fused)
   float *d_partials = nullptr, *h_tot = nullptr;
   unsigned int* d_arrive = nullptr;   // arrive counter of k_eval_fused (zero between launches)

@@ -292,6 +292,41 @@ typedef struct dmvio_hip_set_ref_window {   /* as dmvio_hip_tracker_set_ref, one
 int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmvio_hip_set_ref_window* win);
 /* what the last call enqueued: kernel launches, host-to-device copies, device-to-host copies, stream waits */
 int dmvio_hip_set_ref_batch_last_work(dmvio_hip_set_ref_batch* b, int* launches, int* uploads, int* downloads, int* waits);
+/* CoarseTracker::setCoarseTrackingRef + makeCoarseDepthL0 (CoarseTracker.cpp:524-538, 138-295) with the point loop (CoarseTracker.cpp:138-161) reading a RESIDENT window
+ * optimiser instead of host arrays: what the loop takes per point — centerProjectedTo of the point's residual to the newest keyframe and efPoint->HdiF — is on the device
+ * when dmvio_hip_ba_optimize (or _optimize_batch, or a linearisation + accumulation) returns, so no point crosses PCIe in either direction and the host does no per-point
+ * work.  It replaces the sequence dmvio_hip_ba_get_res_state + dmvio_hip_ba_get_point_acc, a selection in host code, dmvio_hip_tracker_set_ref / _set_ref_batch.
+ * Selection, at the moment of the call: residual r of the handle's graph yields one template point when res_target[r] == F - 1 (the newest keyframe), active[r] != 0 and
+ * newState[r] == 0 (IN), as dmvio_hip_ba_get_res_state returns them; its values are (u, v, idepth) = center3[r] and hdiF = HdiF[res_point[r]] of dmvio_hip_ba_get_point_acc;
+ * the order is the graph's residual order (the reference's `for fh ... for ph`: residuals are sorted by point).  After the call the tracker holds exactly the bytes
+ * dmvio_hip_tracker_set_ref with those arrays leaves: pc_n, the template lists in the tracker's storage order, the flow-sample mask, the dilated planes and the dense map,
+ * exposure and affine pair, the reference set.  *n_selected (may be NULL) is the number of selected residuals; those that round outside level 0 are dropped from the
+ * template as in the host-array call.  More than 256 points on one level-0 pixel are outside the contract, as they are there (ranks clamp at 255).
+ * The BA handle is only read: every getter and every later call on it returns the bits it would have returned without this call.  It must hold a graph and must not be
+ * sharded over ranks (dmvio_hip_ba_set_comm: such a handle holds a part of the points); one BA handle may feed several trackers.  The one handle accepted without a graph
+ * is a window of ONE keyframe (dmvio_hip_ba_set_window with F == 1: it can hold no residual, so dmvio_hip_ba_set_graph has nothing to take): nothing is selected and the
+ * template ends empty, as dmvio_hip_tracker_set_ref with n == 0 leaves it.
+ * Locks and streams: the call takes the BA handles' locks first (in address order), then the context's; BA entry points never take the context's lock.  The work runs on the
+ * context's stream, ordered against the BA handle's stream by events in both directions (no host wait): behind what the handle's stream holds, and a later
+ * dmvio_hip_ba_set_graph on that stream runs behind the last kernel that reads the handle.
+ * Work per call: NO upload of point data (the single call uploads nothing but kernel arguments, the batched call its W records in ONE copy), a number of kernel launches
+ * that depends neither on W nor on the residual count nor on how many points share a pixel (batched: clear, count, scatter, crowded pixels, then pool, dilate, count, scan,
+ * write — 9, 8 for a pyramid of one level), ONE download (pc_n and the selected counts) and ONE wait; dmvio_hip_set_ref_batch_last_work reports the four figures of the
+ * batched call.  max_points_per_window of the batch handle does NOT limit this call (it sizes the point arrays of dmvio_hip_tracker_set_ref_batch; here there are none).
+ * Host-array and from-BA calls, single and batched, may be mixed freely on one tracker and on one batch handle.
+ * Refused as a whole, with a message, before anything is enqueued or any tracker touched: a NULL handle, tracker, BA handle or window array; a tracker or BA handle of
+ * another context; a BA handle without a graph or sharded over ranks; ref_slot out of range; W < 0 or W > max_windows; the same tracker named twice.  W == 0 returns 0. */
+int dmvio_hip_tracker_set_ref_from_ba(dmvio_hip_tracker* trk, dmvio_hip_ba* ba, int ref_slot, float ref_exposure, double ref_aff_a, double ref_aff_b,
+                                      int* n_selected /* may be NULL */);
+typedef struct dmvio_hip_set_ref_ba_window {   /* as dmvio_hip_tracker_set_ref_from_ba, one window */
+  dmvio_hip_tracker* trk;
+  dmvio_hip_ba* ba;
+  int ref_slot;
+  float ref_exposure;
+  double ref_aff_a, ref_aff_b;
+  int n_selected;   /* out */
+} dmvio_hip_set_ref_ba_window;
+int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, dmvio_hip_set_ref_ba_window* win);
 /* FullSystem::trackNewCoarse (FullSystem.cpp:300-539), visual-only path without IMU hint:
  *  - dmvio_hip_make_track_hypotheses builds lastF_2_fh_tries (:364-402: constant / double / half / zero motion, zero motion from the
  *    keyframe, 26 small rotations) from the camToWorld poses of the last two frames and of the reference keyframe; returns the count (31);

@@ -95,6 +95,13 @@ class CoarseTracker {
     refSlot_ = refSlot; refFrameID = frameID; lastRef_aff_g2l = aff_g2l;
     return true;
   }
+  /* the same with the points read from a resident window optimiser (dmvio_hip_tracker_set_ref_from_ba): the residuals into its newest keyframe that are active and IN,
+   * in graph order; nothing is gathered on the host.  nSelected (may be NULL): how many there were */
+  bool setCoarseTrackingRefFromBA(dmvio_hip_ba* ba, int refSlot, int frameID, float ab_exposure, const AffLight& aff_g2l, int* nSelected = nullptr) {
+    if (!trk_ || dmvio_hip_tracker_set_ref_from_ba(trk_, ba, refSlot, ab_exposure, aff_g2l.a, aff_g2l.b, nSelected) != 0) return false;
+    refSlot_ = refSlot; refFrameID = frameID; lastRef_aff_g2l = aff_g2l;
+    return true;
+  }
   /* idepth[lvl] / weightSums[lvl] of the current template (w_lvl * h_lvl floats each): the arrays debugPlotIDepthMap / debugPlotIDepthMapFloat read (CoarseTracker.cpp:772-880) */
   bool idepthMap(int lvl, std::vector<float>& idepth, std::vector<float>& weightSums) const {
     if (!trk_ || lvl < 0 || lvl >= frames_.pyrLevelsUsed()) return false;
@@ -657,6 +664,27 @@ class SetRefBatch {
       win[i].n = (int)w.u.size(); win[i].u = w.u.data(); win[i].v = w.v.data(); win[i].idepth = w.idepth.data(); win[i].hdiF = w.hdiF.data();
     }
     return dmvio_hip_tracker_set_ref_batch(b_, (int)win.size(), win.data()) == 0;
+  }
+  struct BaWindow {
+    const CoarseTracker* tracker;
+    dmvio_hip_ba* ba;            /* the resident window the points are read from (dmvio_hip_tracker_set_ref_from_ba_batch) */
+    int refSlot;
+    float ref_ab_exposure;
+    AffLight ref_aff_g2l;
+    int nSelected;               /* out */
+  };
+  bool setCoarseTrackingRefFromBA(std::vector<BaWindow>& windows) {
+    if (!b_) return false;
+    std::vector<dmvio_hip_set_ref_ba_window> win(windows.size());
+    for (size_t i = 0; i < windows.size(); i++) {
+      const BaWindow& w = windows[i];
+      if (!w.tracker) return false;
+      win[i].trk = w.tracker->handle(); win[i].ba = w.ba; win[i].ref_slot = w.refSlot; win[i].ref_exposure = w.ref_ab_exposure;
+      win[i].ref_aff_a = w.ref_aff_g2l.a; win[i].ref_aff_b = w.ref_aff_g2l.b; win[i].n_selected = 0;
+    }
+    if (dmvio_hip_tracker_set_ref_from_ba_batch(b_, (int)win.size(), win.data()) != 0) return false;
+    for (size_t i = 0; i < windows.size(); i++) windows[i].nSelected = win[i].n_selected;
+    return true;
   }
   bool lastWork(int& launches, int& uploads, int& downloads, int& waits) const { return b_ && dmvio_hip_set_ref_batch_last_work(b_, &launches, &uploads, &downloads, &waits) == 0; }
   dmvio_hip_set_ref_batch* handle() const { return b_; }
