@@ -130,6 +130,20 @@ class SetRefBaWindow(C.Structure):
                 ("n_selected", C.c_int)]
 
 
+class InitializerPointsWindow(C.Structure):
+    """dmvio_hip_initializer_points_window (include/dmvio_hip.h): one window of dmvio_hip_initializer_set_points_batch."""
+    _fields_ = [("ini", C.c_void_p), ("n", C.c_int), ("u", c_f), ("v", c_f), ("iR", c_f), ("isGood", C.POINTER(C.c_ubyte)), ("energy2", c_f), ("outlierTH", c_f)]
+
+
+class InitializerWindow(C.Structure):
+    """dmvio_hip_initializer_window (include/dmvio_hip.h): one window of dmvio_hip_initializer_calc_res_and_gs_batch."""
+    _fields_ = [("ini", C.c_void_p), ("lvl", C.c_int), ("first_slot", C.c_int), ("new_slot", C.c_int), ("Ki9", C.c_double * 9), ("fxfycxcy_lvl", C.c_float * 4),
+                ("refToNew7", C.c_double * 7), ("aff_ab", C.c_double * 2), ("idepth_new", c_f), ("alphaW", C.c_float), ("alphaK", C.c_float),
+                ("couplingWeight", C.c_float), ("priorY", C.c_double), ("priorX", C.c_double), ("H_out64", C.c_float * 64), ("b_out8", C.c_float * 8),
+                ("H_sc64", C.c_float * 64), ("b_sc8", C.c_float * 8), ("res3", C.c_float * 3), ("energy_new2", c_f), ("isGood_new", C.POINTER(C.c_ubyte)),
+                ("maxstep", c_f), ("lastHessian_new", c_f), ("JbBuffer_new10", c_f)]
+
+
 def _sig(L):
     vp = C.c_void_p
     L.dmvio_hip_last_error.restype = C.c_char_p
@@ -192,6 +206,11 @@ def _sig(L):
     L.dmvio_hip_initializer_set_points.argtypes = [vp, C.c_int, c_f, c_f, c_f, c_u8, c_f, c_f]
     L.dmvio_hip_initializer_calc_res_and_gs.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_d, c_f, c_d, c_d, c_f, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double,
                                                         c_f, c_f, c_f, c_f, c_f, c_f, c_u8, c_f, c_f, c_f]
+    L.dmvio_hip_initializer_batch_create.argtypes = [vp, C.c_int]; L.dmvio_hip_initializer_batch_create.restype = vp
+    L.dmvio_hip_initializer_batch_destroy.argtypes = [vp]; L.dmvio_hip_initializer_batch_destroy.restype = None
+    L.dmvio_hip_initializer_set_points_batch.argtypes = [vp, C.c_int, C.POINTER(InitializerPointsWindow)]
+    L.dmvio_hip_initializer_calc_res_and_gs_batch.argtypes = [vp, C.c_int, C.POINTER(InitializerWindow)]
+    L.dmvio_hip_initializer_batch_last_work.argtypes = [vp, c_i, c_i, c_i, c_i]
     L.dmvio_hip_undistorter_create.restype = vp
     L.dmvio_hip_undistorter_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f, c_f]
     L.dmvio_hip_undistorter_destroy.argtypes = [vp]
@@ -968,6 +987,108 @@ class CoarseInitializerHip:
             for k in ("energy_new", "isGood_new", "maxstep", "lastHessian_new", "JbBuffer_new"):
                 del o[k]
         return o
+
+
+class InitializerBatchHip:
+    """calcResAndGS (CoarseInitializer.cpp:331-624) of W CoarseInitializerHip handles of one context per call (dmvio_hip_initializer_calc_res_and_gs_batch): every window's
+    outputs are its single call's bits; one upload, two launches, one download and one wait per calc call (last_work()).  For tests and tools."""
+
+    PER_POINT = ("energy_new", "isGood_new", "maxstep", "lastHessian_new", "JbBuffer_new")
+
+    def __init__(self, ctx, max_windows=64):
+        self.ctx, self.L = ctx, ctx.L
+        p = self.L.dmvio_hip_initializer_batch_create(ctx.p, int(max_windows))
+        if not p:
+            raise HipLibraryError("dmvio_hip_initializer_batch_create: %s" % _err(self.L))
+        self.p = C.c_void_p(p)
+        self.max_windows = int(max_windows)
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.dmvio_hip_initializer_batch_destroy(self.p); self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def grid(n):
+        """workgroups that serve a window of n points: the single call's grid"""
+        return max(1, min(256, (int(n) + 255) // 256))
+
+    @staticmethod
+    def pack_points(windows):
+        """windows: (CoarseInitializerHip or None, pts) pairs, pts as CoarseInitializerHip.set_points takes them -> (array of dmvio_hip_initializer_points_window, what it points into)"""
+        arr = (InitializerPointsWindow * max(len(windows), 1))()
+        keep = []
+        for x, (ini, pts) in zip(arr, windows):
+            a = [np.ascontiguousarray(pts[k], dtype=np.float32) for k in ("u", "v", "iR", "energy", "outlierTH")]
+            good = np.ascontiguousarray(pts["isGood"], dtype=np.uint8)
+            keep.append((a, good))
+            x.ini = None if ini is None else ini.p
+            x.n = len(a[0]); x.u, x.v, x.iR, x.energy2, x.outlierTH = [_f(k) for k in a]; x.isGood = good.ctypes.data_as(c_u8)
+        return arr, keep
+
+    def set_points(self, windows, W=None):
+        """one dmvio_hip_initializer_set_points_batch call (see pack_points()); W overrides the window count handed to the library"""
+        arr, keep = self.pack_points(windows)
+        _chk(self.L, self.L.dmvio_hip_initializer_set_points_batch(self.p, len(windows) if W is None else W, arr), "initializer_set_points_batch")
+        for ini, pts in windows:
+            ini.n = len(pts["u"])
+
+    def pack(self, windows):
+        """windows: one dict per handle with ini (a CoarseInitializerHip or None), lvl, first_slot, new_slot, Ki9, fxfycxcy_lvl, refToNew7, aff_ab, idepth_new (None: NULL) and
+        optionally alphaW, alphaK, couplingWeight, priorY, priorX (CoarseInitializerHip.calcResAndGS's defaults) and per_point (True; False: the five per-point pointers are
+        NULL) -> (array of dmvio_hip_initializer_window, the per-window output dicts its pointers reach into, further arrays to keep alive)"""
+        arr = (InitializerWindow * max(len(windows), 1))()
+        outs, keep = [], []
+        for x, d in zip(arr, windows):
+            ini = d["ini"]
+            n = 0 if ini is None else ini.n
+            x.ini = None if ini is None else ini.p
+            x.lvl, x.first_slot, x.new_slot = int(d["lvl"]), int(d["first_slot"]), int(d["new_slot"])
+            x.Ki9[:] = [float(v) for v in np.asarray(d["Ki9"], dtype=np.float64).reshape(-1)]
+            x.fxfycxcy_lvl[:] = [float(v) for v in np.asarray(d["fxfycxcy_lvl"], dtype=np.float32)]
+            x.refToNew7[:] = [float(v) for v in np.asarray(d["refToNew7"], dtype=np.float64)]
+            x.aff_ab[:] = [float(v) for v in d["aff_ab"]]
+            idn = None if d["idepth_new"] is None else np.ascontiguousarray(d["idepth_new"], dtype=np.float32)
+            keep.append(idn)
+            x.idepth_new = None if idn is None else _f(idn)
+            x.alphaW, x.alphaK, x.couplingWeight = float(d.get("alphaW", 150 * 150)), float(d.get("alphaK", 2.5 * 2.5)), float(d.get("couplingWeight", 1.0))
+            x.priorY, x.priorX = float(d.get("priorY", 0.0)), float(d.get("priorX", 0.0))
+            o = {}
+            if d.get("per_point", True):
+                o = dict(energy_new=np.zeros((n, 2), np.float32), isGood_new=np.zeros(n, np.uint8), maxstep=np.zeros(n, np.float32), lastHessian_new=np.zeros(n, np.float32),
+                         JbBuffer_new=np.zeros((n, 10), np.float32))
+                x.energy_new2, x.maxstep, x.lastHessian_new, x.JbBuffer_new10 = _f(o["energy_new"]), _f(o["maxstep"]), _f(o["lastHessian_new"]), _f(o["JbBuffer_new"])
+                x.isGood_new = o["isGood_new"].ctypes.data_as(c_u8)
+            outs.append(o)
+        return arr, outs, keep
+
+    @staticmethod
+    def unpack(arr, outs):
+        """the reductions of every window out of the structure array, beside its per-point arrays: the dicts CoarseInitializerHip.calcResAndGS returns"""
+        res = []
+        for x, o in zip(arr, outs):
+            r = dict(H=np.array(x.H_out64[:], np.float32).reshape(8, 8), b=np.array(x.b_out8[:], np.float32), Hsc=np.array(x.H_sc64[:], np.float32).reshape(8, 8),
+                     bsc=np.array(x.b_sc8[:], np.float32), res3=np.array(x.res3[:], np.float32))
+            r.update(o)
+            res.append(r)
+        return res
+
+    def calc(self, windows, W=None):
+        """one dmvio_hip_initializer_calc_res_and_gs_batch call (see pack()); W overrides the window count handed to the library"""
+        arr, outs, keep = self.pack(windows)
+        _chk(self.L, self.L.dmvio_hip_initializer_calc_res_and_gs_batch(self.p, len(windows) if W is None else W, arr), "initializer_calc_res_and_gs_batch")
+        return self.unpack(arr, outs)
+
+    def last_work(self):
+        """(kernel launches, uploads, downloads, stream waits) of the last calc call"""
+        v = [C.c_int(0) for _ in range(4)]
+        _chk(self.L, self.L.dmvio_hip_initializer_batch_last_work(self.p, *[C.byref(x) for x in v]), "initializer_batch_last_work")
+        return tuple(x.value for x in v)
 
 
 class ImmaturePointsHip:

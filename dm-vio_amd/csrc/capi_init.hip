@@ -1,8 +1,9 @@
-// C ABI of the initializer hot function (include/dmvio_hip.h): CoarseInitializer::calcResAndGS.
+// C ABI of the initializer hot function (include/dmvio_hip.h): CoarseInitializer::calcResAndGS, one window per call and W windows per call.
 #include <vector>
 #include <cmath>
 #include <cstring>
 #include <cstdio>
+#include <algorithm>
 #include "../../include/dmvio_hip.h"
 #include "internal.h"
 #include "lie_dev.h"
@@ -19,11 +20,31 @@ struct dmvio_hip_initializer {
   float *d_in = nullptr, *d_res = nullptr, *h_in = nullptr, *h_res = nullptr;
   float *d_partials = nullptr, *d_out = nullptr, *h_out = nullptr;
   bool upload_pending = false;
+  // where the point set of the last set_points lives on the device: d_in, or, after dmvio_hip_initializer_set_points_batch, this handle's part of that batch's slab (the
+  // layout of d_in; `owner` is that batch).  Both are only touched under the context's lock.
+  float* pts = nullptr;
+  dmvio_hip_initializer_batch* owner = nullptr;
   std::vector<void*> allocs;
 };
 static inline size_t padn(int n) { return ((size_t)n + 63) & ~(size_t)63; }   // every array of a slab starts on a 256-byte boundary
 enum { IN_FLOATS = 7, RES_FLOATS = 14 };   // per point, + one byte each (isGood / isGood_new) at the end of the slab
 enum { INIT_MAX_BLOCKS = 256 };
+static inline int initGrid(int n) { return std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256)); }
+
+// W windows per call.  The batch owns what a call needs besides the handles: a pinned slab and its device copy for the point sets of set_points_batch (the handles named there
+// read their points from it until their next set_points: `tenants`), a pinned slab and its device copy for the records and idepth_new arrays of a calc call, the partials, and
+// the sums and per-point results with the pinned slab they are downloaded into.  All grow on demand and are kept.
+struct dmvio_hip_initializer_batch {
+  dmvio_hip_ctx* ctx = nullptr;
+  int max_windows = 0;
+  float *h_pts = nullptr, *d_pts = nullptr; size_t pts_cap = 0;     // floats
+  bool pts_pending = false;                                          // h_pts may still be read by the upload of the last set_points_batch
+  std::vector<dmvio_hip_initializer*> tenants;
+  float *h_up = nullptr, *d_up = nullptr; size_t up_cap = 0;        // floats: [W InitWin | idepth_new of every window]
+  float* d_part = nullptr; size_t part_cap = 0;                      // floats
+  float *h_dn = nullptr, *d_dn = nullptr; size_t dn_cap = 0;        // floats: [W x IN_PART sums | results of the windows that asked for any | results of the others]
+  int work[4] = {0, 0, 0, 0};                                        // launches, uploads, downloads, waits of the last calc call
+};
 
 template <class T>
 static int nalloc(dmvio_hip_initializer* m, T** p, size_t n) {
@@ -36,6 +57,137 @@ static int nalloc(dmvio_hip_initializer* m, T** p, size_t n) {
   return 0;
 }
 #define INIT_READY(m) do { if (!(m)) return failmsg("null initializer handle"); HIPCHK(hipSetDevice((m)->ctx->device)); } while (0)
+
+// a device buffer (and, h != NULL, its pinned twin) of at least `need` floats; what it held is not kept.  The stream is drained before the old one is freed.
+static int initGrow(float** h, float** d, size_t* cap, size_t need, hipStream_t s) {
+  if (need <= *cap) return 0;
+  HIPCHK(hipStreamSynchronize(s));
+  if (*d) { HIPCHK(hipFree(*d)); *d = nullptr; }
+  if (h && *h) { HIPCHK(hipHostFree(*h)); *h = nullptr; }
+  *cap = 0;
+  const size_t want = std::max<size_t>(need + need / 2, 1024);
+  HIPCHK(hipMalloc((void**)d, sizeof(float) * want));
+  if (h) HIPCHK(hipHostMalloc((void**)h, sizeof(float) * want, hipHostMallocDefault));
+  *cap = want;
+  return 0;
+}
+// the handle leaves its batch's slab.  keep: its point set goes back into its own d_in first (device to device, stream-ordered); otherwise it is about to be replaced.
+static int initLeaveBatch(dmvio_hip_initializer* m, bool keep) {
+  if (!m->owner) return 0;
+  if (keep && m->n > 0) {
+    const size_t P = padn(m->n);
+    HIPCHK(hipMemcpyAsync(m->d_in, m->pts, sizeof(float) * 6 * P, hipMemcpyDeviceToDevice, m->ctx->stream));
+    HIPCHK(hipMemcpyAsync(m->d_in + 7 * P, m->pts + 7 * P, m->n, hipMemcpyDeviceToDevice, m->ctx->stream));
+  }
+  std::vector<dmvio_hip_initializer*>& t = m->owner->tenants;
+  t.erase(std::remove(t.begin(), t.end(), m), t.end());
+  m->owner = nullptr;
+  m->pts = m->d_in;
+  return 0;
+}
+
+// [u | v | iR | outlierTH | energy(2) | (idepth_new) | isGood] of n points, the layout of d_in
+static void initPackPoints(float* dst, int n, const float* u, const float* v, const float* iR, const unsigned char* isGood, const float* energy2, const float* outlierTH) {
+  const size_t P = padn(n);
+  memcpy(dst, u, sizeof(float) * n); memcpy(dst + P, v, sizeof(float) * n); memcpy(dst + 2 * P, iR, sizeof(float) * n);
+  memcpy(dst + 3 * P, outlierTH, sizeof(float) * n); memcpy(dst + 4 * P, energy2, sizeof(float) * 2 * n);
+  memcpy(dst + 7 * P, isGood, n);
+}
+// k_init_partial reads the first image at (u + dx, v + dy), dx, dy in [-2, 2], and one pixel right / below, without a test: CoarseInitializer::setFirst never
+// places a point where that leaves the level, and a point set that does is refused (the staging slab still holds u, v and isGood of the last set_points).
+// Returns the first offending point or -1.
+static int initFirstPointOutside(const dmvio_hip_initializer* m, int lvl) {
+  const dmvio_hip_ctx* c = m->ctx;
+  const size_t P = padn(m->n);
+  const float *u = m->h_in, *v = m->h_in + P;
+  const unsigned char* good = reinterpret_cast<const unsigned char*>(m->h_in + 7 * P);
+  const float umax = (float)(c->wl[lvl] - 3), vmax = (float)(c->hl[lvl] - 3);
+  for (int i = 0; i < m->n; i++)
+    if (good[i] && !(u[i] >= 2.0f && u[i] < umax && v[i] >= 2.0f && v[i] < vmax)) return i;
+  return -1;
+}
+static std::string initOutsideMsg(const char* who, const dmvio_hip_initializer* m, int lvl, int i) {
+  const dmvio_hip_ctx* c = m->ctx;
+  char msg[224];
+  snprintf(msg, sizeof(msg), "%sgood point %d at (%g, %g) outside [2, %d) x [2, %d) of level %d", who, i, (double)m->h_in[i], (double)m->h_in[padn(m->n) + i], c->wl[lvl] - 3,
+           c->hl[lvl] - 3, lvl);
+  return msg;
+}
+// alpha energy (CoarseInitializer.cpp:497-535); EAlpha.A is identically 0 in the reference.  Returns alphaOpt.
+static float initAlpha(const Pose& T, int n, float alphaW, float alphaK, float* alphaEnergy_out) {
+  const double tsq = T.t[0] * T.t[0] + T.t[1] * T.t[1] + T.t[2] * T.t[2];
+  float alphaEnergy = alphaW * (0.0f + tsq * n);
+  float alphaOpt;
+  if (alphaEnergy > alphaK * n) { alphaOpt = 0; alphaEnergy = alphaK * n; }
+  else alphaOpt = alphaW;
+  *alphaEnergy_out = alphaEnergy;
+  return alphaOpt;
+}
+// the uniform inputs of the evaluation kernel
+static InitArgs initMakeArgs(const dmvio_hip_ctx* c, int lvl, const double Ki9[9], const float fxfycxcy_lvl[4], const Pose& T, const double aff_ab[2], int n, float alphaW,
+                             float alphaK, float couplingWeight) {
+  InitArgs A;
+  double Rd[9];
+  quatToR(T.q, Rd);
+  for (int r = 0; r < 3; r++)
+    for (int q = 0; q < 3; q++) A.RKi[r * 3 + q] = (float)(Rd[r * 3 + 0] * Ki9[q] + Rd[r * 3 + 1] * Ki9[3 + q] + Rd[r * 3 + 2] * Ki9[6 + q]);
+  for (int i = 0; i < 3; i++) A.t[i] = (float)T.t[i];
+  A.aff0 = (float)std::exp(aff_ab[0]); A.aff1 = (float)aff_ab[1];
+  A.fxl = fxfycxcy_lvl[0]; A.fyl = fxfycxcy_lvl[1]; A.cxl = fxfycxcy_lvl[2]; A.cyl = fxfycxcy_lvl[3];
+  A.wl = c->wl[lvl]; A.hl = c->hl[lvl];
+  A.couplingWeight = couplingWeight; A.huberTH = 9.0f;
+  float alphaEnergy;
+  A.alphaOpt = initAlpha(T, n, alphaW, alphaK, &alphaEnergy);
+  return A;
+}
+// where the kernel finds the n points of a handle and leaves their results (`res`: the layout of d_res)
+static InitPts initMakePts(int n, float* in, const float* idepth_new, float* res) {
+  const size_t PN = padn(n);
+  InitPts P;
+  P.n = n; P.u = in; P.v = in + PN; P.iR = in + 2 * PN; P.outlierTH = in + 3 * PN; P.energy = in + 4 * PN; P.idepth_new = idepth_new;
+  P.isGood = reinterpret_cast<unsigned char*>(in + 7 * PN);
+  P.energy_new = res; P.maxstep = res + 2 * PN; P.lastHessian_new = res + 3 * PN; P.JbBuffer_new = res + 4 * PN;
+  P.isGood_new = reinterpret_cast<unsigned char*>(res + 14 * PN);
+  return P;
+}
+// the per-point results from the downloaded slab (the layout of d_res) into the caller's arrays; each may be NULL
+static void initDeliverPoints(const float* h_res, int n, float* energy_new2, unsigned char* isGood_new, float* maxstep, float* lastHessian_new, float* JbBuffer_new10) {
+  const size_t PN = padn(n);
+  if (energy_new2) memcpy(energy_new2, h_res, sizeof(float) * 2 * n);
+  if (maxstep) memcpy(maxstep, h_res + 2 * PN, sizeof(float) * n);
+  if (JbBuffer_new10) memcpy(JbBuffer_new10, h_res + 4 * PN, sizeof(float) * 10 * n);
+  if (isGood_new) memcpy(isGood_new, h_res + 14 * PN, n);
+  if (lastHessian_new) {
+    // written for accepted points only, like the reference's member (CoarseInitializer.cpp:560): the kernel leaves the other entries of the slab as an earlier call,
+    // laid out for another n, left them, so they are not the caller's to see
+    const float* lh = h_res + 3 * PN;
+    const unsigned char* acc = reinterpret_cast<const unsigned char*>(h_res + 14 * PN);
+    for (int i = 0; i < n; i++) if (acc[i]) lastHessian_new[i] = lh[i];
+  }
+}
+// the host tail of calcResAndGS, of the single and of the batched call: the alpha energy and alphaOpt (:497-535), the two upper triangles unpacked, then :582-613
+static void initHostTail(const Pose& T, int n, float alphaW, float alphaK, double priorY, double priorX, const float* sums /* IN_PART */, float* H_out64, float* b_out8,
+                         float* H_sc64, float* b_sc8, float res3[3]) {
+  float alphaEnergy;
+  const float alphaOpt = initAlpha(T, n, alphaW, alphaK, &alphaEnergy);
+  float M[2][9][9];
+  for (int w = 0; w < 2; w++) {
+    int k = 0;
+    for (int r = 0; r < 9; r++) for (int q = r; q < 9; q++) { M[w][r][q] = M[w][q][r] = sums[45 * w + k]; k++; }
+  }
+  for (int r = 0; r < 8; r++) {
+    for (int q = 0; q < 8; q++) { H_out64[r * 8 + q] = M[0][r][q]; H_sc64[r * 8 + q] = M[1][r][q]; }
+    b_out8[r] = M[0][r][8]; b_sc8[r] = M[1][r][8];
+  }
+  H_out64[0] += alphaOpt * n; H_out64[9] += alphaOpt * n; H_out64[18] += alphaOpt * n;
+  double lg[6];
+  poseLogHost(T, lg);
+  const float tlog[3] = {(float)lg[0], (float)lg[1], (float)lg[2]};
+  b_out8[0] += tlog[0] * alphaOpt * n; b_out8[1] += tlog[1] * alphaOpt * n; b_out8[2] += tlog[2] * alphaOpt * n;
+  H_out64[9] += priorY; b_out8[1] += priorY * T.t[1];
+  H_out64[0] += priorX; b_out8[0] += priorX * T.t[0];
+  res3[0] = sums[90]; res3[1] = alphaEnergy; res3[2] = (float)(2 * (size_t)n);   // accE[0].num: every point once per loop (:351-470, :503-516)
+}
 
 extern "C" {
 
@@ -56,11 +208,16 @@ dmvio_hip_initializer* dmvio_hip_initializer_create(dmvio_hip_ctx* ctx, int capa
     delete m;
     return nullptr;
   }
+  m->pts = m->d_in;
   return m;
 }
 void dmvio_hip_initializer_destroy(dmvio_hip_initializer* m) {
   if (!m) return;
   hipSetDevice(m->ctx->device);
+  {
+    std::lock_guard<std::mutex> lk(m->ctx->mu);
+    initLeaveBatch(m, false);
+  }
   hipStreamSynchronize(m->ctx->stream);
   for (void* p : m->allocs) hipFree(p);
   if (m->h_out) hipHostFree(m->h_out);
@@ -74,12 +231,12 @@ int dmvio_hip_initializer_set_points(dmvio_hip_initializer* m, int n, const floa
                                      const float* energy2, const float* outlierTH) {
   INIT_READY(m);
   if (n < 0 || n > m->capacity || !u || !v || !iR || !isGood || !energy2 || !outlierTH) return failmsg("initializer_set_points: bad argument");
+  std::lock_guard<std::mutex> lk(m->ctx->mu);   // (the handle may sit in a batch's slab: that list is the context's)
   hipStream_t s = m->ctx->stream;
   if (m->upload_pending) { HIPCHK(hipStreamSynchronize(s)); m->upload_pending = false; }   // the staging buffer is still being read by the previous upload
+  if (int r = initLeaveBatch(m, false)) return r;
   const size_t P = padn(n);
-  memcpy(m->h_in, u, sizeof(float) * n); memcpy(m->h_in + P, v, sizeof(float) * n); memcpy(m->h_in + 2 * P, iR, sizeof(float) * n);
-  memcpy(m->h_in + 3 * P, outlierTH, sizeof(float) * n); memcpy(m->h_in + 4 * P, energy2, sizeof(float) * 2 * n);
-  memcpy(m->h_in + 7 * P, isGood, n);
+  initPackPoints(m->h_in, n, u, v, iR, isGood, energy2, outlierTH);
   // [u | v | iR | outlierTH | energy] and, behind the gap idepth_new fills per evaluation, isGood: two copies, no wait — the evaluation's own synchronisation covers them
   HIPCHK(hipMemcpyAsync(m->d_in, m->h_in, sizeof(float) * 6 * P, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(m->d_in + 7 * P, m->h_in + 7 * P, n, hipMemcpyHostToDevice, s));
@@ -99,51 +256,18 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   if (lvl < 0 || lvl >= c->levels || first_slot < 0 || first_slot >= c->n_slots || new_slot < 0 || new_slot >= c->n_slots) return failmsg("initializer_calc: level / slot out of range");
   const int n = m->n;
   {
-    // k_init_partial reads the first image at (u + dx, v + dy), dx, dy in [-2, 2], and one pixel right / below, without a test: CoarseInitializer::setFirst never
-    // places a point where that leaves the level, and a point set that does is refused here (the staging slab still holds u, v and isGood of the last set_points)
-    const size_t P = padn(n);
-    const float *u = m->h_in, *v = m->h_in + P;
-    const unsigned char* good = reinterpret_cast<const unsigned char*>(m->h_in + 7 * P);
-    const float umax = (float)(c->wl[lvl] - 3), vmax = (float)(c->hl[lvl] - 3);
-    for (int i = 0; i < n; i++)
-      if (good[i] && !(u[i] >= 2.0f && u[i] < umax && v[i] >= 2.0f && v[i] < vmax)) {
-        char msg[192];
-        snprintf(msg, sizeof(msg), "initializer_calc: good point %d at (%g, %g) outside [2, %d) x [2, %d) of level %d", i, (double)u[i], (double)v[i], c->wl[lvl] - 3,
-                 c->hl[lvl] - 3, lvl);
-        return failmsg(msg);
-      }
+    const int i = initFirstPointOutside(m, lvl);
+    if (i >= 0) return failmsg(initOutsideMsg("initializer_calc: ", m, lvl, i));
   }
   if (lvl == 0) { if (int r = dmv_ensure_row_major_locked(c, first_slot)) return r; if (int r = dmv_ensure_row_major_locked(c, new_slot)) return r; }
   hipStream_t s = c->stream;
   const Pose T = poseFrom7(refToNew7);
-  InitArgs A;
-  {
-    double Rd[9];
-    quatToR(T.q, Rd);
-    for (int r = 0; r < 3; r++)
-      for (int q = 0; q < 3; q++) A.RKi[r * 3 + q] = (float)(Rd[r * 3 + 0] * Ki9[q] + Rd[r * 3 + 1] * Ki9[3 + q] + Rd[r * 3 + 2] * Ki9[6 + q]);
-    for (int i = 0; i < 3; i++) A.t[i] = (float)T.t[i];
-  }
-  A.aff0 = (float)std::exp(aff_ab[0]); A.aff1 = (float)aff_ab[1];
-  A.fxl = fxfycxcy_lvl[0]; A.fyl = fxfycxcy_lvl[1]; A.cxl = fxfycxcy_lvl[2]; A.cyl = fxfycxcy_lvl[3];
-  A.wl = c->wl[lvl]; A.hl = c->hl[lvl];
-  A.couplingWeight = couplingWeight; A.huberTH = 9.0f;
-  // alpha energy (CoarseInitializer.cpp:497-535); EAlpha.A is identically 0 in the reference
-  const double tsq = T.t[0] * T.t[0] + T.t[1] * T.t[1] + T.t[2] * T.t[2];
-  float alphaEnergy = alphaW * (0.0f + tsq * n);
-  float alphaOpt;
-  if (alphaEnergy > alphaK * n) { alphaOpt = 0; alphaEnergy = alphaK * n; }
-  else alphaOpt = alphaW;
-  A.alphaOpt = alphaOpt;
+  const InitArgs A = initMakeArgs(c, lvl, Ki9, fxfycxcy_lvl, T, aff_ab, n, alphaW, alphaK, couplingWeight);
   const size_t PN = padn(n);
   memcpy(m->h_in + 6 * PN, idepth_new, sizeof(float) * n);
-  HIPCHK(hipMemcpyAsync(m->d_in + 6 * PN, m->h_in + 6 * PN, sizeof(float) * n, hipMemcpyHostToDevice, s));
-  InitPts P;
-  P.n = n; P.u = m->d_in; P.v = m->d_in + PN; P.iR = m->d_in + 2 * PN; P.outlierTH = m->d_in + 3 * PN; P.energy = m->d_in + 4 * PN; P.idepth_new = m->d_in + 6 * PN;
-  P.isGood = reinterpret_cast<unsigned char*>(m->d_in + 7 * PN);
-  P.energy_new = m->d_res; P.maxstep = m->d_res + 2 * PN; P.lastHessian_new = m->d_res + 3 * PN; P.JbBuffer_new = m->d_res + 4 * PN;
-  P.isGood_new = reinterpret_cast<unsigned char*>(m->d_res + 14 * PN);
-  const int G = std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256));
+  HIPCHK(hipMemcpyAsync(m->pts + 6 * PN, m->h_in + 6 * PN, sizeof(float) * n, hipMemcpyHostToDevice, s));
+  const InitPts P = initMakePts(n, m->pts, m->pts + 6 * PN, m->d_res);
+  const int G = initGrid(n);
   hipLaunchKernelGGL(k_init_partial, dim3(G), dim3(256), 0, s, c->frames.levelPtr(first_slot, lvl), c->frames.levelPtr(new_slot, lvl), P, A, m->d_partials);
   hipLaunchKernelGGL(k_init_final, dim3(1), dim3(128), 0, s, m->d_partials, G, m->d_out);
   HIPCHK(hipGetLastError());
@@ -152,35 +276,195 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   if (want) HIPCHK(hipMemcpyAsync(m->h_res, m->d_res, sizeof(float) * 14 * PN + n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   m->upload_pending = false;
-  if (energy_new2) memcpy(energy_new2, m->h_res, sizeof(float) * 2 * n);
-  if (maxstep) memcpy(maxstep, m->h_res + 2 * PN, sizeof(float) * n);
-  if (JbBuffer_new10) memcpy(JbBuffer_new10, m->h_res + 4 * PN, sizeof(float) * 10 * n);
-  if (isGood_new) memcpy(isGood_new, m->h_res + 14 * PN, n);
-  if (lastHessian_new) {
-    // written for accepted points only, like the reference's member (CoarseInitializer.cpp:560): the kernel leaves the other entries of the slab as an earlier call,
-    // laid out for another n, left them, so they are not the caller's to see
-    const float* lh = m->h_res + 3 * PN;
-    const unsigned char* acc = reinterpret_cast<const unsigned char*>(m->h_res + 14 * PN);
-    for (int i = 0; i < n; i++) if (acc[i]) lastHessian_new[i] = lh[i];
+  if (m->owner) m->owner->pts_pending = false;
+  initDeliverPoints(m->h_res, n, energy_new2, isGood_new, maxstep, lastHessian_new, JbBuffer_new10);
+  initHostTail(T, n, alphaW, alphaK, priorY, priorX, m->h_out, H_out64, b_out8, H_sc64, b_sc8, res3);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ W windows per call
+dmvio_hip_initializer_batch* dmvio_hip_initializer_batch_create(dmvio_hip_ctx* ctx, int max_windows) {
+  if (!ctx || max_windows < 1 || max_windows > 65535) { failmsg("initializer_batch_create: bad argument (max_windows in [1, 65535]: the window is a grid dimension)"); return nullptr; }
+  dmvio_hip_initializer_batch* b = new dmvio_hip_initializer_batch();
+  b->ctx = ctx; b->max_windows = max_windows;
+  return b;
+}
+void dmvio_hip_initializer_batch_destroy(dmvio_hip_initializer_batch* b) {
+  if (!b) return;
+  hipSetDevice(b->ctx->device);
+  {
+    // the handles that still read their points from this batch's slab take them home first
+    std::lock_guard<std::mutex> lk(b->ctx->mu);
+    while (!b->tenants.empty()) initLeaveBatch(b->tenants.back(), true);
   }
-  // unpack the two upper triangles, then the tail of calcResAndGS (:582-613)
-  float M[2][9][9];
-  for (int w = 0; w < 2; w++) {
-    int k = 0;
-    for (int r = 0; r < 9; r++) for (int q = r; q < 9; q++) { M[w][r][q] = M[w][q][r] = m->h_out[45 * w + k]; k++; }
+  hipStreamSynchronize(b->ctx->stream);
+  if (b->d_pts) hipFree(b->d_pts);
+  if (b->d_up) hipFree(b->d_up);
+  if (b->d_part) hipFree(b->d_part);
+  if (b->d_dn) hipFree(b->d_dn);
+  if (b->h_pts) hipHostFree(b->h_pts);
+  if (b->h_up) hipHostFree(b->h_up);
+  if (b->h_dn) hipHostFree(b->h_dn);
+  delete b;
+}
+
+}  // extern "C"
+
+// what both batched calls refuse of the call as a whole and of window i's handle; 0 or the failure
+static int initBatchCheck(const char* who, const dmvio_hip_initializer_batch* b, int W, const void* win) {
+  char msg[160];
+  if (W < 0 || W > b->max_windows) { snprintf(msg, sizeof(msg), "%s: W = %d outside [0, %d]", who, W, b->max_windows); return failmsg(msg); }
+  if (W > 0 && !win) { snprintf(msg, sizeof(msg), "%s: null window array", who); return failmsg(msg); }
+  return 0;
+}
+template <class WIN>
+static int initBatchCheckHandle(const char* who, const dmvio_hip_initializer_batch* b, const WIN* win, int i) {
+  char msg[160];
+  const dmvio_hip_initializer* m = win[i].ini;
+  if (!m) { snprintf(msg, sizeof(msg), "%s: window %d: null initializer handle", who, i); return failmsg(msg); }
+  if (m->ctx != b->ctx) { snprintf(msg, sizeof(msg), "%s: window %d: the initializer belongs to another context", who, i); return failmsg(msg); }
+  for (int j = 0; j < i; j++)
+    if (win[j].ini == m) { snprintf(msg, sizeof(msg), "%s: window %d: the initializer of window %d named again", who, i, j); return failmsg(msg); }
+  return 0;
+}
+
+extern "C" {
+
+int dmvio_hip_initializer_set_points_batch(dmvio_hip_initializer_batch* b, int W, const dmvio_hip_initializer_points_window* win) {
+  static const char* who = "initializer_set_points_batch";
+  if (!b) return failmsg("initializer_set_points_batch: null batch handle");
+  HIPCHK(hipSetDevice(b->ctx->device));
+  dmvio_hip_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (int r = initBatchCheck(who, b, W, win)) return r;
+  for (int i = 0; i < W; i++) {
+    if (int r = initBatchCheckHandle(who, b, win, i)) return r;
+    const dmvio_hip_initializer_points_window& w = win[i];
+    if (w.n < 0 || w.n > w.ini->capacity || !w.u || !w.v || !w.iR || !w.isGood || !w.energy2 || !w.outlierTH) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "%s: window %d: bad argument (n = %d, capacity %d, or a null array)", who, i, w.n, w.ini->capacity);
+      return failmsg(msg);
+    }
   }
-  for (int r = 0; r < 8; r++) {
-    for (int q = 0; q < 8; q++) { H_out64[r * 8 + q] = M[0][r][q]; H_sc64[r * 8 + q] = M[1][r][q]; }
-    b_out8[r] = M[0][r][8]; b_sc8[r] = M[1][r][8];
+  if (W == 0) return 0;
+  hipStream_t s = c->stream;
+  // the pinned slabs written below may still be read by an earlier upload (the batch's, or a handle's own): the single call waits in the same case
+  bool pending = b->pts_pending;
+  for (int i = 0; i < W; i++) pending = pending || win[i].ini->upload_pending;
+  if (pending) { HIPCHK(hipStreamSynchronize(s)); b->pts_pending = false; for (int i = 0; i < W; i++) win[i].ini->upload_pending = false; }
+  // the handles of this call move into this batch's slab, which is written from its start: those that live there and are not named again take their points home first
+  for (int i = 0; i < W; i++) if (int r = initLeaveBatch(win[i].ini, false)) return r;
+  while (!b->tenants.empty()) if (int r = initLeaveBatch(b->tenants.back(), true)) return r;
+  size_t total = 0;
+  for (int i = 0; i < W; i++) total += (IN_FLOATS + 1) * padn(win[i].n);
+  if (int r = initGrow(&b->h_pts, &b->d_pts, &b->pts_cap, total, s)) return r;
+  size_t off = 0;
+  for (int i = 0; i < W; i++) {
+    const dmvio_hip_initializer_points_window& w = win[i];
+    dmvio_hip_initializer* m = w.ini;
+    const size_t P = padn(w.n);
+    initPackPoints(b->h_pts + off, w.n, w.u, w.v, w.iR, w.isGood, w.energy2, w.outlierTH);
+    initPackPoints(m->h_in, w.n, w.u, w.v, w.iR, w.isGood, w.energy2, w.outlierTH);   // the handle's own staging copy: calc reads u, v and isGood there
+    m->pts = b->d_pts + off; m->owner = b; b->tenants.push_back(m);
+    m->n = w.n;
+    m->upload_pending = true;
+    off += (IN_FLOATS + 1) * P;
   }
-  H_out64[0] += alphaOpt * n; H_out64[9] += alphaOpt * n; H_out64[18] += alphaOpt * n;
-  double lg[6];
-  poseLogHost(T, lg);
-  const float tlog[3] = {(float)lg[0], (float)lg[1], (float)lg[2]};
-  b_out8[0] += tlog[0] * alphaOpt * n; b_out8[1] += tlog[1] * alphaOpt * n; b_out8[2] += tlog[2] * alphaOpt * n;
-  H_out64[9] += priorY; b_out8[1] += priorY * T.t[1];
-  H_out64[0] += priorX; b_out8[0] += priorX * T.t[0];
-  res3[0] = m->h_out[90]; res3[1] = alphaEnergy; res3[2] = (float)(2 * (size_t)n);   // accE[0].num: every point once per loop (:351-470, :503-516)
+  // ONE copy, no wait: the evaluation's own synchronisation covers it
+  if (total) HIPCHK(hipMemcpyAsync(b->d_pts, b->h_pts, sizeof(float) * total, hipMemcpyHostToDevice, s));
+  b->pts_pending = true;
+  return 0;
+}
+
+int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, int W, dmvio_hip_initializer_window* win) {
+  static const char* who = "initializer_calc_batch";
+  if (!b) return failmsg("initializer_calc_batch: null batch handle");
+  HIPCHK(hipSetDevice(b->ctx->device));
+  dmvio_hip_ctx* c = b->ctx;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (int r = initBatchCheck(who, b, W, win)) return r;
+  char msg[320];
+  for (int i = 0; i < W; i++) {
+    if (int r = initBatchCheckHandle(who, b, win, i)) return r;
+    const dmvio_hip_initializer_window& w = win[i];
+    if (w.lvl < 0 || w.lvl >= c->levels || w.first_slot < 0 || w.first_slot >= c->n_slots || w.new_slot < 0 || w.new_slot >= c->n_slots) {
+      snprintf(msg, sizeof(msg), "%s: window %d: level / slot out of range", who, i);
+      return failmsg(msg);
+    }
+    if (w.ini->n > 0 && !w.idepth_new) { snprintf(msg, sizeof(msg), "%s: window %d: null idepth_new", who, i); return failmsg(msg); }
+    const int p = initFirstPointOutside(w.ini, w.lvl);
+    if (p >= 0) { snprintf(msg, sizeof(msg), "%s: window %d: ", who, i); return failmsg(initOutsideMsg(msg, w.ini, w.lvl, p)); }
+  }
+  if (W == 0) { b->work[0] = b->work[1] = b->work[2] = b->work[3] = 0; return 0; }
+  // (not counted: the conversion of an 8x4-tiled level-0 slot, as in the single call)
+  for (int i = 0; i < W; i++)
+    if (win[i].lvl == 0) { if (int r = dmv_ensure_row_major_locked(c, win[i].first_slot)) return r; if (int r = dmv_ensure_row_major_locked(c, win[i].new_slot)) return r; }
+  hipStream_t s = c->stream;
+  // layout, in floats.  upload: [W records | idepth_new of window 0 | ...]; download: [W x IN_PART sums | results of the windows that asked for any | those of the others]
+  const size_t rec_floats = padn((int)((sizeof(InitWin) * (size_t)W + sizeof(float) - 1) / sizeof(float)));
+  std::vector<size_t> id_off(W), res_off(W);
+  std::vector<char> want(W);
+  size_t up = rec_floats, parts = 0;
+  int maxG = 1;
+  for (int i = 0; i < W; i++) {
+    const dmvio_hip_initializer_window& w = win[i];
+    id_off[i] = up; up += padn(w.ini->n);
+    want[i] = w.energy_new2 || w.isGood_new || w.maxstep || w.lastHessian_new || w.JbBuffer_new10;
+    const int G = initGrid(w.ini->n);
+    parts += (size_t)G; maxG = std::max(maxG, G);
+  }
+  const size_t sum_floats = padn(W * IN_PART);
+  size_t dn = sum_floats;
+  for (int pass = 1; pass >= 0; pass--)
+    for (int i = 0; i < W; i++) if ((int)want[i] == pass) { res_off[i] = dn; dn += (RES_FLOATS + 1) * padn(win[i].ini->n); }
+  size_t dn_wanted = sum_floats;
+  for (int i = 0; i < W; i++) if (want[i]) dn_wanted += (RES_FLOATS + 1) * padn(win[i].ini->n);
+  if (int r = initGrow(&b->h_up, &b->d_up, &b->up_cap, up, s)) return r;
+  if (int r = initGrow(nullptr, &b->d_part, &b->part_cap, parts * IN_PART, s)) return r;
+  if (int r = initGrow(&b->h_dn, &b->d_dn, &b->dn_cap, dn, s)) return r;
+  InitWin* rec = reinterpret_cast<InitWin*>(b->h_up);
+  std::vector<Pose> T(W);
+  int part_off = 0;
+  for (int i = 0; i < W; i++) {
+    const dmvio_hip_initializer_window& w = win[i];
+    dmvio_hip_initializer* m = w.ini;
+    const int n = m->n;
+    T[i] = poseFrom7(w.refToNew7);
+    InitWin& R = rec[i];
+    R.Iref = c->frames.levelPtr(w.first_slot, w.lvl); R.Inew = c->frames.levelPtr(w.new_slot, w.lvl);
+    R.P = initMakePts(n, m->pts, b->d_up + id_off[i], b->d_dn + res_off[i]);
+    R.A = initMakeArgs(c, w.lvl, w.Ki9, w.fxfycxcy_lvl, T[i], w.aff_ab, n, w.alphaW, w.alphaK, w.couplingWeight);
+    R.G = initGrid(n); R.part_off = part_off; R.sum_off = i * IN_PART;
+    part_off += R.G;
+    if (n > 0) memcpy(b->h_up + id_off[i], w.idepth_new, sizeof(float) * n);
+  }
+  HIPCHK(hipMemcpyAsync(b->d_up, b->h_up, sizeof(float) * up, hipMemcpyHostToDevice, s));
+  const InitWin* d_rec = reinterpret_cast<const InitWin*>(b->d_up);
+  hipLaunchKernelGGL(k_init_partial_b, dim3(maxG, W), dim3(256), 0, s, d_rec, b->d_part);
+  hipLaunchKernelGGL(k_init_final_b, dim3(W), dim3(128), 0, s, d_rec, (const float*)b->d_part, b->d_dn);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(b->h_dn, b->d_dn, sizeof(float) * dn_wanted, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  b->pts_pending = false;
+  for (int i = 0; i < W; i++) {
+    dmvio_hip_initializer_window& w = win[i];
+    dmvio_hip_initializer* m = w.ini;
+    m->upload_pending = false;
+    if (m->owner) m->owner->pts_pending = false;
+    if (want[i]) initDeliverPoints(b->h_dn + res_off[i], m->n, w.energy_new2, w.isGood_new, w.maxstep, w.lastHessian_new, w.JbBuffer_new10);
+    initHostTail(T[i], m->n, w.alphaW, w.alphaK, w.priorY, w.priorX, b->h_dn + (size_t)i * IN_PART, w.H_out64, w.b_out8, w.H_sc64, w.b_sc8, w.res3);
+  }
+  b->work[0] = 2; b->work[1] = 1; b->work[2] = 1; b->work[3] = 1;
+  return 0;
+}
+
+int dmvio_hip_initializer_batch_last_work(dmvio_hip_initializer_batch* b, int* launches, int* uploads, int* downloads, int* waits) {
+  if (!b) return failmsg("initializer_batch_last_work: null batch handle");
+  std::lock_guard<std::mutex> lk(b->ctx->mu);
+  if (launches) *launches = b->work[0];
+  if (uploads) *uploads = b->work[1];
+  if (downloads) *downloads = b->work[2];
+  if (waits) *waits = b->work[3];
   return 0;
 }
 

@@ -73,8 +73,10 @@ __device__ __forceinline__ void waveOuter9(const float (&J)[9], const float w, f
   __builtin_amdgcn_wave_barrier();
 }
 
-__global__ void __launch_bounds__(256) k_init_partial(const float* __restrict__ Iref, const float* __restrict__ Inew, const InitPts P, const InitArgs A,
-                                                       float* __restrict__ partials /* gridDim.x x IN_PART */) {
+// The body of one workgroup of the evaluation, shared verbatim by k_init_partial and k_init_partial_b: workgroup bx of the G that serve the point set.  The partition of the
+// points into partials (grid-stride G * 256) and the order inside each partial depend on (bx, G) only, so a window of a batch sums what its single call sums, in that order.
+__device__ __forceinline__ void initPartialBody(const float* __restrict__ Iref, const float* __restrict__ Inew, const InitPts& P, const InitArgs& A,
+                                                float* __restrict__ partials /* G x IN_PART */, const int bx, const int G) {
   __shared__ float s_stage[4 * IN_WAVE_FLOATS];
   __shared__ float s_partH[4 * 256], s_partS[4 * 256], s_partE[4];
   for (int k = threadIdx.x; k < 4 * IN_WAVE_FLOATS; k += 256) s_stage[k] = 0.0f;
@@ -84,7 +86,7 @@ __global__ void __launch_bounds__(256) k_init_partial(const float* __restrict__ 
   float* __restrict__ wW = wJ + IN_ROWS * IN_STRIDE;
   init_f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0, h2 = h0, h3 = h0, c0 = h0, c1 = h0, c2 = h0, c3 = h0;
   float Esum = 0.f;
-  const int stride = gridDim.x * 256, base0 = blockIdx.x * 256 + wave * 64;
+  const int stride = G * 256, base0 = bx * 256 + wave * 64;
   for (int base = base0; base < P.n; base += stride) {   // wave-uniform trip count
     const int i = base + lane;
     float rows[8][9];
@@ -211,8 +213,13 @@ __global__ void __launch_bounds__(256) k_init_partial(const float* __restrict__ 
     } else if (k == 90) {
       for (int wv = 0; wv < 4; wv++) s += s_partE[wv];
     }
-    partials[blockIdx.x * IN_PART + k] = s;
+    partials[bx * IN_PART + k] = s;
   }
+}
+
+__global__ void __launch_bounds__(256) k_init_partial(const float* __restrict__ Iref, const float* __restrict__ Inew, const InitPts P, const InitArgs A,
+                                                       float* __restrict__ partials /* gridDim.x x IN_PART */) {
+  initPartialBody(Iref, Inew, P, A, partials, blockIdx.x, gridDim.x);
 }
 
 __global__ void __launch_bounds__(128) k_init_final(const float* __restrict__ partials, const int G, float* __restrict__ out /* IN_PART */) {
@@ -220,6 +227,50 @@ __global__ void __launch_bounds__(128) k_init_final(const float* __restrict__ pa
   float s = 0.f;
   for (int g = 0; g < G; g++) s += partials[g * IN_PART + threadIdx.x];
   out[threadIdx.x] = s;
+}
+
+// ------------------------------------------------------------------------------------------------ W windows per launch (dmvio_hip_initializer_calc_res_and_gs_batch)
+// One record per window in a device table the call uploads; workgroup (x, y) serves window y.  The record is addressed with blockIdx.y, so every member is read with scalar
+// loads and stays wave-uniform; the pointers it holds are read through initGl() (the idiom of ba_batch_kernels.hpp: gl()) — a pointer loaded from memory is otherwise a generic
+// one to the compiler and every access behind it a flat_* instruction.
+struct InitWin {
+  const float *Iref, *Inew;   // the window's level of its first and its new slot
+  InitPts P;
+  InitArgs A;
+  int G;                      // the single call's grid: max(1, min(256, (n + 255) / 256))
+  int part_off, sum_off;      // first partial of the window in the batch's partials (units of IN_PART floats), and its sums in the batch's output (floats)
+};
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wincompatible-pointer-types-discards-qualifiers"
+template <class T> __device__ __forceinline__ T* initGl(T* const& member) {
+  return (T*)(*reinterpret_cast<__attribute__((address_space(1))) T* const*>(&member));
+}
+#pragma clang diagnostic pop
+
+// grid (max_y G_y, W): a workgroup beyond its window's own grid leaves at once; the grid-stride is the window's G, not gridDim.x
+__global__ void __launch_bounds__(256) k_init_partial_b(const InitWin* __restrict__ wins, float* __restrict__ partials) {
+  const InitWin& V = wins[blockIdx.y];
+  const int G = V.G;
+  if ((int)blockIdx.x >= G) return;
+  InitPts P;
+  P.n = V.P.n;
+  P.u = initGl(V.P.u); P.v = initGl(V.P.v); P.idepth_new = initGl(V.P.idepth_new); P.iR = initGl(V.P.iR); P.energy = initGl(V.P.energy); P.outlierTH = initGl(V.P.outlierTH);
+  P.isGood = initGl(V.P.isGood);
+  P.energy_new = initGl(V.P.energy_new); P.maxstep = initGl(V.P.maxstep); P.lastHessian_new = initGl(V.P.lastHessian_new); P.JbBuffer_new = initGl(V.P.JbBuffer_new);
+  P.isGood_new = initGl(V.P.isGood_new);
+  const InitArgs A = V.A;
+  initPartialBody(initGl(V.Iref), initGl(V.Inew), P, A, partials + (size_t)V.part_off * IN_PART, blockIdx.x, G);
+}
+
+// grid W: workgroup y sums window y's G_y partials in index order, as k_init_final
+__global__ void __launch_bounds__(128) k_init_final_b(const InitWin* __restrict__ wins, const float* __restrict__ partials, float* __restrict__ out) {
+  if (threadIdx.x >= IN_PART) return;
+  const InitWin& V = wins[blockIdx.x];
+  const int G = V.G;
+  const float* __restrict__ p = partials + (size_t)V.part_off * IN_PART;
+  float s = 0.f;
+  for (int g = 0; g < G; g++) s += p[g * IN_PART + threadIdx.x];
+  out[V.sum_off + threadIdx.x] = s;
 }
 
 }  // namespace dmv

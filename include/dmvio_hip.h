@@ -873,6 +873,54 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* ini, int lvl, i
                                           const double refToNew7[7], const double aff_ab[2], const float* idepth_new, float alphaW, float alphaK,
                                           float couplingWeight, double priorY, double priorX, float* H_out64, float* b_out8, float* H_sc64, float* b_sc8,
                                           float res3[3], float* energy_new2, unsigned char* isGood_new, float* maxstep, float* lastHessian_new, float* JbBuffer_new10);
+/* CoarseInitializer::calcResAndGS (CoarseInitializer.cpp:331-624) of W initializers of one context per call: window i is what
+ * dmvio_hip_initializer_calc_res_and_gs(win[i].ini, ...) is, and every output — H_out, b_out, H_sc, b_sc, res3 and the five per-point arrays — equals the single call's bit
+ * for bit (each window is evaluated by its own workgroups with the single call's grid, partition into partial sums and summation order; the host tail is one function of
+ * both calls).  lastHessian_new is written for accepted points only, as in the single call.  Windows may differ in n, lvl, slots, pose and every scalar and may share slots;
+ * a window with n == 0 is legal and gives what the single call gives; a window's result does not depend on the other windows of the call or on its position.
+ * dmvio_hip_initializer_set_points_batch is dmvio_hip_initializer_set_points of W handles.  After either batched call a handle is in the state its own single call would
+ * have left: n, the point set every later call reads (a handle named in set_points_batch reads it from the batch's device slab instead of its own until its next set_points;
+ * the batch hands it back when it is destroyed or the slab is rewritten without that handle), the host copy of (u, v, isGood) the range check reads, and the pending-upload
+ * state — so single and batched set_points / calc calls may be mixed freely on a handle.  (The per-point result area and the idepth_new area of a handle's own slab are
+ * scratch that every call rewrites before it reads; the batched calc keeps its own and does not write the handles'.)
+ * Work per calc call, whatever W is: ONE packed upload (the W window records and all idepth_new arrays, from one pinned slab the batch owns, grown on demand and kept), TWO
+ * kernel launches, ONE download (the W sums, and the per-point results of the windows that passed a non-NULL per-point pointer) and ONE wait;
+ * dmvio_hip_initializer_batch_last_work reports these four figures of the last calc call (all 0 after W == 0; a refused call leaves them unchanged; any pointer may be NULL).
+ * set_points_batch is ONE packed upload, no launch and no wait: stream-ordered like the single call (it waits, like the single call, only when a pinned slab it must rewrite
+ * may still be read by an earlier upload, i.e. when no calc came between two set_points).  The conversion of an 8x4-tiled level-0 slot to row-major runs first, as in the single
+ * call, and is not counted.  Both calls run under the context's lock on the context's stream.
+ * A call is refused as a whole, with a message that names the window, before anything is enqueued and before any handle, slot or output is touched: a NULL batch, window array
+ * or handle; idepth_new NULL with n > 0; W < 0 or W > max_windows; the same initializer named twice; a handle of another context; lvl or a slot out of range; n < 0, n above the
+ * handle's capacity or a NULL array (set_points_batch); a good point outside [2, w_lvl - 3) x [2, h_lvl - 3) of the window's level (the message names window and point).
+ * W == 0 returns 0 and does nothing.  max_windows is at most 65535. */
+typedef struct dmvio_hip_initializer_batch dmvio_hip_initializer_batch;
+dmvio_hip_initializer_batch* dmvio_hip_initializer_batch_create(dmvio_hip_ctx* ctx, int max_windows);
+void dmvio_hip_initializer_batch_destroy(dmvio_hip_initializer_batch* b);
+typedef struct dmvio_hip_initializer_points_window {   /* as dmvio_hip_initializer_set_points, one window */
+  dmvio_hip_initializer* ini;
+  int n;
+  const float *u, *v, *iR;
+  const unsigned char* isGood;
+  const float *energy2, *outlierTH;
+} dmvio_hip_initializer_points_window;
+int dmvio_hip_initializer_set_points_batch(dmvio_hip_initializer_batch* b, int W, const dmvio_hip_initializer_points_window* win);
+typedef struct dmvio_hip_initializer_window {          /* as dmvio_hip_initializer_calc_res_and_gs, one window */
+  dmvio_hip_initializer* ini;
+  int lvl, first_slot, new_slot;
+  double Ki9[9];
+  float fxfycxcy_lvl[4];
+  double refToNew7[7], aff_ab[2];
+  const float* idepth_new;
+  float alphaW, alphaK, couplingWeight;
+  double priorY, priorX;
+  float H_out64[64], b_out8[8], H_sc64[64], b_sc8[8], res3[3];   /* out */
+  float* energy_new2;                                            /* out, each may be NULL */
+  unsigned char* isGood_new;
+  float *maxstep, *lastHessian_new, *JbBuffer_new10;
+} dmvio_hip_initializer_window;
+int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, int W, dmvio_hip_initializer_window* win);
+/* what the last calc call enqueued: kernel launches, host-to-device copies, device-to-host copies, stream waits */
+int dmvio_hip_initializer_batch_last_work(dmvio_hip_initializer_batch* b, int* launches, int* uploads, int* downloads, int* waits);
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * Pixel selection: the candidates of a new keyframe, chosen on the device from the resident pyramid.
