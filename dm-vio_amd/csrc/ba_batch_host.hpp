@@ -98,7 +98,7 @@ struct BatchLayout {
   enum : size_t { TRACE = 64 * 4, MIRROR_TRACE = 1, MIRROR_XLAST = 1 + TRACE, MIRROR_STRIDE = 1 + TRACE + BA_BATCH_NMAX };
   const size_t n, F2;
   BatchLayout(const int n_, const int F_) : n((size_t)n_), F2((size_t)F_ * F_) {}
-  static size_t padded(const size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+  static size_t padded(const size_t bytes) { return dmvPad(bytes); }
   size_t tabHM() const { return 0; }
   size_t tabBM() const { return sizeof(double) * n * n; }
   size_t tabBasis() const { return tabBM() + sizeof(double) * n; }
@@ -127,9 +127,7 @@ struct BatchLayout {
   size_t margTabAdTarget() const { return margTabAdHost() + margTabAdBytes(); }
   size_t margTabUsed(const bool adjoints) const { return adjoints ? margTabAdTarget() + margTabAdBytes() : tabPreBytes(); }
   size_t margSysDoubles() const { return outResInA() + 1; }
-  static size_t margCandBytes(const size_t N) { return padded(N); }
   size_t margOutDecision() const { return sizeof(double) * margSysDoubles(); }
-  size_t margOutBytes(const size_t N) const { return padded(margOutDecision() + N); }
   bool margFitsIn(const BatchLayout& cap) const { return margTabUsed(true) <= cap.tabStride(); }
 };
 struct dmvio_hip_ba_batch {
@@ -162,25 +160,28 @@ struct dmvio_hip_ba_batch {
   int lin_lanes = 1;               // dmvio_hip_ba_batch_set_linearize_lanes: 1 = k_ba_linearize_b1 (one lane per residual) from 4 windows on, 8 = always the eight-lane kernel
   int streams = 0;                 // dmvio_hip_ba_batch_set_streams: 0 = automatic, k >= 1 = at most k groups (1: the whole batch on one stream)
   int profile = 0;                 // dmvio_hip_ba_batch_set_profile: events around the stepped linearisation of iteration 1 (k_ba_linearize_b of all windows)
-  // dmvio_hip_ba_marginalize_points_batch: the candidates / systems / decisions of a call (BatchLayout), device and pinned, grown on demand and kept; the event that puts a
-  // handle's own pending work in front of the call; what the last call enqueued
-  char* d_marg = nullptr;
-  char* h_marg = nullptr;
-  size_t marg_cap = 0;
+  // dmvio_hip_ba_marginalize_points_batch: the candidates / systems / decisions of a call (BatchLayout), device and pinned, grown on demand to twice the need and kept
+  // (batch_slab.hpp); the event that puts a handle's own pending work in front of the call; what the last call enqueued
+  DmvSlab marg;
   hipEvent_t marg_ev = nullptr;
-  int marg_work[4] = {0, 0, 0, 0};   // launches, uploads, downloads, waits
+  DmvWork marg_work;
+  // the marginalisation buffer holds `bytes` and its pinned side is free to write; `work` counts what the call does with it
+  int margBegin(const size_t bytes, DmvWork* work) {
+    if (int r = marg.reserve(bytes, bytes * 2, stream)) return r;
+    if (!marg_ev) HIPCHK(hipEventCreateWithFlags(&marg_ev, hipEventDisableTiming));
+    marg.work = work;
+    return marg.begin(stream);
+  }
   float marg_ms = 0;                 // with `profile`: HIP events around the last call's device work (first upload .. the download)
   // dmvio_hip_ba_marginalize_frame_batch: in the same buffers (a call owns them under the batch's lock); the most dynamic LDS a launch may ask for on this device
   // (0: not asked yet — k_ba_marg_frame_b's attribute is set with the first call)
-  int margf_work[4] = {0, 0, 0, 0};
+  DmvWork margf_work;
   float margf_ms = 0;
   size_t margf_lds_limit = 0;
   // dmvio_hip_ba_set_graph_from_batch (ba_graph_batch_host.hpp): the call's records, range / piece tables and flattened graphs, pinned and on the device, grown on demand
   // and kept like the marginalisation buffer; what the last call enqueued
-  char* d_graph = nullptr;
-  char* h_graph = nullptr;
-  size_t graph_cap = 0;
-  int graph_work[4] = {0, 0, 0, 0};   // launches, uploads, downloads, waits
+  DmvSlab graph;
+  DmvWork graph_work;
   float graph_ms = 0;                 // with `profile`: HIP events from the upload to the last kernel
 };
 extern "C" {
@@ -218,10 +219,7 @@ void dmvio_hip_ba_batch_destroy(dmvio_hip_ba_batch* B) {
   if (B->h_tab) hipHostFree(B->h_tab);
   if (B->d_out) hipFree(B->d_out);
   if (B->h_trace) hipHostFree(B->h_trace);
-  if (B->d_marg) hipFree(B->d_marg);
-  if (B->h_marg) hipHostFree(B->h_marg);
-  if (B->d_graph) hipFree(B->d_graph);
-  if (B->h_graph) hipHostFree(B->h_graph);
+  B->marg.release(); B->graph.release();
   if (B->marg_ev) hipEventDestroy(B->marg_ev);
   for (int k = 0; k < 8; k++) if (B->ev[k]) hipEventDestroy(B->ev[k]);
   for (int g = 1; g < dmvio_hip_ba_batch::BA_BATCH_STREAMS; g++) if (B->gstream[g]) { hipStreamSynchronize(B->gstream[g]); hipStreamDestroy(B->gstream[g]); }
@@ -688,7 +686,7 @@ struct MargBatchCall {
   struct Grp { int w0, cnt, F; };
   std::vector<Grp> grp;
   std::vector<size_t> candOff, outOff;       // per record, into the marginalisation buffer
-  size_t inBytes = 0, outBytes = 0;
+  size_t inBytes = 0, outBytes = 0;        // [candidates of every window | per window its systems, resInA and decisions]: the first part goes up, the second comes back
   bool anyAdjoints = false;
   MargBatchCall(dmvio_hip_ba_batch* B_, const int W_, dmvio_hip_ba_marg_window* win_) : B(B_), W(W_), win(win_) {}
 
@@ -701,25 +699,18 @@ struct MargBatchCall {
       grp.push_back(g);
     }
     candOff.resize(W); outOff.resize(W);
-    for (int k = 0; k < W; k++) { candOff[k] = inBytes; inBytes += BatchLayout::margCandBytes((size_t)win[order[k]].ba->H.N); }
+    DmvCursor C;
+    for (int k = 0; k < W; k++) candOff[k] = C.takeBytes((size_t)win[order[k]].ba->H.N);
+    inBytes = C.bytes();
     for (int k = 0; k < W; k++) {
       const dmvio_hip_ba* b = win[order[k]].ba;
       const BatchLayout L(b->H.n(), b->H.F);
       if (!L.margFitsIn(B->slab)) return failmsg("ba_marginalize_points_batch: table slab too small");
-      outOff[k] = inBytes + outBytes; outBytes += L.margOutBytes((size_t)b->H.N);
+      outOff[k] = C.takeBytes(L.margOutDecision() + (size_t)b->H.N);
       anyAdjoints = anyAdjoints || b->adj_dirty;
     }
-    if (inBytes + outBytes > B->marg_cap) {
-      if (B->d_marg) { hipFree(B->d_marg); B->d_marg = nullptr; }
-      if (B->h_marg) { hipHostFree(B->h_marg); B->h_marg = nullptr; }
-      B->marg_cap = 0;
-      const size_t cap = (inBytes + outBytes) * 2;
-      HIPCHK(hipMalloc((void**)&B->d_marg, cap));
-      HIPCHK(hipHostMalloc((void**)&B->h_marg, cap, hipHostMallocDefault));
-      B->marg_cap = cap;
-    }
-    if (!B->marg_ev) HIPCHK(hipEventCreateWithFlags(&B->marg_ev, hipEventDisableTiming));
-    return 0;
+    outBytes = C.bytes() - inBytes;
+    return B->margBegin(C.bytes(), &B->marg_work);
   }
 
   // ---- the host side of record k before the launches: the handle's part of the single call, the window's record and its tables in the pinned slabs
@@ -765,10 +756,10 @@ struct MargBatchCall {
       memcpy(tab + L.margTabAdHost(), H.adHost.data(), L.margTabAdBytes()); memcpy(tab + L.margTabAdTarget(), H.adTarget.data(), L.margTabAdBytes());
       V.adHost = reinterpret_cast<const double*>(dtab + L.margTabAdHost()); V.adTarget = reinterpret_cast<const double*>(dtab + L.margTabAdTarget());
     } else { V.adHost = b->d_adHost; V.adTarget = b->d_adTarget; }
-    memcpy(B->h_marg + candOff[k], q.candidates, (size_t)N);
-    V.margCand = reinterpret_cast<const unsigned char*>(B->d_marg + candOff[k]);
-    V.margSys = reinterpret_cast<double*>(B->d_marg + outOff[k]);
-    V.margDecision = reinterpret_cast<unsigned char*>(B->d_marg + outOff[k] + L.margOutDecision());
+    const auto cand = B->marg.put<unsigned char>(candOff[k]);
+    memcpy(cand.h, q.candidates, (size_t)N); V.margCand = cand.d;
+    V.margSys = B->marg.dev<double>(outOff[k]);
+    V.margDecision = B->marg.dev<unsigned char>(outOff[k] + L.margOutDecision());
     V.margFullJ = b->d_fullJ; V.margRec = b->d_margRec; V.margActive = b->d_margActive;
     V.mHdiF = b->d_mHdiF; V.mbdSumF = b->d_mbdSumF; V.mHcd = b->d_mHcd;
     return 0;
@@ -776,7 +767,7 @@ struct MargBatchCall {
 
   int enqueue() {
     const hipStream_t s = B->stream;
-    int* const work = B->marg_work;
+    DmvWork& work = B->marg_work;
     // a handle's own stream may still hold work (its entry points return on a ticket, not on an empty stream): in front of the call
     for (int k = 0; k < W; k++) {
       dmvio_hip_ba* b = win[order[k]].ba;
@@ -786,12 +777,11 @@ struct MargBatchCall {
     }
     (void)hipGetLastError();   // (hipErrorNotReady of the query above is no error)
     if (B->profile) HIPCHK(hipEventRecord(B->ev[6], s));
-    HIPCHK(hipMemcpyAsync(B->d_wins, B->h_wins, sizeof(BAWinDev) * W, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(B->d_wins, B->h_wins, sizeof(BAWinDev) * W, hipMemcpyHostToDevice, s)); work.uploads++;
     size_t tabWidth = 0;
     for (const Grp& g : grp) tabWidth = std::max(tabWidth, BatchLayout(4 + 8 * g.F, g.F).margTabUsed(anyAdjoints));
-    HIPCHK(hipMemcpy2DAsync(B->dTab(0), B->slab.tabStride(), B->hTab(0), B->slab.tabStride(), tabWidth, W, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(B->d_marg, B->h_marg, inBytes, hipMemcpyHostToDevice, s));
-    work[1] = 3;
+    HIPCHK(hipMemcpy2DAsync(B->dTab(0), B->slab.tabStride(), B->hTab(0), B->slab.tabStride(), tabWidth, W, hipMemcpyHostToDevice, s)); work.uploads++;
+    if (int r = B->marg.upload(s, inBytes)) return r;
     const FrameStore fs = B->ctx->frames.built_and_waited();
     for (const Grp& g : grp) {
       int gx_lin = 0, gx_res = 0, gx_pt = 0, gx_acc = 0;
@@ -801,20 +791,17 @@ struct MargBatchCall {
       }
       const BAWinDev* dw = B->d_wins + g.w0;
       const int F = g.F, n_gather = B->h_wins[g.w0].n_gather_blocks;
-      hipLaunchKernelGGL(k_ba_marg_linearize_b, dim3(gx_lin, g.cnt), dim3(LIN_THREADS), 0, s, dw, fs);
-      hipLaunchKernelGGL(k_ba_marg_apply_fix_b, dim3(gx_res, g.cnt), dim3(256), 0, s, dw);
-      hipLaunchKernelGGL(k_ba_marg_point_sums_b, dim3(gx_pt, g.cnt), dim3(256), 0, s, dw);
-      hipLaunchKernelGGL(k_ba_accumulate_bm, dim3(gx_acc, g.cnt), dim3(256), 0, s, dw);
-      hipLaunchKernelGGL(k_ba_stitch_b, dim3(F + F * F, g.cnt), dim3(64 * F), sizeof(StitchWave) * F, s, dw, (int)BA_GATE_ALWAYS, (int)BA_PASS_M);
-      BA_BY_MAXF(F, M, hipLaunchKernelGGL((k_ba_stitch_gather_b<M>), dim3(n_gather, g.cnt), dim3(256), 0, s, dw, (int)BA_GATE_ALWAYS, (int)BA_PASS_M));
-      work[0] += 6;
+      hipLaunchKernelGGL(k_ba_marg_linearize_b, dim3(gx_lin, g.cnt), dim3(LIN_THREADS), 0, s, dw, fs); work.launches++;
+      hipLaunchKernelGGL(k_ba_marg_apply_fix_b, dim3(gx_res, g.cnt), dim3(256), 0, s, dw); work.launches++;
+      hipLaunchKernelGGL(k_ba_marg_point_sums_b, dim3(gx_pt, g.cnt), dim3(256), 0, s, dw); work.launches++;
+      hipLaunchKernelGGL(k_ba_accumulate_bm, dim3(gx_acc, g.cnt), dim3(256), 0, s, dw); work.launches++;
+      hipLaunchKernelGGL(k_ba_stitch_b, dim3(F + F * F, g.cnt), dim3(64 * F), sizeof(StitchWave) * F, s, dw, (int)BA_GATE_ALWAYS, (int)BA_PASS_M); work.launches++;
+      BA_BY_MAXF(F, M, hipLaunchKernelGGL((k_ba_stitch_gather_b<M>), dim3(n_gather, g.cnt), dim3(256), 0, s, dw, (int)BA_GATE_ALWAYS, (int)BA_PASS_M)); work.launches++;
       HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(B->h_marg + inBytes, B->d_marg + inBytes, outBytes, hipMemcpyDeviceToHost, s));
-    work[2] = 1;
+    if (int r = B->marg.download(s, inBytes, outBytes)) return r;
     if (B->profile) HIPCHK(hipEventRecord(B->ev[7], s));
-    HIPCHK(hipStreamSynchronize(s));
-    work[3] = 1;
+    if (int r = B->marg.wait(s)) return r;
     B->marg_ms = 0;
     if (B->profile) HIPCHK(hipEventElapsedTime(&B->marg_ms, B->ev[6], B->ev[7]));
     return 0;
@@ -826,13 +813,13 @@ struct MargBatchCall {
     BAHost& H = q.ba->H;
     const int n = H.n(), N = H.N;
     const BatchLayout L(n, H.F);
-    const double* M = reinterpret_cast<const double*>(B->h_marg + outOff[k]);
+    const double* M = B->marg.host<const double>(outOff[k]);
     const double* Mb = M + (size_t)n * n; const double* Msc = Mb + n; const double* Mbsc = Msc + (size_t)n * n;
     if (H.HM.size() != (size_t)n * n) { H.HM.assign((size_t)n * n, 0.0); H.bM.assign(n, 0.0); }
     for (size_t i = 0; i < (size_t)n * n; i++) { const double v = BA_MARG_WEIGHT_FAC * (M[i] - Msc[i]); if (q.Hadd) q.Hadd[i] = v; if (q.update_prior) H.HM[i] += v; }
     for (int i = 0; i < n; i++) { const double v = BA_MARG_WEIGHT_FAC * (Mb[i] - Mbsc[i]); if (q.badd) q.badd[i] = v; if (q.update_prior) H.bM[i] += v; }
     q.resInM = (int)M[L.outResInA()];
-    memcpy(q.decision, B->h_marg + outOff[k] + L.margOutDecision(), (size_t)N);
+    memcpy(q.decision, B->marg.host<char>(outOff[k] + L.margOutDecision()), (size_t)N);
     return 0;
   }
 };
@@ -845,7 +832,7 @@ int dmvio_hip_ba_marginalize_points_batch(dmvio_hip_ba_batch* B, int W, dmvio_hi
   if (W < 0) return failmsg("ba_marginalize_points_batch: W < 0");
   if (W > B->cap) return failmsg("ba_marginalize_points_batch: more windows than the batch was created for");
   std::lock_guard<std::mutex> lkB(B->mu);
-  for (int i = 0; i < 4; i++) B->marg_work[i] = 0;
+  B->marg_work.clear();
   if (W == 0) return 0;
   if (!win) return failmsg("ba_marginalize_points_batch: null window list");
   std::vector<dmvio_hip_ba*> order(W);
@@ -856,8 +843,8 @@ int dmvio_hip_ba_marginalize_points_batch(dmvio_hip_ba_batch* B, int W, dmvio_hi
     order[i] = win[i].ba;
   }
   // the handles' locks, in address order (as dmvio_hip_ba_optimize_batch)
+  if (dmvFirstRepeated(win, W, &dmvio_hip_ba_marg_window::ba) >= 0) return failmsg("ba_marginalize_points_batch: a window appears twice");
   std::sort(order.begin(), order.end());
-  for (int i = 1; i < W; i++) if (order[i] == order[i - 1]) return failmsg("ba_marginalize_points_batch: a window appears twice");
   std::vector<std::unique_lock<std::recursive_mutex>> locks;
   for (dmvio_hip_ba* b : order) locks.emplace_back(b->mu);
   for (int i = 0; i < W; i++) {
@@ -880,10 +867,7 @@ int dmvio_hip_ba_batch_last_marg_ms(dmvio_hip_ba_batch* B, float* ms) {
 int dmvio_hip_ba_batch_last_marg_work(dmvio_hip_ba_batch* B, int* launches, int* uploads, int* downloads, int* waits) {
   if (!B) return failmsg("ba_batch_last_marg_work: null batch");
   std::lock_guard<std::mutex> lkB(B->mu);
-  if (launches) *launches = B->marg_work[0];
-  if (uploads) *uploads = B->marg_work[1];
-  if (downloads) *downloads = B->marg_work[2];
-  if (waits) *waits = B->marg_work[3];
+  B->marg_work.report(launches, uploads, downloads, waits);
   return 0;
 }
 // windows[W]: handles of the batch's context, each with its window set (set_window + set_graph), all distinct.  rmse / finalEnergy / iterations: W entries each (may be

@@ -10,7 +10,6 @@
 #include "ba_graph_batch_kernels.hpp"
 
 struct GraphBatchCall {
-  enum { LAUNCHES = 6 };
   dmvio_hip_ba_batch* const B;
   const int W;
   const dmvio_hip_ba_graph_window* const win;
@@ -28,12 +27,13 @@ struct GraphBatchCall {
   size_t slabBytes = 0;
   GraphBatchCall(dmvio_hip_ba_batch* B_, const int W_, const dmvio_hip_ba_graph_window* win_) : B(B_), W(W_), win(win_), w((size_t)W_) {}
   static std::string name(const int i) { return "ba_set_graph_from_batch: window " + std::to_string(i) + ": "; }
-  template <class T> T* hAt(const size_t off) const { return reinterpret_cast<T*>(B->h_graph + off); }
-  template <class T> T* dAt(const size_t off) const { return reinterpret_cast<T*>(B->d_graph + off); }
+  template <class T> T* hAt(const size_t off) const { return B->graph.host<T>(off); }
+  template <class T> T* dAt(const size_t off) const { return B->graph.dev<T>(off); }
 
   // ---- what the graphs themselves may be refused for, their sizes, the sections and the slab.  Nothing of a handle or a graph is written.
   int plan() {
-    size_t off = BatchLayout::padded(sizeof(dmv::BAGraphWinDev) * (size_t)W);
+    DmvCursor C;
+    C.take<dmv::BAGraphWinDev>(W);
     for (int i = 0; i < W; i++) {
       const dmvio_hip_ba* b = win[i].ba;
       dmvio_hip_graph* g = win[i].graph;
@@ -49,26 +49,19 @@ struct GraphBatchCall {
       q.max_ranges = (int)b->arena.chunks.size() + 2;
       const size_t N = (size_t)q.N, R = (size_t)q.R, F2 = (size_t)q.F * q.F;
       GraphSection& o = q.o;
-      auto take = [&off](const size_t bytes) { const size_t at = off; off += BatchLayout::padded(bytes); return at; };
+      auto take = [&C](const size_t bytes) { return C.takeBytes(bytes); };
       o.ranges = take(sizeof(dmv::BAGraphRange) * q.max_ranges); o.segs = take(sizeof(dmv::BAGraphSeg) * dmv::BA_GRAPH_MAX_SEGS);
       o.host = take(4 * N); o.res_begin = take(4 * (N + 1)); o.point = take(4 * R); o.target = take(4 * R); o.u = take(4 * N); o.v = take(4 * N);
       o.color = take(32 * N); o.weights = take(32 * N); o.prior = take(4 * N); o.idepth = take(4 * N);
       o.top_begin = take(4 * (F2 + 1)); o.top_members = take(4 * R); o.pt_first = take(4 * (size_t)q.F); o.pt_last = take(4 * (size_t)q.F); o.slot = take(4 * R);
       o.adHost = take(sizeof(double) * F2 * 64); o.adTarget = take(sizeof(double) * F2 * 64);
-      o.end = off;
+      o.end = C.bytes();
     }
-    slabBytes = off;
-    if (slabBytes > B->graph_cap) {
-      if (B->d_graph) { hipFree(B->d_graph); B->d_graph = nullptr; }
-      if (B->h_graph) { hipHostFree(B->h_graph); B->h_graph = nullptr; }
-      B->graph_cap = 0;
-      const size_t cap = slabBytes * 2;
-      HIPCHK(hipMalloc((void**)&B->d_graph, cap));
-      HIPCHK(hipHostMalloc((void**)&B->h_graph, cap, hipHostMallocDefault));
-      B->graph_cap = cap;
-    }
+    slabBytes = C.bytes();
+    if (int r = B->graph.reserve(slabBytes, slabBytes * 2, B->stream)) return r;   // grown to twice the need and kept, like the marginalisation buffer
     if (!B->marg_ev) HIPCHK(hipEventCreateWithFlags(&B->marg_ev, hipEventDisableTiming));
-    return 0;
+    B->graph.work = &B->graph_work;
+    return B->graph.begin(B->stream);
   }
 
   // ---- part one of the single call for window i, in the slab: the graph flattened in makeIDX order, the host tables derived beside it.  Still nothing of a handle or a
@@ -169,7 +162,7 @@ struct GraphBatchCall {
 
   int enqueue() {
     const hipStream_t s = B->stream;
-    int* const work = B->graph_work;
+    DmvWork& work = B->graph_work;
     // a handle's own stream may still hold work (its entry points return on a ticket, not on an empty stream): in front of the call
     for (int i = 0; i < W; i++) {
       dmvio_hip_ba* b = win[i].ba;
@@ -179,8 +172,7 @@ struct GraphBatchCall {
     }
     (void)hipGetLastError();   // (hipErrorNotReady of the query above is no error)
     if (B->profile) HIPCHK(hipEventRecord(B->ev[6], s));
-    HIPCHK(hipMemcpyAsync(B->d_graph, B->h_graph, slabBytes, hipMemcpyHostToDevice, s));
-    work[1] = 1;
+    if (int r = B->graph.upload(s, slabBytes)) return r;
     // grid extents: the largest window's
     unsigned long long clear16 = 1, piece16 = 1;
     int Rmax = 1, Fmax = 1;
@@ -198,18 +190,16 @@ struct GraphBatchCall {
     const int gx_clear = (int)std::min<unsigned long long>(256, (clear16 + 256 * 16 - 1) / (256 * 16));
     const int gx_piece = (int)std::min<unsigned long long>(32, (piece16 + 255) / 256);
     const dmv::BAGraphWinDev* const dw = dAt<const dmv::BAGraphWinDev>(0);
-    hipLaunchKernelGGL(dmv::k_ba_graph_clear_b, dim3(gx_clear, W), dim3(256), 0, s, dw);
-    hipLaunchKernelGGL(dmv::k_ba_graph_scatter_b, dim3(gx_piece, W), dim3(256), 0, s, dw);
-    hipLaunchKernelGGL(dmv::k_ba_scd_ridx_b, dim3((Rmax + 255) / 256, W), dim3(256), 0, s, dw);
+    hipLaunchKernelGGL(dmv::k_ba_graph_clear_b, dim3(gx_clear, W), dim3(256), 0, s, dw); work.launches++;
+    hipLaunchKernelGGL(dmv::k_ba_graph_scatter_b, dim3(gx_piece, W), dim3(256), 0, s, dw); work.launches++;
+    hipLaunchKernelGGL(dmv::k_ba_scd_ridx_b, dim3((Rmax + 255) / 256, W), dim3(256), 0, s, dw); work.launches++;
     const int gx_lists = Fmax * ((Fmax * Fmax + 3) / 4);
-    hipLaunchKernelGGL(dmv::k_ba_scd_lists_b, dim3(gx_lists, W), dim3(256), 0, s, dw, 0);
-    hipLaunchKernelGGL(dmv::k_ba_scd_scan_b, dim3(1, W), dim3(1024), 0, s, dw);
-    hipLaunchKernelGGL(dmv::k_ba_scd_lists_b, dim3(gx_lists, W), dim3(256), 0, s, dw, 1);
-    work[0] = LAUNCHES;
+    hipLaunchKernelGGL(dmv::k_ba_scd_lists_b, dim3(gx_lists, W), dim3(256), 0, s, dw, 0); work.launches++;
+    hipLaunchKernelGGL(dmv::k_ba_scd_scan_b, dim3(1, W), dim3(1024), 0, s, dw); work.launches++;
+    hipLaunchKernelGGL(dmv::k_ba_scd_lists_b, dim3(gx_lists, W), dim3(256), 0, s, dw, 1); work.launches++;
     HIPCHK(hipGetLastError());
     if (B->profile) HIPCHK(hipEventRecord(B->ev[7], s));
-    HIPCHK(hipStreamSynchronize(s));
-    work[3] = 1;
+    if (int r = B->graph.wait(s)) return r;
     B->graph_ms = 0;
     if (B->profile) HIPCHK(hipEventElapsedTime(&B->graph_ms, B->ev[6], B->ev[7]));
     return 0;
@@ -233,7 +223,7 @@ int dmvio_hip_ba_set_graph_from_batch(dmvio_hip_ba_batch* B, int W, const dmvio_
   if (W < 0) return failmsg("ba_set_graph_from_batch: W < 0");
   if (W > B->cap) return failmsg("ba_set_graph_from_batch: more windows than the batch was created for");
   std::lock_guard<std::mutex> lkB(B->mu);
-  if (W == 0) { for (int i = 0; i < 4; i++) B->graph_work[i] = 0; B->graph_ms = 0; return 0; }
+  if (W == 0) { B->graph_work.clear(); B->graph_ms = 0; return 0; }
   if (!win) return failmsg("ba_set_graph_from_batch: null window list");
   std::vector<dmvio_hip_ba*> order(W);
   for (int i = 0; i < W; i++) {
@@ -243,13 +233,8 @@ int dmvio_hip_ba_set_graph_from_batch(dmvio_hip_ba_batch* B, int W, const dmvio_
     order[i] = win[i].ba;
   }
   // the handles' locks, in address order (as dmvio_hip_ba_marginalize_points_batch)
+  if (const int j = dmvFirstRepeated(win, W, &dmvio_hip_ba_graph_window::ba); j >= 0) return failmsg(GraphBatchCall::name(j) + "its handle appears twice in the call");
   std::sort(order.begin(), order.end());
-  for (int i = 1; i < W; i++)
-    if (order[i] == order[i - 1]) {
-      int j = W - 1;
-      while (j > 0 && win[j].ba != order[i]) j--;
-      return failmsg(GraphBatchCall::name(j) + "its handle appears twice in the call");
-    }
   std::vector<std::unique_lock<std::recursive_mutex>> locks;
   for (dmvio_hip_ba* b : order) locks.emplace_back(b->mu);
   for (int i = 0; i < W; i++) {
@@ -261,7 +246,7 @@ int dmvio_hip_ba_set_graph_from_batch(dmvio_hip_ba_batch* B, int W, const dmvio_
   if (int r = c.plan()) return r;
   if (int r = B->workers.parallelFor(W, [&c](const int i) { return c.prepareWindow(i); })) return r;
   // from here on the handles change
-  for (int i = 0; i < 4; i++) B->graph_work[i] = 0;
+  B->graph_work.clear();
   if (int r = B->workers.parallelFor(W, [&c](const int i) { return c.layoutWindow(i); })) return r;
   if (int r = c.enqueue()) return r;
   return B->workers.parallelFor(W, [&c](const int i) { return c.finishWindow(i); });
@@ -269,10 +254,7 @@ int dmvio_hip_ba_set_graph_from_batch(dmvio_hip_ba_batch* B, int W, const dmvio_
 int dmvio_hip_ba_batch_last_graph_work(dmvio_hip_ba_batch* B, int* launches, int* uploads, int* downloads, int* waits) {
   if (!B) return failmsg("ba_batch_last_graph_work: null batch");
   std::lock_guard<std::mutex> lkB(B->mu);
-  if (launches) *launches = B->graph_work[0];
-  if (uploads) *uploads = B->graph_work[1];
-  if (downloads) *downloads = B->graph_work[2];
-  if (waits) *waits = B->graph_work[3];
+  B->graph_work.report(launches, uploads, downloads, waits);
   return 0;
 }
 int dmvio_hip_ba_batch_last_graph_ms(dmvio_hip_ba_batch* B, float* ms) {

@@ -49,18 +49,12 @@ struct MargFrameBatchCall {
     const int nmax = 4 + 8 * Fmax;
     if (int r = allowLds(sizeof(double) * dmv::baMargFrameLdsDoubles(nmax))) return r;
     inStride = dmv::baMargFrameInDoubles(nmax); outStride = dmv::baMargFrameOutDoubles(nmax);
-    inBytes = BatchLayout::padded(sizeof(double) * inStride * W); outBytes = sizeof(double) * outStride * W;
-    if (inBytes + outBytes > B->marg_cap) {   // the marginalisation buffer's growth (MargBatchCall::plan): kept for the calls that follow
-      if (B->d_marg) { hipFree(B->d_marg); B->d_marg = nullptr; }
-      if (B->h_marg) { hipHostFree(B->h_marg); B->h_marg = nullptr; }
-      B->marg_cap = 0;
-      const size_t cap = (inBytes + outBytes) * 2;
-      HIPCHK(hipMalloc((void**)&B->d_marg, cap));
-      HIPCHK(hipHostMalloc((void**)&B->h_marg, cap, hipHostMallocDefault));
-      B->marg_cap = cap;
-    }
-    if (!B->marg_ev) HIPCHK(hipEventCreateWithFlags(&B->marg_ev, hipEventDisableTiming));
-    return 0;
+    DmvCursor C;   // [W records in | W records out]: the marginalisation buffer of MargBatchCall, grown as there and kept for the calls that follow
+    C.take<double>(inStride * W);
+    inBytes = C.bytes();
+    C.take<double>(outStride * W);
+    outBytes = C.bytes() - inBytes;
+    return B->margBegin(C.bytes(), &B->margf_work);
   }
 
   // ---- record k in the pinned buffer: [HM | bM | prior | delta_prior] at the window's own n, (F, frame) in the stride's last double.  A handle without a prior: zeros
@@ -68,7 +62,7 @@ struct MargFrameBatchCall {
     const dmvio_hip_ba_marg_frame_window& q = win[order[k]];
     const BAHost& H = q.ba->H;
     const size_t n = (size_t)H.n();
-    double* rec = reinterpret_cast<double*>(B->h_marg) + inStride * k;
+    double* rec = B->marg.host<double>(0) + inStride * k;
     if (H.HM.size() == n * n) { memcpy(rec, H.HM.data(), sizeof(double) * n * n); memcpy(rec + n * n, H.bM.data(), sizeof(double) * n); }
     else memset(rec, 0, sizeof(double) * (n * n + n));
     const BAFrameHost& fr = H.fr[q.frame];
@@ -80,7 +74,7 @@ struct MargFrameBatchCall {
 
   int enqueue() {
     const hipStream_t s = B->stream;
-    int* const work = B->margf_work;
+    DmvWork& work = B->margf_work;
     // a handle's own stream may still hold work: in front of the call (as MargBatchCall::enqueue)
     for (int k = 0; k < W; k++) {
       dmvio_hip_ba* b = win[order[k]].ba;
@@ -90,21 +84,18 @@ struct MargFrameBatchCall {
     }
     (void)hipGetLastError();   // (hipErrorNotReady of the query above is no error)
     if (B->profile) HIPCHK(hipEventRecord(B->ev[6], s));
-    const double* d_in = reinterpret_cast<const double*>(B->d_marg);
-    double* d_out = reinterpret_cast<double*>(B->d_marg + inBytes);
-    HIPCHK(hipMemcpyAsync(B->d_marg, B->h_marg, sizeof(double) * inStride * W, hipMemcpyHostToDevice, s));
-    work[1] = 1;
+    const double* d_in = B->marg.dev<const double>(0);
+    double* d_out = B->marg.dev<double>(inBytes);
+    if (int r = B->marg.upload(s, inBytes)) return r;
     for (const Grp& g : grp) {
       const size_t lds = sizeof(double) * dmv::baMargFrameLdsDoubles(4 + 8 * g.F);
       hipLaunchKernelGGL(dmv::k_ba_marg_frame_b, dim3(g.cnt), dim3(dmv::BA_MARGF_THREADS), lds, s, d_in, d_out, inStride, outStride, g.w0);
-      work[0]++;
+      work.launches++;
       HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(B->h_marg + inBytes, B->d_marg + inBytes, outBytes, hipMemcpyDeviceToHost, s));
-    work[2] = 1;
+    if (int r = B->marg.download(s, inBytes, outBytes)) return r;
     if (B->profile) HIPCHK(hipEventRecord(B->ev[7], s));
-    HIPCHK(hipStreamSynchronize(s));
-    work[3] = 1;
+    if (int r = B->marg.wait(s)) return r;
     B->margf_ms = 0;
     if (B->profile) HIPCHK(hipEventElapsedTime(&B->margf_ms, B->ev[6], B->ev[7]));
     return 0;
@@ -113,7 +104,7 @@ struct MargFrameBatchCall {
   int scatterWindow(const int k) {
     const dmvio_hip_ba_marg_frame_window& q = win[order[k]];
     const size_t nd = (size_t)q.ba->H.n() - 8;
-    const double* res = reinterpret_cast<const double*>(B->h_marg + inBytes) + outStride * k;
+    const double* res = B->marg.host<const double>(inBytes) + outStride * k;
     memcpy(q.HM_new, res, sizeof(double) * nd * nd); memcpy(q.bM_new, res + nd * nd, sizeof(double) * nd);
     return 0;
   }
@@ -125,7 +116,7 @@ int dmvio_hip_ba_marginalize_frame_batch(dmvio_hip_ba_batch* B, int W, dmvio_hip
   if (W < 0) return failmsg("ba_marginalize_frame_batch: W < 0");
   if (W > B->cap) return failmsg("ba_marginalize_frame_batch: more windows than the batch was created for");
   std::lock_guard<std::mutex> lkB(B->mu);
-  if (W == 0) { for (int i = 0; i < 4; i++) B->margf_work[i] = 0; B->margf_ms = 0; return 0; }
+  if (W == 0) { B->margf_work.clear(); B->margf_ms = 0; return 0; }
   if (!win) return failmsg("ba_marginalize_frame_batch: null window list");
   std::vector<dmvio_hip_ba*> order(W);
   for (int i = 0; i < W; i++) {
@@ -135,8 +126,8 @@ int dmvio_hip_ba_marginalize_frame_batch(dmvio_hip_ba_batch* B, int W, dmvio_hip
     order[i] = win[i].ba;
   }
   // the handles' locks, in address order (as dmvio_hip_ba_marginalize_points_batch)
+  if (dmvFirstRepeated(win, W, &dmvio_hip_ba_marg_frame_window::ba) >= 0) return failmsg("ba_marginalize_frame_batch: a window appears twice");
   std::sort(order.begin(), order.end());
-  for (int i = 1; i < W; i++) if (order[i] == order[i - 1]) return failmsg("ba_marginalize_frame_batch: a window appears twice");
   std::vector<std::unique_lock<std::recursive_mutex>> locks;
   for (dmvio_hip_ba* b : order) locks.emplace_back(b->mu);
   for (int i = 0; i < W; i++) {
@@ -148,7 +139,7 @@ int dmvio_hip_ba_marginalize_frame_batch(dmvio_hip_ba_batch* B, int W, dmvio_hip
   HIPCHK(hipSetDevice(B->ctx->device));
   MargFrameBatchCall c(B, W, win);
   if (int r = c.plan()) return r;
-  for (int i = 0; i < 4; i++) B->margf_work[i] = 0;
+  B->margf_work.clear();
   if (int r = B->workers.parallelFor(W, [&c](const int k) { return c.fillWindow(k); })) return r;
   if (int r = c.enqueue()) return r;
   return B->workers.parallelFor(W, [&c](const int k) { return c.scatterWindow(k); });
@@ -162,10 +153,7 @@ int dmvio_hip_ba_batch_last_marg_frame_ms(dmvio_hip_ba_batch* B, float* ms) {
 int dmvio_hip_ba_batch_last_marg_frame_work(dmvio_hip_ba_batch* B, int* launches, int* uploads, int* downloads, int* waits) {
   if (!B) return failmsg("ba_batch_last_marg_frame_work: null batch");
   std::lock_guard<std::mutex> lkB(B->mu);
-  if (launches) *launches = B->margf_work[0];
-  if (uploads) *uploads = B->margf_work[1];
-  if (downloads) *downloads = B->margf_work[2];
-  if (waits) *waits = B->margf_work[3];
+  B->margf_work.report(launches, uploads, downloads, waits);
   return 0;
 }
 }  // extern "C"

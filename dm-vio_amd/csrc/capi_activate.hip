@@ -402,25 +402,15 @@ float dmvio_hip_min_act_dist_update(float cur, int nPoints, float desiredDensity
 struct dmvio_hip_activation_batch {
   dmvio_hip_ctx* ctx = nullptr;
   int max_windows = 0;
-  char *h_slab = nullptr, *d_slab = nullptr;
-  size_t slab_cap = 0;
-  int *h_counts = nullptr, *d_counts = nullptr;   // max_windows x ACT_COUNTS ints
+  DmvSlab slab;     // grown to a call's need (batch_slab.hpp)
+  DmvSlab counts;   // max_windows x ACT_COUNTS ints
 };
 enum { ACT_COUNTS = 8 + IMM_MAX_HOSTS };
 
-static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-// the slab holds at least `bytes`; growing it waits for the stream first (an earlier call's kernels may still read the old one)
-static int batchReserve(dmvio_hip_activation_batch* b, size_t bytes) {
-  if (bytes <= b->slab_cap) return 0;
-  HIPCHK(hipStreamSynchronize(b->ctx->stream));
-  if (b->h_slab) HIPCHK(hipHostFree(b->h_slab));
-  if (b->d_slab) HIPCHK(hipFree(b->d_slab));
-  b->h_slab = b->d_slab = nullptr; b->slab_cap = 0;
-  const size_t want = bytes + bytes / 2;
-  HIPCHK(hipHostMalloc((void**)&b->h_slab, want, hipHostMallocDefault));
-  HIPCHK(hipMalloc((void**)&b->d_slab, want));
-  b->slab_cap = want;
-  return 0;
+// the slab holds at least `bytes` (one and a half times the need where it grows) and its pinned side is free to write
+static int batchBegin(dmvio_hip_activation_batch* b, size_t bytes) {
+  if (int r = b->slab.reserve(bytes, bytes + bytes / 2, b->ctx->stream)) return r;
+  return b->slab.begin(b->ctx->stream);
 }
 // the part of a window's record that is the same in every call: the handle's arrays
 static void recordOf(ActWin& R, dmvio_hip_activation_batch* b, int w, dmvio_hip_immature* m, dmvio_hip_distance_map* dm) {
@@ -433,13 +423,7 @@ static void recordOf(ActWin& R, dmvio_hip_activation_batch* b, int w, dmvio_hip_
     R.result = m->d_result; R.idepth = m->d_idepth; R.res_state = m->d_res_state; R.gather_i = m->d_gather_i; R.gather_f = m->d_gather_f;
   }
   if (dm) { R.map = dm->d_map; R.map_bytes = dm->map_bytes; }
-  R.counts = b->d_counts + (size_t)w * ACT_COUNTS;
-}
-static int batchHead(dmvio_hip_activation_batch* b, int W, const void* arr, const char* what) {
-  if (!b) return failmsg(std::string(what) + ": null batch handle");
-  if (W < 0 || W > b->max_windows) return failmsg(std::string(what) + ": W is negative or larger than the batch's max_windows");
-  if (W > 0 && !arr) return failmsg(std::string(what) + ": the window array is NULL");
-  return 0;
+  R.counts = b->counts.dev<int>(0) + (size_t)w * ACT_COUNTS;
 }
 static int maxOf(const std::vector<int>& v) { int m = 0; for (int x : v) m = std::max(m, x); return m; }
 
@@ -451,10 +435,9 @@ dmvio_hip_activation_batch* dmvio_hip_activation_batch_create(dmvio_hip_ctx* ctx
   HIPCHKP(hipSetDevice(ctx->device));
   dmvio_hip_activation_batch* b = new dmvio_hip_activation_batch();
   b->ctx = ctx; b->max_windows = max_windows;
-  const size_t cb = sizeof(int) * ACT_COUNTS * (size_t)max_windows;
-  if (hipHostMalloc((void**)&b->h_counts, cb, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&b->d_counts, cb) != hipSuccess) {
+  if (b->counts.create(sizeof(int) * ACT_COUNTS * (size_t)max_windows)) {
     failmsg("activation_batch_create: allocation failed");
-    if (b->h_counts) hipHostFree(b->h_counts);
+    b->counts.release();
     delete b;
     return nullptr;
   }
@@ -464,35 +447,34 @@ void dmvio_hip_activation_batch_destroy(dmvio_hip_activation_batch* b) {
   if (!b) return;
   hipSetDevice(b->ctx->device);
   hipStreamSynchronize(b->ctx->stream);
-  if (b->h_slab) hipHostFree(b->h_slab);
-  if (b->d_slab) hipFree(b->d_slab);
-  hipHostFree(b->h_counts); hipFree(b->d_counts);
+  b->slab.release(); b->counts.release();
   delete b;
 }
 
 int dmvio_hip_distance_map_make_batch(dmvio_hip_activation_batch* b, int W, dmvio_hip_activation_window* win) {
-  if (int r = batchHead(b, W, win, "distance_map_make_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "distance_map_make_batch")) return r;
   if (W == 0) return 0;
   dmvio_hip_ctx* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> lk(c->mu);
   // every refusal before anything is enqueued or any handle touched
-  size_t bytes = pad256(sizeof(ActWin) * (size_t)W);
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_activation_window::dm);
+  DmvCursor L; L.take<ActWin>(W);   // [ActWin x W | per window: KRKi 9H, Kt 3H | host tag, u, v, idepth of its active points]
+  std::vector<size_t> tabOff(W), actOff(W);
   for (int w = 0; w < W; w++) {
     const dmvio_hip_activation_window& V = win[w];
     if (!V.dm) return failmsg("distance_map_make_batch: a distance map handle is NULL");
     if (V.dm->ctx != c) return failmsg("distance_map_make_batch: a distance map belongs to another context");
-    for (int k = 0; k < w; k++) if (win[k].dm == V.dm) return failmsg("distance_map_make_batch: a distance map appears twice");
+    if (w == rep) return failmsg("distance_map_make_batch: a distance map appears twice");
     if (V.n_hosts < 1 || V.n_hosts > IMM_MAX_HOSTS || !V.KRKi9 || !V.Kt3 || V.n_active < 0 || (V.n_active > 0 && (!V.active_host_tag || !V.active_u || !V.active_v || !V.active_idepth)))
       return failmsg("distance_map_make_batch: bad argument (n_hosts, a table or an active-point array)");
     for (int i = 0; i < V.n_active; i++)
       if (V.active_host_tag[i] < 0 || V.active_host_tag[i] >= V.n_hosts) return failmsg("distance_map_make_batch: a point's host_tag has no table row");
-    bytes += pad256(sizeof(float) * 12 * V.n_hosts) + pad256(sizeof(float) * 4 * (size_t)V.n_active);
+    tabOff[w] = L.take<float>(12 * (size_t)V.n_hosts); actOff[w] = L.take<float>(4 * (size_t)V.n_active);
   }
-  if (int r = batchReserve(b, bytes)) return r;
+  if (int r = batchBegin(b, L.bytes())) return r;
   hipStream_t st = c->stream;
-  ActWin* R = reinterpret_cast<ActWin*>(b->h_slab);
-  size_t off = pad256(sizeof(ActWin) * (size_t)W);
+  ActWin* R = b->slab.host<ActWin>(0);
   std::vector<int> na(W);
   const DmGeom G = win[0].dm->G;
   for (int w = 0; w < W; w++) {
@@ -500,22 +482,18 @@ int dmvio_hip_distance_map_make_batch(dmvio_hip_activation_batch* b, int W, dmvi
     recordOf(R[w], b, w, nullptr, V.dm);
     const size_t n = V.n_active;
     R[w].n_active = na[w] = V.n_active;
-    float* t = reinterpret_cast<float*>(b->h_slab + off);
-    const float* dt = reinterpret_cast<const float*>(b->d_slab + off);
-    memcpy(t, V.KRKi9, sizeof(float) * 9 * V.n_hosts); memcpy(t + 9 * V.n_hosts, V.Kt3, sizeof(float) * 3 * V.n_hosts);
-    R[w].mk_KRKi = dt; R[w].mk_Kt = dt + 9 * V.n_hosts;
-    off += pad256(sizeof(float) * 12 * V.n_hosts);
-    char* a = b->h_slab + off;
-    const char* da = b->d_slab + off;
+    const auto t = b->slab.put<float>(tabOff[w]);
+    memcpy(t.h, V.KRKi9, sizeof(float) * 9 * V.n_hosts); memcpy(t.h + 9 * V.n_hosts, V.Kt3, sizeof(float) * 3 * V.n_hosts);
+    R[w].mk_KRKi = t.d; R[w].mk_Kt = t.d + 9 * V.n_hosts;
+    const auto a = b->slab.put<char>(actOff[w]);
     if (n) {
-      memcpy(a, V.active_host_tag, 4 * n); memcpy(a + 4 * n, V.active_u, 4 * n); memcpy(a + 8 * n, V.active_v, 4 * n); memcpy(a + 12 * n, V.active_idepth, 4 * n);
+      memcpy(a.h, V.active_host_tag, 4 * n); memcpy(a.h + 4 * n, V.active_u, 4 * n); memcpy(a.h + 8 * n, V.active_v, 4 * n); memcpy(a.h + 12 * n, V.active_idepth, 4 * n);
     }
-    R[w].act_host = reinterpret_cast<const int*>(da); R[w].act_u = reinterpret_cast<const float*>(da + 4 * n); R[w].act_v = reinterpret_cast<const float*>(da + 8 * n);
-    R[w].act_idepth = reinterpret_cast<const float*>(da + 12 * n);
-    off += pad256(16 * n);
+    R[w].act_host = reinterpret_cast<const int*>(a.d); R[w].act_u = reinterpret_cast<const float*>(a.d + 4 * n); R[w].act_v = reinterpret_cast<const float*>(a.d + 8 * n);
+    R[w].act_idepth = reinterpret_cast<const float*>(a.d + 12 * n);
   }
-  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, off, hipMemcpyHostToDevice, st));
-  const ActWin* D = reinterpret_cast<const ActWin*>(b->d_slab);
+  if (int r = b->slab.upload(st, L.bytes())) return r;
+  const ActWin* D = b->slab.dev<const ActWin>(0);
   const int npix = G.w1 * G.h1, map_bytes = win[0].dm->map_bytes, amax = maxOf(na);
   hipLaunchKernelGGL(k_dm_fill_b, dim3((map_bytes / 16 + 255) / 256, W), dim3(256), 0, st, D);
   if (amax > 0) {
@@ -523,38 +501,41 @@ int dmvio_hip_distance_map_make_batch(dmvio_hip_activation_batch* b, int W, dmvi
     for (int k = 1; k < DM_STEPS; k++) hipLaunchKernelGGL(k_dm_grow_b, dim3((npix + 255) / 256, W), dim3(256), 0, st, D, G, k);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));   // the one wait: the slab may be rewritten by the next call
+  if (int r = b->slab.wait(st)) return r;   // the one wait: the slab may be rewritten by the next call
   for (int w = 0; w < W; w++) win[w].dm->made = true;
   return 0;
 }
 
 int dmvio_hip_immature_select_for_activation_batch(dmvio_hip_activation_batch* b, int W, dmvio_hip_activation_window* win) {
-  if (int r = batchHead(b, W, win, "immature_select_for_activation_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "immature_select_for_activation_batch")) return r;
   if (W == 0) return 0;
   dmvio_hip_ctx* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> lk(c->mu);
-  size_t bytes = pad256(sizeof(ActWin) * (size_t)W);
+  DmvCursor L; L.take<ActWin>(W);   // [ActWin x W | per window: KRKi 9H, Kt 3H floats, H flag bytes]
+  std::vector<size_t> tabOff(W);
   bool lds = true;
+  const int repImm = dmvFirstRepeated(win, W, &dmvio_hip_activation_window::imm), repDm = dmvFirstRepeated(win, W, &dmvio_hip_activation_window::dm);
   for (int w = 0; w < W; w++) {
     const dmvio_hip_activation_window& V = win[w];
     if (!V.imm || !V.dm) return failmsg("immature_select_for_activation_batch: an immature or distance map handle is NULL");
     if (V.imm->ctx != c || V.dm->ctx != c) return failmsg("immature_select_for_activation_batch: a handle belongs to another context");
-    for (int k = 0; k < w; k++) {
-      if (win[k].imm == V.imm) return failmsg("immature_select_for_activation_batch: an immature handle appears twice");
-      if (win[k].dm == V.dm) return failmsg("immature_select_for_activation_batch: a distance map appears twice");
+    if (w == repImm || w == repDm) {
+      // which of the two a walk over the earlier windows meets first: the earliest window that shares either handle, and there the immature set before the map
+      int k = 0;
+      while (win[k].imm != V.imm && win[k].dm != V.dm) k++;
+      return failmsg(win[k].imm == V.imm ? "immature_select_for_activation_batch: an immature handle appears twice" : "immature_select_for_activation_batch: a distance map appears twice");
     }
     if (!V.dm->made) return failmsg("immature_select_for_activation_batch: a distance map has not been made (dmvio_hip_distance_map_make_batch)");
     if (V.n_hosts < 1 || V.n_hosts > IMM_MAX_HOSTS || !V.KRKi9 || !V.Kt3 || !V.host_flagged) return failmsg("immature_select_for_activation_batch: bad argument (n_hosts, a table or host_flagged)");
     if (V.imm->max_tag >= V.n_hosts) return failmsg("immature_select_for_activation_batch: a point's host_tag has no table row (host_tag >= n_hosts)");
     if (V.imm->force_global_walk || walkLds(true, V.dm->map_bytes) + 1024 > (size_t)ACT_LDS_BUDGET) lds = false;
-    bytes += pad256(sizeof(float) * 12 * V.n_hosts + V.n_hosts);
+    tabOff[w] = L.takeBytes(sizeof(float) * 12 * V.n_hosts + V.n_hosts);
   }
-  if (int r = batchReserve(b, bytes)) return r;
+  if (int r = batchBegin(b, L.bytes())) return r;
   if (lds) if (int r = allowBigLdsBatch()) return r;
   hipStream_t st = c->stream;
-  ActWin* R = reinterpret_cast<ActWin*>(b->h_slab);
-  size_t off = pad256(sizeof(ActWin) * (size_t)W);
+  ActWin* R = b->slab.host<ActWin>(0);
   std::vector<int> nn(W);
   const DmGeom G = win[0].dm->G;
   for (int w = 0; w < W; w++) {
@@ -566,32 +547,30 @@ int dmvio_hip_immature_select_for_activation_batch(dmvio_hip_activation_batch* b
     m->P.n = m->n;
     recordOf(R[w], b, w, m, V.dm);
     nn[w] = m->n;
-    float* t = reinterpret_cast<float*>(b->h_slab + off);
-    const float* dt = reinterpret_cast<const float*>(b->d_slab + off);
-    memcpy(t, V.KRKi9, sizeof(float) * 9 * V.n_hosts); memcpy(t + 9 * V.n_hosts, V.Kt3, sizeof(float) * 3 * V.n_hosts);
-    memcpy(t + 12 * V.n_hosts, V.host_flagged, V.n_hosts);
+    const auto t = b->slab.put<float>(tabOff[w]);
+    memcpy(t.h, V.KRKi9, sizeof(float) * 9 * V.n_hosts); memcpy(t.h + 9 * V.n_hosts, V.Kt3, sizeof(float) * 3 * V.n_hosts);
+    memcpy(t.h + 12 * V.n_hosts, V.host_flagged, V.n_hosts);
     ActArgs& A = R[w].A;
     A.n = m->n; A.n_hosts = V.n_hosts; A.newest_tag = V.newest_tag; A.minActDist = V.minActDist; A.minTraceQuality = V.minTraceQuality;
-    A.KRKi = dt; A.Kt = dt + 9 * V.n_hosts; A.flagged = reinterpret_cast<const unsigned char*>(dt + 12 * V.n_hosts);
-    off += pad256(sizeof(float) * 12 * V.n_hosts + V.n_hosts);
+    A.KRKi = t.d; A.Kt = t.d + 9 * V.n_hosts; A.flagged = reinterpret_cast<const unsigned char*>(t.d + 12 * V.n_hosts);
   }
   const int nmax = maxOf(nn);
   if (nmax > 0) {
-    HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, off, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(b->d_counts, 0, sizeof(int) * ACT_COUNTS * (size_t)W, st));
-    const ActWin* D = reinterpret_cast<const ActWin*>(b->d_slab);
+    if (int r = b->slab.upload(st, L.bytes())) return r;
+    HIPCHK(hipMemsetAsync(b->counts.d, 0, sizeof(int) * ACT_COUNTS * (size_t)W, st));
+    const ActWin* D = b->slab.dev<const ActWin>(0);
     hipLaunchKernelGGL(k_act_classify_b, dim3((nmax + 255) / 256, W), dim3(256), 0, st, D, G);
     const int map_bytes = win[0].dm->map_bytes;
     if (lds) hipLaunchKernelGGL(k_act_ordered_walk_b<true>, dim3(W), dim3(ACT_THREADS), walkLds(true, map_bytes), st, D, G);
     else hipLaunchKernelGGL(k_act_ordered_walk_b<false>, dim3(W), dim3(ACT_THREADS), walkLds(false, 0), st, D, G);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, sizeof(int) * ACT_COUNTS * (size_t)W, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // the one wait of the call
+    if (int r = b->counts.download(st, 0, sizeof(int) * ACT_COUNTS * (size_t)W)) return r;
+    if (int r = b->slab.wait(st)) return r;   // the one wait of the call
   }
   for (int w = 0; w < W; w++) {
     dmvio_hip_immature* m = win[w].imm;
     if (m->n > 0) {
-      const int* hc = b->h_counts + (size_t)w * ACT_COUNTS;
+      const int* hc = b->counts.host<int>(0) + (size_t)w * ACT_COUNTS;
       m->act_stats[0] = hc[ACTC_CLASSIFIED]; m->act_stats[1] = hc[ACTC_SURVIVORS]; m->act_stats[2] = hc[ACTC_ACCEPTED]; m->act_stats[3] = hc[ACTC_DELETED];
       m->n_selected = hc[ACTC_ACCEPTED];
     }
@@ -602,23 +581,25 @@ int dmvio_hip_immature_select_for_activation_batch(dmvio_hip_activation_batch* b
 }
 
 int dmvio_hip_immature_optimize_selected_batch(dmvio_hip_activation_batch* b, int W, dmvio_hip_activation_optimize* win, const double fxfycxcy[4]) {
-  if (int r = batchHead(b, W, win, "immature_optimize_selected_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "immature_optimize_selected_batch")) return r;
   if (W == 0) return 0;
   dmvio_hip_ctx* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> lk(c->mu);
   if (!fxfycxcy) return failmsg("immature_optimize_selected_batch: fxfycxcy is NULL");
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_activation_optimize::imm);
   for (int w = 0; w < W; w++) {
     const dmvio_hip_activation_optimize& V = win[w];
     if (!V.imm) return failmsg("immature_optimize_selected_batch: an immature handle is NULL");
     if (V.imm->ctx != c) return failmsg("immature_optimize_selected_batch: a handle belongs to another context");
-    for (int k = 0; k < w; k++) if (win[k].imm == V.imm) return failmsg("immature_optimize_selected_batch: an immature handle appears twice");
+    if (w == rep) return failmsg("immature_optimize_selected_batch: an immature handle appears twice");
     if (!V.imm->have_selection) return failmsg("immature_optimize_selected_batch: a handle has no selection (dmvio_hip_immature_select_for_activation_batch)");
     if (V.F < 2 || V.F > 8 || !V.frame_slots || !V.w2c7 || !V.aff2 || !V.exposure) return failmsg("immature_optimize_selected_batch: bad argument (F or a per-frame array)");
     if (V.imm->max_tag >= V.F) return failmsg("immature_optimize_selected_batch: a point's host_tag is not a keyframe index of its window (host_tag >= F)");
     for (int f = 0; f < V.F; f++) if (V.frame_slots[f] < 0 || V.frame_slots[f] >= c->n_slots) return failmsg("immature_optimize_selected_batch: frame slot out of range");
   }
-  if (int r = batchReserve(b, pad256(sizeof(ActWin) * (size_t)W))) return r;
+  DmvCursor L; L.take<ActWin>(W);
+  if (int r = batchBegin(b, L.bytes())) return r;
   hipStream_t st = c->stream;
   HIPCHK(hipStreamSynchronize(st));   // the handles' pinned tables are free to rewrite; nothing below waits until the end of the call
   std::vector<int> ns(W);
@@ -632,13 +613,13 @@ int dmvio_hip_immature_optimize_selected_batch(dmvio_hip_activation_batch* b, in
   }
   const int smax = maxOf(ns);
   if (smax == 0) return 0;
-  ActWin* R = reinterpret_cast<ActWin*>(b->h_slab);
+  ActWin* R = b->slab.host<ActWin>(0);
   for (int w = 0; w < W; w++) { recordOf(R[w], b, w, win[w].imm, nullptr); R[w].F = win[w].F; }
-  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, sizeof(ActWin) * (size_t)W, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(b->d_counts, 0, sizeof(int) * ACT_COUNTS * (size_t)W, st));
-  hipLaunchKernelGGL(k_act_gather_b, dim3((smax + 255) / 256, W), dim3(256), 0, st, reinterpret_cast<const ActWin*>(b->d_slab));
+  if (int r = b->slab.upload(st, L.bytes())) return r;
+  HIPCHK(hipMemsetAsync(b->counts.d, 0, sizeof(int) * ACT_COUNTS * (size_t)W, st));
+  hipLaunchKernelGGL(k_act_gather_b, dim3((smax + 255) / 256, W), dim3(256), 0, st, b->slab.dev<const ActWin>(0));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, sizeof(int) * ACT_COUNTS * (size_t)W, hipMemcpyDeviceToHost, st));
+  if (int r = b->counts.download(st, 0, sizeof(int) * ACT_COUNTS * (size_t)W)) return r;
   std::vector<std::vector<int>> rs8(W);
   for (int w = 0; w < W; w++) {
     dmvio_hip_activation_optimize& V = win[w];
@@ -649,49 +630,51 @@ int dmvio_hip_immature_optimize_selected_batch(dmvio_hip_activation_batch* b, in
     if (V.idepth) HIPCHK(m->bounce.d2h(V.idepth, m->d_gather_f, sizeof(float) * n, st));
     if (V.res_state) { rs8[w].resize(8 * n); HIPCHK(m->bounce.d2h(rs8[w].data(), m->d_gather_i + 2 * n, sizeof(int) * 8 * n, st)); }
   }
-  HIPCHK(hipStreamSynchronize(st));   // the one wait for the results; the handles' deliveries below find the stream idle
+  if (int r = b->slab.wait(st)) return r;   // the one wait for the results; the handles' deliveries below find the stream idle
   for (int w = 0; w < W; w++) {
     dmvio_hip_activation_optimize& V = win[w];
     dmvio_hip_immature* m = V.imm;
     if (!ns[w]) continue;
     HIPCHK(m->bounce.finish(st));
     if (V.res_state) for (int k = 0; k < ns[w]; k++) for (int t = 0; t < V.F; t++) V.res_state[(size_t)k * V.F + t] = rs8[w][8 * (size_t)k + t];
-    m->n_activated = V.n_activated = b->h_counts[(size_t)w * ACT_COUNTS + ACTC_ACTIVATED];
+    m->n_activated = V.n_activated = b->counts.host<int>(0)[(size_t)w * ACT_COUNTS + ACTC_ACTIVATED];
   }
   return 0;
 }
 
 int dmvio_hip_immature_remove_marked_batch(dmvio_hip_activation_batch* b, int W, dmvio_hip_immature* const* imm, int* n_left) {
-  if (int r = batchHead(b, W, imm, "immature_remove_marked_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, imm, "immature_remove_marked_batch")) return r;
   if (W == 0) return 0;
   dmvio_hip_ctx* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> lk(c->mu);
+  const int rep = dmvFirstRepeated(reinterpret_cast<const void* const*>(imm), W);
   for (int w = 0; w < W; w++) {
     if (!imm[w]) return failmsg("immature_remove_marked_batch: an immature handle is NULL");
     if (imm[w]->ctx != c) return failmsg("immature_remove_marked_batch: a handle belongs to another context");
-    for (int k = 0; k < w; k++) if (imm[k] == imm[w]) return failmsg("immature_remove_marked_batch: an immature handle appears twice");
+    if (w == rep) return failmsg("immature_remove_marked_batch: an immature handle appears twice");
     if (!imm[w]->have_selection) return failmsg("immature_remove_marked_batch: a handle has no marks (dmvio_hip_immature_select_for_activation_batch)");
   }
-  if (int r = batchReserve(b, pad256(sizeof(ActWin) * (size_t)W))) return r;
+  DmvCursor L; L.take<ActWin>(W);
+  if (int r = batchBegin(b, L.bytes())) return r;
   hipStream_t st = c->stream;
-  ActWin* R = reinterpret_cast<ActWin*>(b->h_slab);
+  ActWin* R = b->slab.host<ActWin>(0);
   std::vector<int> nn(W);
   for (int w = 0; w < W; w++) { recordOf(R[w], b, w, imm[w], nullptr); nn[w] = imm[w]->n; }
   const int nmax = maxOf(nn);
   if (nmax > 0) {
-    HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, sizeof(ActWin) * (size_t)W, hipMemcpyHostToDevice, st));
-    const ActWin* D = reinterpret_cast<const ActWin*>(b->d_slab);
+    if (int r = b->slab.upload(st, L.bytes())) return r;
+    const ActWin* D = b->slab.dev<const ActWin>(0);
     hipLaunchKernelGGL(k_rm_plan_b, dim3(W), dim3(ACT_THREADS), 0, st, D);
     hipLaunchKernelGGL(k_rm_apply_b, dim3((nmax + 255) / 256, W), dim3(256), 0, st, D);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, sizeof(int) * ACT_COUNTS * (size_t)W, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // the one wait of the call
+    if (int r = b->counts.download(st, 0, sizeof(int) * ACT_COUNTS * (size_t)W)) return r;
+    if (int r = b->slab.wait(st)) return r;   // the one wait of the call
   }
   for (int w = 0; w < W; w++) {
     dmvio_hip_immature* m = imm[w];
     if (m->n > 0) {
-      const int* hc = b->h_counts + (size_t)w * ACT_COUNTS;
+      const int* hc = b->counts.host<int>(0) + (size_t)w * ACT_COUNTS;
       const int n_tags = m->max_tag + 1;
       std::swap(m->P, m->P2);
       m->n = hc[ACTC_NEW_N];

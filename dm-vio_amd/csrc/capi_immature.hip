@@ -11,23 +11,10 @@
 using namespace dmv;
 
 // ---- W windows per call: the slab of dmvio_hip_trace_batch (immature_handle.h) ----
-static size_t tracePad(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t traceRecordBytes(int W) { return tracePad(sizeof(TraceWin) * (size_t)W); }
-static size_t traceTableBytes(int n_hosts) { return tracePad(sizeof(float) * 14 * (size_t)n_hosts); }
 static void traceBatchFree(dmvio_hip_trace_batch* b) {
-  for (int k = 0; k < 2; k++) {
-    if (b->uploaded[k]) hipEventDestroy(b->uploaded[k]);
-    if (b->h_slab[k]) hipHostFree(b->h_slab[k]);
-  }
+  b->slab.release();
   if (b->h_counts) hipHostFree(b->h_counts);
-  if (b->d_slab) hipFree(b->d_slab);
   delete b;
-}
-static int traceBatchHead(dmvio_hip_trace_batch* b, int W, const void* arr, const char* what) {
-  if (!b) return failmsg(std::string(what) + ": null batch handle");
-  if (W < 0 || W > b->max_windows) return failmsg(std::string(what) + ": W is negative or larger than the batch's max_windows");
-  if (W > 0 && !arr) return failmsg(std::string(what) + ": the window array is NULL");
-  return 0;
 }
 // The body of both batched calls; the caller holds the context's mutex.  Every refusal comes before anything is enqueued or any handle touched.  counts: NULL, or 6 ints per
 // window; then the histogram follows the trace and the stream is waited for once.
@@ -35,11 +22,12 @@ static int traceBatchLocked(dmvio_hip_trace_batch* b, int W, const dmvio_hip_tra
   dmvio_hip_ctx* c = b->ctx;
   const std::string pre = std::string(what) + ": ";
   int nmax = 0;
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_trace_tables_window::imm);
   for (int k = 0; k < W; k++) {
     const dmvio_hip_trace_tables_window& V = win[k];
     if (!V.imm) return failmsg(pre + "an immature handle is NULL");
     if (V.imm->ctx != c) return failmsg(pre + "an immature handle belongs to another context");
-    for (int j = 0; j < k; j++) if (win[j].imm == V.imm) return failmsg(pre + "an immature handle appears twice");
+    if (k == rep) return failmsg(pre + "an immature handle appears twice");
     if (V.new_slot < 0 || V.new_slot >= c->n_slots) return failmsg(pre + "frame slot out of range");
     if (V.n_hosts < 1 || V.n_hosts > IMM_MAX_HOSTS) return failmsg(pre + "n_hosts out of range (1..64)");
     if (!V.KRKi9 || !V.Kt3 || !V.aff2) return failmsg(pre + "a table is NULL");
@@ -49,34 +37,29 @@ static int traceBatchLocked(dmvio_hip_trace_batch* b, int W, const dmvio_hip_tra
   for (int k = 0; k < W; k++) if (int r = dmv_ensure_row_major_locked(c, win[k].new_slot)) return r;
   if (counts) memset(counts, 0, sizeof(int) * 6 * (size_t)W);
   if (nmax == 0) return 0;   // every window is empty: nothing to launch
-  const int mi = b->next;
-  if (b->in_flight[mi]) { HIPCHK(hipEventSynchronize(b->uploaded[mi])); b->in_flight[mi] = false; }   // this mirror's last upload, two calls ago: not the stream
-  char* H = b->h_slab[mi];
-  size_t off = traceRecordBytes(W);
+  if (int r = b->slab.begin(c->stream)) return r;   // this mirror's last upload, two calls ago: not the stream
+  DmvCursor L;
+  TraceWin* H = b->slab.host<TraceWin>(dmvRecords(L, sizeof(TraceWin), W));
   for (int k = 0; k < W; k++) {
     const dmvio_hip_trace_tables_window& V = win[k];
     dmvio_hip_immature* m = V.imm;
     const size_t nh = V.n_hosts;
-    float* t = reinterpret_cast<float*>(H + off);
-    const float* dt = reinterpret_cast<const float*>(b->d_slab + off);
-    memcpy(t, V.KRKi9, sizeof(float) * 9 * nh); memcpy(t + 9 * nh, V.Kt3, sizeof(float) * 3 * nh); memcpy(t + 12 * nh, V.aff2, sizeof(float) * 2 * nh);
-    off += traceTableBytes(V.n_hosts);
+    const auto t = b->slab.put<float>(dmvTraceTable(L, V.n_hosts));
+    memcpy(t.h, V.KRKi9, sizeof(float) * 9 * nh); memcpy(t.h + 9 * nh, V.Kt3, sizeof(float) * 3 * nh); memcpy(t.h + 12 * nh, V.aff2, sizeof(float) * 2 * nh);
     m->P.n = m->n;
     TraceWin r{};
     r.I = c->frames.levelPtr(V.new_slot, 0); r.P = m->P; r.S = m->S;
-    r.KRKi = dt; r.Kt = dt + 9 * nh; r.aff = dt + 12 * nh;
+    r.KRKi = t.d; r.Kt = t.d + 9 * nh; r.aff = t.d + 12 * nh;
     r.w = c->w; r.h = c->h;
-    memcpy(H + sizeof(TraceWin) * (size_t)k, &r, sizeof(r));
+    memcpy(&H[k], &r, sizeof(r));
   }
-  HIPCHK(hipMemcpyAsync(b->d_slab, H, off, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(b->uploaded[mi], c->stream));
-  b->in_flight[mi] = true; b->next = mi ^ 1;
-  const TraceWin* D = reinterpret_cast<const TraceWin*>(b->d_slab);
+  if (int r = b->slab.upload(c->stream, L.bytes())) return r;
+  const TraceWin* D = b->slab.dev<const TraceWin>(0);
   hipLaunchKernelGGL(k_immature_trace_b, dim3((nmax + 3) / 4, W), dim3(256), 0, c->stream, D);
   if (counts) hipLaunchKernelGGL(k_status_hist_b, dim3(W), dim3(1024), 0, c->stream, D, b->h_counts);
   HIPCHK(hipGetLastError());
   if (counts) {
-    HIPCHK(hipStreamSynchronize(c->stream));   // the call's one wait
+    if (int r = b->slab.wait(c->stream)) return r;   // the call's one wait
     memcpy(counts, b->h_counts, sizeof(int) * 6 * (size_t)W);
   }
   return 0;
@@ -183,20 +166,20 @@ int dmvio_hip_immature_add_selected_batch(dmvio_hip_pixel_selector_batch* batch,
   int max_windows = 0;
   char* d_records = nullptr;
   if (int r = dmv_selector_batch_traces(batch, sizeof(NewTracesWin), &c, &max_windows, &d_records)) return r;
-  if (W < 0 || W > max_windows) return failmsg("immature_add_selected_batch: W is negative or larger than the batch's max_windows");
-  if (W > 0 && !win) return failmsg("immature_add_selected_batch: the window array is NULL");
+  if (int r = dmvBatchHead(batch, W, max_windows, win, "immature_add_selected_batch")) return r;
   if (W == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> lk(c->mu);
   // every refusal before anything is enqueued or any handle touched
   std::vector<int> nn(W);
   std::vector<const float*> du(W), dv(W);
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_new_traces_window::imm);
   for (int k = 0; k < W; k++) {
     const dmvio_hip_new_traces_window& V = win[k];
     if (!V.imm) return failmsg("immature_add_selected_batch: an immature handle is NULL");
     if (!V.sel) return failmsg("immature_add_selected_batch: a selector handle is NULL");
     if (V.imm->ctx != c) return failmsg("immature_add_selected_batch: an immature handle belongs to another context");
-    for (int j = 0; j < k; j++) if (win[j].imm == V.imm) return failmsg("immature_add_selected_batch: an immature handle appears twice");
+    if (k == rep) return failmsg("immature_add_selected_batch: an immature handle appears twice");
     dmvio_hip_ctx* sc = nullptr;
     nn[k] = dmv_selector_window_list(V.sel, &sc, &du[k], &dv[k]);
     if (nn[k] < 0) return nn[k];
@@ -348,11 +331,8 @@ dmvio_hip_trace_batch* dmvio_hip_trace_batch_create(dmvio_hip_ctx* ctx, int max_
   HIPCHKP(hipSetDevice(ctx->device));
   dmvio_hip_trace_batch* b = new dmvio_hip_trace_batch();
   b->ctx = ctx; b->max_windows = max_windows;
-  b->slab_bytes = traceRecordBytes(max_windows) + (size_t)max_windows * traceTableBytes(IMM_MAX_HOSTS);
-  bool ok = hipMalloc((void**)&b->d_slab, b->slab_bytes) == hipSuccess && hipHostMalloc((void**)&b->h_counts, sizeof(int) * 6 * (size_t)max_windows, hipHostMallocDefault) == hipSuccess;
-  for (int k = 0; k < 2 && ok; k++)
-    ok = hipHostMalloc((void**)&b->h_slab[k], b->slab_bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&b->uploaded[k], hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
+  if (b->slab.create(dmvTraceSlabBytes(sizeof(TraceWin), max_windows, IMM_MAX_HOSTS), 2, true) ||
+      hipHostMalloc((void**)&b->h_counts, sizeof(int) * 6 * (size_t)max_windows, hipHostMallocDefault) != hipSuccess) {
     failmsg("trace_batch_create: allocation failed");
     traceBatchFree(b);
     return nullptr;
@@ -368,7 +348,7 @@ void dmvio_hip_trace_batch_destroy(dmvio_hip_trace_batch* b) {
 
 // traceOn of every point of every window: as dmvio_hip_immature_trace it does not wait
 int dmvio_hip_immature_trace_batch(dmvio_hip_trace_batch* b, int W, const dmvio_hip_trace_tables_window* win) {
-  if (int r = traceBatchHead(b, W, win, "immature_trace_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "immature_trace_batch")) return r;
   if (W == 0) return 0;
   HIPCHK(hipSetDevice(b->ctx->device));
   std::lock_guard<std::mutex> lk(b->ctx->mu);
@@ -378,7 +358,7 @@ int dmvio_hip_immature_trace_batch(dmvio_hip_trace_batch* b, int W, const dmvio_
 // FullSystem::traceNewCoarse (FullSystem.cpp:541-584) for every window: the tables of each window from its poses by the single call's host functions, one trace launch, and
 // with want_counts one histogram launch and the call's only wait
 int dmvio_hip_trace_new_coarse_batch(dmvio_hip_trace_batch* b, int W, dmvio_hip_trace_window* win, const double fxfycxcy[4], int want_counts) {
-  if (int r = traceBatchHead(b, W, win, "trace_new_coarse_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "trace_new_coarse_batch")) return r;
   if (!fxfycxcy) return failmsg("trace_new_coarse_batch: fxfycxcy is NULL");
   if (W == 0) return 0;
   size_t rows = 0;

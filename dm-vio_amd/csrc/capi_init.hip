@@ -26,7 +26,7 @@ struct dmvio_hip_initializer {
   dmvio_hip_initializer_batch* owner = nullptr;
   std::vector<void*> allocs;
 };
-static inline size_t padn(int n) { return ((size_t)n + 63) & ~(size_t)63; }   // every array of a slab starts on a 256-byte boundary
+static inline size_t padn(int n) { return dmvPad(sizeof(float) * (size_t)n) / sizeof(float); }   // floats: every array of a slab starts on a 256-byte boundary
 enum { IN_FLOATS = 7, RES_FLOATS = 14 };   // per point, + one byte each (isGood / isGood_new) at the end of the slab
 enum { INIT_MAX_BLOCKS = 256 };
 static inline int initGrid(int n) { return std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256)); }
@@ -37,13 +37,12 @@ static inline int initGrid(int n) { return std::max(1, std::min((int)INIT_MAX_BL
 struct dmvio_hip_initializer_batch {
   dmvio_hip_ctx* ctx = nullptr;
   int max_windows = 0;
-  float *h_pts = nullptr, *d_pts = nullptr; size_t pts_cap = 0;     // floats
-  bool pts_pending = false;                                          // h_pts may still be read by the upload of the last set_points_batch
+  DmvSlab pts;    // the point sets; busy() while the upload of the last set_points_batch may still read the pinned side
   std::vector<dmvio_hip_initializer*> tenants;
-  float *h_up = nullptr, *d_up = nullptr; size_t up_cap = 0;        // floats: [W InitWin | idepth_new of every window]
-  float* d_part = nullptr; size_t part_cap = 0;                      // floats
-  float *h_dn = nullptr, *d_dn = nullptr; size_t dn_cap = 0;        // floats: [W x IN_PART sums | results of the windows that asked for any | results of the others]
-  int work[4] = {0, 0, 0, 0};                                        // launches, uploads, downloads, waits of the last calc call
+  DmvSlab up;     // [W InitWin | idepth_new of every window]
+  DmvSlab part;   // the partials: device only
+  DmvSlab dn;     // [W x IN_PART sums | results of the windows that asked for any | results of the others]
+  DmvWork work;   // of the last calc call
 };
 
 template <class T>
@@ -58,19 +57,8 @@ static int nalloc(dmvio_hip_initializer* m, T** p, size_t n) {
 }
 #define INIT_READY(m) do { if (!(m)) return failmsg("null initializer handle"); HIPCHK(hipSetDevice((m)->ctx->device)); } while (0)
 
-// a device buffer (and, h != NULL, its pinned twin) of at least `need` floats; what it held is not kept.  The stream is drained before the old one is freed.
-static int initGrow(float** h, float** d, size_t* cap, size_t need, hipStream_t s) {
-  if (need <= *cap) return 0;
-  HIPCHK(hipStreamSynchronize(s));
-  if (*d) { HIPCHK(hipFree(*d)); *d = nullptr; }
-  if (h && *h) { HIPCHK(hipHostFree(*h)); *h = nullptr; }
-  *cap = 0;
-  const size_t want = std::max<size_t>(need + need / 2, 1024);
-  HIPCHK(hipMalloc((void**)d, sizeof(float) * want));
-  if (h) HIPCHK(hipHostMalloc((void**)h, sizeof(float) * want, hipHostMallocDefault));
-  *cap = want;
-  return 0;
-}
+// a slab of at least `need` bytes whose pinned side may be written; what it held is not kept (DmvSlab::reserve drains the stream before the old one is freed)
+static int initReserve(DmvSlab& slab, size_t need, hipStream_t s) { if (int r = slab.reserve(need, std::max<size_t>(need + need / 2, 4096), s)) return r; return slab.begin(s); }
 // the handle leaves its batch's slab.  keep: its point set goes back into its own d_in first (device to device, stream-ordered); otherwise it is about to be replaced.
 static int initLeaveBatch(dmvio_hip_initializer* m, bool keep) {
   if (!m->owner) return 0;
@@ -276,7 +264,7 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   if (want) HIPCHK(hipMemcpyAsync(m->h_res, m->d_res, sizeof(float) * 14 * PN + n, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   m->upload_pending = false;
-  if (m->owner) m->owner->pts_pending = false;
+  if (m->owner) m->owner->pts.settled();
   initDeliverPoints(m->h_res, n, energy_new2, isGood_new, maxstep, lastHessian_new, JbBuffer_new10);
   initHostTail(T, n, alphaW, alphaK, priorY, priorX, m->h_out, H_out64, b_out8, H_sc64, b_sc8, res3);
   return 0;
@@ -287,6 +275,8 @@ dmvio_hip_initializer_batch* dmvio_hip_initializer_batch_create(dmvio_hip_ctx* c
   if (!ctx || max_windows < 1 || max_windows > 65535) { failmsg("initializer_batch_create: bad argument (max_windows in [1, 65535]: the window is a grid dimension)"); return nullptr; }
   dmvio_hip_initializer_batch* b = new dmvio_hip_initializer_batch();
   b->ctx = ctx; b->max_windows = max_windows;
+  b->part.mirrors = 0;
+  b->up.work = b->dn.work = &b->work;
   return b;
 }
 void dmvio_hip_initializer_batch_destroy(dmvio_hip_initializer_batch* b) {
@@ -298,33 +288,31 @@ void dmvio_hip_initializer_batch_destroy(dmvio_hip_initializer_batch* b) {
     while (!b->tenants.empty()) initLeaveBatch(b->tenants.back(), true);
   }
   hipStreamSynchronize(b->ctx->stream);
-  if (b->d_pts) hipFree(b->d_pts);
-  if (b->d_up) hipFree(b->d_up);
-  if (b->d_part) hipFree(b->d_part);
-  if (b->d_dn) hipFree(b->d_dn);
-  if (b->h_pts) hipHostFree(b->h_pts);
-  if (b->h_up) hipHostFree(b->h_up);
-  if (b->h_dn) hipHostFree(b->h_dn);
+  b->pts.release(); b->up.release(); b->part.release(); b->dn.release();
   delete b;
 }
 
 }  // extern "C"
 
 // what both batched calls refuse of the call as a whole and of window i's handle; 0 or the failure
-static int initBatchCheck(const char* who, const dmvio_hip_initializer_batch* b, int W, const void* win) {
-  char msg[160];
-  if (W < 0 || W > b->max_windows) { snprintf(msg, sizeof(msg), "%s: W = %d outside [0, %d]", who, W, b->max_windows); return failmsg(msg); }
-  if (W > 0 && !win) { snprintf(msg, sizeof(msg), "%s: null window array", who); return failmsg(msg); }
-  return 0;
+static int initBatchHead(const char* who, const dmvio_hip_initializer_batch* b, int W, const void* win) {
+  char range[96];
+  snprintf(range, sizeof(range), ": W = %d outside [0, %d]", W, b->max_windows);
+  const char* const text[3] = {": null batch handle", range, ": null window array"};
+  return dmvBatchHead(b, W, b->max_windows, win, who, text);
 }
+// rep: the first window that names an earlier window's handle (dmvFirstRepeated over the call's windows), or -1
 template <class WIN>
-static int initBatchCheckHandle(const char* who, const dmvio_hip_initializer_batch* b, const WIN* win, int i) {
+static int initBatchCheckHandle(const char* who, const dmvio_hip_initializer_batch* b, const WIN* win, int i, int rep) {
   char msg[160];
   const dmvio_hip_initializer* m = win[i].ini;
   if (!m) { snprintf(msg, sizeof(msg), "%s: window %d: null initializer handle", who, i); return failmsg(msg); }
   if (m->ctx != b->ctx) { snprintf(msg, sizeof(msg), "%s: window %d: the initializer belongs to another context", who, i); return failmsg(msg); }
-  for (int j = 0; j < i; j++)
-    if (win[j].ini == m) { snprintf(msg, sizeof(msg), "%s: window %d: the initializer of window %d named again", who, i, j); return failmsg(msg); }
+  if (i == rep) {
+    int j = 0;
+    while (win[j].ini != m) j++;
+    snprintf(msg, sizeof(msg), "%s: window %d: the initializer of window %d named again", who, i, j); return failmsg(msg);
+  }
   return 0;
 }
 
@@ -336,9 +324,10 @@ int dmvio_hip_initializer_set_points_batch(dmvio_hip_initializer_batch* b, int W
   HIPCHK(hipSetDevice(b->ctx->device));
   dmvio_hip_ctx* c = b->ctx;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (int r = initBatchCheck(who, b, W, win)) return r;
+  if (int r = initBatchHead(who, b, W, win)) return r;
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_initializer_points_window::ini);
   for (int i = 0; i < W; i++) {
-    if (int r = initBatchCheckHandle(who, b, win, i)) return r;
+    if (int r = initBatchCheckHandle(who, b, win, i, rep)) return r;
     const dmvio_hip_initializer_points_window& w = win[i];
     if (w.n < 0 || w.n > w.ini->capacity || !w.u || !w.v || !w.iR || !w.isGood || !w.energy2 || !w.outlierTH) {
       char msg[160];
@@ -349,30 +338,28 @@ int dmvio_hip_initializer_set_points_batch(dmvio_hip_initializer_batch* b, int W
   if (W == 0) return 0;
   hipStream_t s = c->stream;
   // the pinned slabs written below may still be read by an earlier upload (the batch's, or a handle's own): the single call waits in the same case
-  bool pending = b->pts_pending;
+  bool pending = b->pts.busy();
   for (int i = 0; i < W; i++) pending = pending || win[i].ini->upload_pending;
-  if (pending) { HIPCHK(hipStreamSynchronize(s)); b->pts_pending = false; for (int i = 0; i < W; i++) win[i].ini->upload_pending = false; }
+  if (pending) { HIPCHK(hipStreamSynchronize(s)); b->pts.settled(); for (int i = 0; i < W; i++) win[i].ini->upload_pending = false; }
   // the handles of this call move into this batch's slab, which is written from its start: those that live there and are not named again take their points home first
   for (int i = 0; i < W; i++) if (int r = initLeaveBatch(win[i].ini, false)) return r;
   while (!b->tenants.empty()) if (int r = initLeaveBatch(b->tenants.back(), true)) return r;
-  size_t total = 0;
-  for (int i = 0; i < W; i++) total += (IN_FLOATS + 1) * padn(win[i].n);
-  if (int r = initGrow(&b->h_pts, &b->d_pts, &b->pts_cap, total, s)) return r;
-  size_t off = 0;
+  DmvCursor L;   // per window the layout of d_in
+  std::vector<size_t> off(W);
+  for (int i = 0; i < W; i++) off[i] = L.take<float>((IN_FLOATS + 1) * padn(win[i].n));
+  if (int r = initReserve(b->pts, L.bytes(), s)) return r;
   for (int i = 0; i < W; i++) {
     const dmvio_hip_initializer_points_window& w = win[i];
     dmvio_hip_initializer* m = w.ini;
-    const size_t P = padn(w.n);
-    initPackPoints(b->h_pts + off, w.n, w.u, w.v, w.iR, w.isGood, w.energy2, w.outlierTH);
+    const auto at = b->pts.put<float>(off[i]);
+    initPackPoints(at.h, w.n, w.u, w.v, w.iR, w.isGood, w.energy2, w.outlierTH);
     initPackPoints(m->h_in, w.n, w.u, w.v, w.iR, w.isGood, w.energy2, w.outlierTH);   // the handle's own staging copy: calc reads u, v and isGood there
-    m->pts = b->d_pts + off; m->owner = b; b->tenants.push_back(m);
+    m->pts = at.d; m->owner = b; b->tenants.push_back(m);
     m->n = w.n;
     m->upload_pending = true;
-    off += (IN_FLOATS + 1) * P;
   }
   // ONE copy, no wait: the evaluation's own synchronisation covers it
-  if (total) HIPCHK(hipMemcpyAsync(b->d_pts, b->h_pts, sizeof(float) * total, hipMemcpyHostToDevice, s));
-  b->pts_pending = true;
+  if (L.bytes()) if (int r = b->pts.upload(s, L.bytes())) return r;
   return 0;
 }
 
@@ -382,10 +369,11 @@ int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, 
   HIPCHK(hipSetDevice(b->ctx->device));
   dmvio_hip_ctx* c = b->ctx;
   std::lock_guard<std::mutex> lk(c->mu);
-  if (int r = initBatchCheck(who, b, W, win)) return r;
+  if (int r = initBatchHead(who, b, W, win)) return r;
   char msg[320];
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_initializer_window::ini);
   for (int i = 0; i < W; i++) {
-    if (int r = initBatchCheckHandle(who, b, win, i)) return r;
+    if (int r = initBatchCheckHandle(who, b, win, i, rep)) return r;
     const dmvio_hip_initializer_window& w = win[i];
     if (w.lvl < 0 || w.lvl >= c->levels || w.first_slot < 0 || w.first_slot >= c->n_slots || w.new_slot < 0 || w.new_slot >= c->n_slots) {
       snprintf(msg, sizeof(msg), "%s: window %d: level / slot out of range", who, i);
@@ -395,34 +383,34 @@ int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, 
     const int p = initFirstPointOutside(w.ini, w.lvl);
     if (p >= 0) { snprintf(msg, sizeof(msg), "%s: window %d: ", who, i); return failmsg(initOutsideMsg(msg, w.ini, w.lvl, p)); }
   }
-  if (W == 0) { b->work[0] = b->work[1] = b->work[2] = b->work[3] = 0; return 0; }
+  b->work.clear();
+  if (W == 0) return 0;
   // (not counted: the conversion of an 8x4-tiled level-0 slot, as in the single call)
   for (int i = 0; i < W; i++)
     if (win[i].lvl == 0) { if (int r = dmv_ensure_row_major_locked(c, win[i].first_slot)) return r; if (int r = dmv_ensure_row_major_locked(c, win[i].new_slot)) return r; }
   hipStream_t s = c->stream;
-  // layout, in floats.  upload: [W records | idepth_new of window 0 | ...]; download: [W x IN_PART sums | results of the windows that asked for any | those of the others]
-  const size_t rec_floats = padn((int)((sizeof(InitWin) * (size_t)W + sizeof(float) - 1) / sizeof(float)));
+  // layout.  upload: [W records | idepth_new of window 0 | ...]; download: [W x IN_PART sums | results of the windows that asked for any | those of the others]
+  DmvCursor up, dn;
   std::vector<size_t> id_off(W), res_off(W);
   std::vector<char> want(W);
-  size_t up = rec_floats, parts = 0;
+  up.take<InitWin>(W); dn.take<float>((size_t)W * IN_PART);
+  size_t parts = 0;
   int maxG = 1;
   for (int i = 0; i < W; i++) {
     const dmvio_hip_initializer_window& w = win[i];
-    id_off[i] = up; up += padn(w.ini->n);
+    id_off[i] = up.take<float>(w.ini->n);
     want[i] = w.energy_new2 || w.isGood_new || w.maxstep || w.lastHessian_new || w.JbBuffer_new10;
     const int G = initGrid(w.ini->n);
     parts += (size_t)G; maxG = std::max(maxG, G);
   }
-  const size_t sum_floats = padn(W * IN_PART);
-  size_t dn = sum_floats;
-  for (int pass = 1; pass >= 0; pass--)
-    for (int i = 0; i < W; i++) if ((int)want[i] == pass) { res_off[i] = dn; dn += (RES_FLOATS + 1) * padn(win[i].ini->n); }
-  size_t dn_wanted = sum_floats;
-  for (int i = 0; i < W; i++) if (want[i]) dn_wanted += (RES_FLOATS + 1) * padn(win[i].ini->n);
-  if (int r = initGrow(&b->h_up, &b->d_up, &b->up_cap, up, s)) return r;
-  if (int r = initGrow(nullptr, &b->d_part, &b->part_cap, parts * IN_PART, s)) return r;
-  if (int r = initGrow(&b->h_dn, &b->d_dn, &b->dn_cap, dn, s)) return r;
-  InitWin* rec = reinterpret_cast<InitWin*>(b->h_up);
+  size_t dn_wanted = 0;   // what comes back: the sums and the results somebody asked for
+  for (int pass = 1; pass >= 0; pass--) {
+    for (int i = 0; i < W; i++) if ((int)want[i] == pass) res_off[i] = dn.take<float>((RES_FLOATS + 1) * padn(win[i].ini->n));
+    if (pass) dn_wanted = dn.bytes();
+  }
+  int held = initReserve(b->up, up.bytes(), s);
+  if (held || (held = initReserve(b->part, sizeof(float) * parts * IN_PART, s)) || (held = initReserve(b->dn, dn.bytes(), s))) return held;
+  InitWin* rec = b->up.host<InitWin>(0);
   std::vector<Pose> T(W);
   int part_off = 0;
   for (int i = 0; i < W; i++) {
@@ -432,39 +420,36 @@ int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, 
     T[i] = poseFrom7(w.refToNew7);
     InitWin& R = rec[i];
     R.Iref = c->frames.levelPtr(w.first_slot, w.lvl); R.Inew = c->frames.levelPtr(w.new_slot, w.lvl);
-    R.P = initMakePts(n, m->pts, b->d_up + id_off[i], b->d_dn + res_off[i]);
+    const auto idepth = b->up.put<float>(id_off[i]);
+    R.P = initMakePts(n, m->pts, idepth.d, b->dn.dev<float>(res_off[i]));
     R.A = initMakeArgs(c, w.lvl, w.Ki9, w.fxfycxcy_lvl, T[i], w.aff_ab, n, w.alphaW, w.alphaK, w.couplingWeight);
     R.G = initGrid(n); R.part_off = part_off; R.sum_off = i * IN_PART;
     part_off += R.G;
-    if (n > 0) memcpy(b->h_up + id_off[i], w.idepth_new, sizeof(float) * n);
+    if (n > 0) memcpy(idepth.h, w.idepth_new, sizeof(float) * n);
   }
-  HIPCHK(hipMemcpyAsync(b->d_up, b->h_up, sizeof(float) * up, hipMemcpyHostToDevice, s));
-  const InitWin* d_rec = reinterpret_cast<const InitWin*>(b->d_up);
-  hipLaunchKernelGGL(k_init_partial_b, dim3(maxG, W), dim3(256), 0, s, d_rec, b->d_part);
-  hipLaunchKernelGGL(k_init_final_b, dim3(W), dim3(128), 0, s, d_rec, (const float*)b->d_part, b->d_dn);
+  if (int r = b->up.upload(s, up.bytes())) return r;
+  const InitWin* d_rec = b->up.dev<const InitWin>(0);
+  hipLaunchKernelGGL(k_init_partial_b, dim3(maxG, W), dim3(256), 0, s, d_rec, b->part.dev<float>(0)); b->work.launches++;
+  hipLaunchKernelGGL(k_init_final_b, dim3(W), dim3(128), 0, s, d_rec, b->part.dev<const float>(0), b->dn.dev<float>(0)); b->work.launches++;
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(b->h_dn, b->d_dn, sizeof(float) * dn_wanted, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  b->pts_pending = false;
+  if (int r = b->dn.download(s, 0, dn_wanted)) return r;
+  if (int r = b->up.wait(s)) return r;
+  b->pts.settled();
   for (int i = 0; i < W; i++) {
     dmvio_hip_initializer_window& w = win[i];
     dmvio_hip_initializer* m = w.ini;
     m->upload_pending = false;
-    if (m->owner) m->owner->pts_pending = false;
-    if (want[i]) initDeliverPoints(b->h_dn + res_off[i], m->n, w.energy_new2, w.isGood_new, w.maxstep, w.lastHessian_new, w.JbBuffer_new10);
-    initHostTail(T[i], m->n, w.alphaW, w.alphaK, w.priorY, w.priorX, b->h_dn + (size_t)i * IN_PART, w.H_out64, w.b_out8, w.H_sc64, w.b_sc8, w.res3);
+    if (m->owner) m->owner->pts.settled();
+    if (want[i]) initDeliverPoints(b->dn.host<float>(res_off[i]), m->n, w.energy_new2, w.isGood_new, w.maxstep, w.lastHessian_new, w.JbBuffer_new10);
+    initHostTail(T[i], m->n, w.alphaW, w.alphaK, w.priorY, w.priorX, b->dn.host<float>(0) + (size_t)i * IN_PART, w.H_out64, w.b_out8, w.H_sc64, w.b_sc8, w.res3);
   }
-  b->work[0] = 2; b->work[1] = 1; b->work[2] = 1; b->work[3] = 1;
   return 0;
 }
 
 int dmvio_hip_initializer_batch_last_work(dmvio_hip_initializer_batch* b, int* launches, int* uploads, int* downloads, int* waits) {
   if (!b) return failmsg("initializer_batch_last_work: null batch handle");
   std::lock_guard<std::mutex> lk(b->ctx->mu);
-  if (launches) *launches = b->work[0];
-  if (uploads) *uploads = b->work[1];
-  if (downloads) *downloads = b->work[2];
-  if (waits) *waits = b->work[3];
+  b->work.report(launches, uploads, downloads, waits);
   return 0;
 }
 

@@ -156,18 +156,12 @@ int dmvio_hip_tracker_set_template_order(dmvio_hip_tracker* t, int row_major) {
 struct dmvio_hip_set_ref_batch {
   dmvio_hip_ctx* ctx = nullptr;
   int max_windows = 0, max_points = 0;
-  size_t slab_bytes = 0;
-  char *h_slab = nullptr, *d_slab = nullptr;
-  int *h_pcn = nullptr, *d_pcn = nullptr;      // [max_windows][DMV_MAX_LEVELS + 1]; a call uses [W][levels], a from-BA call W selected counts behind them
+  DmvSlab slab;   // records, then floats, then bytes, or the records of a from-BA call (dmvRefSlabBytes, batch_slab.hpp); sized at creation
+  DmvSlab pcn;    // ints [max_windows][DMV_MAX_LEVELS + 1]; a call uses [W][levels], a from-BA call W selected counts behind them
   RefRanker ranker;
-  std::vector<const dmvio_hip_tracker*> seen;  // the duplicate test
-  int last_launches = 0, last_uploads = 0, last_downloads = 0, last_waits = 0;
+  DmvWork work;   // of the last call
 };
-// the slab: records, then floats, then bytes; every part starts on a 16-byte boundary
-static size_t refSlabPointsOff(int W) { return (sizeof(RefWin) * (size_t)W + 15) & ~(size_t)15; }
-static size_t refSlabRanksOff(int W, size_t total_points) { return (refSlabPointsOff(W) + sizeof(float) * 4 * total_points + 15) & ~(size_t)15; }
-// a from-BA call: the W RefWin records, then W RefBaWin records where the points of a host-array call start
-static size_t refSlabBaBytes(int W) { return refSlabPointsOff(W) + sizeof(RefBaWin) * (size_t)W; }
+static const char* const REF_HEAD_TEXT[3] = {": null handle", ": W outside 0 .. max_windows", ": null window array"};
 
 // a tracker's buffers as the W-window kernels find them; the points of the window (none here) are the caller's part
 static void refWinRecord(RefWin& V, dmvio_hip_tracker* t, int* pc_n_row, int ref_slot) {
@@ -185,16 +179,9 @@ dmvio_hip_set_ref_batch* dmvio_hip_set_ref_batch_create(dmvio_hip_ctx* c, int ma
   HIPCHKP(hipSetDevice(c->device));
   dmvio_hip_set_ref_batch* b = new dmvio_hip_set_ref_batch();
   b->ctx = c; b->max_windows = max_windows; b->max_points = max_points_per_window;
-  const size_t total = (size_t)max_windows * (size_t)max_points_per_window;
-  b->slab_bytes = std::max(refSlabRanksOff(max_windows, total) + total, refSlabBaBytes(max_windows));
-  auto init = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&b->d_slab, b->slab_bytes));
-    HIPCHK(hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&b->d_pcn, sizeof(int) * (DMV_MAX_LEVELS + 1) * (size_t)max_windows));
-    HIPCHK(hipHostMalloc((void**)&b->h_pcn, sizeof(int) * (DMV_MAX_LEVELS + 1) * (size_t)max_windows, hipHostMallocDefault));
-    return 0;
-  };
-  if (init()) { dmvio_hip_set_ref_batch_destroy(b); return nullptr; }
+  b->slab.work = b->pcn.work = &b->work;
+  if (b->slab.create(dmvRefSlabBytes(sizeof(RefWin), sizeof(RefBaWin), max_windows, max_points_per_window)) ||
+      b->pcn.create(sizeof(int) * (DMV_MAX_LEVELS + 1) * (size_t)max_windows)) { dmvio_hip_set_ref_batch_destroy(b); return nullptr; }
   return b;
 }
 
@@ -202,31 +189,22 @@ void dmvio_hip_set_ref_batch_destroy(dmvio_hip_set_ref_batch* b) {
   if (!b) return;
   hipSetDevice(b->ctx->device);
   hipStreamSynchronize(b->ctx->stream);
-  if (b->d_slab) hipFree(b->d_slab);
-  if (b->h_slab) hipHostFree(b->h_slab);
-  if (b->d_pcn) hipFree(b->d_pcn);
-  if (b->h_pcn) hipHostFree(b->h_pcn);
+  b->slab.release(); b->pcn.release();
   delete b;
 }
 
 int dmvio_hip_set_ref_batch_last_work(dmvio_hip_set_ref_batch* b, int* launches, int* uploads, int* downloads, int* waits) {
   if (!b) return failmsg("set_ref_batch_last_work: null handle");
   std::lock_guard<std::mutex> lk(b->ctx->mu);
-  if (launches) *launches = b->last_launches;
-  if (uploads) *uploads = b->last_uploads;
-  if (downloads) *downloads = b->last_downloads;
-  if (waits) *waits = b->last_waits;
+  b->work.report(launches, uploads, downloads, waits);
   return 0;
 }
 
 int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmvio_hip_set_ref_window* win) {
   // every refusal stands before the first enqueue and before the first write to a tracker
-  if (!b) return failmsg("tracker_set_ref_batch: null handle");
-  if (W < 0 || W > b->max_windows) return failmsg("tracker_set_ref_batch: W outside 0 .. max_windows");
-  if (W > 0 && !win) return failmsg("tracker_set_ref_batch: null window array");
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "tracker_set_ref_batch", REF_HEAD_TEXT)) return r;
   dmvio_hip_ctx* c = b->ctx;
   std::lock_guard<std::mutex> lk(c->mu);
-  b->seen.clear();
   size_t total = 0;
   int max_n = 0;
   for (int w = 0; w < W; w++) {
@@ -236,14 +214,12 @@ int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmv
     if (x.ref_slot < 0 || x.ref_slot >= c->n_slots) return failmsg("tracker_set_ref_batch: slot out of range");
     if (x.n < 0 || x.n > b->max_points) return failmsg("tracker_set_ref_batch: n outside 0 .. max_points_per_window");
     if (x.n > 0 && (!x.u || !x.v || !x.idepth || !x.hdiF)) return failmsg("tracker_set_ref_batch: null point array");
-    b->seen.push_back(x.trk);
     total += (size_t)x.n;
     max_n = std::max(max_n, x.n);
   }
-  std::sort(b->seen.begin(), b->seen.end());
-  if (std::adjacent_find(b->seen.begin(), b->seen.end()) != b->seen.end())
+  if (dmvFirstRepeated(win, W, &dmvio_hip_set_ref_window::trk) >= 0)
     return failmsg("tracker_set_ref_batch: the same tracker is named twice (two windows would write one set of buffers)");
-  b->last_launches = b->last_uploads = b->last_downloads = b->last_waits = 0;
+  b->work.clear();
   if (W == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
   // reference slots whose level 0 is stored in 8x4 tiles go back to row-major first, as in the single call (their launches are not part of last_work's figures)
@@ -254,29 +230,31 @@ int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmv
   const int n_tiles = win[0].trk->n_tiles, flow_words = (int)win[0].trk->flow_words;
   const int n0 = R.w[0] * R.h[0];
   // the slab: caller arrays are copied into the handle's pinned memory (internal.h: DmvBounce has the reason) and go up in one copy
-  RefWin* h_wins = reinterpret_cast<RefWin*>(b->h_slab);
-  size_t pts = refSlabPointsOff(W) / sizeof(float), ranks = refSlabRanksOff(W, total);
+  if (int r = b->slab.begin(s)) return r;
+  DmvCursor L;
+  RefWin* h_wins = b->slab.host<RefWin>(dmvRecords(L, sizeof(RefWin), W));
+  size_t pts = dmvRefPoints(L, total) / sizeof(float), ranks = dmvRefRanks(L, total);
+  int* const d_pcn = b->pcn.dev<int>(0); const int* const h_pcn = b->pcn.host<int>(0);
   int max_rank = 0;
   for (int w = 0; w < W; w++) {
     const dmvio_hip_set_ref_window& x = win[w];
     dmvio_hip_tracker* t = x.trk;
     RefWin& V = h_wins[w];
-    refWinRecord(V, t, b->d_pcn + (size_t)w * R.levels, x.ref_slot);
+    refWinRecord(V, t, d_pcn + (size_t)w * R.levels, x.ref_slot);
     V.pts_off = pts; V.rank_off = ranks; V.n = x.n;
     if (x.n > 0) {
-      float* hp = reinterpret_cast<float*>(b->h_slab) + pts;
+      float* hp = b->slab.host<float>(0) + pts;
       memcpy(hp, x.u, sizeof(float) * x.n); memcpy(hp + x.n, x.v, sizeof(float) * x.n);
       memcpy(hp + 2 * (size_t)x.n, x.idepth, sizeof(float) * x.n); memcpy(hp + 3 * (size_t)x.n, x.hdiF, sizeof(float) * x.n);
-      V.max_rank = b->ranker.rank(R.w[0], R.h[0], x.n, x.u, x.v, reinterpret_cast<unsigned char*>(b->h_slab) + ranks);
+      V.max_rank = b->ranker.rank(R.w[0], R.h[0], x.n, x.u, x.v, b->slab.host<unsigned char>(ranks));
     }
     max_rank = std::max(max_rank, V.max_rank);
     pts += 4 * (size_t)x.n; ranks += (size_t)x.n;
   }
-  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, ranks, hipMemcpyHostToDevice, s));
-  b->last_uploads = 1;
-  const RefWin* d_wins = reinterpret_cast<const RefWin*>(b->d_slab);
-  const float* d_slab = reinterpret_cast<const float*>(b->d_slab);
-  int launches = 0;
+  if (int r = b->slab.upload(s, L.bytes())) return r;
+  const RefWin* d_wins = b->slab.dev<const RefWin>(0);
+  const float* d_slab = b->slab.dev<const float>(0);
+  int& launches = b->work.launches;
   const unsigned gw = (unsigned)W;
   hipLaunchKernelGGL(k_ref_clear_w, dim3((unsigned)(((n0 + 3) / 4 + 255) / 256), gw), dim3(256), 0, s, d_wins, n0, flow_words); launches++;
   // ranks 0 and 1 together, then every further rank of the batch behind them: a window whose own largest rank is below the launch's leaves at once
@@ -293,12 +271,9 @@ int dmvio_hip_tracker_set_ref_batch(dmvio_hip_set_ref_batch* b, int W, const dmv
   hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
   hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->frames.built_and_waited()); launches++;
   HIPCHK(hipGetLastError());
-  b->last_launches = launches;
-  HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * R.levels, hipMemcpyDeviceToHost, s));
-  b->last_downloads = 1;
-  HIPCHK(hipStreamSynchronize(s));
-  b->last_waits = 1;
-  for (int w = 0; w < W; w++) refPublish(win[w].trk, b->h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
+  if (int r = b->pcn.download(s, 0, sizeof(int) * (size_t)W * R.levels)) return r;
+  if (int r = b->slab.wait(s)) return r;
+  for (int w = 0; w < W; w++) refPublish(win[w].trk, h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
   return 0;
 }
 
@@ -393,9 +368,7 @@ int dmvio_hip_tracker_set_ref_from_ba(dmvio_hip_tracker* t, dmvio_hip_ba* ba, in
 
 int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, dmvio_hip_set_ref_ba_window* win) {
   // every refusal stands before the first enqueue and before the first write to a tracker
-  if (!b) return failmsg("tracker_set_ref_from_ba_batch: null handle");
-  if (W < 0 || W > b->max_windows) return failmsg("tracker_set_ref_from_ba_batch: W outside 0 .. max_windows");
-  if (W > 0 && !win) return failmsg("tracker_set_ref_from_ba_batch: null window array");
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "tracker_set_ref_from_ba_batch", REF_HEAD_TEXT)) return r;
   dmvio_hip_ctx* c = b->ctx;
   std::vector<dmvio_hip_ba*> bas;
   for (int w = 0; w < W; w++) {
@@ -407,18 +380,15 @@ int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, d
   bl.lock(bas);
   std::lock_guard<std::mutex> lk(c->mu);
   std::vector<DmvBaRefSource> S(W);
-  b->seen.clear();
   int max_R = 0;
   for (int w = 0; w < W; w++) {
     dmv_ba_ref_source_locked(win[w].ba, &S[w]);
     if (int r = refBaCheck("tracker_set_ref_from_ba_batch", c, win[w].trk, S[w], win[w].ref_slot)) return r;
-    b->seen.push_back(win[w].trk);
     max_R = std::max(max_R, S[w].R);
   }
-  std::sort(b->seen.begin(), b->seen.end());
-  if (std::adjacent_find(b->seen.begin(), b->seen.end()) != b->seen.end())
+  if (dmvFirstRepeated(win, W, &dmvio_hip_set_ref_ba_window::trk) >= 0)
     return failmsg("tracker_set_ref_from_ba_batch: the same tracker is named twice (two windows would write one set of buffers)");
-  b->last_launches = b->last_uploads = b->last_downloads = b->last_waits = 0;
+  b->work.clear();
   if (W == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
   for (int w = 0; w < W; w++) if (int r = dmv_ensure_row_major_locked(c, win[w].ref_slot)) return r;
@@ -429,19 +399,22 @@ int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, d
   const int n_tiles = win[0].trk->n_tiles, flow_words = (int)win[0].trk->flow_words;
   const int n0 = R.w[0] * R.h[0];
   // the slab: two records per window, nothing else — no point crosses PCIe
-  RefWin* h_wins = reinterpret_cast<RefWin*>(b->h_slab);
-  RefBaWin* h_bas = reinterpret_cast<RefBaWin*>(b->h_slab + refSlabPointsOff(W));
-  int* d_nsel = b->d_pcn + (size_t)W * R.levels;
+  if (int r = b->slab.begin(s)) return r;
+  DmvCursor L;
+  const auto wins = b->slab.put<RefWin>(dmvRecords(L, sizeof(RefWin), W));
+  const auto recs = b->slab.put<RefBaWin>(dmvRecords(L, sizeof(RefBaWin), W));
+  RefWin* h_wins = wins.h; RefBaWin* h_bas = recs.h;
+  int* const d_pcn = b->pcn.dev<int>(0); const int* const h_pcn = b->pcn.host<int>(0);
+  int* d_nsel = d_pcn + (size_t)W * R.levels;
   for (int w = 0; w < W; w++) {
     dmvio_hip_tracker* t = win[w].trk;
-    refWinRecord(h_wins[w], t, b->d_pcn + (size_t)w * R.levels, win[w].ref_slot);
+    refWinRecord(h_wins[w], t, d_pcn + (size_t)w * R.levels, win[w].ref_slot);
     RefBaWin& A = h_bas[w];
     A.res_point = S[w].res_point; A.res_target = S[w].res_target; A.newState = S[w].newState; A.active = S[w].active; A.center = S[w].center; A.HdiF = S[w].HdiF;
     A.n_selected = d_nsel + w; A.n_crowded = t->d_pc_n + dmvio_hip_tracker::REF_BA_CROWDED; A.crowded = t->d_ba_crowded;
     A.R = S[w].R; A.newest = S[w].F - 1; A.cap = t->ba_crowded_cap; A.pad = 0;
   }
-  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, refSlabBaBytes(W), hipMemcpyHostToDevice, s));
-  b->last_uploads = 1;
+  if (int r = b->slab.upload(s, L.bytes())) return r;
   // the context's stream behind whatever the BA handles' streams still hold
   for (dmvio_hip_ba* ba : bl.held)
     for (int w = 0; w < W; w++)
@@ -450,9 +423,8 @@ int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, d
         HIPCHK(hipStreamWaitEvent(s, win[w].trk->ev_ba_ready, 0));
         break;
       }
-  const RefWin* d_wins = reinterpret_cast<const RefWin*>(b->d_slab);
-  const RefBaWin* d_bas = reinterpret_cast<const RefBaWin*>(b->d_slab + refSlabPointsOff(W));
-  int launches = 0;
+  const RefWin* d_wins = wins.d; const RefBaWin* d_bas = recs.d;
+  int& launches = b->work.launches;
   const unsigned gw = (unsigned)W;
   const unsigned gr = (unsigned)std::max(1, (max_R + 255) / 256);
   hipLaunchKernelGGL(k_ref_ba_clear_w, dim3((unsigned)(((n0 + 3) / 4 + 255) / 256), gw), dim3(256), 0, s, d_wins, d_bas, n0, flow_words); launches++;
@@ -474,14 +446,11 @@ int dmvio_hip_tracker_set_ref_from_ba_batch(dmvio_hip_set_ref_batch* b, int W, d
   hipLaunchKernelGGL(k_ref_scan_w, dim3(2 * R.levels, gw), dim3(1024), 0, s, d_wins, R); launches++;
   hipLaunchKernelGGL(k_ref_write_w, dim3(n_tiles, gw), dim3(256), 0, s, d_wins, R, c->frames.built_and_waited()); launches++;
   HIPCHK(hipGetLastError());
-  b->last_launches = launches;
-  HIPCHK(hipMemcpyAsync(b->h_pcn, b->d_pcn, sizeof(int) * (size_t)W * (R.levels + 1), hipMemcpyDeviceToHost, s));   // [W][levels] pc_n, then the W selected counts
-  b->last_downloads = 1;
-  HIPCHK(hipStreamSynchronize(s));
-  b->last_waits = 1;
+  if (int r = b->pcn.download(s, 0, sizeof(int) * (size_t)W * (R.levels + 1))) return r;   // [W][levels] pc_n, then the W selected counts
+  if (int r = b->slab.wait(s)) return r;
   for (int w = 0; w < W; w++) {
-    refPublish(win[w].trk, b->h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
-    win[w].n_selected = b->h_pcn[(size_t)W * R.levels + w];
+    refPublish(win[w].trk, h_pcn + (size_t)w * R.levels, win[w].ref_exposure, win[w].ref_aff_a, win[w].ref_aff_b);
+    win[w].n_selected = h_pcn[(size_t)W * R.levels + w];
   }
   return 0;
 }

@@ -48,7 +48,6 @@ static int salloc(dmvio_hip_pixel_selector* s, T** p, size_t n) {
   s->allocs.push_back(*p);
   return 0;
 }
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 #define SEL_READY(s) do { if (!(s)) return failmsg("null pixel selector handle"); HIPCHK(hipSetDevice((s)->ctx->device)); } while (0)
 
 // geometry and scratch layout of one select() pass at potential `pot`: what the single call and a window of a batch share.  Sets s->d_counters / s->d_map.
@@ -75,12 +74,12 @@ static int selectLayout(dmvio_hip_pixel_selector* s, int pot, float thFactor, Se
   if (G.ncell > s->ncell_max) return failmsg("pixel_selector: internal: cell count exceeds the scratch");
   const size_t N = G.ncell;
   size_t off = 0;
-  s->d_counters = reinterpret_cast<int*>(s->d_zero + off); off += up256(sizeof(int) * SELC_COUNT);
-  L.d_mask = reinterpret_cast<unsigned int*>(s->d_zero + off); off += up256(sizeof(unsigned int) * N);
+  s->d_counters = reinterpret_cast<int*>(s->d_zero + off); off += dmvPad(sizeof(int) * SELC_COUNT);
+  L.d_mask = reinterpret_cast<unsigned int*>(s->d_zero + off); off += dmvPad(sizeof(unsigned int) * N);
   // the three key arrays lie back to back: k_sel_pick addresses them as one (N is a multiple of 16)
-  L.d_key2 = reinterpret_cast<unsigned long long*>(s->d_zero + off); off += up256(sizeof(unsigned long long) * (N + N / 4 + N / 16));
+  L.d_key2 = reinterpret_cast<unsigned long long*>(s->d_zero + off); off += dmvPad(sizeof(unsigned long long) * (N + N / 4 + N / 16));
   L.d_key3 = L.d_key2 + N; L.d_key4 = L.d_key3 + N / 4;
-  s->d_map = reinterpret_cast<unsigned char*>(s->d_zero + off); off += up256((size_t)wh);
+  s->d_map = reinterpret_cast<unsigned char*>(s->d_zero + off); off += dmvPad((size_t)wh);
   if (off > s->zero_cap) return failmsg("pixel_selector: internal: scratch layout exceeds its allocation");
   L.bytes = off;
   return 0;
@@ -171,7 +170,7 @@ dmvio_hip_pixel_selector* dmvio_hip_pixel_selector_create(dmvio_hip_ctx* ctx, co
   const size_t wh = (size_t)s->w * s->h;
   s->ncell_max = 16 * ((s->w + 3) / 4) * ((s->h + 3) / 4);
   const size_t N = s->ncell_max;
-  s->zero_cap = up256(sizeof(int) * SELC_COUNT) + up256(4 * N) + up256(8 * N) + up256(8 * (N / 4)) + up256(8 * (N / 16)) + up256(wh);
+  s->zero_cap = dmvPad(sizeof(int) * SELC_COUNT) + dmvPad(4 * N) + dmvPad(8 * N) + dmvPad(8 * (N / 4)) + dmvPad(8 * (N / 16)) + dmvPad(wh);
   const size_t nag = wh + (size_t)ctx->wl[1] * ctx->hl[1] + (size_t)ctx->wl[2] * ctx->hl[2];
   const size_t ntiles = (std::max(N, wh) + SEL_TILE - 1) / SEL_TILE + 1;
   if (salloc(s, &s->d_pattern, wh) || salloc(s, &s->d_lut, 256) || salloc(s, &s->d_ag, nag) || salloc(s, &s->d_ths, (size_t)s->nbW * s->nbH) ||
@@ -325,32 +324,26 @@ int dmvio_hip_pixel_selector_get_stats(dmvio_hip_pixel_selector* s, long long st
 struct dmvio_hip_pixel_selector_batch {
   dmvio_hip_ctx* ctx = nullptr;
   int max_windows = 0;
-  char *h_slab = nullptr, *d_slab = nullptr;      // max_windows x (SelWin | 256 floats), sized at creation
-  size_t slab_bytes = 0, b_off = 0;
-  int *h_counts = nullptr, *d_counts = nullptr;   // max_windows x SELC_COUNT ints
+  DmvSlab slab;                                   // max_windows x (SelWin | 256 floats), sized at creation (dmvSelSlabBytes, batch_slab.hpp)
+  DmvSlab counts;                                 // max_windows x SELC_COUNT ints
   char* d_traces = nullptr;                       // max_windows records of dmvio_hip_immature_add_selected_batch (capi_immature.hip)
   size_t traces_bytes = 0;
 };
 enum { SEL_TRACES_RECORD = 512 };   // bytes reserved per window in d_traces (capi_immature.hip checks its record against it)
 
-static int selBatchHead(dmvio_hip_pixel_selector_batch* b, int W, const void* arr, const char* what) {
-  if (!b) return failmsg(std::string(what) + ": null batch handle");
-  if (W < 0 || W > b->max_windows) return failmsg(std::string(what) + ": W is negative or larger than the batch's max_windows");
-  if (W > 0 && !arr) return failmsg(std::string(what) + ": the window array is NULL");
-  return 0;
-}
 // the record of window `k` for a select pass at its selector's current potential (active) or for a phase it only watches (inactive: the layout of its last pass stays)
-static int selRecord(dmvio_hip_pixel_selector_batch* b, SelWin& R, int k, const dmvio_hip_pixel_selector_window& V, bool pass) {
+static int selRecord(dmvio_hip_pixel_selector_batch* b, SelWin& R, size_t lut_off, int k, const dmvio_hip_pixel_selector_window& V, bool pass) {
   dmvio_hip_pixel_selector* s = V.sel;
   dmvio_hip_ctx* c = b->ctx;
   memset(&R, 0, sizeof(R));
   R.I0 = c->frames.levelPtr(V.slot, 0); R.I1 = c->frames.levelPtr(V.slot, 1); R.I2 = c->frames.levelPtr(V.slot, 2);
   if (V.B_lut256) {
-    memcpy(b->h_slab + b->b_off + (size_t)k * 1024, V.B_lut256, sizeof(float) * 256);
-    R.B = reinterpret_cast<const float*>(b->d_slab + b->b_off + (size_t)k * 1024);
+    const auto B = b->slab.put<float>(lut_off);
+    memcpy(B.h + 256 * (size_t)k, V.B_lut256, sizeof(float) * 256);
+    R.B = B.d + 256 * (size_t)k;
   }
   R.ag = s->d_ag; R.ths = s->d_ths; R.thsS = s->d_thsS; R.pattern = s->d_pattern;
-  R.counters = b->d_counts + (size_t)k * SELC_COUNT;
+  R.counters = b->counts.dev<int>(0) + (size_t)k * SELC_COUNT;
   R.n2ex = s->d_n2ex; R.tiles = s->d_tiles; R.rn = s->d_rn; R.lu = s->d_lu; R.lv = s->d_lv; R.lt = s->d_lt; R.wu = s->d_wu; R.wv = s->d_wv;
   R.h1 = c->hl[1]; R.h2 = c->hl[2]; R.nbH = s->nbH;
   R.histCut = s->S.minGradHistCut; R.histAdd = s->S.minGradHistAdd;
@@ -377,18 +370,11 @@ dmvio_hip_pixel_selector_batch* dmvio_hip_pixel_selector_batch_create(dmvio_hip_
   HIPCHKP(hipSetDevice(ctx->device));
   dmvio_hip_pixel_selector_batch* b = new dmvio_hip_pixel_selector_batch();
   b->ctx = ctx; b->max_windows = max_windows;
-  b->b_off = up256(sizeof(SelWin) * (size_t)max_windows);
-  b->slab_bytes = b->b_off + (size_t)1024 * max_windows;
   b->traces_bytes = (size_t)SEL_TRACES_RECORD * max_windows;
-  const size_t cb = sizeof(int) * SELC_COUNT * (size_t)max_windows;
-  if (hipHostMalloc((void**)&b->h_slab, b->slab_bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&b->d_slab, b->slab_bytes) != hipSuccess ||
-      hipHostMalloc((void**)&b->h_counts, cb, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&b->d_counts, cb) != hipSuccess ||
+  if (b->slab.create(dmvSelSlabBytes(sizeof(SelWin), max_windows)) || b->counts.create(sizeof(int) * SELC_COUNT * (size_t)max_windows) ||
       hipMalloc((void**)&b->d_traces, b->traces_bytes) != hipSuccess) {
     failmsg("pixel_selector_batch_create: allocation failed");
-    if (b->h_slab) hipHostFree(b->h_slab);
-    if (b->d_slab) hipFree(b->d_slab);
-    if (b->h_counts) hipHostFree(b->h_counts);
-    if (b->d_counts) hipFree(b->d_counts);
+    b->slab.release(); b->counts.release();
     delete b;
     return nullptr;
   }
@@ -398,30 +384,35 @@ void dmvio_hip_pixel_selector_batch_destroy(dmvio_hip_pixel_selector_batch* b) {
   if (!b) return;
   hipSetDevice(b->ctx->device);
   hipStreamSynchronize(b->ctx->stream);
-  hipHostFree(b->h_slab); hipFree(b->d_slab); hipHostFree(b->h_counts); hipFree(b->d_counts); hipFree(b->d_traces);
+  b->slab.release(); b->counts.release(); hipFree(b->d_traces);
   delete b;
 }
 
 int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, int W, dmvio_hip_pixel_selector_window* win) {
-  if (int r = selBatchHead(b, W, win, "pixel_selector_make_maps_batch")) return r;
+  if (int r = dmvBatchHead(b, W, b ? b->max_windows : 0, win, "pixel_selector_make_maps_batch")) return r;
   if (W == 0) return 0;
   dmvio_hip_ctx* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   std::lock_guard<std::mutex> lk(c->mu);
   // every refusal before anything is enqueued or any handle touched
+  const int rep = dmvFirstRepeated(win, W, &dmvio_hip_pixel_selector_window::sel);
   for (int k = 0; k < W; k++) {
     const dmvio_hip_pixel_selector_window& V = win[k];
     if (!V.sel) return failmsg("pixel_selector_make_maps_batch: a selector handle is NULL");
     if (V.sel->ctx != c) return failmsg("pixel_selector_make_maps_batch: a selector belongs to another context");
-    for (int j = 0; j < k; j++) if (win[j].sel == V.sel) return failmsg("pixel_selector_make_maps_batch: a selector appears twice");
+    if (k == rep) return failmsg("pixel_selector_make_maps_batch: a selector appears twice");
     if (V.slot < 0 || V.slot >= c->n_slots) return failmsg("pixel_selector_make_maps_batch: frame slot out of range");
   }
   for (int k = 0; k < W; k++) if (int r = dmv_ensure_row_major_locked(c, win[k].slot)) return r;
   hipStream_t st = c->stream;
   const int w = c->w, h = c->h, wh = w * h;
-  SelWin* R = reinterpret_cast<SelWin*>(b->h_slab);
-  const SelWin* D = reinterpret_cast<const SelWin*>(b->d_slab);
-  const size_t up_bytes = b->b_off + (size_t)1024 * W, cnt_bytes = sizeof(int) * SELC_COUNT * (size_t)W;
+  DmvCursor L;
+  dmvRecords(L, sizeof(SelWin), W);
+  const size_t lut_off = dmvSelLuts(L, W), cnt_bytes = sizeof(int) * SELC_COUNT * (size_t)W;
+  if (int r = b->slab.begin(st)) return r;   // (every round ends in a wait: the slab is free to rewrite)
+  SelWin* R = b->slab.host<SelWin>(0);
+  const SelWin* D = b->slab.dev<const SelWin>(0);
+  const int* h_counts = b->counts.host<int>(0);
   std::vector<SelRecursion> rec(W);
   std::vector<char> running(W, 1);
   for (int k = 0; k < W; k++) {
@@ -433,11 +424,11 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
   for (int round = 0;; round++) {
     int zmax = 0, tmax = 0, cmax = 0;
     for (int k = 0; k < W; k++) {
-      if (int r = selRecord(b, R[k], k, win[k], running[k] != 0)) return r;
+      if (int r = selRecord(b, R[k], lut_off, k, win[k], running[k] != 0)) return r;
       if (!running[k]) continue;
       zmax = std::max(zmax, R[k].zero_words); tmax = std::max(tmax, (R[k].A.n + SEL_TILE - 1) / SEL_TILE); cmax = std::max(cmax, R[k].G.ncell);
     }
-    HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, up_bytes, hipMemcpyHostToDevice, st));
+    if (int r = b->slab.upload(st, L.bytes())) return r;
     if (round == 0) {
       // FrameHessian::makeImages' absSquaredGrad and makeHists of every window
       const int nag = wh + c->wl[1] * c->hl[1] + c->wl[2] * c->hl[2];
@@ -456,12 +447,12 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
     hipLaunchKernelGGL(k_sel_pick_b, dim3((wh + 255) / 256, W), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_sel_write_b, dim3((cmax + 1023) / 1024, W), dim3(1024), 0, st, D);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, cnt_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));   // the one wait of the round
+    if (int r = b->counts.download(st, 0, cnt_bytes)) return r;
+    if (int r = b->slab.wait(st)) return r;   // the one wait of the round
     bool any = false;
     for (int k = 0; k < W; k++) {
       if (!running[k]) continue;
-      running[k] = selectDecide(win[k].sel, b->h_counts + (size_t)k * SELC_COUNT, rec[k]) ? 1 : 0;
+      running[k] = selectDecide(win[k].sel, h_counts + (size_t)k * SELC_COUNT, rec[k]) ? 1 : 0;
       any = any || running[k];
     }
     if (!any) break;
@@ -470,7 +461,7 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
   bool anySub = false;
   int nmaps = 0;
   for (int k = 0; k < W; k++) {
-    if (int r = selRecord(b, R[k], k, win[k], false)) return r;
+    if (int r = selRecord(b, R[k], lut_off, k, win[k], false)) return r;
     R[k].A.n = wh;
     if ((double)rec[k].quotia < 0.95) {
       R[k].A.charTH = (int)(unsigned char)(255 * rec[k].quotia);
@@ -479,7 +470,7 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
     }
     if (win[k].map_out_host) nmaps++;
   }
-  HIPCHK(hipMemcpyAsync(b->d_slab, b->h_slab, up_bytes, hipMemcpyHostToDevice, st));
+  if (int r = b->slab.upload(st, L.bytes())) return r;
   const int ntiles = (wh + SEL_TILE - 1) / SEL_TILE;
   if (anySub) {
     hipLaunchKernelGGL(k_sel_scanA_b<SEL_MODE_NZ>, dim3(ntiles, W), dim3(256), 0, st, D);
@@ -490,10 +481,10 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
   hipLaunchKernelGGL(k_sel_scanB_b, dim3(W), dim3(256), 0, st, D, (int)SEL_MODE_SURV, (int)SELC_NSEL, (int)SELC_NWIN);
   hipLaunchKernelGGL(k_sel_scanC_b<SEL_MODE_SURV>, dim3(ntiles, W), dim3(256), 0, st, D);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(b->h_counts, b->d_counts, cnt_bytes, hipMemcpyDeviceToHost, st));
+  if (int r = b->counts.download(st, 0, cnt_bytes)) return r;
   // the status maps the caller asked for come back through the bounce buffer: ONE reservation (a second one could drain and rewind the staging area under the first)
   size_t moff = 0;
-  const size_t mstep = up256((size_t)wh);
+  const size_t mstep = dmvPad((size_t)wh);
   if (nmaps) {
     HIPCHK(c->bounce.reserve(mstep * nmaps, st, &moff));
     int j = 0;
@@ -501,6 +492,7 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
       if (win[k].map_out_host) HIPCHK(hipMemcpyAsync(c->bounce.h + moff + mstep * (j++), win[k].sel->d_map, (size_t)wh, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(c->bounce.finish(st));   // the one wait of the final phase
+  b->slab.settled();
   int j = 0;
   for (int k = 0; k < W; k++) {
     dmvio_hip_pixel_selector* s = win[k].sel;
@@ -508,7 +500,7 @@ int dmvio_hip_pixel_selector_make_maps_batch(dmvio_hip_pixel_selector_batch* b, 
       const unsigned char* m = reinterpret_cast<const unsigned char*>(c->bounce.h + moff + mstep * (j++));
       for (int i = 0; i < wh; i++) win[k].map_out_host[i] = (float)m[i];
     }
-    const int* hc = b->h_counts + (size_t)k * SELC_COUNT;
+    const int* hc = h_counts + (size_t)k * SELC_COUNT;
     s->currentPotential = rec[k].idealPotential;   // :273
     s->n_selected = hc[SELC_NSEL];
     s->n_window = hc[SELC_NWIN];

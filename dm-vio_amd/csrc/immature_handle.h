@@ -60,17 +60,12 @@ static int dmv_immature_alloc_pts(dmvio_hip_immature* m, dmv::ImmaturePts& P) {
 }
 
 // traceNewCoarse of W windows per call (capi_immature.hip).  One slab per call: [TraceWin x W | every window's table rows KRKi 9H, Kt 3H, aff 2H], filled in a pinned
-// mirror and uploaded in one copy.  A call that does not wait leaves that copy in flight, so the batch alternates between two mirrors and records an event behind each
-// upload; before a mirror is filled again only its own event is waited for (the upload before the previous one), never the stream.
+// mirror and uploaded in one copy.  A call that does not wait leaves that copy in flight, so the slab has two mirrors and an event behind each upload; before a mirror
+// is filled again only its own event is waited for (the upload before the previous one), never the stream (DmvSlab::begin, batch_slab.hpp).
 struct dmvio_hip_trace_batch {
   dmvio_hip_ctx* ctx = nullptr;
   int max_windows = 0;
-  size_t slab_bytes = 0;       // max_windows records + max_windows x 64 x 14 floats
-  char* d_slab = nullptr;
-  char* h_slab[2] = {nullptr, nullptr};      // pinned
-  hipEvent_t uploaded[2] = {nullptr, nullptr};
-  bool in_flight[2] = {false, false};
-  int next = 0;                // the mirror the next call fills
+  DmvSlab slab;                // max_windows records + max_windows x 64 x 14 floats (dmvTraceSlabBytes)
   int* h_counts = nullptr;     // pinned, 6 x max_windows: k_status_hist_b stores straight into it
 };
 

@@ -105,6 +105,7 @@ struct DmvBounce {
 };
 
 #include "frame_store_host.hpp"
+#include "batch_slab.hpp"   // the slabs, head checks and work counters of the W-windows-per-call entry points: the one place their alignment and rewrite rules stand
 
 struct dmvio_hip_ctx {
   int device = 0, w = 0, h = 0, levels = 0, n_slots = 0;

@@ -141,6 +141,32 @@ def test_position_in_the_batch_and_repeated_data(pkg, gpu_required):
         _make_and_select(batch, [_window(pkg, ctx, _BY_NAME[name])], "W=1 ")
 
 
+def test_one_batch_grows_and_is_reused(pkg, gpu_required):
+    """The batch's slab is sized by the call: W = 1 without active points, then W = 3 with 851 of them (the slab is freed and allocated again, more than four times the
+    first call's need), then W = 1 again in the grown slab.  Every call gives the fixture's results, and what a fresh batch object gives, byte for byte; remove_marked, whose
+    slab holds the records alone, runs behind each."""
+    ctx = _ctx(pkg, 256, 192)
+    batch = pkg.ActivationBatchHip(ctx, 3)
+    steps = (("empty_map",), ("small", "dist4", "fractional"), ("dist0",))
+    assert [sum(len(_BY_NAME[n]["active_u"]) for n in names) for names in steps] == [0, 851, 200]
+    for names in steps:
+        outs = []
+        for b in (batch, pkg.ActivationBatchHip(ctx, 3)):
+            wins = [_window(pkg, ctx, _BY_NAME[n]) for n in names]
+            _make_and_select(b, wins, "W=%d " % len(names))
+            state = [(w["imm"].get_activation(), w["dm"].get(), w["imm"].get_marks(), w["imm"].activation_stats()) for w in wins]
+            for w in wins:
+                w["imm"].mark_optimized(w["case"]["imm"]["result"][w["imm"].get_activation()[1]])
+            left = b.remove_marked([w["imm"] for w in wins])
+            assert left == [len(w["c"]["lists"]) for w in wins]
+            outs.append((state, [_snapshot(w["imm"]) for w in wins]))
+        for (a, sa), (f, sf) in zip(zip(*outs[0]), zip(*outs[1])):
+            assert np.array_equal(a[0][0], f[0][0]) and np.array_equal(a[0][1], f[0][1]) and np.array_equal(_bytes(a[1]), _bytes(f[1])) and np.array_equal(a[2], f[2])
+            assert a[3] == f[3]
+            for k in sa:
+                assert np.array_equal(_bytes(sa[k]), _bytes(sf[k])), k
+
+
 def test_big_maps_three_windows_one_cut_short(pkg, gpu_required):
     c = _BY_NAME["big"]
     assert list(c["wh"]) == [512, 512, 8]

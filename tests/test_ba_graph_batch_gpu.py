@@ -256,6 +256,12 @@ def test_refusals(pkg, gpu_required):
     refused([good, None], [g6, g6], "window 1", "null handle")
     refused([good, other], [g6, None], "window 1", "null graph")
     refused([good, good], [g6, g6], "window 1", "twice")
+    B3 = pkg.BundleAdjusterBatch(ctx, 3)   # named three times: the refusal names the first window that repeats an earlier one
+    with pytest.raises(pkg.HipLibraryError, match="window 1: its handle appears twice"):
+        B3.set_graph_from([good, good, good], [g6, g6, g6])
+    with pytest.raises(pkg.HipLibraryError, match="window 2: its handle appears twice"):
+        B3.set_graph_from([other, good, other], [g6, g6, g6])
+    B3.close()
     foreign = pkg.BundleAdjusterHip(ctx2)
     refused([good, foreign], [g6, g6], "window 1", "another context")
     bare = pkg.BundleAdjusterHip(ctx)

@@ -171,6 +171,48 @@ def test_cycle_order_on_one_batch_object(pkg, gpu_required):
     B.close(); B1.close(); _close(S, Bt); ctx.close()
 
 
+def test_one_marginalisation_buffer_grows_and_is_reused(pkg, gpu_required):
+    """Point and frame marginalisation share one buffer of the batch object, laid out per call and grown to the call's need.  One batch object goes through
+    frames / points / frames of one 4-keyframe window (the buffer is allocated by the frame call, the point call finds it large enough), of three 6-keyframe windows (more
+    than four times either need: the frame call grows it, the point call lays it out anew) and of a 4-keyframe window again (both in the grown buffer); every result
+    equals, byte for byte, the same call of a batch object created for it, on twin handles."""
+    steps = [([mc.spec("k4a", 22)], [3]), ([mc.spec("k6b", 1), mc.spec("k6a", 0), mc.spec("k6b", 0)], [0, 2, 5]), ([mc.spec("k4a", 22)], [1])]
+    ctx, slots = fc.upload_case(pkg, [sp[0] for specs, _ in steps for sp in specs])
+
+    def prepared(specs):
+        hs = [fc.full_handle(pkg, ctx, slots[sp[0]], sp) for sp in specs]
+        for ba, sp in zip(hs, specs):
+            mc.prepare(ba, sp[2])
+        return hs
+
+    def fresh_batch(call, *args, **kw):
+        Bf = pkg.BundleAdjusterBatch(ctx, 3)
+        r = getattr(Bf, call)(*args, **kw)
+        Bf.close()
+        return r
+
+    B = pkg.BundleAdjusterBatch(ctx, 3)
+    for step, (specs, frames) in enumerate(steps):
+        cands = [mc.candidates(bc.case(sp[0])) for sp in specs]
+        one, twin = prepared(specs), prepared(specs)
+        first = [0] * len(specs)          # (a handle whose prior was never set: only its first keyframe, held by its own pose prior, leaves a regular block)
+        got = [B.marginalize_frames(one, first), B.marginalize_points(one, cands, update_prior=True), B.marginalize_frames(one, frames)]
+        assert B.last_marg_frame_work() == ONE_PER_COUNT and B.last_marg_work() == dict(launches=6, uploads=3, downloads=1, waits=1)
+        ref = [fresh_batch("marginalize_frames", twin, first), fresh_batch("marginalize_points", twin, cands, update_prior=True),
+               fresh_batch("marginalize_frames", twin, frames)]
+        for w in range(len(specs)):
+            what = "step %d window %d" % (step, w)
+            for k in (0, 2):
+                _same(ref[k][w][0], got[k][w][0], what + " HM_new, frame call %d" % k); _same(ref[k][w][1], got[k][w][1], what + " bM_new, frame call %d" % k)
+            assert np.array_equal(ref[1][w][0], got[1][w][0]) and ref[1][w][3] == got[1][w][3], what + " decisions"
+            _same(ref[1][w][1], got[1][w][1], what + " Hadd"); _same(ref[1][w][2], got[1][w][2], what + " badd")
+            assert got[1][w][1].any() and got[2][w][0].any() and not np.array_equal(got[0][w][0], got[2][w][0])
+            Ha, ba_ = one[w].get_marg_prior(); Hb, bb = twin[w].get_marg_prior()
+            _same(Hb, Ha, what + " prior HM"); _same(bb, ba_, what + " prior bM")
+        _close(one, twin)
+    B.close(); ctx.close()
+
+
 def test_refusals(pkg, gpu_required):
     """every refusal gives a message, writes nothing into the callers' arrays and leaves the work counters of the call before it; W == 0 returns 0 and zeroes them"""
     F = 3

@@ -334,6 +334,23 @@ def test_zero_windows(rig, oracle, synth):
     assert_same(bt.calc([win(cases[0], A[0])])[0], ref[0], "after W = 0")
 
 
+def test_one_batch_grows_and_is_reused(rig, oracle, synth):
+    """The batch's four slabs are sized by the call.  W = 1 with 5 points, then W = 3 with 257 + 700 + 65 (every slab is freed and allocated again: more than four times
+    the first call's need, and above the 4 KiB a slab starts with), then W = 1 with 63 points in the grown slabs: every call equals the single calls and the same call on
+    a batch object created for it; the work figures are counted per call, a call without windows counts nothing."""
+    steps = [[B.case(synth, oracle, "small", 1, 5, seed=150)],
+             [B.case(synth, oracle, "small", 1, 257, seed=151), B.case(synth, oracle, "large", 2, 700, seed=152), B.case(synth, oracle, "huber", 1, 65, seed=153)],
+             [B.case(synth, oracle, "large", 2, 63, seed=154)]]
+    bt = rig.batch(3)
+    for s, cases in enumerate(steps):
+        got, *_ = batch_vs_single(rig, cases, bt=bt, label="step %d" % s)
+        assert bt.last_work() == (2, 1, 1, 1)
+        fresh, *_ = batch_vs_single(rig, cases, label="step %d, fresh batch" % s)
+        for i in range(len(cases)):
+            assert_same(got[i], fresh[i], "step %d window %d against a fresh batch" % (s, i))
+        assert rig.pkg.load_library().dmvio_hip_initializer_calc_res_and_gs_batch(bt.p, 0, None) == 0 and bt.last_work() == (0, 0, 0, 0)
+
+
 def test_same_batched_call_twice_same_bits(rig, oracle, synth):
     cases = B.mixed_batch(synth, oracle)
     got, ref, A, R, bt = batch_vs_single(rig, cases, label="first")

@@ -246,6 +246,55 @@ def test_two_calls_with_nothing_between_them(pkg, env):
         _assert_state(imms[ci].get_state(), env["cases"][ci]["ref"][1], "window %d after two frames, tables" % ci)
 
 
+def test_four_calls_back_to_back_reuse_both_mirrors(pkg, env):
+    """the slab has two pinned mirrors: the third and fourth call without a wait fill a mirror an earlier call of the row uploaded from, behind that mirror's event.
+    W = 2, seven points per window, other tables in every call; every call against the single call on twin handles, bit for bit."""
+    ctx = env["ctx"]
+    NP = 7
+
+    def small(ci):
+        c = env["cases"][ci]
+        imm = pkg.ImmaturePointsHip(ctx, capacity=16)
+        assert imm.add_points(0, c["slot"], c["u"][:NP], c["v"][:NP]) == 0
+        return imm
+
+    def tables(ci, k):
+        """call k's tables of window ci: the case's own of frames 1..3, then frame 1's with another translation"""
+        KRKi, Kt, aff = env["cases"][ci]["tables"][k % 3]
+        return dict(new_slot=env["cases"][ci]["slot"] + 1 + k % 3, KRKi=KRKi, Kt=Kt * np.float32(0.5) if k == 3 else Kt, aff=aff)
+
+    single = {}
+    for ci in (0, 1):
+        for k in range(4):
+            twin = small(ci)
+            twin.trace(**tables(ci, k))
+            single[ci, k] = twin.get_state()
+        twin = small(ci)
+        single[ci, "counts"] = twin.traceNewCoarse(**{k: v for k, v in _win(env, twin, ci, 1).items() if k != "imm"}, fxfycxcy=env["K4"])
+        single[ci, 4] = twin.get_state()
+    assert any(not _same(single[0, 0][name], single[0, 3][name]) for name in FLOATS)          # the fourth tables are not the first
+    # on one pair of handles, the state set back between the calls (which drains the stream: the events are waited for, and found done)
+    batch = pkg.TraceBatchHip(ctx, 2)
+    X, Y = small(0), small(1)
+    fresh = [m.get_state() for m in (X, Y)]
+    for k in range(4):
+        for m, s in zip((X, Y), fresh):
+            m.set_state(s["idepth_min"], s["idepth_max"], s["quality"], s["lastTraceStatus"])
+        batch.trace([dict(imm=X, **tables(0, k)), dict(imm=Y, **tables(1, k))])
+        for ci, m in enumerate((X, Y)):
+            _assert_state(m.get_state(), single[ci, k], "call %d window %d" % (k, ci))
+    # on a fresh batch and a pair of handles per call: nothing at all between the four calls, then the counted one
+    batch = pkg.TraceBatchHip(ctx, 2)
+    pairs = [(small(0), small(1)) for _ in range(5)]
+    for k in range(4):
+        batch.trace([dict(imm=pairs[k][0], **tables(0, k)), dict(imm=pairs[k][1], **tables(1, k))])
+    counts = batch.trace_new_coarse([_win(env, pairs[4][0], 0, 1), _win(env, pairs[4][1], 1, 1)], env["K4"])
+    for k in range(5):
+        for ci in (0, 1):
+            _assert_state(pairs[k][ci].get_state(), single[ci, k], "back to back: call %d window %d" % (k, ci))
+    assert counts == [single[0, "counts"], single[1, "counts"]]
+
+
 def test_refusals_leave_the_handles_usable(pkg, env):
     lib = pkg.load_library()
     ctx, K4 = env["ctx"], env["K4"]
