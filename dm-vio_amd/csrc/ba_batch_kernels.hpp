@@ -328,27 +328,13 @@ __global__ void __launch_bounds__(256) k_ba_lin_energy_b(BAWinDev* __restrict__ 
     float* __restrict__ e = linE + (size_t)ri * 8;
     if (lin[ri] && active[ri]) {
       const int pi = gl(V.Rs.point)[ri];
-      const float* __restrict__ J = gl(V.fullJ) + (size_t)ri * 74;
+      const float* __restrict__ J = gl(V.fullJ) + (size_t)ri * FJ_FLOATS;
       const float* __restrict__ rtz = gl(V.rtz) + (size_t)ri * 8;
       const float* __restrict__ dp = adHT + (size_t)(gl(V.P.host)[pi] + V.W.F * gl(V.Rs.target)[ri]) * 8;
-      const float dd = 0.0f;
-      float sx = 0, sy = 0, cx = 0, cy = 0;
+      float Jp_delta_x, Jp_delta_y;
+      baJpDelta(J, dp, V.cDeltaF[0], 0.0f, Jp_delta_x, Jp_delta_y);
 #pragma unroll
-      for (int i = 0; i < 6; i++) { sx += J[8 + i] * dp[i]; sy += J[14 + i] * dp[i]; }
-#pragma unroll
-      for (int i = 0; i < 4; i++) { cx += J[20 + i] * V.cDeltaF[0][i]; cy += J[24 + i] * V.cDeltaF[0][i]; }
-      const float Jp_delta_x = sx + cx + J[28] * dd, Jp_delta_y = sy + cy + J[29] * dd;
-#pragma unroll
-      for (int q = 0; q < 8; q++) {
-        float Jdelta = J[30 + q] * Jp_delta_x;
-        Jdelta = Jdelta + J[38 + q] * Jp_delta_y;
-        Jdelta = Jdelta + J[46 + q] * dp[6];
-        Jdelta = Jdelta + J[54 + q] * dp[7];
-        float r0 = rtz[q];
-        r0 = r0 + r0;
-        r0 = r0 + Jdelta;
-        e[q] = Jdelta * r0;
-      }
+      for (int q = 0; q < 8; q++) e[q] = baLinEnergyTerm(J, rtz, dp, Jp_delta_x, Jp_delta_y, q);
     } else {
 #pragma unroll
       for (int q = 0; q < 8; q++) e[q] = 0.0f;   // (skipped below: the flag is tested again — a +0.0f would not change a sum that is never -0.0f either)

@@ -117,7 +117,7 @@ static int graphLayout(dmvio_hip_ba* b, const GraphPrep& G, GraphDev& D) {
   b->n_lin_blocks = (R + LIN_RES_PER_BLOCK - 1) / LIN_RES_PER_BLOCK; b->n_pt_blocks = (N + 255) / 256; b->n_pt8_blocks = (N + PT_GROUPS_PER_BLOCK - 1) / PT_GROUPS_PER_BLOCK;
   // energy partials (doubles) and the per-residual energies with outliers (floats) share one pinned allocation the kernel stores into
   b->n_epart = std::max(b->n_lin_blocks, F2 * 8);
-  if (dalloc(b, &b->d_spart, 2 * b->n_pt_blocks) || dalloc(b, &b->d_fullJ, (size_t)R * 74)) return -1;
+  if (dalloc(b, &b->d_spart, 2 * b->n_pt_blocks) || dalloc(b, &b->d_fullJ, (size_t)R * FJ_FLOATS)) return -1;
   // what the host reads back every iteration (the stitched system, the energy partials, the per-residual energies) is written by the
   // kernels straight into pinned host memory (h_sys, h_res: allocated with the handle, sized for BA_MAXF_CAP keyframes): no copy engine between the last kernel and the host's wait
   if (dalloc(b, &b->d_sys, (size_t)tot + 1)) return -1;
@@ -238,10 +238,10 @@ static int linAlloc(dmvio_hip_ba* b) {
 static int linFinish(dmvio_hip_ba* b, int* n_linearized) {
   const int R = b->H.R;
   hipStream_t s = b->stream;
-  b->h_linAct.resize(R); b->h_linJ.resize((size_t)R * 74); b->h_rtz.resize((size_t)R * 8);
+  b->h_linAct.resize(R); b->h_linJ.resize((size_t)R * FJ_FLOATS); b->h_rtz.resize((size_t)R * 8);
   HIPCHK(b->bounce.d2h(b->h_lin.data(), b->d_lin, R, s));
   HIPCHK(b->bounce.d2h(b->h_linAct.data(), b->Rs.active, R, s));
-  HIPCHK(b->bounce.d2h(b->h_linJ.data(), b->d_fullJ, sizeof(float) * 74 * R, s));
+  HIPCHK(b->bounce.d2h(b->h_linJ.data(), b->d_fullJ, sizeof(float) * FJ_FLOATS * R, s));
   HIPCHK(b->bounce.d2h(b->h_rtz.data(), b->d_rtz, sizeof(float) * 8 * R, s));
   HIPCHK(b->bounce.finish(s));
   b->n_lin = 0;
@@ -270,13 +270,13 @@ static int linImport(dmvio_hip_ba* b, const unsigned char* flags, const float* J
   if (int r = linAlloc(b)) return r;
   const int n = (int)idx.size();
   if (n > 0) {
-    std::vector<float> packed((size_t)n * 82);
+    std::vector<float> packed((size_t)n * FJ_PACKED);
     for (int k = 0; k < n; k++) {
-      memcpy(&packed[(size_t)k * 82], J74 + (size_t)idx[k] * 74, sizeof(float) * 74);
-      memcpy(&packed[(size_t)k * 82 + 74], rtz + (size_t)idx[k] * 8, sizeof(float) * 8);
+      memcpy(&packed[(size_t)k * FJ_PACKED], J74 + (size_t)idx[k] * FJ_FLOATS, sizeof(float) * FJ_FLOATS);
+      memcpy(&packed[(size_t)k * FJ_PACKED + FJ_FLOATS], rtz + (size_t)idx[k] * 8, sizeof(float) * 8);
     }
     int* d_idx = nullptr; float* d_packed = nullptr;
-    if (dalloc(b, &d_idx, n) || dalloc(b, &d_packed, (size_t)n * 82)) return -1;
+    if (dalloc(b, &d_idx, n) || dalloc(b, &d_packed, (size_t)n * FJ_PACKED)) return -1;
     HIPCHK(b->bounce.h2d(d_idx, idx.data(), sizeof(int) * n, s));
     HIPCHK(b->bounce.h2d(d_packed, packed.data(), sizeof(float) * packed.size(), s));
     hipLaunchKernelGGL(k_ba_lin_import, dim3((n + 255) / 256), dim3(256), 0, s, n, (const int*)d_idx, (const float*)d_packed, b->Rs, b->d_fullJ, b->d_rtz, b->d_linRec, b->d_lin);
@@ -301,7 +301,7 @@ static int setGraphFrom(dmvio_hip_ba* b, dmvio_hip_graph* g) {
     S.host.resize(N); S.u.resize(N); S.v.resize(N); S.idepth.resize(N); S.color.resize(8 * (size_t)N); S.weights.resize(8 * (size_t)N); S.prior.resize(N);
     S.res_point.resize(R); S.res_target.resize(R);
     const bool anyLin = g->nLin > 0;   // residuals that arrive linearised: their flags / Jacobians / res_toZeroF in flat order (only then)
-    if (anyLin) { S.lin.assign(R, 0); S.linJ.resize((size_t)R * 74); S.linRtz.resize((size_t)R * 8); } else S.lin.clear();
+    if (anyLin) { S.lin.assign(R, 0); S.linJ.resize((size_t)R * FJ_FLOATS); S.linRtz.resize((size_t)R * 8); } else S.lin.clear();
     int pi = 0, ri = 0;
     for (int f = 0; f < (int)g->frames.size(); f++)
       for (const DmvGraphPoint& P : g->frames[f]) {
@@ -311,7 +311,7 @@ static int setGraphFrom(dmvio_hip_ba* b, dmvio_hip_graph* g) {
           S.res_point[ri] = pi; S.res_target[ri] = P.target[k];
           if (anyLin && P.lin[k] >= 0) {
             S.lin[ri] = 1;
-            memcpy(&S.linJ[(size_t)ri * 74], g->linPool[P.lin[k]].J, sizeof(float) * 74); memcpy(&S.linRtz[(size_t)ri * 8], g->linPool[P.lin[k]].res_toZeroF, sizeof(float) * 8);
+            memcpy(&S.linJ[(size_t)ri * FJ_FLOATS], g->linPool[P.lin[k]].J, sizeof(float) * FJ_FLOATS); memcpy(&S.linRtz[(size_t)ri * 8], g->linPool[P.lin[k]].res_toZeroF, sizeof(float) * 8);
           }
         }
         pi++;

@@ -52,6 +52,56 @@ enum {
   REC_HDD = 45, REC_BD = 46, REC_HCD = 47,  // per-residual contributions to the point sums (1, 1, 4)
   REC_PAD = 51
 };
+// The 74-float RawResidualJacobian row (RawResidualJacobian.h:32-61 order; dmvio_hip_ba_get_full_jacobians' layout) of the applied linearisation, kept on request and for
+// the marginalisation: what fixLinearizationF and addPoint<1> / <2> read (fullJ, margFullJ, h_linJ).  A residual that arrives linearised travels as the packed row
+// [J | res_toZeroF (8)] of FJ_PACKED floats.
+enum {
+  FJ_RESF = 0,      // 8   resF
+  FJ_JPDXI0 = 8,    // 6
+  FJ_JPDXI1 = 14,   // 6
+  FJ_JPDC0 = 20,    // 4
+  FJ_JPDC1 = 24,    // 4
+  FJ_JPDD = 28,     // 2
+  FJ_JIDX0 = 30,    // 8   JIdx, x
+  FJ_JIDX1 = 38,    // 8   JIdx, y
+  FJ_JAB0 = 46,     // 8   JabF, a
+  FJ_JAB1 = 54,     // 8   JabF, b
+  FJ_JIDX2 = 62,    // 00, 01, 10, 11
+  FJ_JABJIDX = 66,  // 00, 01, 10, 11
+  FJ_JAB2 = 70,     // 00, 01, 10, 11
+  FJ_FLOATS = 74,
+  FJ_PACKED = FJ_FLOATS + 8
+};
+// What a frozen row J gives at the deltas of a state (EFResidual::fixLinearizationF, EnergyFunctionalStructs.cpp:85-106; addPoint<1>, AccumulatedTopHessian.cpp:84-98;
+// calcLEnergyPt, EnergyFunctional.cpp:349-409).  dp: adHTdeltaF of the residual's (host, target) pair (8 floats), cd: cDeltaF (4), dd: the point's idepth - idepth_zero.
+__host__ __device__ __forceinline__ void baJpDelta(const float* __restrict__ J, const float* __restrict__ dp, const float* __restrict__ cd, const float dd,
+                                                   float& Jp_delta_x, float& Jp_delta_y) {
+  float sx = 0, sy = 0, cx = 0, cy = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) { sx += J[FJ_JPDXI0 + i] * dp[i]; sy += J[FJ_JPDXI1 + i] * dp[i]; }
+#pragma unroll
+  for (int i = 0; i < 4; i++) { cx += J[FJ_JPDC0 + i] * cd[i]; cy += J[FJ_JPDC1 + i] * cd[i]; }
+  Jp_delta_x = sx + cx + J[FJ_JPDD + 0] * dd; Jp_delta_y = sy + cy + J[FJ_JPDD + 1] * dd;
+}
+// res_toZeroF of pattern pixel i: resF - J delta, subtracted term by term
+__device__ __forceinline__ float baResToZero(const float* __restrict__ J, const float* __restrict__ dp, const float Jp_delta_x, const float Jp_delta_y, const int i) {
+  float rtz = J[FJ_RESF + i];
+  rtz = rtz - J[FJ_JIDX0 + i] * Jp_delta_x; rtz = rtz - J[FJ_JIDX1 + i] * Jp_delta_y;
+  rtz = rtz - J[FJ_JAB0 + i] * dp[6]; rtz = rtz - J[FJ_JAB1 + i] * dp[7];
+  return rtz;
+}
+// pattern pixel i's term of the linearised energy: (J delta) (2 res_toZeroF + J delta)
+__host__ __device__ __forceinline__ float baLinEnergyTerm(const float* __restrict__ J, const float* __restrict__ rtz, const float* __restrict__ dp, const float Jp_delta_x,
+                                                          const float Jp_delta_y, const int i) {
+  float Jdelta = J[FJ_JIDX0 + i] * Jp_delta_x;
+  Jdelta = Jdelta + J[FJ_JIDX1 + i] * Jp_delta_y;
+  Jdelta = Jdelta + J[FJ_JAB0 + i] * dp[6];
+  Jdelta = Jdelta + J[FJ_JAB1 + i] * dp[7];
+  float r0 = rtz[i];
+  r0 = r0 + r0;
+  r0 = r0 + Jdelta;
+  return Jdelta * r0;
+}
 
 struct BAPrecalc {  // FrameFramePrecalc (HessianBlocks.h:80-107), the members linearize reads
   float KRKi[9], Kt[3], R0[9], t0[3], aff0, aff1, b0, pad;
@@ -323,6 +373,10 @@ __device__ __forceinline__ void baDecideBlock(const BADecide& D, const int nbloc
 // Eight lanes per residual: lane idx evaluates pattern pixel idx (projection, bilinear tap, weights, its products); the sums over
 // the pattern are formed in pattern order — ((((0 + v0) + v1) + v2) ...) — by seven DPP row-shift adds per quantity, so every
 // value is bit-identical to the reference's sequential loop while the eight gathers of a residual are in flight together.
+// Two bodies: baLinearizeBody (eight lanes per residual) and baLinearizeBody1 (one lane per residual, the batched loop's fast path).  The arithmetic of a residual stands
+// once, in the pieces both call — baPairPrecalc, baCentreProject, baCentreJacobian, baPixelTerms, baWriteRecord, baDotC, baArriveLast — so the two give the same bits by
+// construction.  What is left in the bodies is what differs: which lane stores (the eight-lane body's `lead` guards), how the pattern sums are formed (seqSum8 over the
+// lanes / added in the lane), the one-lane body's patch staging and its once-per-wavefront back-substitution, the partition of the energy partials.
 #define LIN_THREADS 256
 #define BA_PATCH_STRIDE 49   // floats per lane of the one-lane linearisation's 6x8 pattern patch (odd: lanes reading the same patch element meet no bank conflict)
 #define LIN_RES_PER_BLOCK (LIN_THREADS / 8)
@@ -346,6 +400,127 @@ __device__ __forceinline__ float seqSum8(const float v) {
 #pragma unroll
   for (int k = 1; k < 8; k++) s = s + dppShl(v, k);
   return s;
+}
+
+// ---- the per-residual arithmetic, written once for the eight-lane body (baLinearizeBody) and the one-lane body (baLinearizeBody1)
+// FrameFramePrecalc of the ordered pair (host, target); use_dyn: the step-dependent members come from the kernel arguments (BAPreDynT)
+__device__ __forceinline__ BAPrecalc baPairPrecalc(const BAPrecalc* __restrict__ pre, const int F, const int hi, const int ti, const float (*__restrict__ Tv)[14], const int use_dyn) {
+  BAPrecalc pc = pre[hi + F * ti];
+  if (use_dyn) {
+    const float* __restrict__ dv = Tv[baPairIndex(hi, ti, F)];
+#pragma unroll
+    for (int k = 0; k < 9; k++) pc.KRKi[k] = dv[k];
+    pc.Kt[0] = dv[9]; pc.Kt[1] = dv[10]; pc.Kt[2] = dv[11]; pc.aff0 = dv[12]; pc.aff1 = dv[13];
+  }
+  return pc;
+}
+// centre pixel at the LINEARISATION point (idepth_zero, evalPT poses); returns whether it lands inside the target
+struct BACentre { float Kx, Ky, u, v, drescale, Ku, Kv, new_idepth; };
+__device__ __forceinline__ bool baCentreProject(const BAWindow& W, const BAPrecalc& pc, const float pu, const float pv, const float idz, BACentre& c) {
+  c.Kx = (pu + 0 - W.cx) * W.fxi; c.Ky = (pv + 0 - W.cy) * W.fyi;
+  const float p0 = pc.R0[0] * c.Kx + pc.R0[1] * c.Ky + pc.R0[2] * 1.0f + pc.t0[0] * idz;
+  const float p1 = pc.R0[3] * c.Kx + pc.R0[4] * c.Ky + pc.R0[5] * 1.0f + pc.t0[1] * idz;
+  const float p2 = pc.R0[6] * c.Kx + pc.R0[7] * c.Ky + pc.R0[8] * 1.0f + pc.t0[2] * idz;
+  c.drescale = 1.0f / p2;
+  c.new_idepth = idz * c.drescale;
+  c.u = p0 * c.drescale; c.v = p1 * c.drescale;
+  c.Ku = c.u * W.fx + W.cx; c.Kv = c.v * W.fy + W.cy;
+  return c.drescale > 0 && (c.Ku > 1.1f && c.Kv > 1.1f && c.Ku < W.wM3 && c.Kv < W.hM3);
+}
+// the geometric Jacobian rows of the centre pixel (Residuals.cpp:118-160)
+struct BAJacRows { float d_xi_x[6], d_xi_y[6], d_C_x[4], d_C_y[4], d_d_x, d_d_y; };
+__device__ __forceinline__ void baCentreJacobian(const BAWindow& W, const BAPrecalc& pc, const BACentre& c, BAJacRows& J) {
+  const float u = c.u, v = c.v, drescale = c.drescale, new_idepth = c.new_idepth;
+  J.d_d_x = drescale * (pc.t0[0] - pc.t0[2] * u) * 1.0f * W.fx;
+  J.d_d_y = drescale * (pc.t0[1] - pc.t0[2] * v) * 1.0f * W.fy;
+  J.d_C_x[2] = drescale * (pc.R0[6] * u - pc.R0[0]);
+  J.d_C_x[3] = W.fx * drescale * (pc.R0[7] * u - pc.R0[1]) * W.fyi;
+  J.d_C_x[0] = c.Kx * J.d_C_x[2];
+  J.d_C_x[1] = c.Ky * J.d_C_x[3];
+  J.d_C_y[2] = W.fy * drescale * (pc.R0[6] * v - pc.R0[3]) * W.fxi;
+  J.d_C_y[3] = drescale * (pc.R0[7] * v - pc.R0[4]);
+  J.d_C_y[0] = c.Kx * J.d_C_y[2];
+  J.d_C_y[1] = c.Ky * J.d_C_y[3];
+  J.d_C_x[0] = (J.d_C_x[0] + u) * 50.0f; J.d_C_x[1] *= 50.0f; J.d_C_x[2] = (J.d_C_x[2] + 1) * 50.0f; J.d_C_x[3] *= 50.0f;   // SCALE_F, SCALE_C
+  J.d_C_y[0] *= 50.0f; J.d_C_y[1] = (J.d_C_y[1] + v) * 50.0f; J.d_C_y[2] *= 50.0f; J.d_C_y[3] = (J.d_C_y[3] + 1) * 50.0f;
+  J.d_xi_x[0] = new_idepth * W.fx; J.d_xi_x[1] = 0; J.d_xi_x[2] = -new_idepth * u * W.fx;
+  J.d_xi_x[3] = -u * v * W.fx; J.d_xi_x[4] = (1 + u * u) * W.fx; J.d_xi_x[5] = -v * W.fx;
+  J.d_xi_y[0] = 0; J.d_xi_y[1] = new_idepth * W.fy; J.d_xi_y[2] = -new_idepth * v * W.fy;
+  J.d_xi_y[3] = -(1 + v * v) * W.fy; J.d_xi_y[4] = u * v * W.fy; J.d_xi_y[5] = u * W.fy;
+}
+// The photometric terms of ONE pattern pixel, in the order the pattern sums are formed and stored: energy, JIdx2 (00, 11, 10), JabJIdx (00, 01, 10, 11), Jab2 (00, 01, 11),
+// the weighted gradient norm of the outlier test, and the accumulation-side inner products of addPoint<0> (resApprox = resF; AccumulatedTopHessian.cpp:103-113).
+// hit: (value, dx, dy) of the target image at the projected pixel.  The eight-lane body feeds the terms to seqSum8, the one-lane body adds them in the lane.
+enum { PX_E = 0, PX_JI00, PX_JI11, PX_JI10, PX_JA00, PX_JA01, PX_JA10, PX_JA11, PX_JB00, PX_JB01, PX_JB11, PX_WJI2, PX_JIR0, PX_JIR1, PX_JAR0, PX_JAR1, PX_RR, PX_TERMS };
+struct BAPixel { float t[PX_TERMS]; float resF, dIx, dIy, jab0, jab1; };   // the five values of the pixel's column of the full Jacobian row beside the terms
+__device__ __forceinline__ void baPixelTerms(float3 hit, const float color, const float weight, const BAPrecalc& pc, const BAWindow& W, BAPixel& px) {
+  const float residual = hit.x - (pc.aff0 * color + pc.aff1);
+  const float drdA = (color - pc.b0);
+  float wgt = sqrtf(W.outlierTHSum / (W.outlierTHSum + (hit.y * hit.y + hit.z * hit.z)));
+  wgt = 0.5f * (wgt + weight);
+  float hw = fabsf(residual) < W.huberTH ? 1.0f : W.huberTH / fabsf(residual);
+  px.t[PX_E] = wgt * wgt * hw * residual * residual * (2 - hw);
+  if (hw < 1) hw = sqrtf(hw);
+  hw = hw * wgt;
+  hit.y *= hw; hit.z *= hw;
+  const float resF = residual * hw;
+  float jab0 = drdA * hw, jab1 = hw;
+  px.t[PX_JI00] = hit.y * hit.y; px.t[PX_JI11] = hit.z * hit.z; px.t[PX_JI10] = hit.y * hit.z;
+  px.t[PX_JA00] = drdA * hw * hit.y; px.t[PX_JA01] = drdA * hw * hit.z; px.t[PX_JA10] = hw * hit.y; px.t[PX_JA11] = hw * hit.z;
+  px.t[PX_JB00] = drdA * drdA * hw * hw; px.t[PX_JB01] = drdA * hw * hw; px.t[PX_JB11] = hw * hw;
+  px.t[PX_WJI2] = hw * hw * (hit.y * hit.y + hit.z * hit.z);
+  if (W.modeA < 0) jab0 = 0;
+  if (W.modeB < 0) jab1 = 0;
+  px.t[PX_JIR0] = resF * hit.y; px.t[PX_JIR1] = resF * hit.z; px.t[PX_JAR0] = resF * jab0; px.t[PX_JAR1] = resF * jab1; px.t[PX_RR] = resF * resF;
+  px.resF = resF; px.dIx = hit.y; px.dIy = hit.z; px.jab0 = jab0; px.jab1 = jab1;
+}
+// The compact record from the Jacobian rows and the pattern sums s[PX_*] (PX_E and PX_WJI2 are not part of it), with takeDataF (EnergyFunctionalStructs.cpp:39-49) and
+// the per-point contributions (AccumulatedTopHessian.cpp:131-134).  REC_PAD is left alone.
+__device__ __forceinline__ void baWriteRecord(float* __restrict__ rec, const BAJacRows& J, const float* s) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) { rec[REC_JPDC0 + k] = J.d_C_x[k]; rec[REC_JPDC1 + k] = J.d_C_y[k]; }
+#pragma unroll
+  for (int k = 0; k < 6; k++) { rec[REC_JPDXI0 + k] = J.d_xi_x[k]; rec[REC_JPDXI1 + k] = J.d_xi_y[k]; }
+  rec[REC_JIDX2 + 0] = s[PX_JI00]; rec[REC_JIDX2 + 1] = s[PX_JI10]; rec[REC_JIDX2 + 2] = s[PX_JI11];
+  rec[REC_JABJIDX + 0] = s[PX_JA00]; rec[REC_JABJIDX + 1] = s[PX_JA01]; rec[REC_JABJIDX + 2] = s[PX_JA10]; rec[REC_JABJIDX + 3] = s[PX_JA11];
+  rec[REC_JAB2 + 0] = s[PX_JB00]; rec[REC_JAB2 + 1] = s[PX_JB01]; rec[REC_JAB2 + 2] = s[PX_JB11];
+  rec[REC_JI_R + 0] = s[PX_JIR0]; rec[REC_JI_R + 1] = s[PX_JIR1]; rec[REC_JAB_R + 0] = s[PX_JAR0]; rec[REC_JAB_R + 1] = s[PX_JAR1]; rec[REC_RR] = s[PX_RR];
+  rec[REC_JPDD + 0] = J.d_d_x; rec[REC_JPDD + 1] = J.d_d_y;
+  const float v0 = s[PX_JI00] * J.d_d_x + s[PX_JI10] * J.d_d_y, v1 = s[PX_JI10] * J.d_d_x + s[PX_JI11] * J.d_d_y;
+#pragma unroll
+  for (int k = 0; k < 6; k++) rec[REC_JPJD + k] = J.d_xi_x[k] * v0 + J.d_xi_y[k] * v1;
+  rec[REC_JPJD + 6] = s[PX_JA00] * J.d_d_x + s[PX_JA01] * J.d_d_y;
+  rec[REC_JPJD + 7] = s[PX_JA10] * J.d_d_x + s[PX_JA11] * J.d_d_y;
+  rec[REC_BD] = s[PX_JIR0] * J.d_d_x + s[PX_JIR1] * J.d_d_y;
+  rec[REC_HDD] = v0 * J.d_d_x + v1 * J.d_d_y;
+#pragma unroll
+  for (int k = 0; k < 4; k++) rec[REC_HCD + k] = J.d_C_x[k] * v0 + J.d_C_y[k] * v1;
+}
+// head of a point's back-substitution (EnergyFunctional.cpp:300-303): xc . Hcd, what comes off bdSumF before the residuals' products
+__device__ __forceinline__ float baDotC(const float* __restrict__ xc, const float hc0, const float hc1, const float hc2, const float hc3) {
+  float dotc = 0;
+  dotc += xc[0] * (hc0 + 0.0f); dotc += xc[1] * (hc1 + 0.0f); dotc += xc[2] * (hc2 + 0.0f); dotc += xc[3] * (hc3 + 0.0f);
+  return dotc;
+}
+// Arrive of a linearisation's workgroup in front of the decision pass; true in every thread of the LAST workgroup to arrive (which has reset the counter).
+// What the deciding workgroup reads (energy partials, per-residual energies) was stored with agent-scope atomic stores, i.e. written
+// through to the device's coherence point; every wave WAITS for its own stores (s_waitcnt vmcnt(0)) before the workgroup's RELAXED arrive.
+// The workgroup-scope release alone does not make it wait: the waves of a workgroup share a compute unit, so that scope needs no wait for
+// global stores, the barrier does not wait for them either, and the arrive is issued by another wave than the one that stored the partial —
+// seen as an energy sum that held a partial of the previous linearisation (about one batched call in 300, in the trace's E_A alone where
+// the accept test's margin was large).  An agent-scope release / acquire here would write back and invalidate the whole L2 of the XCD —
+// once per workgroup, with megabytes of freshly written records in it (measured: +40 us per launch).
+__device__ __forceinline__ bool baArriveLast(BACtl* __restrict__ ctl, const int nblocks) {
+  __shared__ int s_last;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(&ctl->cnt_lin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(nblocks - 1) ? 1 : 0;
+  __syncthreads();
+  if (!s_last) return false;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  if (threadIdx.x == 0) __hip_atomic_store(&ctl->cnt_lin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
 }
 
 // gate: BA_GATE_REJECTED = this launch is the relinearisation that follows a rejected step (loadSateBackup + linearizeAll,
@@ -387,13 +562,7 @@ __device__ __forceinline__ void baLinearizeBody(const BAWindow& W, const BAPoint
     if (Rs.lin && !pt_mask && Rs.lin[ri]) { myE = 0.0; done = true; }   // kept linearised: outside activeResiduals (only the point's back-substitution below concerns it)
     const int pi = Rs.point[ri], ti = Rs.target[ri];
     const int hi = P.host[pi];
-    BAPrecalc pc = pre[hi + W.F * ti];
-    if (use_dyn) {
-      const float* __restrict__ dv = Tv[baPairIndex(hi, ti, W.F)];
-#pragma unroll
-      for (int k = 0; k < 9; k++) pc.KRKi[k] = dv[k];
-      pc.Kt[0] = dv[9]; pc.Kt[1] = dv[10]; pc.Kt[2] = dv[11]; pc.aff0 = dv[12]; pc.aff1 = dv[13];
-    }
+    const BAPrecalc pc = baPairPrecalc(pre, W.F, hi, ti, Tv, use_dyn);
     const float pu = P.u[pi], pv = P.v[pi];
     // do_resub: EnergyFunctional::resubstituteFPt (EnergyFunctional.cpp:295-321) + the point part of doStepFromBackup for this residual's point,
     // fused in front of the linearisation of the stepped state (every group of a point's residuals computes the same step — lane q takes the
@@ -404,12 +573,7 @@ __device__ __forceinline__ void baLinearizeBody(const BAWindow& W, const BAPoint
       const int r0 = P.res_begin[pi], r1 = P.res_begin[pi + 1];
       const float bk = P.idepth_backup[pi];
       float bsum = P.bdSumF[pi];
-      {
-        float dotc = 0;
-        dotc += Xxc[0] * (P.Hcd[4 * pi + 0] + 0.0f); dotc += Xxc[1] * (P.Hcd[4 * pi + 1] + 0.0f);
-        dotc += Xxc[2] * (P.Hcd[4 * pi + 2] + 0.0f); dotc += Xxc[3] * (P.Hcd[4 * pi + 3] + 0.0f);
-        bsum -= dotc;
-      }
+      bsum -= baDotC(Xxc, P.Hcd[4 * pi + 0], P.Hcd[4 * pi + 1], P.Hcd[4 * pi + 2], P.Hcd[4 * pi + 3]);
       const int grp = (threadIdx.x & 63) & ~7;
       int ngood = 0;
       for (int rb = r0; rb < r1; rb += 8) {
@@ -432,45 +596,20 @@ __device__ __forceinline__ void baLinearizeBody(const BAWindow& W, const BAPoint
       id_new = bk + 1.0f * st;
       if (lead && r0 == ri) { P.step[pi] = st; P.idepth[pi] = id_new; P.idepth_zero[pi] = id_new; }
     }
-    float d_xi_x[6], d_xi_y[6], d_C_x[4], d_C_y[4], d_d_x = 0, d_d_y = 0;
+    BAJacRows Jc;
     if (!done) {
-      // centre pixel at the LINEARISATION point (idepth_zero, evalPT poses)
       const float idz = do_resub ? id_new : (use_backup ? P.idepth_backup[pi] : P.idepth_zero[pi]);
-      const float Kx = (pu + 0 - W.cx) * W.fxi, Ky = (pv + 0 - W.cy) * W.fyi;
-      const float p0 = pc.R0[0] * Kx + pc.R0[1] * Ky + pc.R0[2] * 1.0f + pc.t0[0] * idz;
-      const float p1 = pc.R0[3] * Kx + pc.R0[4] * Ky + pc.R0[5] * 1.0f + pc.t0[1] * idz;
-      const float p2 = pc.R0[6] * Kx + pc.R0[7] * Ky + pc.R0[8] * 1.0f + pc.t0[2] * idz;
-      const float drescale = 1.0f / p2;
-      const float new_idepth = idz * drescale;
-      bool ok = drescale > 0;
-      const float u = p0 * drescale, v = p1 * drescale;
-      const float Ku = u * W.fx + W.cx, Kv = v * W.fy + W.cy;
-      ok = ok && (Ku > 1.1f && Kv > 1.1f && Ku < W.wM3 && Kv < W.hM3);
-      if (!ok) { if (lead) Rs.newState[ri] = BA_OOB; myE = oldEnergy; done = true; }
+      BACentre c;
+      if (!baCentreProject(W, pc, pu, pv, idz, c)) { if (lead) Rs.newState[ri] = BA_OOB; myE = oldEnergy; done = true; }
       else {
-        if (lead) { Rs.center[3 * ri + 0] = Ku; Rs.center[3 * ri + 1] = Kv; Rs.center[3 * ri + 2] = new_idepth; }
-        d_d_x = drescale * (pc.t0[0] - pc.t0[2] * u) * 1.0f * W.fx;
-        d_d_y = drescale * (pc.t0[1] - pc.t0[2] * v) * 1.0f * W.fy;
-        d_C_x[2] = drescale * (pc.R0[6] * u - pc.R0[0]);
-        d_C_x[3] = W.fx * drescale * (pc.R0[7] * u - pc.R0[1]) * W.fyi;
-        d_C_x[0] = Kx * d_C_x[2];
-        d_C_x[1] = Ky * d_C_x[3];
-        d_C_y[2] = W.fy * drescale * (pc.R0[6] * v - pc.R0[3]) * W.fxi;
-        d_C_y[3] = drescale * (pc.R0[7] * v - pc.R0[4]);
-        d_C_y[0] = Kx * d_C_y[2];
-        d_C_y[1] = Ky * d_C_y[3];
-        d_C_x[0] = (d_C_x[0] + u) * 50.0f; d_C_x[1] *= 50.0f; d_C_x[2] = (d_C_x[2] + 1) * 50.0f; d_C_x[3] *= 50.0f;   // SCALE_F, SCALE_C
-        d_C_y[0] *= 50.0f; d_C_y[1] = (d_C_y[1] + v) * 50.0f; d_C_y[2] *= 50.0f; d_C_y[3] = (d_C_y[3] + 1) * 50.0f;
-        d_xi_x[0] = new_idepth * W.fx; d_xi_x[1] = 0; d_xi_x[2] = -new_idepth * u * W.fx;
-        d_xi_x[3] = -u * v * W.fx; d_xi_x[4] = (1 + u * u) * W.fx; d_xi_x[5] = -v * W.fx;
-        d_xi_y[0] = 0; d_xi_y[1] = new_idepth * W.fy; d_xi_y[2] = -new_idepth * v * W.fy;
-        d_xi_y[3] = -(1 + v * v) * W.fy; d_xi_y[4] = u * v * W.fy; d_xi_y[5] = u * W.fy;
+        if (lead) { Rs.center[3 * ri + 0] = c.Ku; Rs.center[3 * ri + 1] = c.Kv; Rs.center[3 * ri + 2] = c.new_idepth; }
+        baCentreJacobian(W, pc, c, Jc);
       }
     }
     if (!done) {
       const float* __restrict__ img = fs.level(W.slot[ti], 0);
       const float ids = do_resub ? id_new : (use_backup ? P.idepth_backup[pi] : P.idepth[pi]);
-      float* fj = fullJ ? fullJ + (size_t)ri * 74 : nullptr;
+      float* fj = fullJ ? fullJ + (size_t)ri * FJ_FLOATS : nullptr;
       // this lane's pattern pixel
       const float xu = pu + c_patternP[idx][0], xv = pv + c_patternP[idx][1];
       const float q0 = pc.KRKi[0] * xu + pc.KRKi[1] * xv + pc.KRKi[2] * 1.0f + pc.Kt[0] * ids;
@@ -488,69 +627,30 @@ __device__ __forceinline__ void baLinearizeBody(const BAWindow& W, const BAPoint
       }
       if (!good) { if (lead) Rs.newState[ri] = BA_OOB; myE = oldEnergy; done = true; }
       else {
-        const float color = P.color[pi * 8 + idx];
-        const float residual = hit.x - (pc.aff0 * color + pc.aff1);
-        const float drdA = (color - pc.b0);
-        float wgt = sqrtf(W.outlierTHSum / (W.outlierTHSum + (hit.y * hit.y + hit.z * hit.z)));
-        wgt = 0.5f * (wgt + P.weights[pi * 8 + idx]);
-        float hw = fabsf(residual) < W.huberTH ? 1.0f : W.huberTH / fabsf(residual);
-        const float eTerm = wgt * wgt * hw * residual * residual * (2 - hw);
-        if (hw < 1) hw = sqrtf(hw);
-        hw = hw * wgt;
-        hit.y *= hw; hit.z *= hw;
-        const float resF = residual * hw;
-        float jab0 = drdA * hw, jab1 = hw;
-        const float tJI00 = hit.y * hit.y, tJI11 = hit.z * hit.z, tJI10 = hit.y * hit.z;
-        const float tJa00 = drdA * hw * hit.y, tJa01 = drdA * hw * hit.z, tJa10 = hw * hit.y, tJa11 = hw * hit.z;
-        const float tJb00 = drdA * drdA * hw * hw, tJb01 = drdA * hw * hw, tJb11 = hw * hw;
-        const float twJI2 = hw * hw * (hit.y * hit.y + hit.z * hit.z);
-        if (W.modeA < 0) jab0 = 0;
-        if (W.modeB < 0) jab1 = 0;
-        // accumulation-side inner products of addPoint<0> (resApprox = resF)  (AccumulatedTopHessian.cpp:103-113)
-        const float tJIr0 = resF * hit.y, tJIr1 = resF * hit.z, tJar0 = resF * jab0, tJar1 = resF * jab1, trr = resF * resF;
-        if (fj) { fj[idx] = resF; fj[30 + idx] = hit.y; fj[38 + idx] = hit.z; fj[46 + idx] = jab0; fj[54 + idx] = jab1; }
+        BAPixel px;
+        baPixelTerms(hit, P.color[pi * 8 + idx], P.weights[pi * 8 + idx], pc, W, px);
+        if (fj) { fj[FJ_RESF + idx] = px.resF; fj[FJ_JIDX0 + idx] = px.dIx; fj[FJ_JIDX1 + idx] = px.dIy; fj[FJ_JAB0 + idx] = px.jab0; fj[FJ_JAB1 + idx] = px.jab1; }
         // sums over the pattern, in pattern order (valid in the leading lane)
-        float energyLeft = seqSum8(eTerm);
-        const float JI00 = seqSum8(tJI00), JI11 = seqSum8(tJI11), JI10 = seqSum8(tJI10);
-        const float Ja00 = seqSum8(tJa00), Ja01 = seqSum8(tJa01), Ja10 = seqSum8(tJa10), Ja11 = seqSum8(tJa11);
-        const float Jb00 = seqSum8(tJb00), Jb01 = seqSum8(tJb01), Jb11 = seqSum8(tJb11), wJI2 = seqSum8(twJI2);
-        const float JIr0 = seqSum8(tJIr0), JIr1 = seqSum8(tJIr1), Jar0 = seqSum8(tJar0), Jar1 = seqSum8(tJar1), rr = seqSum8(trr);
+        float s[PX_TERMS];
+#pragma unroll
+        for (int q = 0; q < PX_TERMS; q++) s[q] = seqSum8(px.t[q]);
         if (lead) {
+          float energyLeft = s[PX_E];
           Rs.newEnergyWO[ri] = energyLeft;
           { const int sl = Rs.newestSlot[ri]; if (sl >= 0) __hip_atomic_store(Rs.newestE + sl, energyLeft, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
           const float th = fmaxf(D.frameTH[hi], D.frameTH[ti]);
-          if (energyLeft > th || wJI2 < 2) { energyLeft = th; Rs.newState[ri] = BA_OUTLIER; }
+          if (energyLeft > th || s[PX_WJI2] < 2) { energyLeft = th; Rs.newState[ri] = BA_OUTLIER; }
           else Rs.newState[ri] = BA_IN;
           Rs.newEnergy[ri] = energyLeft;
           myE = energyLeft;
-          // compact record
-#pragma unroll
-          for (int k = 0; k < 4; k++) { rec[REC_JPDC0 + k] = d_C_x[k]; rec[REC_JPDC1 + k] = d_C_y[k]; }
-#pragma unroll
-          for (int k = 0; k < 6; k++) { rec[REC_JPDXI0 + k] = d_xi_x[k]; rec[REC_JPDXI1 + k] = d_xi_y[k]; }
-          rec[REC_JIDX2 + 0] = JI00; rec[REC_JIDX2 + 1] = JI10; rec[REC_JIDX2 + 2] = JI11;
-          rec[REC_JABJIDX + 0] = Ja00; rec[REC_JABJIDX + 1] = Ja01; rec[REC_JABJIDX + 2] = Ja10; rec[REC_JABJIDX + 3] = Ja11;
-          rec[REC_JAB2 + 0] = Jb00; rec[REC_JAB2 + 1] = Jb01; rec[REC_JAB2 + 2] = Jb11;
-          rec[REC_JI_R + 0] = JIr0; rec[REC_JI_R + 1] = JIr1; rec[REC_JAB_R + 0] = Jar0; rec[REC_JAB_R + 1] = Jar1; rec[REC_RR] = rr;
-          rec[REC_JPDD + 0] = d_d_x; rec[REC_JPDD + 1] = d_d_y;
-          // takeDataF (EnergyFunctionalStructs.cpp:39-49)
-          const float v0 = JI00 * d_d_x + JI10 * d_d_y, v1 = JI10 * d_d_x + JI11 * d_d_y;
-#pragma unroll
-          for (int k = 0; k < 6; k++) rec[REC_JPJD + k] = d_xi_x[k] * v0 + d_xi_y[k] * v1;
-          rec[REC_JPJD + 6] = Ja00 * d_d_x + Ja01 * d_d_y;
-          rec[REC_JPJD + 7] = Ja10 * d_d_x + Ja11 * d_d_y;
-          // per-point contributions (AccumulatedTopHessian.cpp:131-134)
-          rec[REC_BD] = JIr0 * d_d_x + JIr1 * d_d_y;
-          rec[REC_HDD] = v0 * d_d_x + v1 * d_d_y;
-#pragma unroll
-          for (int k = 0; k < 4; k++) rec[REC_HCD + k] = d_C_x[k] * v0 + d_C_y[k] * v1;
+          baWriteRecord(rec, Jc, s);
           if (fj) {
-            for (int k = 0; k < 6; k++) { fj[8 + k] = d_xi_x[k]; fj[14 + k] = d_xi_y[k]; }
-            for (int k = 0; k < 4; k++) { fj[20 + k] = d_C_x[k]; fj[24 + k] = d_C_y[k]; }
-            fj[28] = d_d_x; fj[29] = d_d_y;
-            fj[62] = JI00; fj[63] = JI10; fj[64] = JI10; fj[65] = JI11;
-            fj[66] = Ja00; fj[67] = Ja01; fj[68] = Ja10; fj[69] = Ja11;
-            fj[70] = Jb00; fj[71] = Jb01; fj[72] = Jb01; fj[73] = Jb11;
+            for (int k = 0; k < 6; k++) { fj[FJ_JPDXI0 + k] = Jc.d_xi_x[k]; fj[FJ_JPDXI1 + k] = Jc.d_xi_y[k]; }
+            for (int k = 0; k < 4; k++) { fj[FJ_JPDC0 + k] = Jc.d_C_x[k]; fj[FJ_JPDC1 + k] = Jc.d_C_y[k]; }
+            fj[FJ_JPDD + 0] = Jc.d_d_x; fj[FJ_JPDD + 1] = Jc.d_d_y;
+            fj[FJ_JIDX2 + 0] = s[PX_JI00]; fj[FJ_JIDX2 + 1] = s[PX_JI10]; fj[FJ_JIDX2 + 2] = s[PX_JI10]; fj[FJ_JIDX2 + 3] = s[PX_JI11];
+            fj[FJ_JABJIDX + 0] = s[PX_JA00]; fj[FJ_JABJIDX + 1] = s[PX_JA01]; fj[FJ_JABJIDX + 2] = s[PX_JA10]; fj[FJ_JABJIDX + 3] = s[PX_JA11];
+            fj[FJ_JAB2 + 0] = s[PX_JB00]; fj[FJ_JAB2 + 1] = s[PX_JB01]; fj[FJ_JAB2 + 2] = s[PX_JB01]; fj[FJ_JAB2 + 3] = s[PX_JB11];
           }
         }
       }
@@ -572,22 +672,7 @@ __device__ __forceinline__ void baLinearizeBody(const BAWindow& W, const BAPoint
   }
   if (D.mode < 0) return;
   // the last workgroup to arrive takes the decisions (energy sum, threshold of the newest keyframe, accept / reject)
-  // What the deciding workgroup reads (energy partials, per-residual energies) was stored with agent-scope atomic stores, i.e. written
-  // through to the device's coherence point; every wave WAITS for its own stores (s_waitcnt vmcnt(0)) before the workgroup's RELAXED arrive.
-  // The workgroup-scope release alone does not make it wait: the waves of a workgroup share a compute unit, so that scope needs no wait for
-  // global stores, the barrier does not wait for them either, and the arrive is issued by another wave than the one that stored the partial —
-  // seen as an energy sum that held a partial of the previous linearisation (about one batched call in 300, in the trace's E_A alone where
-  // the accept test's margin was large).  An agent-scope release / acquire here would write back and invalidate the whole L2 of the XCD —
-  // once per workgroup, with megabytes of freshly written records in it (measured: +40 us per launch).
-  __shared__ int s_last;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(&D.ctl->cnt_lin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(nblocks - 1) ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if (threadIdx.x == 0) __hip_atomic_store(&D.ctl->cnt_lin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!baArriveLast(D.ctl, nblocks)) return;
   if (D.mode == 3) baPackBlock(D, nblocks);
   else baDecideBlock(D, nblocks, t_kernel0);
 }
@@ -617,13 +702,7 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
     if (Rs.lin && Rs.lin[ri]) { myE = 0.0; done = true; }
     const int pi = Rs.point[ri], ti = Rs.target[ri];
     const int hi = P.host[pi];
-    BAPrecalc pc = pre[hi + W.F * ti];
-    if (use_dyn) {
-      const float* __restrict__ dv = Tv[baPairIndex(hi, ti, W.F)];
-#pragma unroll
-      for (int k = 0; k < 9; k++) pc.KRKi[k] = dv[k];
-      pc.Kt[0] = dv[9]; pc.Kt[1] = dv[10]; pc.Kt[2] = dv[11]; pc.aff0 = dv[12]; pc.aff1 = dv[13];
-    }
+    const BAPrecalc pc = baPairPrecalc(pre, W.F, hi, ti, Tv, use_dyn);
     const float pu = P.u[pi], pv = P.v[pi];
     float id_new = 0.0f;
     if (do_resub) {   // resubstituteFPt + the point part of doStepFromBackup (see baLinearizeBody)
@@ -636,12 +715,7 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
         const int r1 = P.res_begin[pi + 1];
         const float bk = P.idepth_backup[pi];
         float bsum = P.bdSumF[pi];
-        {
-          float dotc = 0;
-          dotc += Xxc[0] * (P.Hcd[4 * pi + 0] + 0.0f); dotc += Xxc[1] * (P.Hcd[4 * pi + 1] + 0.0f);
-          dotc += Xxc[2] * (P.Hcd[4 * pi + 2] + 0.0f); dotc += Xxc[3] * (P.Hcd[4 * pi + 3] + 0.0f);
-          bsum -= dotc;
-        }
+        bsum -= baDotC(Xxc, P.Hcd[4 * pi + 0], P.Hcd[4 * pi + 1], P.Hcd[4 * pi + 2], P.Hcd[4 * pi + 3]);
         int ngood = 0;
         for (int rq = r0; rq < r1; rq++) {
           if (Rs.active[rq] == 0) continue;   // the eight-lane form subtracts +0.0f for it
@@ -659,43 +733,21 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
       }
       id_new = __shfl(id_new, lead, 64);
     }
-    float d_xi_x[6], d_xi_y[6], d_C_x[4], d_C_y[4], d_d_x = 0, d_d_y = 0;
+    BAJacRows Jc;
     if (!done) {
       const float idz = do_resub ? id_new : (use_backup ? P.idepth_backup[pi] : P.idepth_zero[pi]);
-      const float Kx = (pu + 0 - W.cx) * W.fxi, Ky = (pv + 0 - W.cy) * W.fyi;
-      const float p0 = pc.R0[0] * Kx + pc.R0[1] * Ky + pc.R0[2] * 1.0f + pc.t0[0] * idz;
-      const float p1 = pc.R0[3] * Kx + pc.R0[4] * Ky + pc.R0[5] * 1.0f + pc.t0[1] * idz;
-      const float p2 = pc.R0[6] * Kx + pc.R0[7] * Ky + pc.R0[8] * 1.0f + pc.t0[2] * idz;
-      const float drescale = 1.0f / p2;
-      const float new_idepth = idz * drescale;
-      bool ok = drescale > 0;
-      const float u = p0 * drescale, v = p1 * drescale;
-      const float Ku = u * W.fx + W.cx, Kv = v * W.fy + W.cy;
-      ok = ok && (Ku > 1.1f && Kv > 1.1f && Ku < W.wM3 && Kv < W.hM3);
-      if (!ok) { Rs.newState[ri] = BA_OOB; myE = oldEnergy; done = true; }
+      BACentre c;
+      if (!baCentreProject(W, pc, pu, pv, idz, c)) { Rs.newState[ri] = BA_OOB; myE = oldEnergy; done = true; }
       else {
-        Rs.center[3 * ri + 0] = Ku; Rs.center[3 * ri + 1] = Kv; Rs.center[3 * ri + 2] = new_idepth;
-        d_d_x = drescale * (pc.t0[0] - pc.t0[2] * u) * 1.0f * W.fx;
-        d_d_y = drescale * (pc.t0[1] - pc.t0[2] * v) * 1.0f * W.fy;
-        d_C_x[2] = drescale * (pc.R0[6] * u - pc.R0[0]);
-        d_C_x[3] = W.fx * drescale * (pc.R0[7] * u - pc.R0[1]) * W.fyi;
-        d_C_x[0] = Kx * d_C_x[2];
-        d_C_x[1] = Ky * d_C_x[3];
-        d_C_y[2] = W.fy * drescale * (pc.R0[6] * v - pc.R0[3]) * W.fxi;
-        d_C_y[3] = drescale * (pc.R0[7] * v - pc.R0[4]);
-        d_C_y[0] = Kx * d_C_y[2];
-        d_C_y[1] = Ky * d_C_y[3];
-        d_C_x[0] = (d_C_x[0] + u) * 50.0f; d_C_x[1] *= 50.0f; d_C_x[2] = (d_C_x[2] + 1) * 50.0f; d_C_x[3] *= 50.0f;   // SCALE_F, SCALE_C
-        d_C_y[0] *= 50.0f; d_C_y[1] = (d_C_y[1] + v) * 50.0f; d_C_y[2] *= 50.0f; d_C_y[3] = (d_C_y[3] + 1) * 50.0f;
-        d_xi_x[0] = new_idepth * W.fx; d_xi_x[1] = 0; d_xi_x[2] = -new_idepth * u * W.fx;
-        d_xi_x[3] = -u * v * W.fx; d_xi_x[4] = (1 + u * u) * W.fx; d_xi_x[5] = -v * W.fx;
-        d_xi_y[0] = 0; d_xi_y[1] = new_idepth * W.fy; d_xi_y[2] = -new_idepth * v * W.fy;
-        d_xi_y[3] = -(1 + v * v) * W.fy; d_xi_y[4] = u * v * W.fy; d_xi_y[5] = u * W.fy;
+        Rs.center[3 * ri + 0] = c.Ku; Rs.center[3 * ri + 1] = c.Kv; Rs.center[3 * ri + 2] = c.new_idepth;
+        baCentreJacobian(W, pc, c, Jc);
       }
     }
     if (!done) {
       const float* __restrict__ img = fs.level(W.slot[ti], 0);
       const float ids = do_resub ? id_new : (use_backup ? P.idepth_backup[pi] : P.idepth[pi]);
+      // the pattern sums, 0 + v0 + v1 + ... in the lane.  Named scalars, not an array summed in a loop like the eight-lane body's: the array form compiled to other
+      // compare encodings and other SGPR spill traffic in this kernel (profiles/ba_linearize_shared.md)
       float energyLeft = 0.0f, JI00 = 0.0f, JI11 = 0.0f, JI10 = 0.0f, Ja00 = 0.0f, Ja01 = 0.0f, Ja10 = 0.0f, Ja11 = 0.0f, Jb00 = 0.0f, Jb01 = 0.0f, Jb11 = 0.0f, wJI2 = 0.0f;
       float JIr0 = 0.0f, JIr1 = 0.0f, Jar0 = 0.0f, Jar1 = 0.0f, rr = 0.0f;
       bool allGood = true;
@@ -753,33 +805,19 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
         } else interp33Load(img, Ku, Kv, W.w, tp);
         float3 hit = interp33Finish<true>(tp, Ku, Kv);
         allGood = allGood && inb && isfinite(hit.x);
-        const float color = P.color[pi * 8 + idx];
-        const float residual = hit.x - (pc.aff0 * color + pc.aff1);
-        const float drdA = (color - pc.b0);
-        float wgt = sqrtf(W.outlierTHSum / (W.outlierTHSum + (hit.y * hit.y + hit.z * hit.z)));
-        wgt = 0.5f * (wgt + P.weights[pi * 8 + idx]);
-        float hw = fabsf(residual) < W.huberTH ? 1.0f : W.huberTH / fabsf(residual);
-        const float eTerm = wgt * wgt * hw * residual * residual * (2 - hw);
-        if (hw < 1) hw = sqrtf(hw);
-        hw = hw * wgt;
-        hit.y *= hw; hit.z *= hw;
-        const float resF = residual * hw;
-        float jab0 = drdA * hw, jab1 = hw;
-        const float tJa00 = drdA * hw * hit.y, tJa01 = drdA * hw * hit.z, tJa10 = hw * hit.y, tJa11 = hw * hit.z;
-        const float tJb00 = drdA * drdA * hw * hw, tJb01 = drdA * hw * hw, tJb11 = hw * hw;
-        const float twJI2 = hw * hw * (hit.y * hit.y + hit.z * hit.z);
-        if (W.modeA < 0) jab0 = 0;
-        if (W.modeB < 0) jab1 = 0;
-        energyLeft = energyLeft + eTerm;
-        JI00 = JI00 + hit.y * hit.y; JI11 = JI11 + hit.z * hit.z; JI10 = JI10 + hit.y * hit.z;
-        Ja00 = Ja00 + tJa00; Ja01 = Ja01 + tJa01; Ja10 = Ja10 + tJa10; Ja11 = Ja11 + tJa11;
-        Jb00 = Jb00 + tJb00; Jb01 = Jb01 + tJb01; Jb11 = Jb11 + tJb11; wJI2 = wJI2 + twJI2;
-        JIr0 = JIr0 + resF * hit.y; JIr1 = JIr1 + resF * hit.z; Jar0 = Jar0 + resF * jab0; Jar1 = Jar1 + resF * jab1; rr = rr + resF * resF;
+        BAPixel px;
+        baPixelTerms(hit, P.color[pi * 8 + idx], P.weights[pi * 8 + idx], pc, W, px);
+        energyLeft = energyLeft + px.t[PX_E];
+        JI00 = JI00 + px.t[PX_JI00]; JI11 = JI11 + px.t[PX_JI11]; JI10 = JI10 + px.t[PX_JI10];
+        Ja00 = Ja00 + px.t[PX_JA00]; Ja01 = Ja01 + px.t[PX_JA01]; Ja10 = Ja10 + px.t[PX_JA10]; Ja11 = Ja11 + px.t[PX_JA11];
+        Jb00 = Jb00 + px.t[PX_JB00]; Jb01 = Jb01 + px.t[PX_JB01]; Jb11 = Jb11 + px.t[PX_JB11]; wJI2 = wJI2 + px.t[PX_WJI2];
+        JIr0 = JIr0 + px.t[PX_JIR0]; JIr1 = JIr1 + px.t[PX_JIR1]; Jar0 = Jar0 + px.t[PX_JAR0]; Jar1 = Jar1 + px.t[PX_JAR1]; rr = rr + px.t[PX_RR];
       }
       }
       // the residual goes OOB if ANY of its pattern pixels fails (the reference breaks out of the loop at the first one)
       if (!allGood) { Rs.newState[ri] = BA_OOB; myE = oldEnergy; }
       else {
+        const float s[PX_TERMS] = {energyLeft, JI00, JI11, JI10, Ja00, Ja01, Ja10, Ja11, Jb00, Jb01, Jb11, wJI2, JIr0, JIr1, Jar0, Jar1, rr};   // PX_* order
         Rs.newEnergyWO[ri] = energyLeft;
         if (sl >= 0) __hip_atomic_store(Rs.newestE + sl, energyLeft, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const float th = fmaxf(D.frameTH[hi], D.frameTH[ti]);
@@ -789,24 +827,7 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
         myE = energyLeft;
         // compact record: lane l writes record l's floats 208 bytes apart.  Staging the records through LDS so that a store instruction covers consecutive floats was
         // measured SLOWER (318 vs 267 us for 64 windows: the staging traffic and its 28 KB of LDS cost more than the scattered stores, which L2 merges)
-#pragma unroll
-        for (int k = 0; k < 4; k++) { rec[REC_JPDC0 + k] = d_C_x[k]; rec[REC_JPDC1 + k] = d_C_y[k]; }
-#pragma unroll
-        for (int k = 0; k < 6; k++) { rec[REC_JPDXI0 + k] = d_xi_x[k]; rec[REC_JPDXI1 + k] = d_xi_y[k]; }
-        rec[REC_JIDX2 + 0] = JI00; rec[REC_JIDX2 + 1] = JI10; rec[REC_JIDX2 + 2] = JI11;
-        rec[REC_JABJIDX + 0] = Ja00; rec[REC_JABJIDX + 1] = Ja01; rec[REC_JABJIDX + 2] = Ja10; rec[REC_JABJIDX + 3] = Ja11;
-        rec[REC_JAB2 + 0] = Jb00; rec[REC_JAB2 + 1] = Jb01; rec[REC_JAB2 + 2] = Jb11;
-        rec[REC_JI_R + 0] = JIr0; rec[REC_JI_R + 1] = JIr1; rec[REC_JAB_R + 0] = Jar0; rec[REC_JAB_R + 1] = Jar1; rec[REC_RR] = rr;
-        rec[REC_JPDD + 0] = d_d_x; rec[REC_JPDD + 1] = d_d_y;
-        const float v0 = JI00 * d_d_x + JI10 * d_d_y, v1 = JI10 * d_d_x + JI11 * d_d_y;   // takeDataF (EnergyFunctionalStructs.cpp:39-49)
-#pragma unroll
-        for (int k = 0; k < 6; k++) rec[REC_JPJD + k] = d_xi_x[k] * v0 + d_xi_y[k] * v1;
-        rec[REC_JPJD + 6] = Ja00 * d_d_x + Ja01 * d_d_y;
-        rec[REC_JPJD + 7] = Ja10 * d_d_x + Ja11 * d_d_y;
-        rec[REC_BD] = JIr0 * d_d_x + JIr1 * d_d_y;
-        rec[REC_HDD] = v0 * d_d_x + v1 * d_d_y;
-#pragma unroll
-        for (int k = 0; k < 4; k++) rec[REC_HCD + k] = d_C_x[k] * v0 + d_C_y[k] * v1;
+        baWriteRecord(rec, Jc, s);
       }
     }
   }
@@ -829,15 +850,7 @@ __device__ __forceinline__ void baLinearizeBody1(const BAWindow& W, const BAPoin
     if (P.res_begin[pi] == ri) { const float bk = P.idepth_backup[pi]; P.idepth[pi] = bk; P.idepth_zero[pi] = bk; }
   }
   if (D.mode < 0) return;
-  __shared__ int s_last1;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every wave's write-through stores are acknowledged before the arrive (see baLinearizeBody)
-  __syncthreads();
-  if (threadIdx.x == 0) s_last1 = __hip_atomic_fetch_add(&D.ctl->cnt_lin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned int)(nblocks - 1) ? 1 : 0;
-  __syncthreads();
-  if (!s_last1) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if (threadIdx.x == 0) __hip_atomic_store(&D.ctl->cnt_lin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!baArriveLast(D.ctl, nblocks)) return;
   if (D.mode == 3) baPackBlock(D, nruns);
   else baDecideBlock<true>(D, nruns, t_kernel0, reinterpret_cast<unsigned int*>(patch));   // (every lane is done with its patch: behind the barrier above)
 }
@@ -970,8 +983,8 @@ __device__ __forceinline__ void baPointSumsBody(const BAWindow& W, const BAPoint
 // ------------------------------------------------------------------------------------------------ point marginalisation
 // EFResidual::fixLinearizationF (EnergyFunctionalStructs.cpp:76-106) for the active residuals of the points to marginalise, and the
 // record AccumulatedTopHessianSSE::addPoint<2> consumes: identical to the applied record except that the inner products with the
-// residual use res_toZeroF (AccumulatedTopHessian.cpp:70-71,103-113,131).  fullJ: the 74-float RawResidualJacobian of the applied
-// linearisation ([0,8) resF, [8,20) Jpdxi, [20,28) Jpdc, 28-29 Jpdd, [30,46) JIdx, [46,62) JabF).
+// residual use res_toZeroF (AccumulatedTopHessian.cpp:70-71,103-113,131).  fullJ: the RawResidualJacobian rows (FJ_*) of the applied
+// linearisation.
 // The settings of the point marginalisation (settings.cpp: setting_minIdepthH_marg, setting_idepthFixPriorMargFac, setting_margWeightFac), for the single call
 // (capi_ba.hip) and the batched one (ba_batch_kernels.hpp / ba_batch_host.hpp)
 constexpr float BA_MARG_MIN_IDEPTH_H = 50;
@@ -1001,30 +1014,23 @@ __device__ __forceinline__ void baFixLinearizationBody(const BAWindow& W, const 
   const bool on = dec == 1 && Rs.active[ri] != 0;
   margActive[ri] = on ? 1 : 0;
   if (!on) return;
-  const float* __restrict__ J = fullJ + (size_t)ri * 74;
+  const float* __restrict__ J = fullJ + (size_t)ri * FJ_FLOATS;
   const float* __restrict__ dp = adHTdeltaF + (size_t)(P.host[pi] + W.F * Rs.target[ri]) * 8;
-  const float dd = P.idepth[pi] - P.idepth_zero[pi];
   const float cd[4] = {cDeltaF.x, cDeltaF.y, cDeltaF.z, cDeltaF.w};
-  float sx = 0, sy = 0, cx = 0, cy = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) { sx += J[8 + i] * dp[i]; sy += J[14 + i] * dp[i]; }
-#pragma unroll
-  for (int i = 0; i < 4; i++) { cx += J[20 + i] * cd[i]; cy += J[24 + i] * cd[i]; }
-  const float Jp_delta_x = sx + cx + J[28] * dd, Jp_delta_y = sy + cy + J[29] * dd;
+  float Jp_delta_x, Jp_delta_y;
+  baJpDelta(J, dp, cd, P.idepth[pi] - P.idepth_zero[pi], Jp_delta_x, Jp_delta_y);
   float JIr0 = 0, JIr1 = 0, Jar0 = 0, Jar1 = 0, rr = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    float rtz = J[i];
-    rtz = rtz - J[30 + i] * Jp_delta_x; rtz = rtz - J[38 + i] * Jp_delta_y;
-    rtz = rtz - J[46 + i] * dp[6]; rtz = rtz - J[54 + i] * dp[7];
+    const float rtz = baResToZero(J, dp, Jp_delta_x, Jp_delta_y, i);
     if (res_toZeroF) res_toZeroF[(size_t)ri * 8 + i] = rtz;
-    JIr0 += rtz * J[30 + i]; JIr1 += rtz * J[38 + i]; Jar0 += rtz * J[46 + i]; Jar1 += rtz * J[54 + i]; rr += rtz * rtz;
+    JIr0 += rtz * J[FJ_JIDX0 + i]; JIr1 += rtz * J[FJ_JIDX1 + i]; Jar0 += rtz * J[FJ_JAB0 + i]; Jar1 += rtz * J[FJ_JAB1 + i]; rr += rtz * rtz;
   }
   const float* __restrict__ src = baRec(Rs, Rs.which[ri]) + (size_t)ri * REC_FLOATS;
   float* __restrict__ dst = margRec + (size_t)ri * REC_FLOATS;
   for (int k = 0; k < REC_FLOATS; k++) dst[k] = src[k];
   dst[REC_JI_R + 0] = JIr0; dst[REC_JI_R + 1] = JIr1; dst[REC_JAB_R + 0] = Jar0; dst[REC_JAB_R + 1] = Jar1; dst[REC_RR] = rr;
-  dst[REC_BD] = JIr0 * J[28] + JIr1 * J[29];
+  dst[REC_BD] = JIr0 * J[FJ_JPDD + 0] + JIr1 * J[FJ_JPDD + 1];
 }
 // decision of flagPointsForRemoval for the candidates: marginalise (1) if idepth_hessian > setting_minIdepthH_marg, else drop (2)
 __global__ void __launch_bounds__(256) k_ba_marg_decide(const int N, const unsigned char* __restrict__ cand, const float* __restrict__ idepth_hessian,
@@ -1080,23 +1086,13 @@ __global__ void __launch_bounds__(256) k_ba_lin_fix(const BAWindow W, const BAPo
   if (ri >= W.R) return;
   if (!mask[ri] || lin[ri] || !Rs.active[ri] || Rs.removed[ri]) return;
   const int pi = Rs.point[ri];
-  const float* __restrict__ J = fullJ + (size_t)ri * 74;
+  const float* __restrict__ J = fullJ + (size_t)ri * FJ_FLOATS;
   const float* __restrict__ dp = adHTdeltaF + (size_t)(P.host[pi] + W.F * Rs.target[ri]) * 8;
-  const float dd = P.idepth[pi] - P.idepth_zero[pi];
   const float cd[4] = {cDeltaF.x, cDeltaF.y, cDeltaF.z, cDeltaF.w};
-  float sx = 0, sy = 0, cx = 0, cy = 0;
+  float Jp_delta_x, Jp_delta_y;
+  baJpDelta(J, dp, cd, P.idepth[pi] - P.idepth_zero[pi], Jp_delta_x, Jp_delta_y);
 #pragma unroll
-  for (int i = 0; i < 6; i++) { sx += J[8 + i] * dp[i]; sy += J[14 + i] * dp[i]; }
-#pragma unroll
-  for (int i = 0; i < 4; i++) { cx += J[20 + i] * cd[i]; cy += J[24 + i] * cd[i]; }
-  const float Jp_delta_x = sx + cx + J[28] * dd, Jp_delta_y = sy + cy + J[29] * dd;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    float rtz = J[i];
-    rtz = rtz - J[30 + i] * Jp_delta_x; rtz = rtz - J[38 + i] * Jp_delta_y;
-    rtz = rtz - J[46 + i] * dp[6]; rtz = rtz - J[54 + i] * dp[7];
-    res_toZeroF[(size_t)ri * 8 + i] = rtz;
-  }
+  for (int i = 0; i < 8; i++) res_toZeroF[(size_t)ri * 8 + i] = baResToZero(J, dp, Jp_delta_x, Jp_delta_y, i);
   const float* __restrict__ src = baRec(Rs, Rs.which[ri]) + (size_t)ri * REC_FLOATS;
   float* __restrict__ dst = linRec + (size_t)ri * REC_FLOATS;
   for (int k = 0; k < REC_FLOATS; k++) dst[k] = src[k];
@@ -1104,47 +1100,49 @@ __global__ void __launch_bounds__(256) k_ba_lin_fix(const BAWindow W, const BAPo
 }
 // A residual that ARRIVES linearised (dmvio_hip_ba_set_linearized_residuals: EFResidual::isLinearized with its RawResidualJacobian and res_toZeroF, EnergyFunctionalStructs.h:
 // 63-87): what k_ba_lin_fix leaves behind for one linearised on the resident graph — the frozen Jacobian row, res_toZeroF, the Jacobian part of the applied record (formed
-// from J by the linearisation's own expressions, takeDataF EnergyFunctionalStructs.cpp:39-49 included) — plus the state an active residual of the reference has
-// (ResState::IN, in the energy functional).  idx: the n flagged residuals; packed: n x 82 floats [J (74) | res_toZeroF (8)].
+// from J by baWriteRecord's expressions, takeDataF included) — plus the state an active residual of the reference has
+// (ResState::IN, in the energy functional).  idx: the n flagged residuals; packed: n x FJ_PACKED floats [J | res_toZeroF (8)].
 __global__ void __launch_bounds__(256) k_ba_lin_import(const int n, const int* __restrict__ idx, const float* __restrict__ packed, const BARes Rs, float* __restrict__ fullJ,
                                                         float* __restrict__ res_toZeroF, float* __restrict__ linRec, unsigned char* __restrict__ lin) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   const int ri = idx[k];
-  const float* __restrict__ J = packed + (size_t)k * 82;
-  float* __restrict__ fj = fullJ + (size_t)ri * 74;
-  for (int i = 0; i < 74; i++) fj[i] = J[i];
-  for (int i = 0; i < 8; i++) res_toZeroF[(size_t)ri * 8 + i] = J[74 + i];
+  const float* __restrict__ J = packed + (size_t)k * FJ_PACKED;
+  float* __restrict__ fj = fullJ + (size_t)ri * FJ_FLOATS;
+  for (int i = 0; i < FJ_FLOATS; i++) fj[i] = J[i];
+  for (int i = 0; i < 8; i++) res_toZeroF[(size_t)ri * 8 + i] = J[FJ_FLOATS + i];
+  // The record is written out here a second time, not through baWriteRecord: with the rows and sums copied out of J for it, or handed over as pointers into J, this kernel's
+  // loads merged differently and its VGPR count moved (profiles/ba_linearize_shared.md).  The expressions are baWriteRecord's.
   float rec[REC_FLOATS];
-  const float d_d_x = J[28], d_d_y = J[29];
-  const float JI00 = J[62], JI10 = J[63], JI11 = J[65];
-  const float Ja00 = J[66], Ja01 = J[67], Ja10 = J[68], Ja11 = J[69];
+  const float d_d_x = J[FJ_JPDD + 0], d_d_y = J[FJ_JPDD + 1];
+  const float JI00 = J[FJ_JIDX2 + 0], JI10 = J[FJ_JIDX2 + 1], JI11 = J[FJ_JIDX2 + 3];
+  const float Ja00 = J[FJ_JABJIDX + 0], Ja01 = J[FJ_JABJIDX + 1], Ja10 = J[FJ_JABJIDX + 2], Ja11 = J[FJ_JABJIDX + 3];
 #pragma unroll
-  for (int i = 0; i < 4; i++) { rec[REC_JPDC0 + i] = J[20 + i]; rec[REC_JPDC1 + i] = J[24 + i]; }
+  for (int i = 0; i < 4; i++) { rec[REC_JPDC0 + i] = J[FJ_JPDC0 + i]; rec[REC_JPDC1 + i] = J[FJ_JPDC1 + i]; }
 #pragma unroll
-  for (int i = 0; i < 6; i++) { rec[REC_JPDXI0 + i] = J[8 + i]; rec[REC_JPDXI1 + i] = J[14 + i]; }
+  for (int i = 0; i < 6; i++) { rec[REC_JPDXI0 + i] = J[FJ_JPDXI0 + i]; rec[REC_JPDXI1 + i] = J[FJ_JPDXI1 + i]; }
   rec[REC_JIDX2 + 0] = JI00; rec[REC_JIDX2 + 1] = JI10; rec[REC_JIDX2 + 2] = JI11;
   rec[REC_JABJIDX + 0] = Ja00; rec[REC_JABJIDX + 1] = Ja01; rec[REC_JABJIDX + 2] = Ja10; rec[REC_JABJIDX + 3] = Ja11;
-  rec[REC_JAB2 + 0] = J[70]; rec[REC_JAB2 + 1] = J[71]; rec[REC_JAB2 + 2] = J[73];
+  rec[REC_JAB2 + 0] = J[FJ_JAB2 + 0]; rec[REC_JAB2 + 1] = J[FJ_JAB2 + 1]; rec[REC_JAB2 + 2] = J[FJ_JAB2 + 3];
   // the inner products with resF in pattern order, as the linearisation sums them (the applied record of the linearisation this residual was frozen at; the L pass works on
   // linRec, where k_ba_lin_records replaces them by those with resApprox)
   float JIr0 = 0.f, JIr1 = 0.f, Jar0 = 0.f, Jar1 = 0.f, rr = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    const float resF = J[i];
-    JIr0 = JIr0 + resF * J[30 + i]; JIr1 = JIr1 + resF * J[38 + i]; Jar0 = Jar0 + resF * J[46 + i]; Jar1 = Jar1 + resF * J[54 + i]; rr = rr + resF * resF;
+    const float resF = J[FJ_RESF + i];
+    JIr0 = JIr0 + resF * J[FJ_JIDX0 + i]; JIr1 = JIr1 + resF * J[FJ_JIDX1 + i]; Jar0 = Jar0 + resF * J[FJ_JAB0 + i]; Jar1 = Jar1 + resF * J[FJ_JAB1 + i]; rr = rr + resF * resF;
   }
   rec[REC_JI_R + 0] = JIr0; rec[REC_JI_R + 1] = JIr1; rec[REC_JAB_R + 0] = Jar0; rec[REC_JAB_R + 1] = Jar1; rec[REC_RR] = rr;
   rec[REC_JPDD + 0] = d_d_x; rec[REC_JPDD + 1] = d_d_y;
   const float v0 = JI00 * d_d_x + JI10 * d_d_y, v1 = JI10 * d_d_x + JI11 * d_d_y;
 #pragma unroll
-  for (int i = 0; i < 6; i++) rec[REC_JPJD + i] = J[8 + i] * v0 + J[14 + i] * v1;
+  for (int i = 0; i < 6; i++) rec[REC_JPJD + i] = J[FJ_JPDXI0 + i] * v0 + J[FJ_JPDXI1 + i] * v1;
   rec[REC_JPJD + 6] = Ja00 * d_d_x + Ja01 * d_d_y;
   rec[REC_JPJD + 7] = Ja10 * d_d_x + Ja11 * d_d_y;
   rec[REC_BD] = JIr0 * d_d_x + JIr1 * d_d_y;
   rec[REC_HDD] = v0 * d_d_x + v1 * d_d_y;
 #pragma unroll
-  for (int i = 0; i < 4; i++) rec[REC_HCD + i] = J[20 + i] * v0 + J[24 + i] * v1;
+  for (int i = 0; i < 4; i++) rec[REC_HCD + i] = J[FJ_JPDC0 + i] * v0 + J[FJ_JPDC1 + i] * v1;
   rec[REC_PAD] = 0.f;
   // the applied record (both buffers: whichever the selector points at) — the Schur pass and the points' back-substitution read JpJdF from it — and the frozen copy
   float* __restrict__ d0 = Rs.rec[0] + (size_t)ri * REC_FLOATS;
@@ -1176,27 +1174,22 @@ __device__ __forceinline__ void baLinRecordsBody(const BAWindow& W, const BAPoin
   topActive[ri] = (act && !isLin) ? 1 : 0;
   if (!(act && isLin)) return;
   const int pi = Rs.point[ri];
-  const float* __restrict__ J = fullJ + (size_t)ri * 74;
+  const float* __restrict__ J = fullJ + (size_t)ri * FJ_FLOATS;
   const float* __restrict__ dp = adHTdeltaF + (size_t)(P.host[pi] + W.F * Rs.target[ri]) * 8;
-  const float dd = P.idepth[pi] - P.idepth_zero[pi];
   const float cd[4] = {cDeltaF.x, cDeltaF.y, cDeltaF.z, cDeltaF.w};
-  float sx = 0, sy = 0, cx = 0, cy = 0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) { sx += J[8 + i] * dp[i]; sy += J[14 + i] * dp[i]; }
-#pragma unroll
-  for (int i = 0; i < 4; i++) { cx += J[20 + i] * cd[i]; cy += J[24 + i] * cd[i]; }
-  const float Jp_delta_x = sx + cx + J[28] * dd, Jp_delta_y = sy + cy + J[29] * dd;
+  float Jp_delta_x, Jp_delta_y;
+  baJpDelta(J, dp, cd, P.idepth[pi] - P.idepth_zero[pi], Jp_delta_x, Jp_delta_y);
   float JIr0 = 0, JIr1 = 0, Jar0 = 0, Jar1 = 0, rr = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     float ra = res_toZeroF[(size_t)ri * 8 + i];
-    ra = ra + J[30 + i] * Jp_delta_x; ra = ra + J[38 + i] * Jp_delta_y;
-    ra = ra + J[46 + i] * dp[6]; ra = ra + J[54 + i] * dp[7];
-    JIr0 += ra * J[30 + i]; JIr1 += ra * J[38 + i]; Jar0 += ra * J[46 + i]; Jar1 += ra * J[54 + i]; rr += ra * ra;
+    ra = ra + J[FJ_JIDX0 + i] * Jp_delta_x; ra = ra + J[FJ_JIDX1 + i] * Jp_delta_y;
+    ra = ra + J[FJ_JAB0 + i] * dp[6]; ra = ra + J[FJ_JAB1 + i] * dp[7];
+    JIr0 += ra * J[FJ_JIDX0 + i]; JIr1 += ra * J[FJ_JIDX1 + i]; Jar0 += ra * J[FJ_JAB0 + i]; Jar1 += ra * J[FJ_JAB1 + i]; rr += ra * ra;
   }
   float* __restrict__ dst = linRec + (size_t)ri * REC_FLOATS;
   dst[REC_JI_R + 0] = JIr0; dst[REC_JI_R + 1] = JIr1; dst[REC_JAB_R + 0] = Jar0; dst[REC_JAB_R + 1] = Jar1; dst[REC_RR] = rr;
-  dst[REC_BD] = JIr0 * J[28] + JIr1 * J[29];
+  dst[REC_BD] = JIr0 * J[FJ_JPDD + 0] + JIr1 * J[FJ_JPDD + 1];
 }
 // Hdd_accLF, bd_accLF, Hcd_accLF (AccumulatedTopHessian.cpp:131-143, mode 1): sequential over the point's linearised active residuals
 __device__ __forceinline__ void baLinPointSumsBody(const BAWindow& W, const BAPoints& P, const float* __restrict__ linRec, const unsigned char* __restrict__ linActive,
@@ -1959,11 +1952,7 @@ __device__ __forceinline__ void baResubstituteBody(const BAWindow& W, const BAPo
   const float hc0 = P.Hcd[4 * pi + 0], hc1 = P.Hcd[4 * pi + 1], hc2 = P.Hcd[4 * pi + 2], hc3 = P.Hcd[4 * pi + 3];
   const int grp = (threadIdx.x & 63) & ~7;
   float b = bdSum;
-  {
-    float dotc = 0;
-    dotc += xc[0] * (hc0 + 0.0f); dotc += xc[1] * (hc1 + 0.0f); dotc += xc[2] * (hc2 + 0.0f); dotc += xc[3] * (hc3 + 0.0f);
-    b -= dotc;
-  }
+  b -= baDotC(xc, hc0, hc1, hc2, hc3);
   int ngood = 0;
   for (int rb = r0; rb < r1; rb += 8) {
     const int ri = min(rb + q, r1 - 1);

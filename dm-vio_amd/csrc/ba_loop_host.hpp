@@ -168,25 +168,13 @@ static double linEnergy(dmvio_hip_ba* b) {
     for (int pi = p0; pi < std::min(H.N, p0 + 50); pi++)
       for (int ri = b->h_res_begin[pi]; ri < b->h_res_begin[pi + 1]; ri++) {
         if (!b->h_lin[ri] || !b->h_linAct[ri]) continue;
-        const float* J = &b->h_linJ[(size_t)ri * 74];
+        const float* J = &b->h_linJ[(size_t)ri * FJ_FLOATS];
         const float* rtz = &b->h_rtz[(size_t)ri * 8];
         const float* dp = &adHT[(size_t)(b->h_host[pi] + H.F * b->h_target[ri]) * 8];
-        const float dd = 0.0f;
-        float sx = 0, sy = 0, cx = 0, cy = 0;
-        for (int i = 0; i < 6; i++) { sx += J[8 + i] * dp[i]; sy += J[14 + i] * dp[i]; }
-        for (int i = 0; i < 4; i++) { cx += J[20 + i] * H.cDeltaF[i]; cy += J[24 + i] * H.cDeltaF[i]; }
-        const float Jp_delta_x = sx + cx + J[28] * dd, Jp_delta_y = sy + cy + J[29] * dd;
+        float Jp_delta_x, Jp_delta_y;
+        baJpDelta(J, dp, H.cDeltaF, 0.0f, Jp_delta_x, Jp_delta_y);
         for (int i = 0; i < 8; i += 4)
-          for (int k = 0; k < 4; k++) {
-            float Jdelta = J[30 + i + k] * Jp_delta_x;
-            Jdelta = Jdelta + J[38 + i + k] * Jp_delta_y;
-            Jdelta = Jdelta + J[46 + i + k] * dp[6];
-            Jdelta = Jdelta + J[54 + i + k] * dp[7];
-            float r0 = rtz[i + k];
-            r0 = r0 + r0;
-            r0 = r0 + Jdelta;
-            d1[k] = d1[k] + Jdelta * r0;
-          }
+          for (int k = 0; k < 4; k++) d1[k] = d1[k] + baLinEnergyTerm(J, rtz, dp, Jp_delta_x, Jp_delta_y, i + k);
       }
     A += (double)(d1[0] + d1[1] + d1[2] + d1[3]);
   }

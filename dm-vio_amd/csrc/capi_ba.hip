@@ -525,11 +525,11 @@ int dmvio_hip_ba_get_linearized_residuals(dmvio_hip_ba* b, int R, unsigned char*
   BA_LOCK(b);
   if (!b->graph_ready) return failmsg("ba: set_window + set_graph first");
   if (R != b->H.R) return failmsg("ba_get_linearized_residuals: R differs from the graph's residual count");
-  const bool have = b->d_lin != nullptr && (int)b->h_lin.size() == R && b->h_linJ.size() == (size_t)R * 74;
+  const bool have = b->d_lin != nullptr && (int)b->h_lin.size() == R && b->h_linJ.size() == (size_t)R * FJ_FLOATS;
   for (int ri = 0; ri < R; ri++) {
     const bool l = have && b->h_lin[ri];
     if (isLinearized) isLinearized[ri] = l ? 1 : 0;
-    if (J74) { if (l) memcpy(J74 + (size_t)ri * 74, &b->h_linJ[(size_t)ri * 74], sizeof(float) * 74); else memset(J74 + (size_t)ri * 74, 0, sizeof(float) * 74); }
+    if (J74) { if (l) memcpy(J74 + (size_t)ri * FJ_FLOATS, &b->h_linJ[(size_t)ri * FJ_FLOATS], sizeof(float) * FJ_FLOATS); else memset(J74 + (size_t)ri * FJ_FLOATS, 0, sizeof(float) * FJ_FLOATS); }
     if (res_toZeroF) { if (l) memcpy(res_toZeroF + (size_t)ri * 8, &b->h_rtz[(size_t)ri * 8], sizeof(float) * 8); else memset(res_toZeroF + (size_t)ri * 8, 0, sizeof(float) * 8); }
   }
   return 0;
@@ -585,7 +585,7 @@ int dmvio_hip_ba_get_res_state(dmvio_hip_ba* b, unsigned char* newState, float* 
 int dmvio_hip_ba_get_jacobians(dmvio_hip_ba* b, float* J74) {
   BA_READY(b);
   if (!b->keep_fullJ) return failmsg("ba_get_jacobians: call dmvio_hip_ba_keep_jacobians(ba, 1) before the linearisation");
-  HIPCHK(b->bounce.d2h(J74, b->d_fullJ, sizeof(float) * 74 * b->H.R, b->stream));
+  HIPCHK(b->bounce.d2h(J74, b->d_fullJ, sizeof(float) * FJ_FLOATS * b->H.R, b->stream));
   HIPCHK(b->bounce.finish(b->stream));
   return 0;
 }

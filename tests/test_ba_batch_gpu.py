@@ -3,8 +3,14 @@
 per launch sequence.  Checked against (i) the oracle (= the reference's arithmetic, same bars as test_ba_gpu.py::test_optimize_parity), (ii) the library's host-driven loop
 (the same window, same kernels for the photometric part: the two loops differ in the elementary functions of the frame step and, by default, in the association of the back
 substitution), (iii) itself: a window's result must not depend on what else is in the batch."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_ba_lanes_cpu import LANES_CASE  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +190,49 @@ def test_groups_streams_and_the_one_lane_linearisation_change_no_bit(pkg, synth,
         for h in hs:
             h.close()
     B1.close(); B8.close(); ctx.close()
+
+
+def test_one_lane_linearisation_taps_the_image_where_a_half_leaves_its_window(pkg, oracle, synth, gpu_required):
+    """The one-lane linearisation (k_ba_linearize_b1) interpolates a pattern half from a 6 x 8 window of the image where the half's tap neighbourhoods fit one, and taps
+    the image directly where they do not — both in one launch.  A small window that holds both kinds of halves (tests/test_ba_lanes_cpu.py asserts that it does) goes
+    through optimize(3) of a BundleAdjusterBatch with the eight-lane kernel and with the one-lane kernel, on fresh handles: traces, finalEnergy, rmse, poses, inverse
+    depths and every residual's state, energies and centre projection bit for bit.  The library takes the one-lane kernel from four windows on, so the window is
+    there four times.  The batched call hands out no per-residual state between its linearisations; the oracle comes in through the chain: its linearize_all equals the
+    eight-lane kernel's first linearisation of this window residual by residual (single handle), its energy is the first row of both batched traces to 1e-9, and
+    the two batched runs agree in every bit they leave behind."""
+    case = synth.ba_case(**LANES_CASE)
+    F = case["n_frames"]
+    ctx = _ctx_with(pkg, case)
+    W = oracle.BAWindow(case)
+    W.activate_all(); e_o = W.linearize_all(False); so = W.res_state()
+    one = pkg.BundleAdjusterHip(ctx); one.set_case(case, list(range(F)))
+    one.activate_all(); e_g = one.linearize_all(False); sg = one.res_state()
+    assert np.array_equal(sg["newState"], so["newState"].astype(np.uint8))
+    assert np.array_equal(sg["newEnergy"], so["newEnergy"].astype(np.float32)) and np.array_equal(sg["newEnergyWO"], so["newEnergyWO"].astype(np.float32))
+    assert abs(e_g - e_o) <= 1e-9 * e_o
+    assert (so["newState"] == 0).sum() > 0.5 * W.R
+    one.close()
+    out = {}
+    for lanes in (8, 1):
+        B = pkg.BundleAdjusterBatch(ctx, 4); B.set_linearize_lanes(lanes)
+        hs = []
+        for _ in range(4):
+            ba = pkg.BundleAdjusterHip(ctx); ba.set_case(case, list(range(F))); hs.append(ba)
+        rb = B.optimize(hs, 3)
+        out[lanes] = [(r, _poses(h, F), h.point_state()[0], h.res_state()) for r, h in zip(rb, hs)]
+        for o in hs + [B]:
+            o.close()
+    ctx.close()
+    print("first linearisation: oracle %.17g, eight lanes %.17g, one lane %.17g" % (e_o, out[8][0][0]["trace"][0, 0], out[1][0][0]["trace"][0, 0]))
+    for (r8, p8, d8, s8), (r1, p1, d1, s1) in zip(out[8], out[1]):
+        assert abs(r8["trace"][0, 0] - e_o) <= 1e-9 * e_o and abs(r1["trace"][0, 0] - e_o) <= 1e-9 * e_o
+        assert r8["iterations"] == r1["iterations"] == 3 and np.array_equal(r8["trace"], r1["trace"])
+        assert r8["finalEnergy"] == r1["finalEnergy"] and r8["rmse"] == r1["rmse"]
+        assert np.array_equal(p8, p1) and np.array_equal(d8, d1)
+        for k in ("newState", "newEnergy", "newEnergyWO", "isActive"):
+            assert np.array_equal(s8[k].view(np.uint8), s1[k].view(np.uint8)), k
+        ok = s8["newState"] != 1   # (an out-of-bounds residual has no centre projection)
+        assert np.array_equal(s8["center"][ok].view(np.uint32), s1["center"][ok].view(np.uint32))
 
 
 def test_device_loop_with_a_marginalisation_prior_and_fej_deltas(pkg, synth, gpu_required):

@@ -39,3 +39,10 @@ def test_no_generic_pointer_reaches_global_memory():
                 assert r[k]["scratch_load"] + r[k]["scratch_store"] == 0, (k, r[k])
     for k in [k for k in r if k.split(":")[1].startswith("k_track_lm")]:
         assert r[k]["flat_load"] + r[k]["flat_store"] == 0, (k, r[k])
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not installed")
+def test_isa_diff_explains_nothing_between_a_tree_and_itself(tmp_path, capsys):
+    import isa_diff
+    isa_diff.dump(str(tmp_path))
+    assert isa_diff.main(str(tmp_path), str(tmp_path), True) == 0 and capsys.readouterr().out.rstrip().endswith("identical")

@@ -4,10 +4,11 @@ labels .LBB<n>_<m> / .Ltmp<n> renumbered in order of appearance, `;` comments st
 checks itself with: every kernel of A must be in B and identical, and B must not add one.  Kernels are matched by symbol over the union of all units, so a kernel that
 changed its translation unit is compared all the same and reported as moved (which alone is no difference).
 
-usage: python tools/isa_diff.py <dirA> <dirB>        directories of <unit>.s files
+usage: python tools/isa_diff.py [--explain] <dirA> <dirB>   directories of <unit>.s files; --explain: per differing kernel, the .amdhsa_ lines and the opcode counts that differ
        python tools/isa_diff.py --dump <dir> [csrc]  compile the units of dm-vio_amd/csrc (or of another tree's csrc) into <dir> first (hipcc -S --cuda-device-only, the Makefile's flags)
 exit status 0: identical; 1: differences (listed)."""
 import os, re, subprocess, sys
+from collections import Counter
 from concurrent.futures import ThreadPoolExecutor
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -65,7 +66,15 @@ def tree(d):
     return res
 
 
-def main(a, b):
+def explain(va, vb):
+    """what differs between two versions of a kernel: the .amdhsa_ lines (registers, LDS, scratch) and the opcodes whose counts differ, as (A, B)"""
+    for t in sorted(set(va[2]) ^ set(vb[2])):
+        print("    %s %s" % ("A" if t in va[2] else "B", t))
+    ca, cb = (Counter("label" if l.endswith(":") else l.split()[0] for l in v[1]) for v in (va, vb))
+    print("    " + (", ".join("%s (%d, %d)" % (o, ca[o], cb[o]) for o in sorted(set(ca) | set(cb)) if ca[o] != cb[o]) or "same opcode counts: order or operands differ"))
+
+
+def main(a, b, why=False):
     ka, kb = tree(a), tree(b)
     bad = moved = 0
     for k in sorted(set(ka) | set(kb)):
@@ -79,6 +88,7 @@ def main(a, b):
         else: continue
         bad += 1
         print("%s: %s: %s" % ((ka.get(k) or kb[k])[0], k, what))
+        if why and k in ka and k in kb: explain(ka[k], kb[k])
     for u in sorted(set(v[0] for v in ka.values()) | set(v[0] for v in kb.values())):
         print("%s: %d kernels in A, %d in B" % (u, sum(v[0] == u for v in ka.values()), sum(v[0] == u for v in kb.values())))
     print("%d kernels in A, %d in B, %d moved; %s" % (len(ka), len(kb), moved, "identical" if not bad else "%d kernels differ" % bad))
@@ -88,6 +98,8 @@ def main(a, b):
 if __name__ == "__main__":
     if len(sys.argv) >= 3 and sys.argv[1] == "--dump":
         dump(sys.argv[2], *sys.argv[3:4])
+    elif len(sys.argv) == 4 and sys.argv[1] == "--explain":
+        sys.exit(main(sys.argv[2], sys.argv[3], True))
     elif len(sys.argv) == 3:
         sys.exit(main(sys.argv[1], sys.argv[2]))
     else:
