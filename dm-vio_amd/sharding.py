@@ -18,17 +18,13 @@ import numpy as np
 def partition_points_by_host(host, world, max_imbalance=1.25):
     """Point indices owned by every rank — the library's policy (dmvio_hip_ba_partition_points, include/dmvio_hip.h: whole keyframes per rank, largest first, greedy; equal
     contiguous point ranges when the keyframe split is more unbalanced than max_imbalance).  This is only a caller: a C++ host gets the same split from the same entry point."""
-    import ctypes
     from . import load_library, HipLibraryError
     host = np.ascontiguousarray(host, dtype=np.int32)
     n = len(host)
     owner = np.zeros(n, dtype=np.int32)
     L = load_library()
-    L.dmvio_hip_ba_partition_points.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]
-    L.dmvio_hip_ba_partition_points.restype = ctypes.c_int
     r = L.dmvio_hip_ba_partition_points(host.ctypes.data, n, int(world), float(max_imbalance), owner.ctypes.data)
     if r < 0:
-        L.dmvio_hip_last_error.restype = ctypes.c_char_p
         raise HipLibraryError("dmvio_hip_ba_partition_points: %s" % (L.dmvio_hip_last_error() or b"").decode())
     return [np.nonzero(owner == q)[0] for q in range(world)]
 

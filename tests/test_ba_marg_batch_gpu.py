@@ -277,7 +277,7 @@ def test_refusals(pkg, gpu_required):
     B = pkg.BundleAdjusterBatch(ctx, 2)
     B3 = pkg.BundleAdjusterBatch(ctx, 4)
     L = ctx.L
-    fn = L.dmvio_hip_ba_marginalize_points_batch; fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(pkg.BAMargWindow)]; fn.restype = C.c_int
+    fn = L.dmvio_hip_ba_marginalize_points_batch
 
     def raw(batch, W, entries):
         """entries: (handle pointer, candidates or None, decision or None)"""

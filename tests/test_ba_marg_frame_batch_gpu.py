@@ -221,7 +221,7 @@ def test_refusals(pkg, gpu_required):
     B = pkg.BundleAdjusterBatch(ctx, 2)
     B3 = pkg.BundleAdjusterBatch(ctx, 4)
     L = ctx.L
-    fn = L.dmvio_hip_ba_marginalize_frame_batch; fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(pkg.BAMargFrameWindow)]; fn.restype = C.c_int
+    fn = L.dmvio_hip_ba_marginalize_frame_batch
     SENT = -12345.5
     nd = 4 + 8 * F - 8
     outH = [np.full((nd, nd), SENT) for _ in range(3)]

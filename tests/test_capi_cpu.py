@@ -45,7 +45,6 @@ def test_no_cpu_fallback_without_device(pkg):
         pytest.skip("a GPU is visible; the no-device refusal is exercised on the CPU box")
     with pytest.raises(pkg.HipLibraryError):
         pkg.Context(64, 64, 2)
-    lib.dmvio_hip_create.restype = ctypes.c_void_p
     assert not lib.dmvio_hip_create(0, 64, 64, 2)
     assert lib.dmvio_hip_last_error()
 

@@ -159,7 +159,6 @@ def test_ba_solve_ldlt_is_the_references_non_gtsam_solve(pkg, oracle):
     import ctypes as C
     L = pkg.load_library()
     c_d = C.POINTER(C.c_double)
-    L.dmvio_hip_ba_solve_ldlt.argtypes = [C.c_int, c_d, c_d, c_d]; L.dmvio_hip_ba_solve_ldlt.restype = C.c_int
     rng = np.random.RandomState(12)
     for n in (12, 36, 68):
         A = rng.standard_normal((n, 3 * n)); H = A @ A.T + np.diag(rng.uniform(0.0, 50.0, n)); H = 0.5 * (H + H.T)

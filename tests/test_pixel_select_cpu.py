@@ -91,8 +91,6 @@ def test_isa_check_lists_the_selector_kernels():
 
 def test_no_device_no_selector(pkg):
     """no CPU fallback: without a device there is no context, hence no selector; NULL arguments are refused with a message"""
-    import ctypes
     lib = pkg.load_library()
-    lib.dmvio_hip_pixel_selector_create.restype = ctypes.c_void_p
     assert not lib.dmvio_hip_pixel_selector_create(None, None)
     assert b"null context" in lib.dmvio_hip_last_error()

@@ -148,7 +148,6 @@ def test_add_selected_equals_add_points(pkg, synth, gpu_required):
 
 def test_error_paths(pkg, synth, gpu_required):
     L = pkg.load_library()
-    L.dmvio_hip_pixel_selector_create.restype = ctypes.c_void_p
     pat = _pattern(512 * 512)
     ctx = pkg.Context(200, 120, n_slots=1)                      # not divisible by 16
     assert not L.dmvio_hip_pixel_selector_create(ctx.p, pat.ctypes.data_as(pkg.c_u8))

@@ -52,8 +52,6 @@ def test_partition_entry_point_equals_the_stated_policy(pkg):
     import ctypes
     import dmvio_amd.sharding as sh
     L = pkg.load_library()
-    L.dmvio_hip_ba_partition_points.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]
-    L.dmvio_hip_ba_partition_points.restype = ctypes.c_int
     rng = np.random.RandomState(3)
     seen = set()
     for trial in range(300):

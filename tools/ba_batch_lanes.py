@@ -12,8 +12,8 @@ for k in range(F):
     ctx.frame_upload(k, case["imgs"][k])
 B = pkg.BundleAdjusterBatch(ctx, 64)
 pool = [pkg.BundleAdjusterHip(ctx) for _ in range(64)]
-fl = B.L.dmvio_hip_ba_batch_set_linearize_lanes; fl.argtypes = [C.c_void_p, C.c_int]; fl.restype = C.c_int
-fs = B.L.dmvio_hip_ba_batch_set_streams; fs.argtypes = [C.c_void_p, C.c_int]; fs.restype = C.c_int
+fl = B.L.dmvio_hip_ba_batch_set_linearize_lanes
+fs = B.L.dmvio_hip_ba_batch_set_streams
 for W in (8, 16, 24, 32, 64):
     for lanes in (1, 8):
         for streams in (3, 4):

@@ -33,6 +33,6 @@ for W in Ws:
     acc = sum(int(r["trace"][1:, 3].sum()) for r in rs)
     w = np.median(walls[1:5]); d = np.median([x[0] + x[1] for x in dev[1:5]])
     import ctypes as C
-    tk = (C.c_int * 12)(); B.L.dmvio_hip_ba_batch_last_solve_ticks.argtypes = [C.c_void_p, C.c_void_p]; B.L.dmvio_hip_ba_batch_last_solve_ticks(B.p, tk)
+    tk = (C.c_int * 12)(); B.L.dmvio_hip_ba_batch_last_solve_ticks(B.p, tk)
     print("   k_ba_solve timeline (us):", [round(t / 100.0, 1) for t in tk])
     print("W=%3d: wall %.3f ms, device %.3f ms, accepted %d -> %.1f it/s, %.1f us per accepted iteration per window-batch; stepped linearisation %.1f us" % (W, 1e3 * w, d, acc, acc / w, 1e6 * w / acc * W, 1e3 * dev[5][2]))

@@ -25,7 +25,6 @@ dt = time.perf_counter() - t0
 print("%.1f GN-iterations/s, %.1f us per iteration, %d of %d accepted" % (n_it / dt, 1e6 * dt / n_it, acc, n_it))
 import ctypes as C
 tk = (C.c_int * 4)()
-ba.L.dmvio_hip_ba_last_decide_ticks.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
 ba.L.dmvio_hip_ba_last_decide_ticks(ba.p, tk)
 print("last decision pass, us since its workgroup started: begin %.2f, energy %.2f, keys %.2f, done %.2f" % tuple(t / 100.0 for t in tk))
 # FullSystem::optimize as the reference calls it once per keyframe: 6 GN iterations from the perturbed window + the final fix-linearisation

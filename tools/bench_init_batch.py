@@ -49,15 +49,7 @@ def main():
     import torch
     P = g.load_package()
     if a.lib:
-        P.LIB_PATH = os.path.abspath(a.lib)
-        if a.single_only:      # a build from before the batched entry points: their signatures are not set
-            sig = P._sig
-            def tolerant(L):
-                try:
-                    sig(L)
-                except AttributeError:
-                    pass
-            P._sig = tolerant
+        P.load_library(os.path.abspath(a.lib), allow_missing=a.single_only)   # --single-only: a build from before the batched entry points
     import dmvio_amd.synth as synth
     if not torch.cuda.is_available():
         sys.exit("bench_init_batch: no GPU")
@@ -68,7 +60,7 @@ def main():
     R, t = synth.se3_exp(np.array((0.05, -0.02, 0.01, 0.004, -0.006, 0.002), dtype=np.float64))
     img1, _ = world.render(K4, R, t, w, h, aff=(0.02, 1.5))
     scene = dict(w=w, h=h, img0=img0, img1=img1, id0=id0, pose7=np.asarray(synth.pose7(R, t), dtype=np.float64), K4=np.asarray(K4, dtype=np.float64))
-    out = dict(tool="bench_init_batch", lib=P.LIB_PATH if a.lib else "tree", w=w, h=h, lvl=0, points=a.points, steps=a.steps, warmup=a.warmup, runs=a.runs,
+    out = dict(tool="bench_init_batch", lib=os.path.abspath(a.lib) if a.lib else "tree", w=w, h=h, lvl=0, points=a.points, steps=a.steps, warmup=a.warmup, runs=a.runs,
                unit="us per window", results=[])
     for W in a.batch:
         for case in ("points", "sums"):

@@ -41,7 +41,7 @@ def main():
     import torch
     P = g.load_package()
     if a.lib:
-        P.LIB_PATH = os.path.abspath(a.lib)
+        P.load_library(os.path.abspath(a.lib), allow_missing=True)
     import dmvio_amd.synth as synth
     if not torch.cuda.is_available():
         sys.exit("bench_marg_frame_batch: no GPU")
@@ -49,7 +49,7 @@ def main():
     share = (400, 350, 300, 300, 250, 250, 150, 0)
     cs = synth.ba_case(w, h, n_frames=8, n_points=a.points, hosts_share=tuple(int(round(x * a.points / 2000.0)) for x in share))
     cand = (np.asarray(cs["host"]) == 0).astype(np.uint8)
-    out = dict(tool="bench_marg_frame_batch", lib=P.LIB_PATH if a.lib else "tree", w=w, h=h, frames=8, points=len(cs["host"]), candidates=int(cand.sum()), frame=a.frame,
+    out = dict(tool="bench_marg_frame_batch", lib=os.path.abspath(a.lib) if a.lib else "tree", w=w, h=h, frames=8, points=len(cs["host"]), candidates=int(cand.sum()), frame=a.frame,
                steps=a.steps, warmup=a.warmup, runs=a.runs, unit="us per window", results=[])
     keys = ("single_host",) if a.single_only else ("single_host", "batch_host", "batch_event")
     for W in a.batch:
@@ -101,7 +101,7 @@ def one_run(a, P, synth, cs, cand, W, seed):
     t = dict(single_host=[], batch_host=[], batch_event=[])
     if not a.single_only:
         B.set_profile(True)
-        batch = L.dmvio_hip_ba_marginalize_frame_batch; batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(P.BAMargFrameWindow)]; batch.restype = C.c_int
+        batch = L.dmvio_hip_ba_marginalize_frame_batch
         bH = [np.zeros((nd, nd)) for _ in range(W)]; bb = [np.zeros(nd) for _ in range(W)]
         arr = (P.BAMargFrameWindow * W)()
         for k in range(W):

@@ -43,11 +43,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_set_graph_batch: no GPU")
     if a.lib:
-        P._lib = C.CDLL(os.path.abspath(a.lib))
-        try:
-            P._sig(P._lib)
-        except AttributeError:   # a build from before the newest entry points: everything up to them is declared
-            pass
+        P.load_library(os.path.abspath(a.lib), allow_missing=True)   # a build from before the newest entry points lacks some
     L = P.load_library()
     have_batch = hasattr(L, "dmvio_hip_ba_set_graph_from_batch") and not a.singles_only
     w = h = 512
@@ -104,7 +100,6 @@ def one_run(a, P, L, torch, synth, cs, Wmax, have_batch, seed):
         ba.set_graph_from(gr)
         hs.append(ba); graphs.append(gr); starts.append(poses)
     B = P.BundleAdjusterBatch(ctx, Wmax)
-    L.dmvio_hip_ba_set_graph_from.argtypes = [C.c_void_p, C.c_void_p]; L.dmvio_hip_ba_set_graph_from.restype = C.c_int
     arr = (P.BAGraphWindow * Wmax)() if have_batch else None
     for k in range(Wmax if have_batch else 0):
         arr[k].ba = hs[k].p.value; arr[k].graph = graphs[k].p.value

@@ -41,7 +41,6 @@ for i in range(B):
 affs0 = np.zeros((B, 2))
 ctx.frames_attach_device_batch(slots, raw.data_ptr(), w * h * 4)
 L = ctx.L
-L.dmvio_hip_tracker_debug_record_replay.argtypes = [C.c_void_p, C.c_int]
 
 
 def timed(n):
@@ -76,7 +75,6 @@ print("k_track_replay       %.3f ms per launch: the same evaluations without the
 print("=> everything the control step costs on the critical path of this batch: %.1f %% of the launch" % (100 * (1 - b / a)))
 print("algorithmic bytes %.3f GB per launch: %.2f TB/s full kernel, %.2f TB/s evaluations alone" % (64 * pe / 1e9, 64 * pe / (a * 1e-3) / 1e12, 64 * pe / (b * 1e-3) / 1e12))
 # ---- part 2: the template stored in the reference's row-major order instead of 8x8 tiles (tools/template_lines.py counts the cache lines per load for both)
-L.dmvio_hip_tracker_set_template_order.argtypes = [C.c_void_p, C.c_int]
 for order, name in ((1, "row-major"), (0, "8x8 tiles (default)")):
     L.dmvio_hip_tracker_set_template_order(trk.p, order)
     trk.setCoarseTrackingRef(0, case["u"], case["v"], case["idepth"], case["hdiF"])
@@ -92,7 +90,6 @@ for order, name in ((1, "row-major"), (0, "8x8 tiles (default)")):
     print("template order %-20s k_track_lm %.3f ms per launch (median of 8), %d point-evaluations, all good: %s, max pose error %.2e m -> %.2f TB/s algorithmic"
           % (name, np.median(tt), pe2, bool(rr["good"].all()), err, 64 * pe2 / (np.median(tt) * 1e-3) / 1e12))
 # ---- part 3: the control step off the evaluation waves' critical path (k_track_lm_pp)
-L.dmvio_hip_tracker_set_batch_kernel.argtypes = [C.c_void_p, C.c_int]
 trk.stage(slots, poses0, affs0)
 trk.launch(); base = trk.fetch()
 L.dmvio_hip_tracker_set_batch_kernel(trk.p, 1)

@@ -22,7 +22,6 @@ ident = np.array([0, 0, 0, 0, 0, 0, 1.0])
 e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
 import ctypes as C
 L = trk.L
-L.dmvio_hip_tracker_set_template_order.argtypes = [C.c_void_p, C.c_int]; L.dmvio_hip_tracker_set_batch_kernel.argtypes = [C.c_void_p, C.c_int]
 for name, shape, bk, order in (("256 x 4 (default)", (0, 0, 0, 0), 0, 0), ("256 x 2", (0, 256, 2, 0), 0, 0), ("512 x 4", (0, 512, 4, 0), 0, 0), ("512 x 2", (0, 512, 2, 0), 0, 0),
                                ("two problems per workgroup", (0, 0, 0, 0), 1, 0), ("row-major template", (0, 0, 0, 0), 0, 1)):
     trk.set_launch_shape(*shape); L.dmvio_hip_tracker_set_batch_kernel(trk.p, bk); L.dmvio_hip_tracker_set_template_order(trk.p, order)
