@@ -260,7 +260,9 @@ int dmvio_hip_tracker_eval(dmvio_hip_tracker* t, int lvl, int new_slot, float ne
   EvalP e;
   makeEvalP(t->dev, lvl, poseFrom7(pose7), aff[0], aff[1], new_exposure, cutoffTH, e);
   const int n = t->dev.pc_n[lvl];
-  if (int r = evalFused(t, lvl, new_slot, e, (n + 255) / 256)) return r;
+  // eval_blocks of dmvio_hip_tracker_set_launch_shape is "workgroups per fused evaluation": this call is one (it used to ignore the knob, so that no grouping but one
+  // point per thread was reachable from here — the grouping the LM kernels never run at)
+  if (int r = evalFused(t, lvl, new_slot, e, t->eval_blocks_override > 0 ? t->eval_blocks_override : (n + 255) / 256)) return r;
   if (res6) res6FromSums(t->h_tot, res6);
   if (H && b) systemFromSums(t->h_tot, H, b);
   return 0;

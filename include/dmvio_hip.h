@@ -147,7 +147,8 @@ int dmvio_hip_tracker_get_pc(dmvio_hip_tracker* trk, int lvl, float* u, float* v
 int dmvio_hip_tracker_get_idepth_map(dmvio_hip_tracker* trk, int lvl, float* idepth_out, float* weightSums_out);
 /* One fused CoarseTracker::calcRes + calcGSSSE evaluation (CoarseTracker.cpp:361-517, 299-356) at refToNew.
  * res6 = {E, numTermsInE, flowT, 0, flowRT, saturatedRatio}; H (8x8 row-major) and b are the SCALE_*-scaled
- * system handed to IMUIntegration::computeCoarseUpdate in VIO mode (CoarseTracker.cpp:612-637). */
+ * system handed to IMUIntegration::computeCoarseUpdate in VIO mode (CoarseTracker.cpp:612-637).  Workgroups: eval_blocks of
+ * dmvio_hip_tracker_set_launch_shape, by default one per 256 template points of the level. */
 int dmvio_hip_tracker_eval(dmvio_hip_tracker* trk, int lvl, int new_slot, float new_exposure,
                            const double pose7_ref_to_new[7], const double aff_g2l_new[2], float cutoffTH,
                            double res6[6], double H[64], double b[8]);
