@@ -412,9 +412,35 @@ SIGNATURES = {
     "dmvio_hip_immature_remove_marked_batch": (ci, [vp, ci, C.POINTER(vp), c_i]),
 }
 
+# The same for the extension headers beside include/dmvio_hip.h, header by header, under the same rules: the table above is held to that header alone, entry for entry.
+EXTENSION_SIGNATURES = {
+    "dmvio_hip_init_resident.h": {
+        "dmvio_hip_initializer_set_resident": (ci, [vp, ci, c_f, c_f, c_f, c_f, c_u8, c_f, c_f, c_f, c_i, c_i]),
+        "dmvio_hip_initializer_resident_reset_unsnapped": (ci, [vp]),
+        "dmvio_hip_initializer_resident_reset_points": (ci, [vp, ci]),
+        "dmvio_hip_initializer_resident_do_step": (ci, [vp, cf, c_f]),
+        "dmvio_hip_initializer_resident_apply_step": (ci, [vp]),
+        "dmvio_hip_initializer_resident_opt_reg": (ci, [vp, cf]),
+        "dmvio_hip_initializer_resident_propagate_down": (ci, [vp, vp, cf, ci]),
+        "dmvio_hip_initializer_resident_propagate_up": (ci, [vp, vp, cf, ci]),
+        "dmvio_hip_initializer_resident_calc": (ci, [vp, ci, ci, ci, c_d, c_f, c_d, c_d, cf, cf, cf, cd, cd, ci, c_f, c_f, c_f, c_f, c_f, c_f]),
+        "dmvio_hip_initializer_resident_get_state": (ci, [vp, c_f, c_f, c_u8, c_f, c_f, c_f, c_u8, c_f, c_f, c_f, c_f]),
+        "dmvio_hip_initializer_resident_set_state": (ci, [vp, c_f, c_f, c_u8, c_f, c_f, c_f, c_u8, c_f, c_f, c_f, c_f, c_f]),
+        "dmvio_hip_initializer_resident_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
+    },
+}
+
+
+def all_signatures():
+    """every entry point of the library the package knows: the main header's table, then the extension headers'"""
+    out = dict(SIGNATURES)
+    for table in EXTENSION_SIGNATURES.values():
+        out.update(table)
+    return out
+
 
 def apply_signatures(L, allow_missing=False):
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in all_signatures().items():
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -8,28 +8,13 @@
 #include "internal.h"
 #include "lie_dev.h"
 #include "init_kernels.hpp"
+#include "init_handle.h"   // struct dmvio_hip_initializer and what the resident unit (capi_init_resident.hip) borrows of this one
 
 using namespace dmv;
 
-struct dmvio_hip_initializer {
-  dmvio_hip_ctx* ctx = nullptr;
-  int capacity = 0, n = 0;
-  // ONE device slab for the inputs and one for the per-point results, laid out per call for the n points of the level ([u | v | iR | outlierTH | energy(2) | idepth_new | isGood]
-  // and [energy_new(2) | maxstep | lastHessian_new | JbBuffer_new(10) | isGood_new]); each crosses PCIe as ONE copy from / into pinned staging memory — a calcResAndGS call of
-  // the initializer's LM loop is ~15 us of kernels, thirteen separate pageable copies cost ten times that
-  float *d_in = nullptr, *d_res = nullptr, *h_in = nullptr, *h_res = nullptr;
-  float *d_partials = nullptr, *d_out = nullptr, *h_out = nullptr;
-  bool upload_pending = false;
-  // where the point set of the last set_points lives on the device: d_in, or, after dmvio_hip_initializer_set_points_batch, this handle's part of that batch's slab (the
-  // layout of d_in; `owner` is that batch).  Both are only touched under the context's lock.
-  float* pts = nullptr;
-  dmvio_hip_initializer_batch* owner = nullptr;
-  std::vector<void*> allocs;
-};
-static inline size_t padn(int n) { return dmvPad(sizeof(float) * (size_t)n) / sizeof(float); }   // floats: every array of a slab starts on a 256-byte boundary
-enum { IN_FLOATS = 7, RES_FLOATS = 14 };   // per point, + one byte each (isGood / isGood_new) at the end of the slab
 enum { INIT_MAX_BLOCKS = 256 };
 static inline int initGrid(int n) { return std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256)); }
+static_assert((int)INIT_MAX_BLOCKS == (int)INIT_EVAL_MAX_BLOCKS, "the resident unit sizes its partials by INIT_EVAL_MAX_BLOCKS");
 
 // W windows per call.  The batch owns what a call needs besides the handles: a pinned slab and its device copy for the point sets of set_points_batch (the handles named there
 // read their points from it until their next set_points: `tenants`), a pinned slab and its device copy for the records and idepth_new arrays of a calc call, the partials, and
@@ -112,7 +97,7 @@ static float initAlpha(const Pose& T, int n, float alphaW, float alphaK, float* 
   return alphaOpt;
 }
 // the uniform inputs of the evaluation kernel
-static InitArgs initMakeArgs(const dmvio_hip_ctx* c, int lvl, const double Ki9[9], const float fxfycxcy_lvl[4], const Pose& T, const double aff_ab[2], int n, float alphaW,
+InitArgs initMakeArgs(const dmvio_hip_ctx* c, int lvl, const double Ki9[9], const float fxfycxcy_lvl[4], const Pose& T, const double aff_ab[2], int n, float alphaW,
                              float alphaK, float couplingWeight) {
   InitArgs A;
   double Rd[9];
@@ -154,7 +139,7 @@ static void initDeliverPoints(const float* h_res, int n, float* energy_new2, uns
   }
 }
 // the host tail of calcResAndGS, of the single and of the batched call: the alpha energy and alphaOpt (:497-535), the two upper triangles unpacked, then :582-613
-static void initHostTail(const Pose& T, int n, float alphaW, float alphaK, double priorY, double priorX, const float* sums /* IN_PART */, float* H_out64, float* b_out8,
+void initHostTail(const Pose& T, int n, float alphaW, float alphaK, double priorY, double priorX, const float* sums /* IN_PART */, float* H_out64, float* b_out8,
                          float* H_sc64, float* b_sc8, float res3[3]) {
   float alphaEnergy;
   const float alphaOpt = initAlpha(T, n, alphaW, alphaK, &alphaEnergy);
@@ -175,6 +160,16 @@ static void initHostTail(const Pose& T, int n, float alphaW, float alphaK, doubl
   H_out64[9] += priorY; b_out8[1] += priorY * T.t[1];
   H_out64[0] += priorX; b_out8[0] += priorX * T.t[0];
   res3[0] = sums[90]; res3[1] = alphaEnergy; res3[2] = (float)(2 * (size_t)n);   // accE[0].num: every point once per loop (:351-470, :503-516)
+}
+
+int initEvalGrid(int n) { return initGrid(n); }
+// the evaluation's two launches on the context's stream: the single call's grid, so the sums have the single call's bits wherever the points lie
+int initLaunchEval(dmvio_hip_ctx* c, int lvl, int first_slot, int new_slot, const InitPts& P, const InitArgs& A, float* d_partials, float* d_out) {
+  const int G = initGrid(P.n);
+  hipLaunchKernelGGL(k_init_partial, dim3(G), dim3(256), 0, c->stream, c->frames.levelPtr(first_slot, lvl), c->frames.levelPtr(new_slot, lvl), P, A, d_partials);
+  hipLaunchKernelGGL(k_init_final, dim3(1), dim3(128), 0, c->stream, d_partials, G, d_out);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 extern "C" {
@@ -207,6 +202,7 @@ void dmvio_hip_initializer_destroy(dmvio_hip_initializer* m) {
     initLeaveBatch(m, false);
   }
   hipStreamSynchronize(m->ctx->stream);
+  dmvInitResidentRelease(m);
   for (void* p : m->allocs) hipFree(p);
   if (m->h_out) hipHostFree(m->h_out);
   if (m->h_in) hipHostFree(m->h_in);
@@ -255,10 +251,7 @@ int dmvio_hip_initializer_calc_res_and_gs(dmvio_hip_initializer* m, int lvl, int
   memcpy(m->h_in + 6 * PN, idepth_new, sizeof(float) * n);
   HIPCHK(hipMemcpyAsync(m->pts + 6 * PN, m->h_in + 6 * PN, sizeof(float) * n, hipMemcpyHostToDevice, s));
   const InitPts P = initMakePts(n, m->pts, m->pts + 6 * PN, m->d_res);
-  const int G = initGrid(n);
-  hipLaunchKernelGGL(k_init_partial, dim3(G), dim3(256), 0, s, c->frames.levelPtr(first_slot, lvl), c->frames.levelPtr(new_slot, lvl), P, A, m->d_partials);
-  hipLaunchKernelGGL(k_init_final, dim3(1), dim3(128), 0, s, m->d_partials, G, m->d_out);
-  HIPCHK(hipGetLastError());
+  if (int r = initLaunchEval(c, lvl, first_slot, new_slot, P, A, m->d_partials, m->d_out)) return r;
   HIPCHK(hipMemcpyAsync(m->h_out, m->d_out, sizeof(float) * IN_PART, hipMemcpyDeviceToHost, s));
   const bool want = energy_new2 || isGood_new || maxstep || lastHessian_new || JbBuffer_new10;
   if (want) HIPCHK(hipMemcpyAsync(m->h_res, m->d_res, sizeof(float) * 14 * PN + n, hipMemcpyDeviceToHost, s));

@@ -7,26 +7,11 @@
 #pragma once
 #include "common.h"
 #include "interp.hpp"
+#include "init_types.hpp"
 
 namespace dmv {
 
 typedef float init_f32x4 __attribute__((ext_vector_type(4)));
-enum { IN_STRIDE = 66, IN_ROWS = 16, IN_WAVE_FLOATS = IN_ROWS * IN_STRIDE + 64, IN_PART = 96 };   // partial: 45 H + 45 SC + E + pad
-
-struct InitPts {   // struct Pnt (CoarseInitializer.h:44-83), structure of arrays
-  int n;
-  const float *u, *v, *idepth_new, *iR, *energy /* 2n */, *outlierTH;
-  const unsigned char* isGood;
-  float *energy_new /* 2n */, *maxstep, *lastHessian_new, *JbBuffer_new /* 10n */;
-  unsigned char* isGood_new;
-};
-struct InitArgs {
-  float RKi[9], t[3], aff0, aff1;   // (R * Ki).cast<float>(), translation, (exp(a), b)
-  float fxl, fyl, cxl, cyl;
-  int wl, hl;
-  float alphaOpt, couplingWeight, huberTH;
-};
-
 __constant__ int c_initPattern8[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
 
 // getInterpolatedElement31 on the intensity plane

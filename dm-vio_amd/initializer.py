@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._abi import InitializerPointsWindow, InitializerWindow, _Handle, _chk, _d, _f, _u8
+from ._abi import InitializerPointsWindow, InitializerWindow, _Handle, _chk, _d, _f, _i, _u8
 
 
 class CoarseInitializerHip(_Handle):
@@ -39,6 +39,82 @@ class CoarseInitializerHip(_Handle):
             for k in ("energy_new", "isGood_new", "maxstep", "lastHessian_new", "JbBuffer_new"):
                 del o[k]
         return o
+
+    # ---- the point set resident on the device and the per-point passes of trackFrame on it (include/dmvio_hip_init_resident.h).  For tests and tools.
+    STATE = (("idepth", 1, np.float32), ("iR", 1, np.float32), ("isGood", 1, np.uint8), ("energy", 2, np.float32), ("lastHessian", 1, np.float32),
+             ("idepth_new", 1, np.float32), ("isGood_new", 1, np.uint8), ("energy_new", 2, np.float32), ("lastHessian_new", 1, np.float32), ("maxstep", 1, np.float32),
+             ("JbBuffer", 10, np.float32))
+
+    def _res(self, name, *args):
+        return _chk(self.L, getattr(self.L, "dmvio_hip_initializer_" + name)(self.p, *args), "initializer_" + name)
+
+    def set_resident(self, pts):
+        """pts: u, v, idepth, iR, isGood, energy (n x 2), outlierTH, lastHessian, neighbours (n x 10 ints, -1 = none) and parent (ints; None on the top level)"""
+        f32 = lambda k: np.ascontiguousarray(pts[k], dtype=np.float32)
+        a = [f32(k) for k in ("u", "v", "idepth", "iR")]
+        good = np.ascontiguousarray(pts["isGood"], dtype=np.uint8)
+        b = [f32(k) for k in ("energy", "outlierTH", "lastHessian")]
+        nb = np.ascontiguousarray(pts["neighbours"], dtype=np.int32)
+        par = None if pts.get("parent") is None else np.ascontiguousarray(pts["parent"], dtype=np.int32)
+        n = len(a[0]) if "n" not in pts else int(pts["n"])
+        self._res("set_resident", n, *[_f(x) for x in a], _u8(good), *[_f(x) for x in b], _i(nb), None if par is None else _i(par))
+        self.n_resident = n
+
+    def reset_unsnapped(self):
+        self._res("resident_reset_unsnapped")
+
+    def reset_points(self, is_top_level):
+        self._res("resident_reset_points", int(bool(is_top_level)))
+
+    def do_step(self, lam, inc8):
+        self._res("resident_do_step", float(lam), _f(np.ascontiguousarray(inc8, dtype=np.float32)))
+
+    def apply_step(self):
+        self._res("resident_apply_step")
+
+    def opt_reg(self, regWeight=0.8):
+        self._res("resident_opt_reg", float(regWeight))
+
+    def propagate_down_to(self, lower, regWeight=0.8, snapped=False):
+        """propagateDown from this (the upper) level into `lower`"""
+        _chk(self.L, self.L.dmvio_hip_initializer_resident_propagate_down(self.p, lower.p, float(regWeight), int(bool(snapped))), "initializer_resident_propagate_down")
+
+    def propagate_up_to(self, upper, regWeight=0.8, snapped=False):
+        """propagateUp from this (the lower) level into `upper`"""
+        _chk(self.L, self.L.dmvio_hip_initializer_resident_propagate_up(self.p, upper.p, float(regWeight), int(bool(snapped))), "initializer_resident_propagate_up")
+
+    def calc_resident(self, lvl, first_slot, new_slot, Ki9, fxfycxcy_lvl, refToNew7, aff_ab, snapped, alphaW=150 * 150, alphaK=2.5 * 2.5, couplingWeight=1.0, priorY=0.0,
+                      priorX=0.0, ec=True):
+        """calcResAndGS on the resident points, then calcEC: H, b, Hsc, bsc, res3 and (ec=True) ec3"""
+        o = dict(H=np.zeros((8, 8), np.float32), b=np.zeros(8, np.float32), Hsc=np.zeros((8, 8), np.float32), bsc=np.zeros(8, np.float32), res3=np.zeros(3, np.float32))
+        if ec:
+            o["ec3"] = np.zeros(3, np.float32)
+        self._res("resident_calc", lvl, first_slot, new_slot, _d(np.ascontiguousarray(Ki9, dtype=np.float64)), _f(np.ascontiguousarray(fxfycxcy_lvl, dtype=np.float32)),
+                  _d(np.ascontiguousarray(refToNew7, dtype=np.float64)), _d(np.array(aff_ab, dtype=np.float64)), alphaW, alphaK, couplingWeight, priorY, priorX,
+                  int(bool(snapped)), _f(o["H"]), _f(o["b"]), _f(o["Hsc"]), _f(o["bsc"]), _f(o["res3"]), _f(o["ec3"]) if ec else None)
+        return o
+
+    def get_state(self, fields=None):
+        """the resident point set's fields (STATE), or those named"""
+        n = self.n_resident
+        o = {k: np.zeros((n, w) if w > 1 else n, t) for k, w, t in self.STATE if fields is None or k in fields}
+        self._res("resident_get_state", *[None if k not in o else (_u8(o[k]) if t is np.uint8 else _f(o[k])) for k, w, t in self.STATE])
+        return o
+
+    def set_state(self, **fields):
+        """replace the resident fields named (STATE's names, and JbBuffer_new)"""
+        keep = []
+        args = []
+        for k, w, t in self.STATE + (("JbBuffer_new", 10, np.float32),):
+            a = None if fields.get(k) is None else np.ascontiguousarray(fields[k], dtype=t)
+            keep.append(a)
+            args.append(None if a is None else (_u8(a) if t is np.uint8 else _f(a)))
+        assert not set(fields) - {k for k, w, t in self.STATE} - {"JbBuffer_new"}, sorted(fields)
+        self._res("resident_set_state", *args)
+
+    def resident_last_work(self):
+        """(kernel launches, uploads, downloads, stream waits) since the last calc_resident / get_state returned, those calls' own included"""
+        return self._outs("initializer_resident_last_work", C.c_int, 4)
 
 
 class InitializerBatchHip(_Handle):

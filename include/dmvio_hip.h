@@ -922,6 +922,7 @@ typedef struct dmvio_hip_initializer_window {          /* as dmvio_hip_initializ
 int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, int W, dmvio_hip_initializer_window* win);
 /* what the last calc call enqueued: kernel launches, host-to-device copies, device-to-host copies, stream waits */
 int dmvio_hip_initializer_batch_last_work(dmvio_hip_initializer_batch* b, int* launches, int* uploads, int* downloads, int* waits);
+/* The point set of a level resident on the device and the per-point passes of CoarseInitializer::trackFrame on it: dmvio_hip_init_resident.h, beside this header. */
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * Pixel selection: the candidates of a new keyframe, chosen on the device from the resident pyramid.
