@@ -428,6 +428,13 @@ EXTENSION_SIGNATURES = {
         "dmvio_hip_initializer_resident_set_state": (ci, [vp, c_f, c_f, c_u8, c_f, c_f, c_f, c_u8, c_f, c_f, c_f, c_f, c_f]),
         "dmvio_hip_initializer_resident_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
     },
+    "dmvio_hip_init_lm.h": {
+        "dmvio_hip_initializer_lm_control_host": (ci, [c_f, c_f, c_f, c_f, cf, ci, c_f, ci, c_d, c_d, c_f, c_d, c_d, c_d]),
+        "dmvio_hip_initializer_debug_lm_control": (ci, [vp, c_f, c_f, c_f, c_f, cf, ci, c_f, ci, c_d, c_d, c_f, c_d, c_d, c_d]),
+        "dmvio_hip_initializer_resident_track_level": (ci, [vp, ci, ci, ci, c_d, c_f, cf, cf, cf, cf, cd, cd, c_f, ci, ci, ci, c_d, c_d, c_f, c_i, ci, c_d, c_f, c_i]),
+        "dmvio_hip_initializer_resident_track_frame": (ci, [C.POINTER(vp), ci, ci, ci, c_d, c_f, cf, cf, cf, cf, cd, cd, c_f, ci, c_i, c_d, c_d, c_f, c_i, ci, c_d, c_f, c_i]),
+        "dmvio_hip_initializer_lm_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
+    },
 }
 
 

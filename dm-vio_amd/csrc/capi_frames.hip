@@ -92,6 +92,7 @@ void dmvio_hip_destroy(dmvio_hip_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);   // (null only in a handle whose creation failed)
   c->frames.release();
+  dmvInitLmRelease(c);
   hipFree(c->d_upload);
   c->bounce.release();
   hipFree(c->d_f3);

@@ -8,6 +8,7 @@
 #include "internal.h"
 #include "lie_dev.h"
 #include "init_kernels.hpp"
+#include "init_tail.hpp"
 #include "init_handle.h"   // struct dmvio_hip_initializer and what the resident unit (capi_init_resident.hip) borrows of this one
 
 using namespace dmv;
@@ -86,32 +87,10 @@ static std::string initOutsideMsg(const char* who, const dmvio_hip_initializer* 
            c->hl[lvl] - 3, lvl);
   return msg;
 }
-// alpha energy (CoarseInitializer.cpp:497-535); EAlpha.A is identically 0 in the reference.  Returns alphaOpt.
-static float initAlpha(const Pose& T, int n, float alphaW, float alphaK, float* alphaEnergy_out) {
-  const double tsq = T.t[0] * T.t[0] + T.t[1] * T.t[1] + T.t[2] * T.t[2];
-  float alphaEnergy = alphaW * (0.0f + tsq * n);
-  float alphaOpt;
-  if (alphaEnergy > alphaK * n) { alphaOpt = 0; alphaEnergy = alphaK * n; }
-  else alphaOpt = alphaW;
-  *alphaEnergy_out = alphaEnergy;
-  return alphaOpt;
-}
-// the uniform inputs of the evaluation kernel
+// the uniform inputs of the evaluation kernel (init_tail.hpp)
 InitArgs initMakeArgs(const dmvio_hip_ctx* c, int lvl, const double Ki9[9], const float fxfycxcy_lvl[4], const Pose& T, const double aff_ab[2], int n, float alphaW,
                              float alphaK, float couplingWeight) {
-  InitArgs A;
-  double Rd[9];
-  quatToR(T.q, Rd);
-  for (int r = 0; r < 3; r++)
-    for (int q = 0; q < 3; q++) A.RKi[r * 3 + q] = (float)(Rd[r * 3 + 0] * Ki9[q] + Rd[r * 3 + 1] * Ki9[3 + q] + Rd[r * 3 + 2] * Ki9[6 + q]);
-  for (int i = 0; i < 3; i++) A.t[i] = (float)T.t[i];
-  A.aff0 = (float)std::exp(aff_ab[0]); A.aff1 = (float)aff_ab[1];
-  A.fxl = fxfycxcy_lvl[0]; A.fyl = fxfycxcy_lvl[1]; A.cxl = fxfycxcy_lvl[2]; A.cyl = fxfycxcy_lvl[3];
-  A.wl = c->wl[lvl]; A.hl = c->hl[lvl];
-  A.couplingWeight = couplingWeight; A.huberTH = 9.0f;
-  float alphaEnergy;
-  A.alphaOpt = initAlpha(T, n, alphaW, alphaK, &alphaEnergy);
-  return A;
+  return initMakeArgsAt(c->wl[lvl], c->hl[lvl], Ki9, fxfycxcy_lvl, T, aff_ab, n, alphaW, alphaK, couplingWeight);
 }
 // where the kernel finds the n points of a handle and leaves their results (`res`: the layout of d_res)
 static InitPts initMakePts(int n, float* in, const float* idepth_new, float* res) {
@@ -138,28 +117,10 @@ static void initDeliverPoints(const float* h_res, int n, float* energy_new2, uns
     for (int i = 0; i < n; i++) if (acc[i]) lastHessian_new[i] = lh[i];
   }
 }
-// the host tail of calcResAndGS, of the single and of the batched call: the alpha energy and alphaOpt (:497-535), the two upper triangles unpacked, then :582-613
+// the host tail of calcResAndGS, of the single and of the batched call (init_tail.hpp)
 void initHostTail(const Pose& T, int n, float alphaW, float alphaK, double priorY, double priorX, const float* sums /* IN_PART */, float* H_out64, float* b_out8,
                          float* H_sc64, float* b_sc8, float res3[3]) {
-  float alphaEnergy;
-  const float alphaOpt = initAlpha(T, n, alphaW, alphaK, &alphaEnergy);
-  float M[2][9][9];
-  for (int w = 0; w < 2; w++) {
-    int k = 0;
-    for (int r = 0; r < 9; r++) for (int q = r; q < 9; q++) { M[w][r][q] = M[w][q][r] = sums[45 * w + k]; k++; }
-  }
-  for (int r = 0; r < 8; r++) {
-    for (int q = 0; q < 8; q++) { H_out64[r * 8 + q] = M[0][r][q]; H_sc64[r * 8 + q] = M[1][r][q]; }
-    b_out8[r] = M[0][r][8]; b_sc8[r] = M[1][r][8];
-  }
-  H_out64[0] += alphaOpt * n; H_out64[9] += alphaOpt * n; H_out64[18] += alphaOpt * n;
-  double lg[6];
-  poseLogHost(T, lg);
-  const float tlog[3] = {(float)lg[0], (float)lg[1], (float)lg[2]};
-  b_out8[0] += tlog[0] * alphaOpt * n; b_out8[1] += tlog[1] * alphaOpt * n; b_out8[2] += tlog[2] * alphaOpt * n;
-  H_out64[9] += priorY; b_out8[1] += priorY * T.t[1];
-  H_out64[0] += priorX; b_out8[0] += priorX * T.t[0];
-  res3[0] = sums[90]; res3[1] = alphaEnergy; res3[2] = (float)(2 * (size_t)n);   // accE[0].num: every point once per loop (:351-470, :503-516)
+  initTail(T, n, alphaW, alphaK, priorY, priorX, sums, H_out64, b_out8, H_sc64, b_sc8, res3, nullptr);
 }
 
 int initEvalGrid(int n) { return initGrid(n); }

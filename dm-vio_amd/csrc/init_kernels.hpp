@@ -12,7 +12,7 @@
 namespace dmv {
 
 typedef float init_f32x4 __attribute__((ext_vector_type(4)));
-__constant__ int c_initPattern8[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
+static __constant__ int c_initPattern8[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
 
 // getInterpolatedElement31 on the intensity plane
 __device__ __forceinline__ float initInterp31(const float* __restrict__ I, const float x, const float y, const int w) {
@@ -202,12 +202,12 @@ __device__ __forceinline__ void initPartialBody(const float* __restrict__ Iref, 
   }
 }
 
-__global__ void __launch_bounds__(256) k_init_partial(const float* __restrict__ Iref, const float* __restrict__ Inew, const InitPts P, const InitArgs A,
+inline __global__ void __launch_bounds__(256) k_init_partial(const float* __restrict__ Iref, const float* __restrict__ Inew, const InitPts P, const InitArgs A,
                                                        float* __restrict__ partials /* gridDim.x x IN_PART */) {
   initPartialBody(Iref, Inew, P, A, partials, blockIdx.x, gridDim.x);
 }
 
-__global__ void __launch_bounds__(128) k_init_final(const float* __restrict__ partials, const int G, float* __restrict__ out /* IN_PART */) {
+inline __global__ void __launch_bounds__(128) k_init_final(const float* __restrict__ partials, const int G, float* __restrict__ out /* IN_PART */) {
   if (threadIdx.x >= IN_PART) return;
   float s = 0.f;
   for (int g = 0; g < G; g++) s += partials[g * IN_PART + threadIdx.x];
@@ -233,7 +233,7 @@ template <class T> __device__ __forceinline__ T* initGl(T* const& member) {
 #pragma clang diagnostic pop
 
 // grid (max_y G_y, W): a workgroup beyond its window's own grid leaves at once; the grid-stride is the window's G, not gridDim.x
-__global__ void __launch_bounds__(256) k_init_partial_b(const InitWin* __restrict__ wins, float* __restrict__ partials) {
+inline __global__ void __launch_bounds__(256) k_init_partial_b(const InitWin* __restrict__ wins, float* __restrict__ partials) {
   const InitWin& V = wins[blockIdx.y];
   const int G = V.G;
   if ((int)blockIdx.x >= G) return;
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256) k_init_partial_b(const InitWin* __restric
 }
 
 // grid W: workgroup y sums window y's G_y partials in index order, as k_init_final
-__global__ void __launch_bounds__(128) k_init_final_b(const InitWin* __restrict__ wins, const float* __restrict__ partials, float* __restrict__ out) {
+inline __global__ void __launch_bounds__(128) k_init_final_b(const InitWin* __restrict__ wins, const float* __restrict__ partials, float* __restrict__ out) {
   if (threadIdx.x >= IN_PART) return;
   const InitWin& V = wins[blockIdx.x];
   const int G = V.G;

@@ -9,26 +9,30 @@ namespace dmv {
 struct InitInc8 { float v[8]; };
 
 // trackFrame's reset while the initializer has not snapped (:100-114)
-__global__ void __launch_bounds__(256) k_init_reset_unsnapped(const int n, float* __restrict__ iR, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
+inline __global__ void __launch_bounds__(256) k_init_reset_unsnapped(const int n, float* __restrict__ iR, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   iR[i] = 1.0f; idepth_new[i] = 1.0f; lastHessian[i] = 0.0f;
 }
 
+// The per-point bodies below (initResetPoint, initDoStepPoint, initApplyStepPoint) are shared with the device-resident LM loop (init_lm_kernels.hpp: k_init_lm), which runs
+// them for the same i from one workgroup.
+
 // resetPoints, the part every level takes (:895-898)
-__global__ void __launch_bounds__(256) k_init_reset_points(const int n, const float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ energy /* 2n */) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void initResetPoint(const int i, const float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ energy /* 2n */) {
   energy[2 * i] = 0.0f; energy[2 * i + 1] = 0.0f;
   idepth_new[i] = idepth[i];
 }
-
-// doStep (:919-947).  The 8-term dot is summed in index order, then added to Jb[8]: the order the compiled reference's Eigen stand-in takes.
-__global__ void __launch_bounds__(256) k_init_do_step(const int n, const float lambda, const InitInc8 inc, const unsigned char* __restrict__ isGood,
-                                                      const float* __restrict__ Jb /* 10n */, const float* __restrict__ maxstep_in, const float* __restrict__ idepth,
-                                                      float* __restrict__ idepth_new) {
+inline __global__ void __launch_bounds__(256) k_init_reset_points(const int n, const float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ energy /* 2n */) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  initResetPoint(i, idepth, idepth_new, energy);
+}
+
+// doStep (:919-947).  The 8-term dot is summed in index order, then added to Jb[8]: the order the compiled reference's Eigen stand-in takes.
+__device__ __forceinline__ void initDoStepPoint(const int i, const float lambda, const InitInc8& inc, const unsigned char* __restrict__ isGood,
+                                                const float* __restrict__ Jb /* 10n */, const float* __restrict__ maxstep_in, const float* __restrict__ idepth,
+                                                float* __restrict__ idepth_new) {
   if (!isGood[i]) return;
   const float* __restrict__ J = Jb + 10 * (size_t)i;
   float s = J[0] * inc.v[0];
@@ -45,19 +49,32 @@ __global__ void __launch_bounds__(256) k_init_do_step(const int n, const float l
   if (newIdepth > 50) newIdepth = 50;
   idepth_new[i] = newIdepth;
 }
-
-// applyStep (:948-963); the swap of the two JbBuffers (:964) is a pointer swap in the handle
-__global__ void __launch_bounds__(256) k_init_apply_step(const int n, unsigned char* __restrict__ isGood, const unsigned char* __restrict__ isGood_new,
-                                                         float* __restrict__ idepth, float* __restrict__ idepth_new, const float* __restrict__ iR,
-                                                         float* __restrict__ energy, const float* __restrict__ energy_new, float* __restrict__ lastHessian,
-                                                         const float* __restrict__ lastHessian_new) {
+inline __global__ void __launch_bounds__(256) k_init_do_step(const int n, const float lambda, const InitInc8 inc, const unsigned char* __restrict__ isGood,
+                                                      const float* __restrict__ Jb /* 10n */, const float* __restrict__ maxstep_in, const float* __restrict__ idepth,
+                                                      float* __restrict__ idepth_new) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  initDoStepPoint(i, lambda, inc, isGood, Jb, maxstep_in, idepth, idepth_new);
+}
+
+// applyStep (:948-963); the swap of the two JbBuffers (:964) is a pointer swap in the handle
+__device__ __forceinline__ void initApplyStepPoint(const int i, unsigned char* __restrict__ isGood, const unsigned char* __restrict__ isGood_new,
+                                                   float* __restrict__ idepth, float* __restrict__ idepth_new, const float* __restrict__ iR,
+                                                   float* __restrict__ energy, const float* __restrict__ energy_new, float* __restrict__ lastHessian,
+                                                   const float* __restrict__ lastHessian_new) {
   if (!isGood[i]) { const float r = iR[i]; idepth[i] = r; idepth_new[i] = r; return; }
   energy[2 * i] = energy_new[2 * i]; energy[2 * i + 1] = energy_new[2 * i + 1];
   isGood[i] = isGood_new[i];
   idepth[i] = idepth_new[i];
   lastHessian[i] = lastHessian_new[i];
+}
+inline __global__ void __launch_bounds__(256) k_init_apply_step(const int n, unsigned char* __restrict__ isGood, const unsigned char* __restrict__ isGood_new,
+                                                         float* __restrict__ idepth, float* __restrict__ idepth_new, const float* __restrict__ iR,
+                                                         float* __restrict__ energy, const float* __restrict__ energy_new, float* __restrict__ lastHessian,
+                                                         const float* __restrict__ lastHessian_new) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  initApplyStepPoint(i, isGood, isGood_new, idepth, idepth_new, iR, energy, energy_new, lastHessian, lastHessian_new);
 }
 
 // ---- the ordered sweeps.  ONE workgroup of one wavefront walks the levels of the static schedule (init_resident_host.hpp); iR and isGood of the whole point set live in
@@ -116,7 +133,7 @@ struct InitSweepResetTop {   // resetPoints on the top level: a point that is no
 };
 
 template <class BODY>
-__global__ void __launch_bounds__(64) k_init_sweep(const int n, const int levels, const int* __restrict__ level_begin, const int* __restrict__ order,
+inline __global__ void __launch_bounds__(64) k_init_sweep(const int n, const int levels, const int* __restrict__ level_begin, const int* __restrict__ order,
                                                    const int* __restrict__ neighbours /* 10n */, float* __restrict__ iR, unsigned char* __restrict__ isGood, const BODY body) {
   extern __shared__ float s_sweep[];
   float* __restrict__ s_iR = s_sweep;
@@ -142,7 +159,7 @@ __global__ void __launch_bounds__(64) k_init_sweep(const int n, const int levels
 
 // propagateUp (:713-744): one thread per parent walks its children in ascending index, as the reference's loop over the lower level meets them.
 // n_listed: the parents child_begin covers (1 + the largest parent index of the lower level); a parent beyond has no child.
-__global__ void __launch_bounds__(256) k_init_propagate_up(const int n_dst, const int n_listed, const int* __restrict__ child_begin, const int* __restrict__ children,
+inline __global__ void __launch_bounds__(256) k_init_propagate_up(const int n_dst, const int n_listed, const int* __restrict__ child_begin, const int* __restrict__ children,
                                                            const unsigned char* __restrict__ src_good, const float* __restrict__ src_iR, const float* __restrict__ src_lastHessian,
                                                            float* __restrict__ iR, float* __restrict__ idepth, unsigned char* __restrict__ isGood) {
   const int p = blockIdx.x * 256 + threadIdx.x;
@@ -168,7 +185,7 @@ __global__ void __launch_bounds__(256) k_init_propagate_up(const int n_dst, cons
 }
 
 // propagateDown (:758-775): one thread per point of the lower level
-__global__ void __launch_bounds__(256) k_init_propagate_down(const int n, const int* __restrict__ parent, const unsigned char* __restrict__ par_good,
+inline __global__ void __launch_bounds__(256) k_init_propagate_down(const int n, const int* __restrict__ parent, const unsigned char* __restrict__ par_good,
                                                              const float* __restrict__ par_iR, const float* __restrict__ par_lastHessian, unsigned char* __restrict__ isGood,
                                                              float* __restrict__ iR, float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -198,11 +215,12 @@ __device__ __forceinline__ float initWaveSum(float x) {
   for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
   return x;
 }
-__global__ void __launch_bounds__(256) k_init_ec(const int n, const unsigned char* __restrict__ isGood_new, const float* __restrict__ idepth, const float* __restrict__ idepth_new,
-                                                 const float* __restrict__ iR, float* __restrict__ partials /* gridDim.x x IN_EC */) {
+// workgroup bx of the G (of 256 threads) that serve the point set; shared with k_init_lm, which runs bx = 0 .. G - 1 one after the other
+__device__ __forceinline__ void initEcPartialBody(const int n, const unsigned char* __restrict__ isGood_new, const float* __restrict__ idepth, const float* __restrict__ idepth_new,
+                                                  const float* __restrict__ iR, float* __restrict__ partials /* G x IN_EC */, const int bx, const int G) {
   __shared__ float s_part[4][3];
   float a = 0, b = 0, c = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+  for (int i = bx * 256 + threadIdx.x; i < n; i += G * 256) {
     if (!isGood_new[i]) continue;
     const float r = iR[i];
     const float rOld = idepth[i] - r, rNew = idepth_new[i] - r;
@@ -215,10 +233,15 @@ __global__ void __launch_bounds__(256) k_init_ec(const int n, const unsigned cha
   if (threadIdx.x < 3) {
     float s = s_part[0][threadIdx.x];
     for (int w = 1; w < 4; w++) s += s_part[w][threadIdx.x];
-    partials[blockIdx.x * IN_EC + threadIdx.x] = s;
+    partials[bx * IN_EC + threadIdx.x] = s;
   }
 }
-__global__ void __launch_bounds__(64) k_init_ec_final(const int G, const float* __restrict__ partials, float* __restrict__ out3) {
+inline __global__ void __launch_bounds__(256) k_init_ec(const int n, const unsigned char* __restrict__ isGood_new, const float* __restrict__ idepth, const float* __restrict__ idepth_new,
+                                                 const float* __restrict__ iR, float* __restrict__ partials /* gridDim.x x IN_EC */) {
+  initEcPartialBody(n, isGood_new, idepth, idepth_new, iR, partials, blockIdx.x, gridDim.x);
+}
+// one wavefront (threadIdx.x < 64 of the caller); lane 0 stores
+__device__ __forceinline__ void initEcFinalBody(const int G, const float* __restrict__ partials, float* __restrict__ out3) {
   float s[3] = {0, 0, 0};
   bool first = true;
   for (int g = threadIdx.x; g < G; g += 64) {
@@ -230,10 +253,13 @@ __global__ void __launch_bounds__(64) k_init_ec_final(const int G, const float* 
   for (int k = 0; k < 3; k++) s[k] = initWaveSum(s[k]);
   if (threadIdx.x == 0) { out3[0] = s[0]; out3[1] = s[1]; out3[2] = s[2]; }
 }
+inline __global__ void __launch_bounds__(64) k_init_ec_final(const int G, const float* __restrict__ partials, float* __restrict__ out3) {
+  initEcFinalBody(G, partials, out3);
+}
 
 // good points whose pattern would leave the level (the evaluation reads (u + dx, v + dy), dx, dy in [-2, 2], and one pixel right / below, without a test): the count the
 // resident evaluation's range check is made from where the host copy of (u, v) holds such a point at all
-__global__ void __launch_bounds__(256) k_init_count_outside(const int n, const unsigned char* __restrict__ isGood, const float* __restrict__ u, const float* __restrict__ v,
+inline __global__ void __launch_bounds__(256) k_init_count_outside(const int n, const unsigned char* __restrict__ isGood, const float* __restrict__ u, const float* __restrict__ v,
                                                             const float umax, const float vmax, int* __restrict__ count) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool out = i < n && isGood[i] && !(u[i] >= 2.0f && u[i] < umax && v[i] >= 2.0f && v[i] < vmax);

@@ -119,8 +119,10 @@ struct dmvio_hip_ctx {
   int raw_batch_kernel = 1;             // dmvio_hip_set_raw_batch_kernel: 1 = the wave-autonomous register build where the geometry allows (<= 4 levels, sides % 8 == 0), 0 = the LDS-tile build
   int raw_batch_layout = 0;              // dmvio_hip_set_raw_batch_layout: what dmvio_hip_frames_from_raw_device_batch writes (1 = tiles where the image size allows)
   DmvBounce bounce;             // caller-owned arrays cross PCIe through here (used under `mu`)
+  struct DmvInitLmCtx* init_lm = nullptr;   // the device record of the initializer's LM loop and its problem table (capi_init_lm.hip), made on first use; under `mu`
   std::mutex mu;
 };
+void dmvInitLmRelease(dmvio_hip_ctx* c);   // (capi_init_lm.hip, for dmvio_hip_destroy: the stream has been waited for)
 
 // Level 0 of `slot` back into the row-major layout if the batched raw-image build stored it in 8x4 tiles (FrameStore::tiled0): called by every consumer of a level-0 plane
 // other than the coarse tracker's batch kernel (reference template, single-frame tracking, window optimiser, immature points, initializer, downloads) before it reads the

@@ -205,8 +205,9 @@ DMV_HD void poseTo7(const Pose& T, double p[7]) {
   p[3] = T.q.x; p[4] = T.q.y; p[5] = T.q.z; p[6] = T.q.w;
 }
 
-// log of an SE3 element (se3.hpp:560-586, so3.hpp:497-540) — host only (nullspace construction)
-inline void poseLogHost(const Pose& T, double out[6]) {
+// log of an SE3 element (se3.hpp:560-586, so3.hpp:497-540).  The host calls the C library's atan / tan like the reference's Sophus; device code (the initializer's LM loop,
+// which needs the translation part for its alpha prior) the device library's, which may differ from them in the last place.
+DMV_HD void poseLog(const Pose& T, double out[6]) {
   const double n2 = T.q.x * T.q.x + T.q.y * T.q.y + T.q.z * T.q.z, n = sqrt(n2), w = T.q.w;
   double f;
   if (n < 1e-10) f = 2.0 / w - 2.0 * n2 / (w * w * w);
@@ -224,6 +225,7 @@ inline void poseLogHost(const Pose& T, double out[6]) {
     out[i] = s;
   }
 }
+inline void poseLogHost(const Pose& T, double out[6]) { poseLog(T, out); }
 
 // AffLight::fromToVecExposure (src/dso/util/NumType.h:174-186)
 DMV_HD void affFromTo(float exposureF, float exposureT, double aF, double bF, double aT, double bT, double out[2]) {
@@ -234,58 +236,69 @@ DMV_HD void affFromTo(float exposureF, float exposureT, double aF, double bF, do
 }
 
 // Symmetric n x n (n <= NMAX) solve by LDL^T with diagonal pivoting (largest |d_kk| first), the
-// decomposition CoarseTracker.cpp:639 uses through Eigen.  m: row-major, leading dimension ld, destroyed.
-template <int NMAX>
-DMV_HD void ldltSolveInPlace(double* m, int ld, double* d /*rhs in, x out*/, int n) {
-  int tr[NMAX];
-  double temp[NMAX];
+// decomposition CoarseTracker.cpp:639 uses through Eigen.  m: row-major, leading dimension ld, destroyed; only its lower triangle is read.
+// S: double (the tracker, the window optimiser) or float (the initializer's Mat88f / Mat66f solve, CoarseInitializer.cpp:173-177): the same operations in the scalar's
+// own precision.
+DMV_HD double ldltAbs(const double x) { return fabs(x); }
+DMV_HD float ldltAbs(const float x) { return fabsf(x); }
+DMV_HD double ldltTiny(const double) { return 2.2250738585072014e-308; }   // the smallest normal number of the scalar (std::numeric_limits<S>::min())
+DMV_HD float ldltTiny(const float) { return 1.17549435e-38f; }
+// tr, temp: n entries of workspace each (a device caller keeps them, like m and d, where dynamic indexing costs no scratch memory: in LDS)
+template <class S>
+DMV_HD void ldltSolveInPlaceWs(S* m, int ld, S* d /*rhs in, x out*/, int n, int* tr, S* temp) {
   bool zero = false;
   for (int k = 0; k < n; k++) {
     int big = k;
-    double bigv = fabs(m[k * ld + k]);
+    S bigv = ldltAbs(m[k * ld + k]);
     for (int i = k + 1; i < n; i++) {
-      const double v = fabs(m[i * ld + i]);
+      const S v = ldltAbs(m[i * ld + i]);
       if (v > bigv) { bigv = v; big = i; }
     }
     tr[k] = big;
     if (k != big) {
-      for (int c = 0; c < k; c++) { double s = m[k * ld + c]; m[k * ld + c] = m[big * ld + c]; m[big * ld + c] = s; }
-      for (int r = big + 1; r < n; r++) { double s = m[r * ld + k]; m[r * ld + k] = m[r * ld + big]; m[r * ld + big] = s; }
-      { double s = m[k * ld + k]; m[k * ld + k] = m[big * ld + big]; m[big * ld + big] = s; }
-      for (int i = k + 1; i < big; i++) { double s = m[i * ld + k]; m[i * ld + k] = m[big * ld + i]; m[big * ld + i] = s; }
+      for (int c = 0; c < k; c++) { S s = m[k * ld + c]; m[k * ld + c] = m[big * ld + c]; m[big * ld + c] = s; }
+      for (int r = big + 1; r < n; r++) { S s = m[r * ld + k]; m[r * ld + k] = m[r * ld + big]; m[r * ld + big] = s; }
+      { S s = m[k * ld + k]; m[k * ld + k] = m[big * ld + big]; m[big * ld + big] = s; }
+      for (int i = k + 1; i < big; i++) { S s = m[i * ld + k]; m[i * ld + k] = m[big * ld + i]; m[big * ld + i] = s; }
     }
     if (k > 0) {
       for (int j = 0; j < k; j++) temp[j] = m[j * ld + j] * m[k * ld + j];
-      double s = 0;
+      S s = 0;
       for (int j = 0; j < k; j++) s += m[k * ld + j] * temp[j];
       m[k * ld + k] -= s;
       for (int r = k + 1; r < n; r++) {
-        double s2 = 0;
+        S s2 = 0;
         for (int j = 0; j < k; j++) s2 += m[r * ld + j] * temp[j];
         m[r * ld + k] -= s2;
       }
     }
-    const double akk = m[k * ld + k];
-    const bool ok = fabs(akk) > 0;
+    const S akk = m[k * ld + k];
+    const bool ok = ldltAbs(akk) > 0;
     if (k == 0 && !ok) { zero = true; break; }
     if (ok) for (int r = k + 1; r < n; r++) m[r * ld + k] /= akk;
   }
   if (zero) { for (int i = 0; i < n; i++) d[i] = 0; return; }
-  for (int k = 0; k < n; k++) if (tr[k] != k) { double s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
+  for (int k = 0; k < n; k++) if (tr[k] != k) { S s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
   for (int i = 0; i < n; i++) {
-    double s = d[i];
+    S s = d[i];
     for (int j = 0; j < i; j++) s -= m[i * ld + j] * d[j];
     d[i] = s;
   }
   for (int i = 0; i < n; i++) {
-    if (fabs(m[i * ld + i]) > 2.2250738585072014e-308) d[i] /= m[i * ld + i]; else d[i] = 0;
+    if (ldltAbs(m[i * ld + i]) > ldltTiny(S(0))) d[i] /= m[i * ld + i]; else d[i] = 0;
   }
   for (int i = n - 1; i >= 0; i--) {
-    double s = d[i];
+    S s = d[i];
     for (int j = i + 1; j < n; j++) s -= m[j * ld + i] * d[j];
     d[i] = s;
   }
-  for (int k = n - 1; k >= 0; k--) if (tr[k] != k) { double s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
+  for (int k = n - 1; k >= 0; k--) if (tr[k] != k) { S s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
+}
+template <int NMAX, class S>
+DMV_HD void ldltSolveInPlace(S* m, int ld, S* d /*rhs in, x out*/, int n) {
+  int tr[NMAX];
+  S temp[NMAX];
+  ldltSolveInPlaceWs(m, ld, d, n, tr, temp);
 }
 
 }  // namespace dmv

@@ -5,6 +5,91 @@ import numpy as np
 from ._abi import InitializerPointsWindow, InitializerWindow, _Handle, _chk, _d, _f, _i, _u8
 
 
+WM8 = (1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 10.0, 1000.0)   # CoarseInitializer's wM: SCALE_XI_ROT x 3, SCALE_XI_TRANS x 3, SCALE_A, SCALE_B
+LM_TRACE_D, LM_TRACE_F = 20, 176                       # doubles and floats per trace record (include/dmvio_hip_init_lm.h)
+
+
+def _state10(state):
+    pose7, aff, snapped = state
+    return np.concatenate([np.asarray(pose7, np.float64).reshape(7), np.asarray(aff, np.float64).reshape(2), [1.0 if snapped else 0.0]])
+
+
+def trace_records(trace_d, trace_f):
+    """the trace arrays of track_level / track_frame as one dict per accept test, by the header's indices"""
+    out = []
+    for d, f in zip(trace_d, trace_f):
+        out.append(dict(incNorm=d[0], pose7=d[1:8].copy(), aff=d[8:10].copy(), pose7_new=d[10:17].copy(), aff_new=d[17:19].copy(), lvl=int(f[0]), iteration=int(f[1]),
+                        lam=f[2], accept=bool(f[3]), snapped=bool(f[4]), inc=f[5:13].copy(), resOld=f[13:16].copy(), resNew=f[16:19].copy(), ec3=f[19:22].copy(),
+                        eOld=f[22], eNew=f[23], tlog=f[24:27].copy(), fails=int(f[27]), lam_after=f[28], quit=bool(f[29]), H=f[32:96].reshape(8, 8).copy(),
+                        b=f[96:104].copy(), Hsc=f[104:168].reshape(8, 8).copy(), bsc=f[168:176].copy()))
+    return out
+
+
+class _LmOut:
+    """the output arrays of one track_level / track_frame call and the tail of its argument list"""
+
+    def __init__(self, n_levels, trace_capacity, wait):
+        self.wait = wait
+        self.state = np.zeros(10, np.float64)
+        self.res3 = np.zeros((n_levels, 3), np.float32)
+        self.iterations = np.zeros(n_levels, np.int32)
+        self.cap = int(trace_capacity)
+        self.td = np.zeros((max(self.cap, 1), LM_TRACE_D), np.float64)
+        self.tf = np.zeros((max(self.cap, 1), LM_TRACE_F), np.float32)
+        self.nrec = C.c_int(0)
+
+    def args(self, state):
+        self.state_in = None if state is None else _state10(state)
+        tr = self.cap > 0
+        return [None if self.state_in is None else _d(self.state_in), _d(self.state) if self.wait else None, _f(self.res3), _i(self.iterations), self.cap,
+                _d(self.td) if tr else None, _f(self.tf) if tr else None, C.byref(self.nrec) if tr else None]
+
+    def result(self):
+        if not self.wait:
+            return None
+        o = dict(pose7=self.state[:7].copy(), aff=self.state[7:9].copy(), snapped=bool(self.state[9]), res3=self.res3, iterations=self.iterations)
+        if self.cap > 0:
+            o["trace"] = trace_records(self.td[:self.nrec.value], self.tf[:self.nrec.value])
+        return o
+
+
+def lm_control_host(L, H, b, Hsc, bsc, lam, wh, pose7, aff, fix_affine=True, wM8=WM8, ctx=None):
+    """the control step of trackFrame's LM loop (CoarseInitializer.cpp:159-185) by the library: on the host, or (ctx given) by the same function on the device
+    -> (inc8, incNorm, pose7_new, aff_new)"""
+    a = [np.ascontiguousarray(x, dtype=np.float32) for x in (H, b, Hsc, bsc)]
+    w = np.ascontiguousarray(wM8, dtype=np.float32)
+    p, ab = np.ascontiguousarray(pose7, dtype=np.float64), np.ascontiguousarray(aff, dtype=np.float64)
+    inc, norm, p2, ab2 = np.zeros(8, np.float32), C.c_double(0), np.zeros(7, np.float64), np.zeros(2, np.float64)
+    args = [_f(a[0]), _f(a[1]), _f(a[2]), _f(a[3]), float(lam), int(wh), _f(w), int(bool(fix_affine)), _d(p), _d(ab), _f(inc), C.byref(norm), _d(p2), _d(ab2)]
+    if ctx is None:
+        _chk(L, L.dmvio_hip_initializer_lm_control_host(*args), "initializer_lm_control_host")
+    else:
+        _chk(L, L.dmvio_hip_initializer_debug_lm_control(ctx.p, *args), "initializer_debug_lm_control")
+    return inc, norm.value, p2, ab2
+
+
+def track_frame(handles, first_slot, new_slot, Ki9_levels, fxfycxcy_levels, max_iterations, state=None, fix_affine=True, wM8=WM8, alphaW=150 * 150, alphaK=2.5 * 2.5,
+                regWeight=0.8, couplingWeight=1.0, priorY=0.0, priorX=0.0, trace=False, wait=True):
+    """trackFrame over the resident point sets of handles[0 .. n_levels - 1] (level k = handles[k]) on the device (dmvio_hip_initializer_resident_track_frame); state as
+    CoarseInitializerHip.track_level -> dict(pose7, aff, snapped, res3 (n_levels x 3), iterations (n_levels)[, trace]); wait=False only enqueues and returns None"""
+    L = handles[0].L
+    n = len(handles)
+    arr = (C.c_void_p * n)(*[h.p for h in handles])
+    mi = np.ascontiguousarray(max_iterations, dtype=np.int32)
+    o = _LmOut(n, int(mi.sum()) + n if trace else 0, wait)
+    _chk(L, L.dmvio_hip_initializer_resident_track_frame(
+        arr, n, int(first_slot), int(new_slot), _d(np.ascontiguousarray(Ki9_levels, dtype=np.float64)), _f(np.ascontiguousarray(fxfycxcy_levels, dtype=np.float32)), alphaW, alphaK,
+        regWeight, couplingWeight, priorY, priorX, _f(np.ascontiguousarray(wM8, dtype=np.float32)), int(bool(fix_affine)), _i(mi), *o.args(state)), "initializer_resident_track_frame")
+    return o.result()
+
+
+def lm_last_work(ctx):
+    """(kernel launches, uploads, downloads, stream waits) of the context's last track_level / track_frame"""
+    out = [C.c_int() for _ in range(4)]
+    _chk(ctx.L, ctx.L.dmvio_hip_initializer_lm_last_work(ctx.p, *[C.byref(x) for x in out]), "initializer_lm_last_work")
+    return tuple(x.value for x in out)
+
+
 class CoarseInitializerHip(_Handle):
     """Mirror of CoarseInitializer's hot function calcResAndGS (CoarseInitializer.cpp:331-624) for one pyramid level's point set."""
     _destroy = "dmvio_hip_initializer_destroy"
@@ -115,6 +200,17 @@ class CoarseInitializerHip(_Handle):
     def resident_last_work(self):
         """(kernel launches, uploads, downloads, stream waits) since the last calc_resident / get_state returned, those calls' own included"""
         return self._outs("initializer_resident_last_work", C.c_int, 4)
+
+    def track_level(self, lvl, first_slot, new_slot, Ki9, fxfycxcy_lvl, state=None, max_iterations=5, is_top_level=False, fix_affine=True, wM8=WM8, alphaW=150 * 150,
+                    alphaK=2.5 * 2.5, regWeight=0.8, couplingWeight=1.0, priorY=0.0, priorX=0.0, trace=False, wait=True):
+        """one level of trackFrame's LM loop on the device (include/dmvio_hip_init_lm.h); state: (pose7, (a, b), snapped) or None to continue from the context's record;
+        wait=False only enqueues and returns None -> dict(pose7, aff, snapped, res3, iterations[, trace])"""
+        o = _LmOut(1, max_iterations + 1 if trace else 0, wait)
+        _chk(self.L, self.L.dmvio_hip_initializer_resident_track_level(
+            self.p, int(lvl), int(first_slot), int(new_slot), _d(np.ascontiguousarray(Ki9, dtype=np.float64)), _f(np.ascontiguousarray(fxfycxcy_lvl, dtype=np.float32)),
+            alphaW, alphaK, regWeight, couplingWeight, priorY, priorX, _f(np.ascontiguousarray(wM8, dtype=np.float32)), int(bool(fix_affine)), int(max_iterations),
+            int(bool(is_top_level)), *o.args(state)), "initializer_resident_track_level")
+        return o.result()
 
 
 class InitializerBatchHip(_Handle):
