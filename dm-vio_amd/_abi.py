@@ -150,6 +150,14 @@ class InitializerWindow(C.Structure):
                 ("maxstep", c_f), ("lastHessian_new", c_f), ("JbBuffer_new10", c_f)]
 
 
+class InitializerLmWindow(C.Structure):
+    """dmvio_hip_initializer_lm_window (include/dmvio_hip_init_lm_batch.h): one window of dmvio_hip_initializer_resident_track_frame_batch."""
+    _fields_ = [("levels", C.POINTER(vp)), ("n_levels", ci), ("first_slot", ci), ("new_slot", ci), ("Ki9_levels", c_d), ("fxfycxcy_levels", c_f),
+                ("alphaW", cf), ("alphaK", cf), ("regWeight", cf), ("couplingWeight", cf), ("priorY", cd), ("priorX", cd), ("wM8", c_f), ("fix_affine", ci),
+                ("max_iterations", c_i), ("state_slot", ci), ("state_in10", c_d), ("state_out10", c_d), ("res3_levels", c_f), ("iterations_levels", c_i),
+                ("trace_capacity", ci), ("trace_d", c_d), ("trace_f", c_f), ("trace_records", c_i), ("snapped", ci)]
+
+
 # every `typedef struct` of the header that has a body -> its mirror
 MIRRORS = {
     "dmvio_hip_tracker_settings": TrackerSettings, "dmvio_hip_coarse_callbacks": CoarseCallbacks, "dmvio_hip_set_ref_window": SetRefWindow,
@@ -435,6 +443,16 @@ EXTENSION_SIGNATURES = {
         "dmvio_hip_initializer_resident_track_frame": (ci, [C.POINTER(vp), ci, ci, ci, c_d, c_f, cf, cf, cf, cf, cd, cd, c_f, ci, c_i, c_d, c_d, c_f, c_i, ci, c_d, c_f, c_i]),
         "dmvio_hip_initializer_lm_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
     },
+    "dmvio_hip_init_lm_batch.h": {
+        "dmvio_hip_initializer_lm_batch_create": (vp, [vp, ci]),
+        "dmvio_hip_initializer_lm_batch_destroy": (None, [vp]),
+        "dmvio_hip_initializer_resident_track_frame_batch": (ci, [vp, ci, C.POINTER(InitializerLmWindow)]),
+        "dmvio_hip_initializer_lm_batch_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
+    },
+}
+# the structs of the extension headers -> their mirrors, header by header (MIRRORS is held to include/dmvio_hip.h alone)
+EXTENSION_MIRRORS = {
+    "dmvio_hip_init_lm_batch.h": {"dmvio_hip_initializer_lm_window": InitializerLmWindow},
 }
 
 

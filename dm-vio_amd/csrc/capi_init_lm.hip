@@ -7,9 +7,7 @@
 #include <cstdio>
 #include <algorithm>
 #include "../../include/dmvio_hip_init_lm.h"
-#include "init_handle.h"
-#include "init_resident_state.h"
-#include "init_lm_kernels.hpp"
+#include "init_lm_host.hpp"   // the handle, the resident state, the kernels; a call's levels, lmCheck and lmFillProb
 
 using namespace dmv;
 
@@ -61,80 +59,8 @@ static int lmCtx(dmvio_hip_ctx* c, DmvInitLmCtx** out) {
   return 0;
 }
 
-struct LmLevel { dmvio_hip_initializer* m; int lvl, max_iterations, is_top_level; const double* Ki9; const float* K4; };
-struct LmCommon {
-  int first_slot, new_slot, fix_affine;
-  float alphaW, alphaK, regWeight, couplingWeight;
-  double priorY, priorX;
-  const float* wM8;
-};
-
-// every refusal of a call, in the header's order; P levels in execution order (the top level first)
-// first_outside (may be NULL): for a level whose loop revives no point — a lone track_level that is not the top level — a point outside the margin is no refusal here;
-// its index comes back and the caller counts the GOOD points outside on the device, as dmvio_hip_initializer_resident_calc does.  Everywhere else (the top level's
-// resetPoints and a frame's propagateDown turn bad points into good ones inside the call) any point outside refuses.
-static int lmCheck(const char* who, dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, const LmCommon& K, const double* state_in10, int trace_capacity,
-                   const double* trace_d, const float* trace_f, const int* trace_records, int* first_outside) {
-  if (first_outside) *first_outside = -1;
-  char msg[320];
-  auto no = [&](const char* what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return failmsg(msg); };
-  if (!K.wM8) return no("null wM8");
-  if (K.first_slot < 0 || K.first_slot >= c->n_slots || K.new_slot < 0 || K.new_slot >= c->n_slots) return no("slot out of range");
-  int tests = 0;
-  for (int p = 0; p < P; p++) {
-    const LmLevel& v = lv[p];
-    if (!v.Ki9 || !v.K4) return no("null argument");
-    if (!v.m->resident || !v.m->resident->live) { snprintf(msg, sizeof(msg), "%s: the handle of level %d has no resident point set (dmvio_hip_initializer_set_resident)", who, v.lvl); return failmsg(msg); }
-    if (v.lvl < 0 || v.lvl >= c->levels) return no("level out of range");
-    if (v.max_iterations < 0 || v.max_iterations > INIT_LM_MAX_ITER) { snprintf(msg, sizeof(msg), "%s: max_iterations = %d outside [0, %d]", who, v.max_iterations, (int)INIT_LM_MAX_ITER); return failmsg(msg); }
-    tests += v.max_iterations + 1;
-    const DmvInitResident* R = v.m->resident;
-    if (p > 0) {   // lv[p - 1] is the level above
-      const DmvInitResident* U = lv[p - 1].m->resident;
-      if (!R->has_parent) { snprintf(msg, sizeof(msg), "%s: level %d was set without a parent table", who, v.lvl); return failmsg(msg); }
-      if (R->max_parent >= U->n) { snprintf(msg, sizeof(msg), "%s: level %d names parent %d, level %d has %d points", who, v.lvl, R->max_parent, lv[p - 1].lvl, U->n); return failmsg(msg); }
-    }
-    const float *hu = R->st.host<float>(R->o_u), *hv = R->st.host<float>(R->o_v);
-    const float umax = (float)(c->wl[v.lvl] - 3), vmax = (float)(c->hl[v.lvl] - 3);
-    for (int i = 0; i < R->n; i++)
-      if (!(hu[i] >= 2.0f && hu[i] < umax && hv[i] >= 2.0f && hv[i] < vmax)) {
-        if (first_outside && !v.is_top_level) { *first_outside = i; break; }
-        snprintf(msg, sizeof(msg), "%s: point %d of level %d at (%g, %g) outside [2, %d) x [2, %d): the loop may revive and then evaluate any point of the level", who, i, v.lvl,
-                 (double)hu[i], (double)hv[i], c->wl[v.lvl] - 3, c->hl[v.lvl] - 3);
-        return failmsg(msg);
-      }
-    if (L->lds_static + resSweepLds(R->n) > L->lds_limit) {
-      snprintf(msg, sizeof(msg), "%s: the loop of level %d with n = %d points needs %zu bytes of LDS (%zu of its own and 5 n for the ordered sweeps), the device allows a workgroup %zu", who,
-               v.lvl, R->n, L->lds_static + resSweepLds(R->n), L->lds_static, L->lds_limit);
-      return failmsg(msg);
-    }
-  }
-  if (!state_in10 && !L->holds_state) return no("state_in10 is NULL and the context's record holds no state yet");
-  if (trace_d || trace_f) {
-    if (!trace_d || !trace_f || !trace_records) return no("a trace needs trace_d, trace_f and trace_records");
-    if (trace_capacity < tests) { snprintf(msg, sizeof(msg), "%s: trace_capacity = %d, the call can make %d accept tests", who, trace_capacity, tests); return failmsg(msg); }
-  }
-  return 0;
-}
-
-static void lmFillProb(InitLmProb& Q, dmvio_hip_ctx* c, const LmLevel& v, const LmCommon& K, int p, int trace_base) {
-  const DmvInitResident* R = v.m->resident;
-  memset(&Q, 0, sizeof(Q));   // (padding too: the records are compared as bytes)
-  Q.Iref = c->frames.levelPtr(K.first_slot, v.lvl); Q.Inew = c->frames.levelPtr(K.new_slot, v.lvl);
-  Q.u = R->f(R->o_u); Q.v = R->f(R->o_v); Q.outlierTH = R->f(R->o_oth);
-  Q.idepth = R->f(R->o_idepth); Q.idepth_new = R->f(R->o_idn); Q.iR = R->f(R->o_iR); Q.energy = R->f(R->o_energy); Q.energy_new = R->f(R->o_en_new);
-  Q.maxstep = R->f(R->o_maxstep); Q.lastHessian = R->f(R->o_lh); Q.lastHessian_new = R->f(R->o_lh_new); Q.jb[0] = R->f(R->o_jb[0]); Q.jb[1] = R->f(R->o_jb[1]);
-  Q.isGood = R->b(R->o_good); Q.isGood_new = R->b(R->o_good_new);
-  Q.level_begin = R->i(R->o_lbegin); Q.order = R->i(R->o_order); Q.neighbours = R->i(R->o_nb);
-  Q.partials = R->io.dev<float>(0) + RES_OUT_FLOATS; Q.ecpartials = Q.partials + (size_t)INIT_EVAL_MAX_BLOCKS * IN_PART;
-  for (int k = 0; k < 9; k++) Q.Ki9[k] = v.Ki9[k];
-  Q.priorY = K.priorY; Q.priorX = K.priorX;
-  for (int k = 0; k < 4; k++) Q.fxfycxcy[k] = v.K4[k];
-  for (int k = 0; k < 8; k++) Q.wM8[k] = K.wM8[k];
-  Q.alphaW = K.alphaW; Q.alphaK = K.alphaK; Q.regWeight = K.regWeight; Q.couplingWeight = K.couplingWeight;
-  Q.n = R->n; Q.G = initEvalGrid(R->n); Q.sweep_levels = R->levels; Q.cur = R->cur; Q.wl = c->wl[v.lvl]; Q.hl = c->hl[v.lvl]; Q.lvl = v.lvl;
-  Q.is_top_level = v.is_top_level; Q.fix_affine = K.fix_affine; Q.max_iterations = v.max_iterations; Q.out_index = p; Q.trace_base = trace_base;
-}
+// what lmCheck (init_lm_host.hpp) reads of this unit's kernel and record
+static LmLimits lmLimits(const DmvInitLmCtx* L) { return {L->lds_static, L->lds_limit, L->holds_state, "the context's record"}; }
 
 // the checked call: records, the state, the launches, and — with state_out10 — the download, the wait and the delivery.  frame: the reset, propagateDown / Up around the loops.
 static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, const LmCommon& K, bool frame, const double* state_in10, double* state_out10, float* res3,
@@ -153,10 +79,7 @@ static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, co
     memcpy(L->slab.host<char>(0), rec.data(), rec.size());
     size_t bytes = L->o_state;
     if (state_in10) {
-      InitLmState* S = L->slab.host<InitLmState>(L->o_state);
-      memset(S, 0, sizeof(*S));
-      for (int k = 0; k < 7; k++) S->pose7[k] = state_in10[k];
-      S->aff[0] = state_in10[7]; S->aff[1] = state_in10[8]; S->snapped = state_in10[9] != 0.0;
+      lmStateFrom10(L->slab.host<InitLmState>(L->o_state), state_in10);
       bytes = L->o_state + sizeof(InitLmState);
     }
     L->sent.clear();
@@ -208,8 +131,7 @@ static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, co
   if (int r = L->slab.wait(s)) return r;
   for (int p = 0; p < P; p++) lv[p].m->resident->st.settled();
   const InitLmState* S = L->slab.host<InitLmState>(L->o_state);
-  for (int k = 0; k < 7; k++) state_out10[k] = S->pose7[k];
-  state_out10[7] = S->aff[0]; state_out10[8] = S->aff[1]; state_out10[9] = S->snapped ? 1.0 : 0.0;
+  lmStateTo10(S, state_out10);
   const InitLmOut* O = L->slab.host<InitLmOut>(L->o_outs);
   int written = 0;
   for (int p = 0; p < P; p++) {
@@ -283,7 +205,7 @@ int dmvio_hip_initializer_resident_track_level(dmvio_hip_initializer* m, int lvl
   const LmLevel lv = {m, lvl, max_iterations, is_top_level != 0, Ki9, fxfycxcy_lvl};
   const LmCommon K = {first_slot, new_slot, fix_affine != 0, alphaW, alphaK, regWeight, couplingWeight, priorY, priorX, wM8};
   int first = -1;
-  if (int r = lmCheck(who, c, L, &lv, 1, K, state_in10, trace_capacity, trace_d, trace_f, trace_records, &first)) return r;
+  if (int r = lmCheck(who, c, lmLimits(L), &lv, 1, K, state_in10, trace_capacity, trace_d, trace_f, trace_records, &first)) return r;
   if (first >= 0) {   // the range condition of resident_calc: the good points outside, counted on the device in a download and a wait of their own, before the loop is enqueued
     DmvInitResident* R = m->resident;
     hipStream_t s = c->stream;
@@ -331,7 +253,7 @@ int dmvio_hip_initializer_resident_track_frame(dmvio_hip_initializer* const* lev
     lv[p] = {levels[l], l, max_iterations[l], p == 0, Ki9_levels + 9 * (size_t)l, fxfycxcy_levels + 4 * (size_t)l};
   }
   const LmCommon K = {first_slot, new_slot, fix_affine != 0, alphaW, alphaK, regWeight, couplingWeight, priorY, priorX, wM8};
-  if (int r = lmCheck(who, c, L, lv, n_levels, K, state_in10, trace_capacity, trace_d, trace_f, trace_records, nullptr)) return r;
+  if (int r = lmCheck(who, c, lmLimits(L), lv, n_levels, K, state_in10, trace_capacity, trace_d, trace_f, trace_records, nullptr)) return r;
   return lmRun(c, L, lv, n_levels, K, true, state_in10, state_out10, res3_levels, iterations_levels, trace_d, trace_f, trace_records);
 }
 

@@ -158,16 +158,26 @@ struct InitLmCtl {
   int snapped, fails, it, quit, accept, cur_sys, tests, pad;
 };
 
-inline __global__ void __launch_bounds__(256) k_init_lm(const InitLmProb* __restrict__ probs, InitLmState* __restrict__ state, InitLmOut* __restrict__ outs,
-                                                 InitLmTraceRec* __restrict__ trace) {
-  extern __shared__ float s_sweep[];
-  __shared__ InitLmSys s_sys[2];
-  __shared__ float s_sums[IN_PART];
-  __shared__ float s_ecsum[4];
-  __shared__ InitArgs s_A;
-  __shared__ InitLmWs s_ws;
-  __shared__ InitLmCtl s_c;
-  const InitLmProb& V = probs[blockIdx.x];
+// the LDS blocks of one level's loop, beside the sweeps' dynamic 5 n bytes
+struct InitLmLds {
+  InitLmSys sys[2];
+  float sums[IN_PART], ecsum[4];
+  InitArgs A;
+  InitLmWs ws;
+  InitLmCtl c;
+};
+
+// One level of one problem by the 256 threads of the calling workgroup, from the state record to the state record: the body of k_init_lm, and of every level k_init_lm_frame_b
+// (init_lm_batch_kernels.hpp) walks.  Every thread of the workgroup calls it; it ends with the record, the level's out and its trace records written by lane 0 — a caller that
+// goes on in the same launch puts a workgroup barrier behind it.
+__device__ __forceinline__ void initLmLevel(const InitLmProb& V, InitLmState* __restrict__ state, InitLmOut* __restrict__ outs, InitLmTraceRec* __restrict__ trace,
+                                            float* __restrict__ s_sweep, InitLmLds& S) {
+  InitLmSys* const s_sys = S.sys;
+  float* const s_sums = S.sums;
+  float* const s_ecsum = S.ecsum;
+  InitArgs& s_A = S.A;
+  InitLmWs& s_ws = S.ws;
+  InitLmCtl& s_c = S.c;
   const int t = threadIdx.x, n = V.n, G = V.G;
   const float *Iref = initGl(V.Iref), *Inew = initGl(V.Inew), *u = initGl(V.u), *v = initGl(V.v), *outlierTH = initGl(V.outlierTH);
   float *idepth = initGl(V.idepth), *idepth_new = initGl(V.idepth_new), *iR = initGl(V.iR), *energy = initGl(V.energy), *energy_new = initGl(V.energy_new);
@@ -325,13 +335,20 @@ inline __global__ void __launch_bounds__(256) k_init_lm(const InitLmProb* __rest
   }
 }
 
+inline __global__ void __launch_bounds__(256) k_init_lm(const InitLmProb* __restrict__ probs, InitLmState* __restrict__ state, InitLmOut* __restrict__ outs,
+                                                 InitLmTraceRec* __restrict__ trace) {
+  extern __shared__ float s_sweep[];
+  __shared__ InitLmLds s_lm;
+  initLmLevel(probs[blockIdx.x], state, outs, trace, s_sweep, s_lm);
+}
+
 // ------------------------------------------------------------------------------------------------ the frame around the levels (:100-114, propagateDown / Up's optReg)
 // trackFrame's reset while the initializer has not snapped, for every level of the frame: workgroup (x, y) serves level y.  `snapped` is the record's, on the device.
 inline __global__ void __launch_bounds__(256) k_init_lm_frame_begin(const InitLmProb* __restrict__ probs, InitLmState* __restrict__ state) {
   if (state->snapped) return;
   const InitLmProb& V = probs[blockIdx.y];
   float *iR = initGl(V.iR), *idepth_new = initGl(V.idepth_new), *lastHessian = initGl(V.lastHessian);
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < V.n; i += gridDim.x * 256) { iR[i] = 1.0f; idepth_new[i] = 1.0f; lastHessian[i] = 0.0f; }
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < V.n; i += gridDim.x * 256) initResetUnsnappedPoint(i, iR, idepth_new, lastHessian);
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) state->pose7[threadIdx.x] = 0.0;   // thisToNext.translation().setZero() (:102); no workgroup reads the pose
 }
 // optReg of one level where the record says snapped: what propagateDown and propagateUp end in (:746, :776)

@@ -9,14 +9,17 @@ namespace dmv {
 struct InitInc8 { float v[8]; };
 
 // trackFrame's reset while the initializer has not snapped (:100-114)
+__device__ __forceinline__ void initResetUnsnappedPoint(const int i, float* __restrict__ iR, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
+  iR[i] = 1.0f; idepth_new[i] = 1.0f; lastHessian[i] = 0.0f;
+}
 inline __global__ void __launch_bounds__(256) k_init_reset_unsnapped(const int n, float* __restrict__ iR, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  iR[i] = 1.0f; idepth_new[i] = 1.0f; lastHessian[i] = 0.0f;
+  initResetUnsnappedPoint(i, iR, idepth_new, lastHessian);
 }
 
-// The per-point bodies below (initResetPoint, initDoStepPoint, initApplyStepPoint) are shared with the device-resident LM loop (init_lm_kernels.hpp: k_init_lm), which runs
-// them for the same i from one workgroup.
+// The per-point bodies (initResetUnsnappedPoint, initResetPoint, initDoStepPoint, initApplyStepPoint, initPropagateUpPoint, initPropagateDownPoint) are shared with the
+// device-resident LM loop (init_lm_kernels.hpp: k_init_lm; init_lm_batch_kernels.hpp: k_init_lm_frame_b), which runs them for the same i from one workgroup.
 
 // resetPoints, the part every level takes (:895-898)
 __device__ __forceinline__ void initResetPoint(const int i, const float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ energy /* 2n */) {
@@ -159,11 +162,9 @@ inline __global__ void __launch_bounds__(64) k_init_sweep(const int n, const int
 
 // propagateUp (:713-744): one thread per parent walks its children in ascending index, as the reference's loop over the lower level meets them.
 // n_listed: the parents child_begin covers (1 + the largest parent index of the lower level); a parent beyond has no child.
-inline __global__ void __launch_bounds__(256) k_init_propagate_up(const int n_dst, const int n_listed, const int* __restrict__ child_begin, const int* __restrict__ children,
-                                                           const unsigned char* __restrict__ src_good, const float* __restrict__ src_iR, const float* __restrict__ src_lastHessian,
-                                                           float* __restrict__ iR, float* __restrict__ idepth, unsigned char* __restrict__ isGood) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n_dst) return;
+__device__ __forceinline__ void initPropagateUpPoint(const int p, const int n_listed, const int* __restrict__ child_begin, const int* __restrict__ children,
+                                                     const unsigned char* __restrict__ src_good, const float* __restrict__ src_iR, const float* __restrict__ src_lastHessian,
+                                                     float* __restrict__ iR, float* __restrict__ idepth, unsigned char* __restrict__ isGood) {
   float acc = 0, num = 0;
   if (p < n_listed) {
     const int e = child_begin[p + 1];
@@ -183,13 +184,18 @@ inline __global__ void __launch_bounds__(256) k_init_propagate_up(const int n_ds
     iR[p] = acc;   // the sum as far as it got: 0 for a parent without good children
   }
 }
+inline __global__ void __launch_bounds__(256) k_init_propagate_up(const int n_dst, const int n_listed, const int* __restrict__ child_begin, const int* __restrict__ children,
+                                                           const unsigned char* __restrict__ src_good, const float* __restrict__ src_iR, const float* __restrict__ src_lastHessian,
+                                                           float* __restrict__ iR, float* __restrict__ idepth, unsigned char* __restrict__ isGood) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_dst) return;
+  initPropagateUpPoint(p, n_listed, child_begin, children, src_good, src_iR, src_lastHessian, iR, idepth, isGood);
+}
 
 // propagateDown (:758-775): one thread per point of the lower level
-inline __global__ void __launch_bounds__(256) k_init_propagate_down(const int n, const int* __restrict__ parent, const unsigned char* __restrict__ par_good,
-                                                             const float* __restrict__ par_iR, const float* __restrict__ par_lastHessian, unsigned char* __restrict__ isGood,
-                                                             float* __restrict__ iR, float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void initPropagateDownPoint(const int i, const int* __restrict__ parent, const unsigned char* __restrict__ par_good,
+                                                       const float* __restrict__ par_iR, const float* __restrict__ par_lastHessian, unsigned char* __restrict__ isGood,
+                                                       float* __restrict__ iR, float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
   const int p = parent[i];
   const float ph = par_lastHessian[p];
   if (!par_good[p] || ph < 0.1) return;
@@ -203,6 +209,13 @@ inline __global__ void __launch_bounds__(256) k_init_propagate_down(const int n,
     const float newiR = (iR[i] * lh * 2 + par_iR[p] * ph) / (lh * 2 + ph);
     iR[i] = newiR; idepth[i] = newiR; idepth_new[i] = newiR;
   }
+}
+inline __global__ void __launch_bounds__(256) k_init_propagate_down(const int n, const int* __restrict__ parent, const unsigned char* __restrict__ par_good,
+                                                             const float* __restrict__ par_iR, const float* __restrict__ par_lastHessian, unsigned char* __restrict__ isGood,
+                                                             float* __restrict__ iR, float* __restrict__ idepth, float* __restrict__ idepth_new, float* __restrict__ lastHessian) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  initPropagateDownPoint(i, parent, par_good, par_iR, par_lastHessian, isGood, iR, idepth, idepth_new, lastHessian);
 }
 
 // calcEC (:650-670): (sum rOld^2, sum rNew^2, count) over the points the evaluation accepted, in a fixed shape.  k_init_ec: initGrid(n) workgroups of 256, every thread

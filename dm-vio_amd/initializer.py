@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-from ._abi import InitializerPointsWindow, InitializerWindow, _Handle, _chk, _d, _f, _i, _u8
+from ._abi import InitializerLmWindow, InitializerPointsWindow, InitializerWindow, _Handle, _chk, _d, _f, _i, _u8
 
 
 WM8 = (1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 10.0, 1000.0)   # CoarseInitializer's wM: SCALE_XI_ROT x 3, SCALE_XI_TRANS x 3, SCALE_A, SCALE_B
@@ -299,3 +299,59 @@ class InitializerBatchHip(_Handle):
     def last_work(self):
         """(kernel launches, uploads, downloads, stream waits) of the last calc call"""
         return self._outs("initializer_batch_last_work", C.c_int, 4)
+
+
+class InitializerLmBatch(_Handle):
+    """trackFrame's LM loop for the frames of W windows per call (include/dmvio_hip_init_lm_batch.h: dmvio_hip_initializer_resident_track_frame_batch): one workgroup per
+    window, one launch per call; every window ends with the bits of its own track_frame call.  The batch keeps max_windows LM records of its own.  For tests and tools."""
+    _destroy = "dmvio_hip_initializer_lm_batch_destroy"
+
+    def __init__(self, ctx, max_windows=64):
+        self.ctx = ctx
+        self._create(ctx.L, "dmvio_hip_initializer_lm_batch_create", ctx.p, int(max_windows))
+        self.max_windows = int(max_windows)
+
+    @staticmethod
+    def pack(windows):
+        """windows: one dict per window with handles (level k = handles[k]), first_slot, new_slot, Ki9_levels, fxfycxcy_levels, max_iterations, state_slot and optionally
+        state ((pose7, (a, b), snapped); None or absent: continue from record state_slot), fix_affine (True), wM8, alphaW, alphaK, regWeight, couplingWeight, priorY,
+        priorX (track_frame's defaults) and trace (False) -> (array of dmvio_hip_initializer_lm_window, the per-window _LmOut its pointers reach into, arrays to keep alive)"""
+        arr = (InitializerLmWindow * max(len(windows), 1))()
+        outs, keep = [], []
+        for x, d in zip(arr, windows):
+            hs = d["handles"]
+            n = len(hs)
+            levels = (C.c_void_p * max(n, 1))(*[None if h is None else h.p for h in hs])
+            mi = np.ascontiguousarray(d["max_iterations"], dtype=np.int32)
+            Ki = np.ascontiguousarray(d["Ki9_levels"], dtype=np.float64)
+            K4 = np.ascontiguousarray(d["fxfycxcy_levels"], dtype=np.float32)
+            wm = np.ascontiguousarray(d.get("wM8", WM8), dtype=np.float32)
+            o = _LmOut(n, int(mi.sum()) + n if d.get("trace", False) else 0, True)
+            tail = o.args(d.get("state"))
+            keep.append((levels, mi, Ki, K4, wm))
+            x.levels, x.n_levels, x.first_slot, x.new_slot = levels, n, int(d["first_slot"]), int(d["new_slot"])
+            x.Ki9_levels, x.fxfycxcy_levels = _d(Ki), _f(K4)
+            x.alphaW, x.alphaK = float(d.get("alphaW", 150 * 150)), float(d.get("alphaK", 2.5 * 2.5))
+            x.regWeight, x.couplingWeight = float(d.get("regWeight", 0.8)), float(d.get("couplingWeight", 1.0))
+            x.priorY, x.priorX = float(d.get("priorY", 0.0)), float(d.get("priorX", 0.0))
+            x.wM8, x.fix_affine, x.max_iterations, x.state_slot = _f(wm), int(bool(d.get("fix_affine", True))), _i(mi), int(d["state_slot"])
+            x.state_in10, x.state_out10, x.res3_levels, x.iterations_levels = tail[0], tail[1], tail[2], tail[3]
+            x.trace_capacity, x.trace_d, x.trace_f = tail[4], tail[5], tail[6]
+            x.trace_records = None if tail[7] is None else C.pointer(o.nrec)
+            x.snapped = -1
+            outs.append(o)
+        return arr, outs, keep
+
+    def track_frame_batch(self, windows, W=None):
+        """one dmvio_hip_initializer_resident_track_frame_batch call (see pack()); W overrides the window count handed to the library -> per window what track_frame returns:
+        dict(pose7, aff, snapped, res3 (n_levels x 3), iterations (n_levels)[, trace])"""
+        arr, outs, keep = self.pack(windows)
+        _chk(self.L, self.L.dmvio_hip_initializer_resident_track_frame_batch(self.p, len(windows) if W is None else W, arr), "initializer_resident_track_frame_batch")
+        res = [o.result() for o in outs]
+        for x, r in zip(arr, res):
+            assert x.snapped == int(r["snapped"]), (x.snapped, r["snapped"])   # the struct's field is the outgoing state's
+        return res
+
+    def last_work(self):
+        """(kernel launches, uploads, downloads, stream waits) of the last track_frame_batch call"""
+        return self._outs("initializer_lm_batch_last_work", C.c_int, 4)

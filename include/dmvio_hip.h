@@ -924,6 +924,7 @@ int dmvio_hip_initializer_calc_res_and_gs_batch(dmvio_hip_initializer_batch* b, 
 int dmvio_hip_initializer_batch_last_work(dmvio_hip_initializer_batch* b, int* launches, int* uploads, int* downloads, int* waits);
 /* The point set of a level resident on the device and the per-point passes of CoarseInitializer::trackFrame on it: dmvio_hip_init_resident.h, beside this header. */
 /* trackFrame's Levenberg-Marquardt loop itself on those resident point sets, one launch a level: dmvio_hip_init_lm.h, beside this header. */
+/* The same loop for the frames of W windows in one launch, one workgroup a window: dmvio_hip_init_lm_batch.h, beside this header. */
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * Pixel selection: the candidates of a new keyframe, chosen on the device from the resident pyramid.
