@@ -16,7 +16,7 @@ from ._abi import (INCLUDE_PATH, LIB_PATH, MIRRORS, SIGNATURES, ActivationOptimi
                    c_d, c_f, c_i, c_u8, declared_symbols, load_library)
 from .frames import Context, UndistorterHip, frame_level0_is_tiled, set_raw_batch_kernel, set_raw_batch_layout  # noqa: F401
 from .tracker import CoarseTrackerHip, SetRefBatchHip, TrackMultiHip, coarse_update_visual, make_track_hypotheses, write_result_txt  # noqa: F401
-from .initializer import CoarseInitializerHip, InitializerBatchHip  # noqa: F401
+from .initializer import CoarseInitializerHip, InitFirstHip, InitializerBatchHip  # noqa: F401
 from .points import (STATUS_NAMES, ActivationBatchHip, DistanceMapHip, ImmaturePointsHip, PixelSelectorBatchHip, PixelSelectorHip, TraceBatchHip, activate_points,  # noqa: F401
                      activate_points_batch, distance_map_tables, min_act_dist_update)
 from .ba import BundleAdjusterBatch, BundleAdjusterHip, RcclCommunicator, WindowGraph, debug_solve, host_solve_ldlt  # noqa: F401

@@ -449,6 +449,16 @@ EXTENSION_SIGNATURES = {
         "dmvio_hip_initializer_resident_track_frame_batch": (ci, [vp, ci, C.POINTER(InitializerLmWindow)]),
         "dmvio_hip_initializer_lm_batch_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
     },
+    "dmvio_hip_init_first.h": {
+        "dmvio_hip_init_first_create": (vp, [vp]),
+        "dmvio_hip_init_first_destroy": (None, [vp]),
+        "dmvio_hip_init_first_make_pixel_status": (ci, [vp, ci, ci, cf, ci, cf, c_i, c_i, c_u8]),
+        "dmvio_hip_init_first_get_passes": (ci, [vp, ci, c_i, c_f, c_i]),
+        "dmvio_hip_init_first_make_nn": (ci, [vp, ci, c_f, c_f, ci, c_f, c_f, c_i, c_i]),
+        "dmvio_hip_initializer_set_first": (ci, [vp, vp, ci, c_f, ci, C.POINTER(vp), c_f, cf, c_i, c_i]),
+        "dmvio_hip_init_first_get_level": (ci, [vp, ci, c_f, c_f, c_f, c_i, c_i]),
+        "dmvio_hip_init_first_last_work": (ci, [vp, c_i, c_i, c_i, c_i]),
+    },
 }
 # the structs of the extension headers -> their mirrors, header by header (MIRRORS is held to include/dmvio_hip.h alone)
 EXTENSION_MIRRORS = {

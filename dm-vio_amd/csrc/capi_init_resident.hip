@@ -59,6 +59,31 @@ static int resOptReg(DmvInitResident* R, hipStream_t s, float regWeight) {
   return resSweep(R, s, body);
 }
 
+// the slab of a point set of n points with `levels` sweep levels and n_listed parents listed: layout set, memory reserved, the pinned side free to write.  The handle is
+// left WITHOUT resident state until the caller sets `live` (a HIP failure on the way leaves no half of one).
+static int resBegin(DmvInitResident* R, int n, int levels, int n_listed, hipStream_t s) {
+  DmvCursor L;
+  DmvInitResidentLayout N;
+  N.o_u = L.take<float>(n); N.o_v = L.take<float>(n); N.o_oth = L.take<float>(n); N.o_nb = L.take<int>(10 * (size_t)n); N.o_parent = L.take<int>(n);
+  N.o_order = L.take<int>(n); N.o_lbegin = L.take<int>((size_t)levels + 1); N.o_cbegin = L.take<int>((size_t)n_listed + 1); N.o_children = L.take<int>(n);
+  N.o_idepth = L.take<float>(n); N.o_iR = L.take<float>(n); N.o_lh = L.take<float>(n); N.o_energy = L.take<float>(2 * (size_t)n); N.o_good = L.take<unsigned char>(n);
+  N.up_end = L.bytes();
+  N.o_idn = L.take<float>(n); N.o_en_new = L.take<float>(2 * (size_t)n); N.o_maxstep = L.take<float>(n); N.o_lh_new = L.take<float>(n);
+  N.o_jb[0] = L.take<float>(10 * (size_t)n); N.o_jb[1] = L.take<float>(10 * (size_t)n); N.o_good_new = L.take<unsigned char>(n);
+  N.total = L.bytes();
+  R->live = false;
+  R->st.work = &R->work; R->io.work = &R->work;
+  if (int r = R->st.reserve(N.total, N.total + N.total / 2, s)) return r;
+  if (int r = R->st.begin(s)) return r;
+  if (!R->io.d) {
+    DmvCursor I;
+    I.take<float>(RES_OUT_FLOATS); I.take<float>((size_t)INIT_EVAL_MAX_BLOCKS * IN_PART); I.take<float>((size_t)INIT_EVAL_MAX_BLOCKS * IN_EC);
+    if (int r = R->io.create(I.bytes())) return r;
+  }
+  static_cast<DmvInitResidentLayout&>(*R) = N;
+  return 0;
+}
+
 extern "C" {
 
 int dmvio_hip_initializer_set_resident(dmvio_hip_initializer* m, int n, const float* u, const float* v, const float* idepth, const float* iR, const unsigned char* isGood,
@@ -96,25 +121,7 @@ int dmvio_hip_initializer_set_resident(dmvio_hip_initializer* m, int n, const fl
   const int n_listed = parent ? max_parent + 1 : 0;
   if (parent) initChildLists(n, parent, n_listed, child_begin, children);
   hipStream_t s = c->stream;
-  DmvCursor L;
-  DmvInitResidentLayout N;
-  N.o_u = L.take<float>(n); N.o_v = L.take<float>(n); N.o_oth = L.take<float>(n); N.o_nb = L.take<int>(10 * (size_t)n); N.o_parent = L.take<int>(n);
-  N.o_order = L.take<int>(n); N.o_lbegin = L.take<int>((size_t)levels + 1); N.o_cbegin = L.take<int>((size_t)n_listed + 1); N.o_children = L.take<int>(n);
-  N.o_idepth = L.take<float>(n); N.o_iR = L.take<float>(n); N.o_lh = L.take<float>(n); N.o_energy = L.take<float>(2 * (size_t)n); N.o_good = L.take<unsigned char>(n);
-  N.up_end = L.bytes();
-  N.o_idn = L.take<float>(n); N.o_en_new = L.take<float>(2 * (size_t)n); N.o_maxstep = L.take<float>(n); N.o_lh_new = L.take<float>(n);
-  N.o_jb[0] = L.take<float>(10 * (size_t)n); N.o_jb[1] = L.take<float>(10 * (size_t)n); N.o_good_new = L.take<unsigned char>(n);
-  N.total = L.bytes();
-  R->live = false;   // (a HIP failure below leaves the handle without resident state, not with half of one)
-  R->st.work = &R->work; R->io.work = &R->work;
-  if (int r = R->st.reserve(N.total, N.total + N.total / 2, s)) return r;
-  if (int r = R->st.begin(s)) return r;
-  if (!R->io.d) {
-    DmvCursor I;
-    I.take<float>(RES_OUT_FLOATS); I.take<float>((size_t)INIT_EVAL_MAX_BLOCKS * IN_PART); I.take<float>((size_t)INIT_EVAL_MAX_BLOCKS * IN_EC);
-    if (int r = R->io.create(I.bytes())) return r;
-  }
-  static_cast<DmvInitResidentLayout&>(*R) = N;
+  if (int r = resBegin(R, n, levels, n_listed, s)) return r;
   resOpen(R);
   char* h = R->st.host<char>(0);
   auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(h + off, src, bytes); };
@@ -367,3 +374,55 @@ int dmvio_hip_initializer_resident_last_work(dmvio_hip_initializer* m, int* laun
 }
 
 }  // extern "C"
+
+// ---- for dmvio_hip_initializer_set_first (capi_init_first.hip; declared in init_handle.h).  The caller holds the context's lock.
+// what set_resident would refuse of n points on this handle, without touching the handle: 0 or <0 with the message
+int dmvInitResidentCheck(dmvio_hip_initializer* m, int n, const char* who) {
+  char msg[256];
+  if (n < 0 || n > m->capacity) { snprintf(msg, sizeof(msg), "%s: n = %d outside [0, %d], the handle's capacity", who, n, m->capacity); return failmsg(msg); }
+  int lim = 0;
+  HIPCHK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, m->ctx->device));
+  if (5 * (size_t)n > (size_t)std::max(lim, 0)) {
+    snprintf(msg, sizeof(msg), "%s: n = %d points need %zu bytes of LDS for the ordered sweeps, the device allows a workgroup %zu (at most %zu points)", who, n, 5 * (size_t)n,
+             (size_t)std::max(lim, 0), (size_t)std::max(lim, 0) / 5);
+    return failmsg(msg);
+  }
+  return 0;
+}
+// The state set_resident leaves when given setFirst's arrays (idepth = iR = 1, isGood = 1, energy = lastHessian = 0, outlierTH constant), from point lists on the device
+// (d_*) of which the host holds a copy (h_*; parent NULL on the top level): the sweep schedule and the children lists are built here from the host copy and are the ONE
+// upload; no point value is uploaded.  The caller has run dmvInitResidentCheck and checked the tables' ranges.
+int dmvInitResidentAdopt(dmvio_hip_initializer* m, int n, const float* d_u, const float* d_v, const int* d_nb, const int* d_parent, const float* h_u, const float* h_v,
+                         const int* h_nb, const int* h_parent, float outlierTH, DmvWork* work) {
+  dmvio_hip_ctx* c = m->ctx;
+  hipStream_t s = c->stream;
+  int max_parent = -1;
+  if (h_parent) for (int i = 0; i < n; i++) max_parent = std::max(max_parent, h_parent[i]);
+  if (!m->resident) m->resident = new DmvInitResident();
+  DmvInitResident* R = m->resident;
+  if (int r = resAllowLds(R, c->device)) return r;
+  std::vector<int> level_begin, order, child_begin, children;
+  const int levels = initSweepSchedule(n, h_nb, level_begin, order);
+  const int n_listed = h_parent ? max_parent + 1 : 0;
+  if (h_parent) initChildLists(n, h_parent, n_listed, child_begin, children);
+  if (int r = resBegin(R, n, levels, n_listed, s)) return r;
+  resOpen(R);
+  char* h = R->st.host<char>(0);
+  auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) memcpy(h + off, src, bytes); };
+  const size_t F = sizeof(float) * (size_t)n, I4 = sizeof(int) * (size_t)n;
+  put(R->o_u, h_u, F); put(R->o_v, h_v, F);   // the host copy of (u, v) the range check of calc reads
+  put(R->o_order, order.data(), I4); put(R->o_lbegin, level_begin.data(), sizeof(int) * level_begin.size());
+  if (h_parent) { put(R->o_cbegin, child_begin.data(), sizeof(int) * child_begin.size()); put(R->o_children, children.data(), I4); }
+  R->n = n; R->levels = levels; R->n_listed = n_listed; R->max_parent = max_parent; R->has_parent = h_parent != nullptr; R->cur = 0;
+  // the tables lie back to back between the static point arrays and the dynamic part: one copy
+  HIPCHK(hipMemcpyAsync(R->st.d + R->o_order, h + R->o_order, R->o_idepth - R->o_order, hipMemcpyHostToDevice, s));
+  R->st.in_flight[R->st.cur] = true;   // (the next writer of the pinned side waits, as behind DmvSlab::upload)
+  R->work.uploads++; if (work) work->uploads++;
+  HIPCHK(hipMemsetAsync(R->st.d + R->o_idepth, 0, R->total - R->o_idepth, s));
+  hipLaunchKernelGGL(k_init_adopt, resGrid(n), dim3(256), 0, s, n, d_u, d_v, d_nb, d_parent, outlierTH, R->f(R->o_u), R->f(R->o_v), R->f(R->o_oth), R->i(R->o_nb),
+                     R->i(R->o_parent), R->f(R->o_idepth), R->f(R->o_iR), R->f(R->o_idn), R->b(R->o_good));
+  HIPCHK(hipGetLastError());
+  R->work.launches++; if (work) work->launches++;
+  R->live = true;
+  return 0;
+}

@@ -211,8 +211,15 @@ int dmvio_hip_pixel_selector_set_potential(dmvio_hip_pixel_selector* s, int pote
 int dmvio_hip_pixel_selector_make_maps(dmvio_hip_pixel_selector* s, int slot, const float* B_lut256, float density, int recursions_left, float th_factor, int* n_selected,
                                        int counts3[3], float* map_out_host) {
   SEL_READY(s);
+  std::lock_guard<std::mutex> lk(s->ctx->mu);
+  return dmv_selector_make_maps_locked(s, slot, B_lut256, density, recursions_left, th_factor, n_selected, counts3, map_out_host);
+}
+}  // extern "C"
+
+// makeMaps under the context's lock, which the caller holds (the entry point above; dmvio_hip_initializer_set_first in capi_init_first.hip)
+int dmv_selector_make_maps_locked(dmvio_hip_pixel_selector* s, int slot, const float* B_lut256, float density, int recursions_left, float th_factor, int* n_selected,
+                                  int counts3[3], float* map_out_host) {
   dmvio_hip_ctx* c = s->ctx;
-  std::lock_guard<std::mutex> lk(c->mu);
   if (slot < 0 || slot >= c->n_slots) return failmsg("pixel_selector_make_maps: frame slot out of range");
   if (!n_selected) return failmsg("pixel_selector_make_maps: n_selected is NULL");
   if (int r = dmv_ensure_row_major_locked(c, slot)) return r;
@@ -276,6 +283,8 @@ int dmvio_hip_pixel_selector_make_maps(dmvio_hip_pixel_selector* s, int slot, co
   if (counts3) for (int k = 0; k < 3; k++) counts3[k] = s->last_counts[k];
   return 0;
 }
+
+extern "C" {
 
 int dmvio_hip_pixel_selector_get_selection(dmvio_hip_pixel_selector* s, int* u, int* v, int* type) {
   SEL_READY(s);
@@ -527,3 +536,4 @@ int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, c
   return s->n_window;
 }
 const unsigned char* dmv_selector_map(dmvio_hip_pixel_selector* s) { return s->d_map; }
+dmvio_hip_ctx* dmv_selector_ctx(dmvio_hip_pixel_selector* s) { return s->ctx; }

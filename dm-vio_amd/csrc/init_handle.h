@@ -45,3 +45,8 @@ void initHostTail(const dmv::Pose& T, int n, float alphaW, float alphaK, double 
                   float res3[3]);
 // ---- capi_init_resident.hip, for dmvio_hip_initializer_destroy (the stream has been waited for)
 void dmvInitResidentRelease(dmvio_hip_initializer* m);
+// ---- capi_init_resident.hip, for dmvio_hip_initializer_set_first (capi_init_first.hip); both under the context's lock.  dmvInitResidentCheck: what set_resident would
+// refuse of n points, the handle untouched.  dmvInitResidentAdopt: the resident state of setFirst's point set from lists on the device and their host copy.
+int dmvInitResidentCheck(dmvio_hip_initializer* m, int n, const char* who);
+int dmvInitResidentAdopt(dmvio_hip_initializer* m, int n, const float* d_u, const float* d_v, const int* d_nb, const int* d_parent, const float* h_u, const float* h_v,
+                         const int* h_nb, const int* h_parent, float outlierTH, DmvWork* work);

@@ -280,4 +280,20 @@ inline __global__ void __launch_bounds__(256) k_init_count_outside(const int n, 
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, __popcll(m));
 }
 
+// The point set setFirst makes (CoarseInitializer.cpp:841-865), adopted from lists that already live on the device (dmvio_hip_initializer_set_first): u, v, the
+// neighbour table and the parents (parent_in NULL: the top level) are copied, idepth = iR = idepth_new = 1, isGood = 1, outlierTH the caller's constant.  Every other
+// dynamic field has been cleared by the caller.
+inline __global__ void __launch_bounds__(256) k_init_adopt(const int n, const float* __restrict__ u_in, const float* __restrict__ v_in, const int* __restrict__ nb_in,
+                                                           const int* __restrict__ parent_in, const float outlierTH, float* __restrict__ u, float* __restrict__ v,
+                                                           float* __restrict__ oth, int* __restrict__ nb, int* __restrict__ parent, float* __restrict__ idepth,
+                                                           float* __restrict__ iR, float* __restrict__ idepth_new, unsigned char* __restrict__ isGood) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  u[i] = u_in[i]; v[i] = v_in[i]; oth[i] = outlierTH;
+#pragma unroll
+  for (int k = 0; k < 10; k++) nb[10 * (size_t)i + k] = nb_in[10 * (size_t)i + k];
+  if (parent_in) parent[i] = parent_in[i];
+  idepth[i] = 1.0f; iR[i] = 1.0f; idepth_new[i] = 1.0f; isGood[i] = 1;
+}
+
 }  // namespace dmv

@@ -178,3 +178,9 @@ int dmv_selector_window_list(dmvio_hip_pixel_selector* s, dmvio_hip_ctx** ctx, c
 // call's records (record_bytes per window, checked against what the batch reserves).  0 or <0.
 struct dmvio_hip_pixel_selector_batch;
 int dmv_selector_batch_traces(dmvio_hip_pixel_selector_batch* b, size_t record_bytes, dmvio_hip_ctx** ctx, int* max_windows, char** d_records);
+// what dmvio_hip_initializer_set_first (capi_init_first.hip) needs of a selector (capi_select.hip): its context, makeMaps with the context's lock already held, and the
+// device status map of the last makeMaps (w * h bytes, valid until the selector's next call)
+dmvio_hip_ctx* dmv_selector_ctx(dmvio_hip_pixel_selector* s);
+int dmv_selector_make_maps_locked(dmvio_hip_pixel_selector* s, int slot, const float* B_lut256, float density, int recursions_left, float th_factor, int* n_selected,
+                                  int counts3[3], float* map_out_host);
+const unsigned char* dmv_selector_map(dmvio_hip_pixel_selector* s);   // (also immature_handle.h)

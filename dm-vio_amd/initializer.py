@@ -213,6 +213,66 @@ class CoarseInitializerHip(_Handle):
         return o.result()
 
 
+class InitFirstHip(_Handle):
+    """CoarseInitializer::setFirst and makeNN on the device (include/dmvio_hip_init_first.h): the coarse selector of the levels >= 1, the raster-ordered point lists,
+    the two nearest-neighbour searches and the hand-over into the resident state of CoarseInitializerHip.  For tests and tools."""
+    _destroy = "dmvio_hip_init_first_destroy"
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._create(ctx.L, "dmvio_hip_init_first_create", ctx.p)
+
+    def make_pixel_status(self, slot, lvl, desired_density, sparsity_factor, recs_left=5, th_factor=1.0, want_map=True):
+        """makePixelStatus on level lvl of the frame in `slot` -> (numGood, the sparsityFactor it leaves, bool map [h_lvl, w_lvl] or None)"""
+        sf, ng = C.c_int(int(sparsity_factor)), C.c_int(0)
+        wl, hl = self.ctx.w >> lvl, self.ctx.h >> lvl
+        m = np.zeros(max(wl * hl, 1), np.uint8) if want_map else None
+        _chk(self.L, self.L.dmvio_hip_init_first_make_pixel_status(self.p, int(slot), int(lvl), float(desired_density), int(recs_left), float(th_factor), C.byref(sf), C.byref(ng),
+                                                                   None if m is None else _u8(m)), "init_first_make_pixel_status")
+        return ng.value, sf.value, (None if m is None else m[:wl * hl].reshape(hl, wl).astype(bool))
+
+    def get_passes(self):
+        """[(pot, THFac, numGood)] of the rounds of the last make_pixel_status"""
+        pot, th, ng = np.zeros(32, np.int32), np.zeros(32, np.float32), np.zeros(32, np.int32)
+        n = _chk(self.L, self.L.dmvio_hip_init_first_get_passes(self.p, 32, _i(pot), _f(th), _i(ng)), "init_first_get_passes")
+        return [(int(pot[k]), float(th[k]), int(ng[k])) for k in range(min(n, 32))]
+
+    def make_nn(self, u, v, u_up=None, v_up=None):
+        """makeNN's searches for one level on host arrays (u_up None: the top level) -> (neighbours n x 10, parent n)"""
+        u, v = np.ascontiguousarray(u, dtype=np.float32), np.ascontiguousarray(v, dtype=np.float32)
+        top = u_up is None
+        uu = None if top else np.ascontiguousarray(u_up, dtype=np.float32)
+        vu = None if top else np.ascontiguousarray(v_up, dtype=np.float32)
+        nb, par = np.zeros((len(u), 10), np.int32), np.zeros(len(u), np.int32)
+        _chk(self.L, self.L.dmvio_hip_init_first_make_nn(self.p, len(u), _f(u), _f(v), 0 if top else len(uu), None if top else _f(uu), None if top else _f(vu), _i(nb), _i(par)),
+             "init_first_make_nn")
+        return nb, par
+
+    def set_first(self, sel, slot, handles, sparsity_factor, outlierTH_per_point, densities=None, B=None):
+        """the whole of setFirst for the frame in `slot` into handles[l] (one CoarseInitializerHip per level) -> (point counts per level, the sparsityFactor it leaves)"""
+        n = len(handles)
+        arr = (C.c_void_p * max(n, 1))(*[None if h is None else h.p for h in handles])
+        dens = None if densities is None else np.ascontiguousarray(densities, dtype=np.float32)
+        Bf = None if B is None else np.ascontiguousarray(B, dtype=np.float32)
+        sf, cnt = C.c_int(int(sparsity_factor)), np.zeros(max(n, 1), np.int32)
+        _chk(self.L, self.L.dmvio_hip_initializer_set_first(self.p, None if sel is None else sel.p, int(slot), None if Bf is None else _f(Bf), n, arr,
+                                                            None if dens is None else _f(dens), float(outlierTH_per_point), C.byref(sf), _i(cnt)), "initializer_set_first")
+        for h, k in zip(handles, cnt):
+            h.n_resident = int(k)
+        return [int(k) for k in cnt[:n]], sf.value
+
+    def get_level(self, lvl):
+        """the point list of level lvl of the last set_first: dict(u, v, my_type, neighbours, parent)"""
+        n = _chk(self.L, self.L.dmvio_hip_init_first_get_level(self.p, int(lvl), None, None, None, None, None), "init_first_get_level")
+        o = dict(u=np.zeros(n, np.float32), v=np.zeros(n, np.float32), my_type=np.zeros(n, np.float32), neighbours=np.zeros((n, 10), np.int32), parent=np.zeros(n, np.int32))
+        _chk(self.L, self.L.dmvio_hip_init_first_get_level(self.p, int(lvl), _f(o["u"]), _f(o["v"]), _f(o["my_type"]), _i(o["neighbours"]), _i(o["parent"])), "init_first_get_level")
+        return o
+
+    def last_work(self):
+        """(kernel launches, uploads, downloads, stream waits) of the last make_pixel_status / make_nn / set_first"""
+        return self._outs("init_first_last_work", C.c_int, 4)
+
+
 class InitializerBatchHip(_Handle):
     """calcResAndGS (CoarseInitializer.cpp:331-624) of W CoarseInitializerHip handles of one context per call (dmvio_hip_initializer_calc_res_and_gs_batch): every window's
     outputs are its single call's bits; one upload, two launches, one download and one wait per calc call (last_work()).  For tests and tools."""

@@ -9,8 +9,9 @@ extern "C" {
 
 /* The point set of a level resident on the device, and the per-point passes of CoarseInitializer::trackFrame on it (CoarseInitializer.cpp:85-281).  After set_resident
  * all of struct Pnt that the passes touch and both JbBuffers live in device memory; the calls below run the reference's loops there, and nothing per point crosses PCIe
- * until get_state.  The LM loop itself, the 8x8 solve, the pose update, setFirst and makeNN stay the caller's, on the host (the loop can also run on the device, on the
- * same resident state: dmvio_hip_init_lm.h).  Every per-point value has the reference's bits.
+ * until get_state.  The LM loop itself, the 8x8 solve and the pose update stay the caller's, on the host (the loop can also run on the device, on the same resident
+ * state: dmvio_hip_init_lm.h).  setFirst and makeNN, which create the point sets, can run on the device too and hand them over without an upload: dmvio_hip_init_first.h
+ * (dmvio_hip_initializer_set_first leaves the state set_resident would).  Every per-point value has the reference's bits.
  *   set_resident        one packed upload of the point set (Pnt's u, v, idepth, iR, isGood, energy, outlierTH, lastHessian, neighbours[10], parent; parent NULL on the top
  *                       level), idepth_new = idepth, the *_new fields, maxstep and both JbBuffers zeroed.  Builds, on the host, the static schedule of the ordered sweeps
  *                       and the children lists of propagateUp.  The handle's non-resident state (set_points, calc_res_and_gs, the batched calls) is not touched, nor does any of

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dm-vio_amd", "csrc")
-UNITS = ["capi", "capi_ref", "capi_frames", "capi_ba", "capi_immature", "capi_init", "capi_init_resident", "capi_select", "capi_activate"]
+UNITS = ["capi", "capi_ref", "capi_frames", "capi_ba", "capi_immature", "capi_init", "capi_init_resident", "capi_init_first", "capi_select", "capi_activate"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics", "-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 KINDS = ("global_load", "global_store", "global_atomic", "flat_load", "flat_store", "flat_atomic", "scratch_load", "scratch_store")
 
