@@ -9,13 +9,9 @@
 #include "lie_dev.h"
 #include "init_kernels.hpp"
 #include "init_tail.hpp"
-#include "init_handle.h"   // struct dmvio_hip_initializer and what the resident unit (capi_init_resident.hip) borrows of this one
+#include "init_handle.h"   // struct dmvio_hip_initializer, the evaluation's grid (initGrid) and what the resident unit (capi_init_resident.hip) borrows of this one
 
 using namespace dmv;
-
-enum { INIT_MAX_BLOCKS = 256 };
-static inline int initGrid(int n) { return std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256)); }
-static_assert((int)INIT_MAX_BLOCKS == (int)INIT_EVAL_MAX_BLOCKS, "the resident unit sizes its partials by INIT_EVAL_MAX_BLOCKS");
 
 // W windows per call.  The batch owns what a call needs besides the handles: a pinned slab and its device copy for the point sets of set_points_batch (the handles named there
 // read their points from it until their next set_points: `tenants`), a pinned slab and its device copy for the records and idepth_new arrays of a calc call, the partials, and
@@ -123,7 +119,6 @@ void initHostTail(const Pose& T, int n, float alphaW, float alphaK, double prior
   initTail(T, n, alphaW, alphaK, priorY, priorX, sums, H_out64, b_out8, H_sc64, b_sc8, res3, nullptr);
 }
 
-int initEvalGrid(int n) { return initGrid(n); }
 // the evaluation's two launches on the context's stream: the single call's grid, so the sums have the single call's bits wherever the points lie
 int initLaunchEval(dmvio_hip_ctx* c, int lvl, int first_slot, int new_slot, const InitPts& P, const InitArgs& A, float* d_partials, float* d_out) {
   const int G = initGrid(P.n);

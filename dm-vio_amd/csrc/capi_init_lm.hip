@@ -1,13 +1,14 @@
 // C ABI of the initializer's LM loop on the device (include/dmvio_hip_init_lm.h): CoarseInitializer::trackFrame (src/dso/FullSystem/CoarseInitializer.cpp:85-281) on the
-// resident point sets of capi_init_resident.hip.  This unit fills the problem records, keeps the context's LM record and enqueues; the loop itself is k_init_lm
-// (init_lm_kernels.hpp).
+// resident point sets of capi_init_resident.hip.  This unit keeps the context's LM record and enqueues; the loop itself is k_init_lm (init_lm_kernels.hpp), the
+// propagation around it and the outside count are the resident unit's launches (init_resident_state.h), and what a call checks, sends and hands back is shared with the
+// batched call (init_lm_host.hpp).
 #include <vector>
 #include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <algorithm>
 #include "../../include/dmvio_hip_init_lm.h"
-#include "init_lm_host.hpp"   // the handle, the resident state, the kernels; a call's levels, lmCheck and lmFillProb
+#include "init_lm_host.hpp"   // the handle, the resident state, the kernels; a call's levels, lmCheck, lmFillProb, lmSend and lmDeliver
 
 using namespace dmv;
 
@@ -38,13 +39,11 @@ void dmvInitLmRelease(dmvio_hip_ctx* c) {
 static int lmCtx(dmvio_hip_ctx* c, DmvInitLmCtx** out) {
   if (!c->init_lm) {
     int lim = 0;
-    HIPCHK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    size_t own = 0, own_reg = 0;
+    HIPCHK(initLdsAllow(c->device, &lim, reinterpret_cast<const void*>(&k_init_lm), &own));
     if (lim <= 0) return failmsg("initializer LM loop: the device reports no LDS per workgroup");
-    hipFuncAttributes fa;
-    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_init_lm)));
-    if (fa.sharedSizeBytes >= (size_t)lim) return failmsg("initializer LM loop: the kernel's own LDS exceeds what the device allows a workgroup");
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_init_lm), hipFuncAttributeMaxDynamicSharedMemorySize, lim - (int)fa.sharedSizeBytes));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_init_lm_opt_reg), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+    if (own >= (size_t)lim) return failmsg("initializer LM loop: the kernel's own LDS exceeds what the device allows a workgroup");
+    HIPCHK(initLdsAllow(c->device, &lim, reinterpret_cast<const void*>(&k_init_lm_opt_reg), &own_reg));
     DmvInitLmCtx* L = new DmvInitLmCtx();
     DmvCursor cur;
     cur.take<InitLmProb>(DMV_MAX_LEVELS);
@@ -52,7 +51,7 @@ static int lmCtx(dmvio_hip_ctx* c, DmvInitLmCtx** out) {
     L->total = cur.bytes();
     L->slab.work = &L->work;
     if (int r = L->slab.create(L->total)) { L->slab.release(); delete L; return r; }
-    L->lds_limit = (size_t)lim; L->lds_static = fa.sharedSizeBytes;
+    L->lds_limit = (size_t)lim; L->lds_static = own;
     c->init_lm = L;
   }
   *out = c->init_lm;
@@ -73,20 +72,9 @@ static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, co
   InitLmProb* Q = reinterpret_cast<InitLmProb*>(rec.data());
   int trace_base = 0;
   for (int p = 0; p < P; p++) { lmFillProb(Q[p], c, lv[p], K, p, trace_base); trace_base += lv[p].max_iterations + 1; }
-  const bool new_records = L->sent != rec;
-  if (new_records || state_in10) {
-    if (int r = L->slab.begin(s)) return r;
-    memcpy(L->slab.host<char>(0), rec.data(), rec.size());
-    size_t bytes = L->o_state;
-    if (state_in10) {
-      lmStateFrom10(L->slab.host<InitLmState>(L->o_state), state_in10);
-      bytes = L->o_state + sizeof(InitLmState);
-    }
-    L->sent.clear();
-    if (int r = L->slab.upload(s, bytes)) return r;
-    L->sent = rec;
-    if (state_in10) L->holds_state = true;
-  }
+  if (int r = lmSend(L->slab, L->sent, rec, state_in10 != nullptr, state_in10 ? L->o_state + sizeof(InitLmState) : L->o_state, s,
+                     [&] { lmStateFrom10(L->slab.host<InitLmState>(L->o_state), state_in10); })) return r;
+  if (state_in10) L->holds_state = true;
   const InitLmProb* d_probs = L->slab.dev<const InitLmProb>(0);
   InitLmState* d_state = L->slab.dev<InitLmState>(L->o_state);
   InitLmOut* d_outs = L->slab.dev<InitLmOut>(L->o_outs);
@@ -105,11 +93,8 @@ static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, co
   }
   for (int p = 0; p < P; p++) {
     DmvInitResident* R = lv[p].m->resident;
-    if (frame && p > 0 && R->n) {   // propagateDown from the level above (:749-777)
-      DmvInitResident* U = lv[p - 1].m->resident;
-      hipLaunchKernelGGL(k_init_propagate_down, dim3((unsigned)((R->n + 255) / 256)), dim3(256), 0, s, R->n, R->i(R->o_parent), U->b(U->o_good), U->f(U->o_iR), U->f(U->o_lh),
-                         R->b(R->o_good), R->f(R->o_iR), R->f(R->o_idepth), R->f(R->o_idn), R->f(R->o_lh));
-      L->work.launches++;
+    if (frame && p > 0) {   // propagateDown from the level above (:749-777)
+      if (int r = resPropagateDown(R, lv[p - 1].m->resident, s, &L->work)) return r;
       optReg(p);
     }
     hipLaunchKernelGGL(k_init_lm, dim3(1), dim3(256), resSweepLds(R->n), s, d_probs + p, d_state, d_outs, d_trace);
@@ -117,11 +102,7 @@ static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, co
   }
   if (frame)
     for (int p = P - 1; p > 0; p--) {   // propagateUp from level lv[p] into lv[p - 1], the lowest pair first (:262-263)
-      DmvInitResident *Lo = lv[p].m->resident, *R = lv[p - 1].m->resident;
-      if (!R->n) continue;
-      hipLaunchKernelGGL(k_init_propagate_up, dim3((unsigned)((R->n + 255) / 256)), dim3(256), 0, s, R->n, Lo->n_listed, Lo->i(Lo->o_cbegin), Lo->i(Lo->o_children),
-                         Lo->b(Lo->o_good), Lo->f(Lo->o_iR), Lo->f(Lo->o_lh), R->f(R->o_iR), R->f(R->o_idepth), R->b(R->o_good));
-      L->work.launches++;
+      if (int r = resPropagateUp(lv[p - 1].m->resident, lv[p].m->resident, s, &L->work)) return r;
       optReg(p - 1);
     }
   HIPCHK(hipGetLastError());
@@ -129,24 +110,9 @@ static int lmRun(dmvio_hip_ctx* c, DmvInitLmCtx* L, const LmLevel* lv, int P, co
   const size_t down = (trace_d ? L->o_trace + sizeof(InitLmTraceRec) * (size_t)trace_base : L->o_trace) - L->o_state;
   if (int r = L->slab.download(s, L->o_state, down)) return r;
   if (int r = L->slab.wait(s)) return r;
-  for (int p = 0; p < P; p++) lv[p].m->resident->st.settled();
   const InitLmState* S = L->slab.host<InitLmState>(L->o_state);
   lmStateTo10(S, state_out10);
-  const InitLmOut* O = L->slab.host<InitLmOut>(L->o_outs);
-  int written = 0;
-  for (int p = 0; p < P; p++) {
-    const int at = frame ? lv[p].lvl : 0;   // the frame call's arrays are indexed by level
-    if (res3) for (int k = 0; k < 3; k++) res3[3 * at + k] = O[p].res3[k];
-    if (iterations) iterations[at] = O[p].iterations;
-    if (trace_d) {
-      const InitLmTraceRec* T = L->slab.host<InitLmTraceRec>(L->o_trace) + Q[p].trace_base;
-      for (int k = 0; k < O[p].tests; k++, written++) {
-        memcpy(trace_d + (size_t)written * INIT_LM_TRACE_D, T[k].d, sizeof(T[k].d));
-        memcpy(trace_f + (size_t)written * INIT_LM_TRACE_F, T[k].f, sizeof(T[k].f));
-      }
-    }
-  }
-  if (trace_d) *trace_records = written;
+  lmDeliver(lv, P, Q, L->slab.host<InitLmOut>(L->o_outs), L->slab.host<InitLmTraceRec>(L->o_trace), frame, res3, iterations, trace_d, trace_f, trace_records);
   return S->snapped ? 1 : 0;
 }
 
@@ -207,16 +173,8 @@ int dmvio_hip_initializer_resident_track_level(dmvio_hip_initializer* m, int lvl
   int first = -1;
   if (int r = lmCheck(who, c, lmLimits(L), &lv, 1, K, state_in10, trace_capacity, trace_d, trace_f, trace_records, &first)) return r;
   if (first >= 0) {   // the range condition of resident_calc: the good points outside, counted on the device in a download and a wait of their own, before the loop is enqueued
-    DmvInitResident* R = m->resident;
-    hipStream_t s = c->stream;
-    const float umax = (float)(c->wl[lvl] - 3), vmax = (float)(c->hl[lvl] - 3);
-    int* d_count = R->io.dev<int>(sizeof(float) * RES_COUNT);
-    HIPCHK(hipMemsetAsync(d_count, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_init_count_outside, dim3((unsigned)((R->n + 255) / 256)), dim3(256), 0, s, R->n, R->b(R->o_good), R->f(R->o_u), R->f(R->o_v), umax, vmax, d_count);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(R->io.host<int>(sizeof(float) * RES_COUNT), d_count, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const int outside = *R->io.host<int>(sizeof(float) * RES_COUNT);
+    int outside = 0;
+    if (int r = resCountOutside(m->resident, c->wl[lvl], c->hl[lvl], c->stream, nullptr, &outside)) return r;   // (counted nowhere: last_work reports the loop's call)
     if (outside) {
       char msg[256];
       snprintf(msg, sizeof(msg), "%s: %d good point(s) outside [2, %d) x [2, %d) of level %d (the first point outside, good or not, is %d)", who, outside, c->wl[lvl] - 3, c->hl[lvl] - 3, lvl, first);
@@ -248,10 +206,7 @@ int dmvio_hip_initializer_resident_track_frame(dmvio_hip_initializer* const* lev
   DmvInitLmCtx* L;
   if (int r = lmCtx(c, &L)) return r;
   LmLevel lv[DMV_MAX_LEVELS];
-  for (int p = 0; p < n_levels; p++) {   // execution order: the top level first
-    const int l = n_levels - 1 - p;
-    lv[p] = {levels[l], l, max_iterations[l], p == 0, Ki9_levels + 9 * (size_t)l, fxfycxcy_levels + 4 * (size_t)l};
-  }
+  lmFrameLevels(lv, levels, n_levels, max_iterations, Ki9_levels, fxfycxcy_levels);
   const LmCommon K = {first_slot, new_slot, fix_affine != 0, alphaW, alphaK, regWeight, couplingWeight, priorY, priorX, wM8};
   if (int r = lmCheck(who, c, lmLimits(L), lv, n_levels, K, state_in10, trace_capacity, trace_d, trace_f, trace_records, nullptr)) return r;
   return lmRun(c, L, lv, n_levels, K, true, state_in10, state_out10, res3_levels, iterations_levels, trace_d, trace_f, trace_records);

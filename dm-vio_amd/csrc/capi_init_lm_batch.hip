@@ -1,7 +1,7 @@
 // C ABI of the initializer's LM loop, the frames of W windows per call (include/dmvio_hip_init_lm_batch.h): CoarseInitializer::trackFrame
 // (src/dso/FullSystem/CoarseInitializer.cpp:85-281) on the resident point sets of capi_init_resident.hip, one workgroup per window.  This unit checks the call — per window by
-// the single call's own lmCheck (init_lm_host.hpp) — fills the records, keeps the batch's LM records and enqueues ONE launch of k_init_lm_frame_b
-// (init_lm_batch_kernels.hpp).
+// the single call's own lmCheck, across the windows (a handle or a state slot named twice) itself — keeps the batch's LM records and enqueues ONE launch of
+// k_init_lm_frame_b (init_lm_batch_kernels.hpp).  A window's levels, its records, their upload and the delivery of its results are the single call's (init_lm_host.hpp).
 #include <vector>
 #include <cstring>
 #include <cstdio>
@@ -33,14 +33,12 @@ dmvio_hip_initializer_lm_batch* dmvio_hip_initializer_lm_batch_create(dmvio_hip_
   if (bad(hipSetDevice(ctx->device))) return nullptr;
   std::lock_guard<std::mutex> lk(ctx->mu);
   int lim = 0;
-  hipFuncAttributes fa;
-  if (bad(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device)) || bad(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_init_lm_frame_b))))
-    return nullptr;
-  if (lim <= 0 || fa.sharedSizeBytes >= (size_t)lim) { failmsg("initializer_lm_batch_create: the kernel's own LDS exceeds what the device allows a workgroup"); return nullptr; }
-  if (bad(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_init_lm_frame_b), hipFuncAttributeMaxDynamicSharedMemorySize, lim - (int)fa.sharedSizeBytes))) return nullptr;
+  size_t own = 0;
+  if (bad(initLdsAllow(ctx->device, &lim, reinterpret_cast<const void*>(&k_init_lm_frame_b), &own))) return nullptr;
+  if (lim <= 0 || own >= (size_t)lim) { failmsg("initializer_lm_batch_create: the kernel's own LDS exceeds what the device allows a workgroup"); return nullptr; }
   dmvio_hip_initializer_lm_batch* b = new dmvio_hip_initializer_lm_batch();
   b->ctx = ctx; b->max_windows = max_windows;
-  b->lds_limit = (size_t)lim; b->lds_static = fa.sharedSizeBytes;
+  b->lds_limit = (size_t)lim; b->lds_static = own;
   b->filled.assign((size_t)max_windows, 0);
   b->slab.work = &b->work;
   // the slab for up to 64 three-level windows without a trace; a call that needs more grows it (DmvSlab::reserve)
@@ -119,12 +117,7 @@ int dmvio_hip_initializer_resident_track_frame_batch(dmvio_hip_initializer_lm_ba
   for (int i = 0; i < W; i++) {
     const dmvio_hip_initializer_lm_window& w = win[i];
     LmLevel* v = lv.data() + first_prob[i];
-    int tests = 0;
-    for (int p = 0; p < w.n_levels; p++) {   // execution order: the top level first
-      const int l = w.n_levels - 1 - p;
-      v[p] = {w.levels[l], l, w.max_iterations[l], p == 0, w.Ki9_levels + 9 * (size_t)l, w.fxfycxcy_levels + 4 * (size_t)l};
-      tests += w.max_iterations[l] + 1;
-    }
+    const int tests = lmFrameLevels(v, w.levels, w.n_levels, w.max_iterations, w.Ki9_levels, w.fxfycxcy_levels);
     K[i] = {w.first_slot, w.new_slot, w.fix_affine != 0, w.alphaW, w.alphaK, w.regWeight, w.couplingWeight, w.priorY, w.priorX, w.wM8};
     snprintf(at, sizeof(at), "%s: window %d", who, i);
     const LmLimits lim = {b->lds_static, b->lds_limit, b->filled[w.state_slot] != 0, "the batch's record of this state_slot"};
@@ -167,21 +160,14 @@ int dmvio_hip_initializer_resident_track_frame_batch(dmvio_hip_initializer_lm_ba
     b->sent.clear();
   }
   b->work.clear();
-  if (any_in || b->sent != rec) {
-    if (int r = b->slab.begin(s)) return r;
-    memcpy(b->slab.host<char>(0), rec.data(), rec.size());
-    if (any_in) {
-      InitLmState* S = b->slab.host<InitLmState>(o_sin);
-      for (int i = 0; i < W; i++) {
-        if (win[i].state_in10) { lmStateFrom10(S + i, win[i].state_in10); S[i].pad = 1; }
-        else memset(S + i, 0, sizeof(InitLmState));
-      }
-    }
-    b->sent.clear();
-    if (int r = b->slab.upload(s, any_in ? up_bytes : rec_bytes)) return r;
-    b->sent = rec;
-    for (int i = 0; i < W; i++) if (win[i].state_in10) b->filled[win[i].state_slot] = 1;
-  }
+  if (int r = lmSend(b->slab, b->sent, rec, any_in, any_in ? up_bytes : rec_bytes, s, [&] {
+        InitLmState* S = b->slab.host<InitLmState>(o_sin);
+        for (int i = 0; i < W; i++) {
+          if (win[i].state_in10) { lmStateFrom10(S + i, win[i].state_in10); S[i].pad = 1; }
+          else memset(S + i, 0, sizeof(InitLmState));
+        }
+      })) return r;
+  for (int i = 0; i < W; i++) if (win[i].state_in10) b->filled[win[i].state_slot] = 1;
 
   // ---- ONE launch, ONE download, ONE wait
   hipLaunchKernelGGL(k_init_lm_frame_b, dim3((unsigned)W), dim3(256), resSweepLds(most), s, b->slab.dev<const InitLmWin>(o_win), b->slab.dev<const InitLmProb>(o_prob),
@@ -198,20 +184,8 @@ int dmvio_hip_initializer_resident_track_frame_batch(dmvio_hip_initializer_lm_ba
     dmvio_hip_initializer_lm_window& w = win[i];
     lmStateTo10(S + i, w.state_out10);
     w.snapped = S[i].snapped ? 1 : 0;
-    int written = 0;
-    for (int p = 0; p < w.n_levels; p++) {
-      const int q = first_prob[i] + p, l = lv[q].lvl;
-      lv[q].m->resident->st.settled();
-      if (w.res3_levels) for (int k = 0; k < 3; k++) w.res3_levels[3 * l + k] = O[q].res3[k];
-      if (w.iterations_levels) w.iterations_levels[l] = O[q].iterations;
-      if (w.trace_d)
-        for (int k = 0; k < O[q].tests; k++, written++) {
-          const InitLmTraceRec& R = T[Q[q].trace_base + k];
-          memcpy(w.trace_d + (size_t)written * INIT_LM_TRACE_D, R.d, sizeof(R.d));
-          memcpy(w.trace_f + (size_t)written * INIT_LM_TRACE_F, R.f, sizeof(R.f));
-        }
-    }
-    if (w.trace_d) *w.trace_records = written;
+    const int q = first_prob[i];
+    lmDeliver(lv.data() + q, w.n_levels, Q + q, O + q, T, true, w.res3_levels, w.iterations_levels, w.trace_d, w.trace_f, w.trace_records);
   }
   return 0;
 }

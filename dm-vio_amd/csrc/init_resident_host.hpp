@@ -1,5 +1,5 @@
-// The two static tables the resident initializer builds on the host, once per point set (dmvio_hip_initializer_set_resident).  No HIP call: compiles under a plain host
-// compiler (tests/init_sweep_harness.cpp).
+// What the resident initializer works out on the host, once per point set (dmvio_hip_initializer_set_resident, dmvInitResidentAdopt): its two static tables and where
+// the arrays lie in the slab.  No HIP call and no include of the project's: compiles under a plain host compiler (tests/init_sweep_harness.cpp).
 //
 // CoarseInitializer::optReg (CoarseInitializer.cpp:671-704) and the top-level branch of resetPoints (:901-916) are in-place loops: point i reads iR / isGood of its ten
 // neighbours, of which those with a lower index have been rewritten by the same loop and those with a higher index have not.  The neighbour table is fixed for the life of
@@ -53,4 +53,27 @@ static inline void initChildLists(int n_src, const int* parent, int n_dst, std::
   children.assign((size_t)std::max(n_src, 0), 0);
   std::vector<int> at(child_begin.begin(), child_begin.end() - 1);
   for (int i = 0; i < n_src; i++) children[(size_t)at[parent[i]]++] = i;
+}
+
+// One slab holds the point set: [static part | dynamic part], byte offsets.  The upload of set_resident covers the static part and the head of the dynamic one (the fields
+// the caller gives, up to up_end); the rest starts zeroed.  get_state downloads the dynamic part.  The four tables the host builds — order, level_begin, child_begin,
+// children — lie back to back in front of the dynamic part: dmvInitResidentAdopt, whose point arrays are written on the device, uploads [o_order, o_idepth) as one copy.
+struct DmvInitResidentLayout {
+  size_t o_u, o_v, o_oth, o_nb, o_parent, o_order, o_lbegin, o_cbegin, o_children;                                           // static
+  size_t o_idepth, o_iR, o_lh, o_energy, o_good, up_end, o_idn, o_en_new, o_maxstep, o_lh_new, o_jb[2], o_good_new, total;   // dynamic
+};
+// n points, `levels` sweep levels, n_listed parents listed.  CURSOR: DmvCursor (batch_slab.hpp), the one alignment rule of the slabs; a parameter so that this header
+// needs nothing but itself.
+template <class CURSOR>
+static inline DmvInitResidentLayout initResidentLayout(int n, int levels, int n_listed) {
+  CURSOR L;
+  DmvInitResidentLayout N;
+  N.o_u = L.template take<float>(n); N.o_v = L.template take<float>(n); N.o_oth = L.template take<float>(n); N.o_nb = L.template take<int>(10 * (size_t)n); N.o_parent = L.template take<int>(n);
+  N.o_order = L.template take<int>(n); N.o_lbegin = L.template take<int>((size_t)levels + 1); N.o_cbegin = L.template take<int>((size_t)n_listed + 1); N.o_children = L.template take<int>(n);
+  N.o_idepth = L.template take<float>(n); N.o_iR = L.template take<float>(n); N.o_lh = L.template take<float>(n); N.o_energy = L.template take<float>(2 * (size_t)n); N.o_good = L.template take<unsigned char>(n);
+  N.up_end = L.bytes();
+  N.o_idn = L.template take<float>(n); N.o_en_new = L.template take<float>(2 * (size_t)n); N.o_maxstep = L.template take<float>(n); N.o_lh_new = L.template take<float>(n);
+  N.o_jb[0] = L.template take<float>(10 * (size_t)n); N.o_jb[1] = L.template take<float>(10 * (size_t)n); N.o_good_new = L.template take<unsigned char>(n);
+  N.total = L.bytes();
+  return N;
 }

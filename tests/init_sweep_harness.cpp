@@ -1,13 +1,17 @@
 // The two host tables of the resident initializer (dm-vio_amd/csrc/init_resident_host.hpp) as a program of their own (tests/test_init_resident_cpu.py compiles it with g++
 // alone, with AddressSanitizer and UBSan where their runtimes exist): for hand-made graphs and for every graph in the files named on the command line, executing the levels
 // of initSweepSchedule in order — every point of a level from the state the levels before it left — equals the serial in-place loop, for two bodies shaped like optReg's and
-// like the top-level resetPoints'; and initChildLists lists every parent's children in ascending index.
+// like the top-level resetPoints'; initChildLists lists every parent's children in ascending index; and initResidentLayout puts every array of the point set's slab on a
+// 256-byte boundary, in declaration order, with the four host-built tables back to back in front of the dynamic part (the one copy of dmvInitResidentAdopt).
 // A graph file: int32 n, then 10 n int32 neighbours (-1 = none), then n int32 parents (-1 throughout = none).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
+static int failmsg(const std::string&) { return -2; }   // (batch_slab.hpp words refusals through it; none is reached here)
+#include "batch_slab.hpp"   // DmvCursor, the cursor the library lays the slab out with
 #include "init_resident_host.hpp"
 
 static int g_fail = 0;
@@ -95,7 +99,37 @@ static void checkChildren(const char* name, int n_src, const std::vector<int>& p
   for (int i = 0; i < n_src; i++) CHECK(seen[i] == 1, "%s: child %d listed %d times", name, i, seen[i]);
 }
 
+static void checkLayout(int n, int levels, int n_listed) {
+  const DmvInitResidentLayout N = initResidentLayout<DmvCursor>(n, levels, n_listed);
+  char name[64];
+  snprintf(name, sizeof(name), "layout n=%d levels=%d listed=%d", n, levels, n_listed);
+  const size_t F = sizeof(float) * (size_t)n, I = sizeof(int) * (size_t)n;
+  // every array in declaration order: offset and bytes
+  const struct { size_t off, bytes; } part[] = {
+      {N.o_u, F}, {N.o_v, F}, {N.o_oth, F}, {N.o_nb, 10 * I}, {N.o_parent, I}, {N.o_order, I}, {N.o_lbegin, sizeof(int) * ((size_t)levels + 1)},
+      {N.o_cbegin, sizeof(int) * ((size_t)n_listed + 1)}, {N.o_children, I}, {N.o_idepth, F}, {N.o_iR, F}, {N.o_lh, F}, {N.o_energy, 2 * F}, {N.o_good, (size_t)n},
+      {N.o_idn, F}, {N.o_en_new, 2 * F}, {N.o_maxstep, F}, {N.o_lh_new, F}, {N.o_jb[0], 10 * F}, {N.o_jb[1], 10 * F}, {N.o_good_new, (size_t)n}};
+  const int parts = (int)(sizeof(part) / sizeof(part[0]));
+  CHECK(N.o_u == 0, "%s: the slab does not start with u", name);
+  for (int k = 0; k < parts; k++) {
+    CHECK(part[k].off % 256 == 0, "%s: array %d at %zu is not 256-byte aligned", name, k, part[k].off);
+    if (k) CHECK(part[k].off >= part[k - 1].off + part[k - 1].bytes, "%s: array %d at %zu starts inside array %d (%zu + %zu)", name, k, part[k].off, k - 1, part[k - 1].off, part[k - 1].bytes);
+  }
+  CHECK(N.up_end % 256 == 0 && N.total % 256 == 0, "%s: up_end %zu or total %zu is not 256-byte aligned", name, N.up_end, N.total);
+  // [o_order, o_idepth) is order | level_begin | child_begin | children, each padded to the boundary, and nothing else
+  const size_t pad = 255;
+  CHECK(N.o_lbegin == N.o_order + ((I + pad) & ~pad), "%s: level_begin does not follow order", name);
+  CHECK(N.o_cbegin == N.o_lbegin + ((part[6].bytes + pad) & ~pad), "%s: child_begin does not follow level_begin", name);
+  CHECK(N.o_children == N.o_cbegin + ((part[7].bytes + pad) & ~pad), "%s: children does not follow child_begin", name);
+  CHECK(N.o_idepth == N.o_children + ((I + pad) & ~pad), "%s: the dynamic part does not follow children", name);
+  CHECK(N.up_end >= N.o_good + (size_t)n && N.up_end <= N.o_idn, "%s: up_end %zu outside [end of isGood %zu, idepth_new %zu]", name, N.up_end, N.o_good + (size_t)n, N.o_idn);
+  CHECK(N.total >= N.o_good_new + (size_t)n, "%s: total %zu does not cover isGood_new (%zu + %d)", name, N.total, N.o_good_new, n);
+}
+
 int main(int argc, char** argv) {
+  for (int n : {0, 1, 63, 64, 65})
+    for (int levels : {1, 3})
+      for (int n_listed : {0, 1, n}) checkLayout(n, levels, n_listed);
   {   // a chain i -> i - 1: n levels of one point
     const int n = 300;
     std::vector<int> nb(10 * n, -1);
@@ -146,6 +180,6 @@ int main(int argc, char** argv) {
     files++;
   }
   if (g_fail) { printf("%d check(s) FAILED\n", g_fail); return 1; }
-  printf("ok init_sweep_harness: hand-made graphs and %d graph file(s)\n", files);
+  printf("ok init_sweep_harness: hand-made graphs, the slab layouts and %d graph file(s)\n", files);
   return 0;
 }

@@ -63,7 +63,7 @@ def test_rejection_window_reaches_every_branch(oracle, synth):
 
 
 def test_harness_grid_is_the_single_calls():
-    src = open(os.path.join(ROOT, "dm-vio_amd", "csrc", "capi_init.hip")).read()
+    src = open(os.path.join(ROOT, "dm-vio_amd", "csrc", "init_handle.h")).read()
     assert "std::max(1, std::min((int)INIT_MAX_BLOCKS, (n + 255) / 256))" in src and re.search(r"INIT_MAX_BLOCKS = 256\b", src)
     import __graft_entry__ as graft
     pkg = graft.load_package()
